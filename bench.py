@@ -15,15 +15,17 @@ scaling), fp32, geometric-init weights seed 0, object_mask all true, rgb_gt = 0 
 1 -> 8 curve compares like with like; BASELINE configs[3] (T=2^22; 16 384 rays over 8 GPUs = the same 2048 rays per
 GPU) is `--cfg C4` and is reported beside the headline as `config4_leg` at every N.
 
-Two legs are timed, each over exactly K steps:
+A plain run times the headline leg alone, over exactly K steps:
   value / ms_per_step   the section-8(d) workload: the weights STAY at the geometric initialisation (the whole
                         iteration runs, optimizer included, with lr = 0), so every timed step traces the same
-                        surface: ~123 SDF evaluations per ray;
-  train_leg             the same iteration with lr = 1e-4 (Adam moves the surface while the clock runs, the per-ray
-                        work drifts with the step count - reported, never the headline).
+                        surface: ~123 SDF evaluations per ray.
 config.sdf_evals_per_step holds the measured SDF evaluations of the timed steps (mean / min / max).
+--dump-outputs DIR writes what the headline leg's last timed step returned (dump_outputs below).
 
-Extra objects on the same line:
+--full adds the other legs and measurements (each reported as an extra object on the same line):
+  train_leg     the same iteration with lr = 1e-4 (Adam moves the surface while the clock runs, the per-ray
+                work drifts with the step count - reported, never the headline), also timed over K steps;
+  lazy_sampler_leg, split_f16x2_leg, config4_leg, config3_leg, config5_leg, config5_leg_plain_bf16 (see main());
   roofline      hash-gather kernel (BASELINE metric "hash-gather HBM GB/s"): algorithmic bytes
                 (1304 B/point at L=16,F=2) x 2^22 points / HIP-event time per launch
   roofline_c4   the same kernel over the configs[3] table (T=2^22: 223.5 MiB, larger than the 32 MiB of L2)
@@ -32,6 +34,7 @@ Extra objects on the same line:
                 against the 157.3 TFLOP/s fp32 MFMA peak
   cpu_baseline  oracle/torch_ref.py (a port: the reference's op sequence on torch-CPU) timed on
                 the host cores on a bounded sample of the same workload
+(--full --no-extras: the train / lazy legs without the rest.)
 """
 import argparse
 import json
@@ -55,6 +58,8 @@ SDF_MAC_PER_POINT = 1966592  # SURVEY.md 8a row A9 (independent of the embedding
 RAYS_PER_GPU = 2048
 LAZY_SAMPLER_HEAD = int(os.environ.get("HM_LAZY_HEAD", "16"))   # RayTracing.sampler_head of the product (model/ray_tracing.py); legs other than "lazy" use 0
 CFG = "C2"          # BASELINE.json configs[1] at EVERY --gpus N (one table for the whole scaling curve); configs[3] = --cfg C4
+DUMP_MAX_ELEMS = 1 << 20   # --dump-outputs: larger arrays (the hash-table gradient) are written as a seeded sample of this size
+DUMP_MAX_BYTES = 64 << 20
 
 
 class Conf(dict):
@@ -122,6 +127,29 @@ def synthetic_batch(seed, n_rays, device):
                object_mask=torch.ones((1, n_rays), dtype=torch.bool, device=device))
     gt = dict(rgb=torch.zeros((1, n_rays, 3), dtype=torch.float32, device=device))
     return inp, gt
+
+
+def dump_outputs(path, model, out, lo):
+    """What a caller of the timed step receives from its last call, as path/<name>.npy: the model's output dict
+    (<key>.npy), the loss terms (loss.<key>.npy) and every parameter's gradient (grad.<parameter name>.npy).  float64
+    stays float64, everything else is written as float32.  An array of more than DUMP_MAX_ELEMS elements is reduced to
+    the flattened elements at a fixed seeded choice of indices (the same for every run at the same configuration)."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    arrays.update({"loss." + k: v for k, v in lo.items()})
+    arrays.update({"grad." + n: p.grad for n, p in model.named_parameters() if p.grad is not None})
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES >> 20} MB")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def gather_bytes_per_point(L, F):
@@ -514,7 +542,7 @@ def _side_leg(cfg, device, bf16, steps=6, warmup=3, sampler_head=0, split=None):
     inp, gt = synthetic_batch(1234, rays, device)
     torch.manual_seed(100)
     opt, lfn = ClipAdam(model.parameters(), lr=0.0, max_norm=1.0), IDRLoss(eikonal_weight=0.1, mask_weight=100.0, alpha=50.0)
-    dt, stats, final_loss, mode = _run_leg(a, model, opt, lfn, None, inp, gt, 1, device, 0, blocks=3)
+    dt, stats, final_loss, mode, _last = _run_leg(a, model, opt, lfn, None, inp, gt, 1, device, 0, blocks=3)
     et, L, T = NFFB_CONFIGS[cfg][0], NFFB_CONFIGS[cfg][1], NFFB_CONFIGS[cfg][2]
     if sampler_head:
         return {"value": round(rays * steps / dt, 1), "unit": "rays/s", "ms_per_step": round(dt / steps * 1e3, 3),
@@ -530,6 +558,7 @@ def _side_leg(cfg, device, bf16, steps=6, warmup=3, sampler_head=0, split=None):
 
 def _run_leg(args, model, opt, loss_fn, reducer, inp, gt, world, device, rank, blocks=1):
     """W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize; max over ranks.
+    Also returns what the last timed step returned: (model outputs, loss terms).
     blocks > 1 (the short side legs only, never the headline): that many consecutive blocks of K timed steps, the MEDIAN
     block is reported - one transient stall in a 6-step block moved a side leg from 9.8 to 14.2 ms once (r3al)."""
     from hashmodnffbanks_idr_amd import parallel
@@ -562,7 +591,7 @@ def _run_leg(args, model, opt, loss_fn, reducer, inp, gt, world, device, rank, b
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            _, lo = run_step()
+            out, lo = run_step()
             if rt._stats_dev is not None:
                 hist[i].copy_(rt._stats_dev, non_blocking=True)
         barrier()
@@ -581,7 +610,7 @@ def _run_leg(args, model, opt, loss_fn, reducer, inp, gt, world, device, rank, b
     mode = ("eager (reference-structured, dynamic shapes)" if args.no_graph
             else ("HIP-graph captured static-shape step" if stepper.g_fb is not None
                   else "eager static-shape step (graph capture unavailable)"))
-    return dt, stats, float(lo["loss"].item()), mode
+    return dt, stats, float(lo["loss"].item()), mode, (out, lo)
 
 
 def main():
@@ -590,16 +619,23 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rays", type=int, default=RAYS_PER_GPU, help="rays per GPU")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline sections")
+    ap.add_argument("--full", action="store_true",
+                    help="also every other leg, kernel roofline and the CPU baseline (a plain run times the headline leg "
+                         "alone); --legs defaults to both")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the roofline / cpu_baseline sections and the split / config 3-5 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-graph", action="store_true",
                     help="eager reference-structured step (dynamic shapes) instead of the HIP-graph captured step")
     ap.add_argument("--torch-adam", action="store_true",
                     help="torch.nn.utils.clip_grad_norm_ + torch.optim.Adam instead of the fused training.optim.ClipAdam")
-    ap.add_argument("--legs", choices=["both", "fixed", "train", "lazy"], default="both",
+    ap.add_argument("--legs", choices=["both", "fixed", "train", "lazy"], default=None,
                     help="fixed = section-8(d) workload (weights stay at geometric init, every sampler ray evaluates all "
                          "n_steps samples like the reference; the headline); train = the same with lr 1e-4; lazy = fixed "
                          "weights with the product's default lazy sampler (RayTracing.sampler_head = 16: samples past a "
-                         "ray's first sign change are not evaluated, outputs bit-identical); both = all three")
+                         "ray's first sign change are not evaluated, outputs bit-identical); both = all three.  Default: "
+                         "fixed, both with --full")
     ap.add_argument("--gather-log2n", type=int, default=22)
     ap.add_argument("--calib", default="1,0", help="gather_calib: lanes per 128-B block, byte stride between them")
     ap.add_argument("--bf16", type=int, default=-1,
@@ -612,6 +648,9 @@ def main():
                     help="hash-grid config (tests/golden/params.py): default C2 = BASELINE configs[1] at every --gpus N; "
                          "C4 = configs[3] (T = 2^22), C3 / C5 = the filter-bank configurations")
     args = ap.parse_args()
+    if args.legs is None:
+        args.legs = "both" if args.full else "fixed"
+    extras = args.full and not args.no_extras
     cfg = args.cfg or os.environ.get("HM_BENCH_CFG") or CFG
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ and not args.only:
         sys.exit(_spawn_ranks(args))
@@ -691,7 +730,8 @@ def main():
         model.ray_tracer.sampler_head = sampler_head
         reducer = _make_reducer(model, world, args.no_graph)
         torch.manual_seed(100 + rank)  # per-rank eikonal points / step fractions
-        dt, stats, final_loss, mode = _run_leg(a, model, make_opt(model, lr), loss_fn, reducer, inp, gt, world, device, rank)
+        dt, stats, final_loss, mode, last = _run_leg(a, model, make_opt(model, lr), loss_fn, reducer, inp, gt, world, device,
+                                                     rank)
         rec = {"value": round(args.rays * world * steps / dt, 1), "unit": "rays/s",
                "ms_per_step": round(dt / steps * 1e3, 3), "lr": lr, "sampler_head": sampler_head,
                "sdf_evals_per_step": stats, "final_loss": round(final_loss, 6), "step": mode}
@@ -699,30 +739,33 @@ def main():
             rec["exchange"] = type(reducer).__name__
             if hasattr(reducer, "check"):
                 reducer.check()        # (host read after the timed region: no touched row may have missed its payload)
-        return rec, model
+        return rec, model, last
 
     legs = {}
     model = None
     for leg, lr, sampler_head in (("fixed", 0.0, 0), ("train", 1.0e-4, 0), ("lazy", 0.0, LAZY_SAMPLER_HEAD)):
         if args.legs not in ("both", leg):
             continue
-        legs[leg], model = run_one(cfg, lr, sampler_head, args.steps, args.warmup, use_bf16, split=use_split)
+        legs[leg], model, last = run_one(cfg, lr, sampler_head, args.steps, args.warmup, use_bf16, split=use_split)
         if leg == "fixed":
             head_model = model
+        if args.dump_outputs and rank == 0 and len(legs) == 1:     # the first leg run is the headline leg
+            dump_outputs(args.dump_outputs, model, *last)
+        del last
     if "fixed" not in legs:
         head_model = model
     split_leg = None
-    if not args.no_extras and cfg in ("C2", "C4") and args.legs in ("both", "fixed") and world == 1:
+    if extras and cfg in ("C2", "C4") and args.legs in ("both", "fixed") and world == 1:
         # the headline iteration with the coarse scans on the split-operand kernel (fp16 hi + lo, 22-bit operands):
         # same workload, same evaluation count; reported beside the headline, which stays exact fp32
-        split_leg, _m = run_one(cfg, 0.0, 0, args.steps, args.warmup, False, split="f16x2")
+        split_leg, _m, _last = run_one(cfg, 0.0, 0, args.steps, args.warmup, False, split="f16x2")
         split_leg["coarse_scans"] = "f16x2 split operands on v_mfma_f32_32x32x16_f16 (csrc/hm_sdf_split.hip)"
         del _m
     c4_leg = None
-    if not args.no_extras and cfg == "C2" and args.rays == RAYS_PER_GPU:
+    if extras and cfg == "C2" and args.rays == RAYS_PER_GPU:
         # BASELINE configs[3] (T = 2^22; 16 384 rays over 8 GPUs = these 2048 rays per GPU), short fixed-weights leg at
         # EVERY N so that its own 1 -> 8 curve exists beside the headline's
-        c4_leg, _m = run_one("C4", 0.0, 0, min(args.steps, 10), 3, False)
+        c4_leg, _m, _last = run_one("C4", 0.0, 0, min(args.steps, 10), 3, False)
         c4_leg["workload"] = "MultiResHash L=16 T=2^22 F=2 (BASELINE.json configs[3]), 2048 rays per GPU, weights at init"
         c4_leg["steps"] = min(args.steps, 10)
         del _m
@@ -770,15 +813,15 @@ def main():
             line["config4_leg"] = c4_leg
         if split_leg is not None:
             line["split_f16x2_leg"] = split_leg
-        if not args.no_extras and world > 1:
+        if extras and world > 1:
             # N > 1: the kernel rooflines / CPU baseline are single-GPU measurements and belong to the N = 1 line
             emb = head_model.implicit_network.embed_model.embedder_obj
             emb = getattr(emb, "grid_enc", emb)
             if not (cfg in NFFB_CONFIGS):
                 line["roofline"] = gather_roofline(emb, args.gather_log2n)
-        elif not args.no_extras and cfg in NFFB_CONFIGS:
+        elif extras and cfg in NFFB_CONFIGS:
             line["cpu_baseline"] = None      # (the torch-CPU port covers the hash-grid embedder only)
-        elif not args.no_extras:
+        elif extras:
             emb = head_model.implicit_network.embed_model.embedder_obj
             line["roofline"] = gather_roofline(emb, args.gather_log2n)
             line["roofline_bwd"] = gather_bwd_roofline(emb, args.gather_log2n, iters=5, warmup=2)

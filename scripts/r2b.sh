@@ -12,6 +12,6 @@ HM_ENCODE_SWEEP=0 timeout -k 10 120 python bench.py --only gather --cfg C4 2>/de
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fixed -- python bench.py --legs fixed --no-extras --steps 10 --warmup 3 > $O/prof_fixed.log 2>&1; echo "prof rc=$?"
 tail -1 $O/prof_fixed.log | cut -c1-300
 for n in 2 4; do
-  HM_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus $n --steps 8 --warmup 3 --no-extras > $O/gloo_n$n.log 2>&1; echo "gloo n=$n rc=$?"
+  HM_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus $n --steps 8 --warmup 3 --no-extras > $O/gloo_n$n.log 2>&1; echo "gloo n=$n rc=$?"
   tail -1 $O/gloo_n$n.log | cut -c1-1500
 done

@@ -9,4 +9,4 @@ for cfg in C2 C4; do for fl in 2 6 8 10 14 13; do
   HM_ENCODE_FLAGS=$fl timeout -k 10 120 python bench.py --only gather --cfg $cfg 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$cfg flags=$fl', d['achieved'], d['avg_launch_ms'], d['min_launch_ms'])" | tee -a $O/gather_sweep.log
 done; done
 for g in 256 384; do for fl in 2 13 14; do HM_ENCODE_FLAGS=$fl HM_ENCODE_GRID=$g timeout -k 10 120 python bench.py --only gather --cfg C4 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('C4 grid=$g flags=$fl', d['achieved'], d['avg_launch_ms'])" | tee -a $O/gather_sweep.log; done; done
-timeout -k 10 280 python bench.py --no-extras > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-1200
+timeout -k 10 280 python bench.py --full --no-extras > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-1200

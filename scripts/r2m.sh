@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r2m; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -q -rf > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee $O/pytest.rc; tail -3 $O/pytest.log
-timeout -k 10 500 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/bench.log > $O/bench_line.json; python - <<'PY'
+timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/bench.log > $O/bench_line.json; python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r2m/bench_line.json'))
 print(d['value'], d['ms_per_step'], d['train_leg']['ms_per_step'])

@@ -2,7 +2,7 @@
 # round 2, run v: step time + kernel-trace launch counts after the fused embedding-row input gradient
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r2v; mkdir -p $O
-timeout -k 10 300 python bench.py --no-extras --steps 40 --warmup 5 2>/dev/null | tail -1 > $O/bench.json
+timeout -k 10 300 python bench.py --full --no-extras --steps 40 --warmup 5 2>/dev/null | tail -1 > $O/bench.json
 python -c "
 import json; d=json.load(open('$O/bench.json')); print('fixed', d['ms_per_step'], d['value'], 'train', d['train_leg']['ms_per_step'], 'lazy', d['lazy_sampler_leg']['ms_per_step'], d['lazy_sampler_leg']['value'])"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o step --output-format csv -- python bench.py --legs fixed --no-extras --steps 10 --warmup 3 > $O/prof.log 2>&1

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r3am; mkdir -p $O
 for i in 1 2; do
-timeout -k 10 400 python bench.py > $O/bench$i.log 2>&1; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $O/bench$i.log 2>&1; echo "bench rc=$?"
 tail -1 $O/bench$i.log | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r3c; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"
 tail -5 $O/pytest_gpu.log | cut -c1-300
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.log 2>&1; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.log 2>&1; echo "bench rc=$?"
 tail -1 $O/bench.log > $O/bench_line.json
 python - <<'PY'
 import json

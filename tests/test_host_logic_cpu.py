@@ -161,14 +161,15 @@ def test_optimizer_state_from_a_reference_shaped_checkpoint(golden):
     st = opt.state[emb.table]
     off = [int(v) for v in emb.desc.row_off]
     j0 = ref_names.index("implicit_network.embed_model.embedder_obj.levels.0.embedding.weight")
+    # (the hash grid puts its table - and Adam its state - on the GPU where there is one: hashGridEmbedding.DEVICE)
     for l in range(emb.n_levels):
-        assert torch.equal(st["exp_avg"][off[l]:off[l + 1]], state[j0 + l]["exp_avg"])
-        assert torch.equal(st["exp_avg_sq"][off[l]:off[l + 1]], state[j0 + l]["exp_avg_sq"])
+        assert torch.equal(st["exp_avg"][off[l]:off[l + 1]].cpu(), state[j0 + l]["exp_avg"])
+        assert torch.equal(st["exp_avg_sq"][off[l]:off[l + 1]].cpu(), state[j0 + l]["exp_avg_sq"])
     assert float(st["step"]) == 12.0
     back = ck.optimizer_state_to_reference(model, opt.state_dict())
     assert set(back["state"]) == set(state)
     for j in state:
-        assert torch.equal(back["state"][j]["exp_avg"], state[j]["exp_avg"]), ref_names[j]
+        assert torch.equal(back["state"][j]["exp_avg"].cpu(), state[j]["exp_avg"]), ref_names[j]
     # levels that disagree on the step count cannot be fused
     bad = {"state": {j: dict(v) for j, v in state.items()}, "param_groups": ref_sd["param_groups"]}
     bad["state"][j0 + 1]["step"] = torch.tensor(13.0)
