@@ -104,4 +104,48 @@ __device__ __forceinline__ uint32_t hm_hash3(uint32_t ux, uint32_t uy, uint32_t 
 __device__ __forceinline__ int32_t hm_trunc_voxel(float x, int32_t res) {
     return (int32_t)__fmul_rn(x, (float)res);
 }
+// one axis of voxel corner `bit`: grid index u and interpolation weight w.  Reference mode: xf = x - x.float() == 0
+// (hashGridEmbedding.py:86), so w = where(mask, 1 - xf, xf) is 1 for bit 0 and 0 for bit 1; trilinear: floor + fraction
+template <int FRAC>
+__device__ __forceinline__ void hm_corner(float x, int32_t res, int bit, uint32_t &u, float &w) {
+    if (FRAC == HM_FRAC_REFERENCE) {
+        u = (uint32_t)hm_trunc_voxel(x, res) + (uint32_t)bit;
+        w = bit ? 0.0f : 1.0f;
+    } else {
+        const float xs = __fmul_rn(x, (float)res);
+        const float fl = floorf(xs);
+        u = (uint32_t)((int32_t)fl) + (uint32_t)bit;
+        const float xf = __fsub_rn(xs, fl);
+        w = bit ? xf : __fsub_rn(1.0f, xf);
+    }
+}
+// Fourier argument a_c = (2 pi x) . B[:, c] (frequency_enc.py:63-67): s_d = 2 pi x_d rounded in fp32, then [N,3]@[3,L]
+// as a k-ordered fma chain (matches torch's CPU sgemm bit for bit, see oracle)
+__device__ __forceinline__ float hm_fourier_arg(const float *__restrict__ Bf, int L, int c, float s0, float s1, float s2) {
+    float a = __fmul_rn(s0, Bf[c]);
+    a = __fmaf_rn(s1, Bf[L + c], a);
+    return __fmaf_rn(s2, Bf[2 * L + c], a);
+}
+// features of one point at level l: the weighted sum of its 8 corner rows of the fp32 table (F <= 8), corners in
+// index order; zero-weight corners add exactly 0 and are skipped (reference mode: only corner 0 survives)
+template <int FRAC>
+__device__ __forceinline__ void hm_level_features(const HmLevels &lv, const float *__restrict__ table, int l, float x0,
+                                                  float x1, float x2, float (&acc)[8]) {
+    const int F = lv.F;
+    for (int f = 0; f < F; ++f) acc[f] = 0.0f;
+    const float *tl = table + (size_t)lv.row_off[l] * F;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        uint32_t ux, uy, uz;
+        float wx, wy, wz;
+        hm_corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
+        hm_corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
+        hm_corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
+        const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
+        if (w != 0.0f) {
+            const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l]);
+            for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(tl[(size_t)id * F + f], w));
+        }
+    }
+}
 #endif

@@ -62,23 +62,6 @@ __device__ __forceinline__ void store_tile_vec(float *dst, unsigned tile_bytes, 
     else __builtin_amdgcn_raw_buffer_store_b128(u, rsrc, i * 16, 0, 17);                  // sc0 sc1
 }
 
-// corner weight for one axis: reference mode => (bit ? xf : 1-xf) with xf == 0
-template <int FRAC>
-__device__ __forceinline__ void voxel_and_weight(float x, int32_t res, int bit, uint32_t &u, float &w) {
-    float xs = __fmul_rn(x, (float)res);
-    if (FRAC == HM_FRAC_REFERENCE) {
-        int32_t xi = (int32_t)xs;  // trunc toward zero
-        u = (uint32_t)xi + (uint32_t)bit;
-        w = bit ? 0.0f : 1.0f;     // where(mask, 1 - xf, xf) with xf = x - x.float() = 0
-    } else {
-        float fl = floorf(xs);
-        int32_t xi = (int32_t)fl;
-        float xf = __fsub_rn(xs, fl);
-        u = (uint32_t)xi + (uint32_t)bit;
-        w = bit ? xf : __fsub_rn(1.0f, xf);
-    }
-}
-
 template <int FRAC>
 __global__ __launch_bounds__(kThreads) void encode_fwd_f2_kernel(HmLevels lv, const float *__restrict__ x, int64_t n,
                                                                  const float2 *__restrict__ table,
@@ -115,11 +98,8 @@ __global__ __launch_bounds__(kThreads) void encode_fwd_f2_kernel(HmLevels lv, co
         const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
         for (int c = cg; c < L; c += 4) {
             // [N,3]@[3,L] as a k-ordered fma chain (matches torch's CPU sgemm bit-for-bit, see oracle)
-            float a = __fmul_rn(s0, Bf[c]);
-            a = __fmaf_rn(s1, Bf[L + c], a);
-            a = __fmaf_rn(s2, Bf[2 * L + c], a);
             float sn, cs;
-            sincosf(a, &sn, &cs);
+            sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
             o[3 + c] = sn;
             o[3 + L + c] = cs;
         }
@@ -143,9 +123,9 @@ __global__ __launch_bounds__(kThreads) void encode_fwd_f2_kernel(HmLevels lv, co
                 const int p = j * 8 + sub;
                 uint32_t ux, uy, uz;
                 float wx, wy, wz;
-                voxel_and_weight<FRAC>(s_x[p * 3 + 0], res, bx, ux, wx);
-                voxel_and_weight<FRAC>(s_x[p * 3 + 1], res, by, uy, wy);
-                voxel_and_weight<FRAC>(s_x[p * 3 + 2], res, bz, uz, wz);
+                hm_corner<FRAC>(s_x[p * 3 + 0], res, bx, ux, wx);
+                hm_corner<FRAC>(s_x[p * 3 + 1], res, by, uy, wy);
+                hm_corner<FRAC>(s_x[p * 3 + 2], res, bz, uz, wz);
                 const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), rows, magic);
                 v[j] = tl[id];
                 w[j] = __fmul_rn(__fmul_rn(wx, wy), wz);
@@ -236,11 +216,8 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_sweep_kernel(HmLevels
             const float two_pi = 6.283185307179586f;
             const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
             for (int c = cg; c < L; c += 2) {
-                float a = __fmul_rn(s0, Bf[c]);
-                a = __fmaf_rn(s1, Bf[L + c], a);
-                a = __fmaf_rn(s2, Bf[2 * L + c], a);
                 float sn, cs;
-                sincosf(a, &sn, &cs);
+                sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
                 o[3 + c] = sn;
                 o[3 + L + c] = cs;
             }
@@ -264,9 +241,9 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_sweep_kernel(HmLevels
                     const int p = wave * 32 + j * 8 + sub;
                     uint32_t ux, uy, uz;
                     float wx, wy, wz;
-                    voxel_and_weight<FRAC>(s_x[p * 3 + 0], res, bx, ux, wx);
-                    voxel_and_weight<FRAC>(s_x[p * 3 + 1], res, by, uy, wy);
-                    voxel_and_weight<FRAC>(s_x[p * 3 + 2], res, bz, uz, wz);
+                    hm_corner<FRAC>(s_x[p * 3 + 0], res, bx, ux, wx);
+                    hm_corner<FRAC>(s_x[p * 3 + 1], res, by, uy, wy);
+                    hm_corner<FRAC>(s_x[p * 3 + 2], res, bz, uz, wz);
                     v[k][j] = tl[hm_mod_rows(hm_hash3(ux, uy, uz), rows, magic)];
                     w[k][j] = __fmul_rn(__fmul_rn(wx, wy), wz);
                 }
@@ -437,11 +414,8 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_zorder_kernel(HmLevel
             const float two_pi = 6.283185307179586f;
             const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
             for (int c = cg; c < L; c += 2) {
-                float a = __fmul_rn(s0, Bf[c]);
-                a = __fmaf_rn(s1, Bf[L + c], a);
-                a = __fmaf_rn(s2, Bf[2 * L + c], a);
                 float sn, cs;
-                sincosf(a, &sn, &cs);
+                sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
                 o[3 + c] = sn;
                 o[3 + L + c] = cs;
             }
@@ -467,9 +441,9 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_zorder_kernel(HmLevel
                     const int p = wave * 32 + j * 8 + sub;
                     uint32_t ux, uy, uz;
                     float wx, wy, wz;
-                    voxel_and_weight<FRAC>(s_x[p * 3 + 0], res, bx, ux, wx);
-                    voxel_and_weight<FRAC>(s_x[p * 3 + 1], res, by, uy, wy);
-                    voxel_and_weight<FRAC>(s_x[p * 3 + 2], res, bz, uz, wz);
+                    hm_corner<FRAC>(s_x[p * 3 + 0], res, bx, ux, wx);
+                    hm_corner<FRAC>(s_x[p * 3 + 1], res, by, uy, wy);
+                    hm_corner<FRAC>(s_x[p * 3 + 2], res, bz, uz, wz);
                     v[kk][j] = tl[hm_mod_rows(hm_hash3(ux, uy, uz), rows, magic)];
                     w[kk][j] = __fmul_rn(__fmul_rn(wx, wy), wz);
                 }
@@ -542,11 +516,8 @@ __global__ __launch_bounds__(kThreads) void encode_fwd_generic_kernel(HmLevels l
         const float two_pi = 6.283185307179586f;
         const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
         for (int c = 0; c < L; ++c) {
-            float a = __fmul_rn(s0, Bf[c]);
-            a = __fmaf_rn(s1, Bf[L + c], a);
-            a = __fmaf_rn(s2, Bf[2 * L + c], a);
             float sn, cs;
-            sincosf(a, &sn, &cs);
+            sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
             o[3 + c] = sn;
             o[3 + L + c] = cs;
         }
@@ -560,7 +531,7 @@ __global__ __launch_bounds__(kThreads) void encode_fwd_generic_kernel(HmLevels l
         float w = 1.0f;
         for (int d = 0; d < 3; ++d) {
             float wd;
-            voxel_and_weight<FRAC>(xin[d], lv.res[l], (c >> d) & 1, u[d], wd);
+            hm_corner<FRAC>(xin[d], lv.res[l], (c >> d) & 1, u[d], wd);
             w = __fmul_rn(w, wd);
         }
         const uint32_t id = hm_mod_rows(hm_hash3(u[0], u[1], u[2]), lv.rows[l], lv.magic[l]);
@@ -609,7 +580,7 @@ __global__ __launch_bounds__(kThreads) void encode_bwd_table_kernel(HmLevels lv,
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         float wd;
-        voxel_and_weight<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
+        hm_corner<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
         w = __fmul_rn(w, wd);
     }
     if (w == 0.0f) return;
@@ -647,7 +618,7 @@ __global__ __launch_bounds__(kThreads) void encode_bwd_table_small_kernel(HmLeve
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             float wd;
-            voxel_and_weight<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
+            hm_corner<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
             w = __fmul_rn(w, wd);
         }
         if (w == 0.0f) continue;
@@ -693,7 +664,7 @@ __global__ __launch_bounds__(kThreads) void encode_bwd_table_tracked_kernel(HmLe
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             float wd;
-            voxel_and_weight<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
+            hm_corner<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
             w = __fmul_rn(w, wd);
         }
         if (w != 0.0f) {
@@ -799,9 +770,9 @@ __global__ __launch_bounds__(kBwdThreads) void encode_bwd_table_zorder_kernel(Hm
         for (int c = 0; c < C; ++c) {
             uint32_t ux, uy, uz;
             float wx, wy, wz;
-            voxel_and_weight<FRAC>(x0, res, c & 1, ux, wx);
-            voxel_and_weight<FRAC>(x1, res, (c >> 1) & 1, uy, wy);
-            voxel_and_weight<FRAC>(x2, res, (c >> 2) & 1, uz, wz);
+            hm_corner<FRAC>(x0, res, c & 1, ux, wx);
+            hm_corner<FRAC>(x1, res, (c >> 1) & 1, uy, wy);
+            hm_corner<FRAC>(x2, res, (c >> 2) & 1, uz, wz);
             const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
             if (w == 0.0f) continue;
             const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), rows, magic);
@@ -859,7 +830,7 @@ __global__ __launch_bounds__(kThreads) void encode_rows_kernel(HmLevels lv, cons
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         float wd;
-        voxel_and_weight<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
+        hm_corner<FRAC>(x[i * 3 + d], lv.res[l], (c >> d) & 1, u[d], wd);
         w = __fmul_rn(w, wd);
     }
     keys[gid] = (int32_t)(lv.row_off[l] + hm_mod_rows(hm_hash3(u[0], u[1], u[2]), lv.rows[l], lv.magic[l]));

@@ -33,12 +33,8 @@ __device__ __forceinline__ CornerJet corner_jet(const HmLevels &lv, int l, int c
     uint32_t u[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const float xs = __fmul_rn(xin[d], (float)res);
-        const float fl = floorf(xs);
-        const float t = __fsub_rn(xs, fl);
         const int bit = (c >> d) & 1;
-        u[d] = (uint32_t)(int32_t)fl + (uint32_t)bit;
-        j.w[d] = bit ? t : __fsub_rn(1.0f, t);
+        hm_corner<HM_FRAC_TRILINEAR>(xin[d], res, bit, u[d], j.w[d]);
         j.s[d] = bit ? 1.0f : -1.0f;
     }
     j.id = hm_mod_rows(hm_hash3(u[0], u[1], u[2]), lv.rows[l], lv.magic[l]);
@@ -148,13 +144,7 @@ __global__ __launch_bounds__(kThreads) void encode_bwd_input_kernel(HmLevels lv,
 }
 
 // ---- Fourier-feature columns of the embedding row [x | sin(a) | cos(a) | hash features], a_c = 2 pi x . B[:, c] -------
-// (frequency_enc.py:63-67; same fp32 expression as the forward kernel: s = 2 pi x, k-ordered fma chain)
-__device__ __forceinline__ float fourier_arg(const float *__restrict__ Bf, int L, int c, float s0, float s1, float s2) {
-    float a = __fmul_rn(s0, Bf[c]);
-    a = __fmaf_rn(s1, Bf[L + c], a);
-    return __fmaf_rn(s2, Bf[2 * L + c], a);
-}
-
+// (frequency_enc.py:63-67; the forward kernels' fp32 expression, hm_fourier_arg)
 // Both Fourier kernels run SIXTEEN lanes per point (lane c takes channels c, c + 16): one thread per point was a serial
 // chain of L sincosf and 2 L strided loads on 12 workgroups for a 3072-point batch - 11 / 20 us per call, six calls per
 // step.  The three sums are reduced over the 16 lanes with xor shuffles.
@@ -183,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void fourier_bwd_input_kernel(const float
     float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
     for (int c = c0; c < L; c += kFLanes) {
         float sn, cs;
-        sincosf(fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
+        sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
         const float q = cs * d[3 + c] - sn * d[3 + L + c];
         g0 += q * Bf[c]; g1 += q * Bf[L + c]; g2 += q * Bf[2 * L + c];
     }
@@ -220,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void fourier_bwd_input_bwd_kernel(const f
     float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
     for (int c = c0; c < L; c += kFLanes) {
         float sn, cs;
-        sincosf(fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
+        sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
         const float b0 = Bf[c], b1 = Bf[L + c], b2 = Bf[2 * L + c];
         const float pc = b0 * q0 + b1 * q1 + b2 * q2;
         if (o) {

@@ -42,20 +42,6 @@ struct NffbArgs {   // by value
     float bound, w0, style_eps;
 };
 
-template <int FRAC>
-__device__ __forceinline__ void nffb_corner(float x, int32_t res, int bit, uint32_t &u, float &w) {
-    const float xs = __fmul_rn(x, (float)res);
-    if (FRAC == HM_FRAC_REFERENCE) {
-        u = (uint32_t)((int32_t)xs) + (uint32_t)bit;
-        w = bit ? 0.0f : 1.0f;
-    } else {
-        const float fl = floorf(xs);
-        const float xf = __fsub_rn(xs, fl);
-        u = (uint32_t)((int32_t)fl) + (uint32_t)bit;
-        w = bit ? xf : __fsub_rn(1.0f, xf);
-    }
-}
-
 // Lane `sub` of a point computes rows sub, sub + 8, ... of y = Wm v + b (k-ordered fma chain per row, the weights
 // read as 16-byte vector loads: the matrices are 12 - 21 KB and stay in the CU's L1) and leaves them in the point's LDS
 // row; the barrier-separated read-back gives every lane of the point the whole vector again.
@@ -131,11 +117,8 @@ __global__ __launch_bounds__(kNT) void nffb_fwd_kernel(HmLevels lv, NffbArgs a, 
             const float two_pi = 6.283185307179586f;
             const float s0 = __fmul_rn(two_pi, u0), s1 = __fmul_rn(two_pi, u1), s2 = __fmul_rn(two_pi, u2);
             for (int c = sub; c < LV; c += kLP) {
-                float ang = __fmul_rn(s0, Bf[c]);
-                ang = __fmaf_rn(s1, Bf[LV + c], ang);
-                ang = __fmaf_rn(s2, Bf[2 * LV + c], ang);
                 float sn, cs;
-                sincosf(ang, &sn, &cs);
+                sincosf(hm_fourier_arg(Bf, LV, c, s0, s1, s2), &sn, &cs);
                 if (c < NG) grow[c] = sn;
                 if (LV + c < NG) grow[LV + c] = cs;
             }
@@ -147,9 +130,9 @@ __global__ __launch_bounds__(kNT) void nffb_fwd_kernel(HmLevels lv, NffbArgs a, 
                 for (int c = 0; c < 8; ++c) {
                     uint32_t ux, uy, uz;
                     float wx, wy, wz;
-                    nffb_corner<FRAC>(u0, lv.res[l], c & 1, ux, wx);
-                    nffb_corner<FRAC>(u1, lv.res[l], (c >> 1) & 1, uy, wy);
-                    nffb_corner<FRAC>(u2, lv.res[l], (c >> 2) & 1, uz, wz);
+                    hm_corner<FRAC>(u0, lv.res[l], c & 1, ux, wx);
+                    hm_corner<FRAC>(u1, lv.res[l], (c >> 1) & 1, uy, wy);
+                    hm_corner<FRAC>(u2, lv.res[l], (c >> 2) & 1, uz, wz);
                     const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
                     if (w != 0.0f) {
                         const float2 r = tl[hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l])];
@@ -323,11 +306,8 @@ __global__ __launch_bounds__(64 * WAVES) void nffb_fwd_mfma_kernel(HmLevels lv, 
                 float v;
                 if (c < 2 * LV) {
                     const int ch = c < LV ? c : c - LV;
-                    float ang = __fmul_rn(s0, Bf[ch]);
-                    ang = __fmaf_rn(s1, Bf[LV + ch], ang);
-                    ang = __fmaf_rn(s2, Bf[2 * LV + ch], ang);
                     float sn, cs;
-                    sincosf(ang, &sn, &cs);
+                    sincosf(hm_fourier_arg(Bf, LV, ch, s0, s1, s2), &sn, &cs);
                     v = c < LV ? sn : cs;
                 } else {
                     const int l = (c - 2 * LV) >> 1, f = (c - 2 * LV) & 1;
@@ -337,9 +317,9 @@ __global__ __launch_bounds__(64 * WAVES) void nffb_fwd_mfma_kernel(HmLevels lv, 
                     for (int cc = 0; cc < 8; ++cc) {
                         uint32_t ux, uy, uz;
                         float wx, wy, wz;
-                        nffb_corner<FRAC>(u0, lv.res[l], cc & 1, ux, wx);
-                        nffb_corner<FRAC>(u1, lv.res[l], (cc >> 1) & 1, uy, wy);
-                        nffb_corner<FRAC>(u2, lv.res[l], (cc >> 2) & 1, uz, wz);
+                        hm_corner<FRAC>(u0, lv.res[l], cc & 1, ux, wx);
+                        hm_corner<FRAC>(u1, lv.res[l], (cc >> 1) & 1, uy, wy);
+                        hm_corner<FRAC>(u2, lv.res[l], (cc >> 2) & 1, uz, wz);
                         const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
                         if (w != 0.0f) {
                             const float2 r = tl[hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l])];

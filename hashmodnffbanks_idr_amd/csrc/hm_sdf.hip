@@ -112,7 +112,6 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
     const int lane = tid & 63;
     const int j = lane & 31;  // point within a 32-point tile / feature row within a 32-feature tile
     const int h = lane >> 5;
-    const int L = lv.L, F = lv.F;
     const int E = lv.E;
     // Tile schedule: `rounds` full rounds of 64-point tiles (tile = round * grid + workgroup), then ONE remainder tile
     // per workgroup.  When the remainder fits 32 points per workgroup it is cut into 32-point HALF tiles (the MFMAs of
@@ -175,41 +174,8 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
             const int p = tid & (kPts - 1);
             const int grp = tid >> 6;  // 0..7
             const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            auto put = [&](int e, float v) { EMB[(e >> 2) * kGroupFloats + p * 4 + (e & 3)] = v; };
-            if (grp == 0) {
-                put(0, x0); put(1, x1); put(2, x2);
-                for (int e = E; e < net.emb_groups * 4; ++e) put(e, 0.0f);  // zero the k padding
-            }
-            const float two_pi = 6.283185307179586f;
-            const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
-            for (int c = grp; c < L; c += kWaves) {
-                float a = __fmul_rn(s0, Bf[c]);
-                a = __fmaf_rn(s1, Bf[L + c], a);
-                a = __fmaf_rn(s2, Bf[2 * L + c], a);
-                float sn, cs;
-                sincosf(a, &sn, &cs);
-                put(3 + c, sn);
-                put(3 + L + c, cs);
-            }
-            for (int l = grp; l < L; l += kWaves) {
-                float acc[8];
-                for (int f = 0; f < F; ++f) acc[f] = 0.0f;
-                const float *tl = table + (size_t)lv.row_off[l] * F;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    uint32_t ux, uy, uz;
-                    float wx, wy, wz;
-                    corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
-                    corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
-                    corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
-                    const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
-                    if (w != 0.0f) {  // zero-weight corners add exactly 0 (reference mode: only corner 0 survives)
-                        const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l]);
-                        for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(tl[(size_t)id * F + f], w));
-                    }
-                }
-                for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
-            }
+            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, grp, kWaves, net.emb_groups * 4,
+                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
         HM_PROBE(1);
@@ -498,7 +464,6 @@ __global__ __launch_bounds__(kThreads32, 2) void sdf_fwd_p32_kernel(HmLevels lv,
     const int lane = tid & 63;
     const int j = lane & 31;  // point / feature row within a 32-feature tile
     const int h = lane >> 5;
-    const int L = lv.L, F = lv.F;
     const int E = lv.E;
     const int64_t n_tiles = (n + kPts32 - 1) / kPts32;
 
@@ -516,41 +481,8 @@ __global__ __launch_bounds__(kThreads32, 2) void sdf_fwd_p32_kernel(HmLevels lv,
             const int p = tid & (kPts32 - 1);
             const int grp = tid >> 5;  // 0..7
             const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            auto put = [&](int e, float v) { EMB[(e >> 2) * kGroupFloats32 + p * 4 + (e & 3)] = v; };
-            if (grp == 0) {
-                put(0, x0); put(1, x1); put(2, x2);
-                for (int e = E; e < net.emb_groups * 4; ++e) put(e, 0.0f);
-            }
-            const float two_pi = 6.283185307179586f;
-            const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
-            for (int c = grp; c < L; c += 8) {
-                float a = __fmul_rn(s0, Bf[c]);
-                a = __fmaf_rn(s1, Bf[L + c], a);
-                a = __fmaf_rn(s2, Bf[2 * L + c], a);
-                float sn, cs;
-                sincosf(a, &sn, &cs);
-                put(3 + c, sn);
-                put(3 + L + c, cs);
-            }
-            for (int l = grp; l < L; l += 8) {
-                float acc[8];
-                for (int f = 0; f < F; ++f) acc[f] = 0.0f;
-                const float *tl = table + (size_t)lv.row_off[l] * F;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    uint32_t ux, uy, uz;
-                    float wx, wy, wz;
-                    corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
-                    corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
-                    corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
-                    const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
-                    if (w != 0.0f) {
-                        const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l]);
-                        for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(tl[(size_t)id * F + f], w));
-                    }
-                }
-                for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
-            }
+            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, grp, 8, net.emb_groups * 4,
+                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats32 + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
 
@@ -726,7 +658,7 @@ __device__ __forceinline__ void sdf_m16_body(const HmLevels &lv, const SdfNet &n
     const int lane16 = lane * 16;
     const int j = lane & 15;  // point
     const int q = lane >> 4;  // k quarter / feature quarter
-    const int L = lv.L, F = lv.F, E = lv.E;
+    const int E = lv.E;
     const int64_t n_tiles = (n + kPts16 - 1) / kPts16;
 
     for (int64_t tile = tile_first; tile < n_tiles; tile += tile_step) {
@@ -744,41 +676,8 @@ __device__ __forceinline__ void sdf_m16_body(const HmLevels &lv, const SdfNet &n
             const int p = tid & (kPts16 - 1);
             const int c0 = tid >> 4;  // 0..31
             const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            auto put = [&](int e, float v) { EMB[(e >> 2) * kGroupFloats16 + p * 4 + (e & 3)] = v; };
-            if (c0 == 0) {
-                put(0, x0); put(1, x1); put(2, x2);
-                for (int e = E; e < emb_groups16 * 4; ++e) put(e, 0.0f);
-            }
-            const float two_pi = 6.283185307179586f;
-            const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
-            for (int c = c0; c < L; c += 32) {
-                float a = __fmul_rn(s0, Bf[c]);
-                a = __fmaf_rn(s1, Bf[L + c], a);
-                a = __fmaf_rn(s2, Bf[2 * L + c], a);
-                float sn, cs;
-                sincosf(a, &sn, &cs);
-                put(3 + c, sn);
-                put(3 + L + c, cs);
-            }
-            for (int l = c0; l < L; l += 32) {
-                float acc[8];
-                for (int f = 0; f < F; ++f) acc[f] = 0.0f;
-                const float *tl = table + (size_t)lv.row_off[l] * F;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    uint32_t ux, uy, uz;
-                    float wx, wy, wz;
-                    corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
-                    corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
-                    corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
-                    const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
-                    if (w != 0.0f) {
-                        const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l]);
-                        for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(tl[(size_t)id * F + f], w));
-                    }
-                }
-                for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
-            }
+            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, c0, 32, emb_groups16 * 4,
+                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats16 + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
 
@@ -988,7 +887,7 @@ __device__ __forceinline__ void sdf_m8_body(const HmLevels &lv, const SdfNet &ne
     const int q = lane >> 4;         // k quarter of the A operand
     const int jj = (lane & 15) >> 2; // feature quad within the 16-feature tile
     const int p4 = lane & 3;         // point within a group of four
-    const int L = lv.L, F = lv.F, E = lv.E;
+    const int E = lv.E;
     constexpr bool TWO = PTS == 8;
     constexpr int RD8 = kRing8;   // (one block deeper for the 4-point variant measured the same: 94 vs 93 us)
     const int64_t n_tiles = (n + PTS - 1) / PTS;
@@ -1009,41 +908,8 @@ __device__ __forceinline__ void sdf_m8_body(const HmLevels &lv, const SdfNet &ne
             const int p = tid & (kPts8 - 1);
             const int c0 = tid >> 3;  // 0..63
             const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            auto put = [&](int e, float v) { EMB[(e >> 2) * kGroupFloats8 + p * 4 + (e & 3)] = v; };
-            if (c0 == 0) {
-                put(0, x0); put(1, x1); put(2, x2);
-                for (int e = E; e < emb_groups16 * 4; ++e) put(e, 0.0f);
-            }
-            const float two_pi = 6.283185307179586f;
-            const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
-            for (int c = c0; c < L; c += 64) {
-                float a = __fmul_rn(s0, Bf[c]);
-                a = __fmaf_rn(s1, Bf[L + c], a);
-                a = __fmaf_rn(s2, Bf[2 * L + c], a);
-                float sn, cs;
-                sincosf(a, &sn, &cs);
-                put(3 + c, sn);
-                put(3 + L + c, cs);
-            }
-            for (int l = c0; l < L; l += 64) {
-                float acc[8];
-                for (int f = 0; f < F; ++f) acc[f] = 0.0f;
-                const float *tl = table + (size_t)lv.row_off[l] * F;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    uint32_t ux, uy, uz;
-                    float wx, wy, wz;
-                    corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
-                    corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
-                    corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
-                    const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
-                    if (w != 0.0f) {
-                        const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l]);
-                        for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(tl[(size_t)id * F + f], w));
-                    }
-                }
-                for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
-            }
+            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, c0, 64, emb_groups16 * 4,
+                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats8 + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
         HM_PROBE_S(1);

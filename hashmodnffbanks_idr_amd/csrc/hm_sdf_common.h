@@ -1,5 +1,5 @@
 // hm_sdf_common.h - device helpers shared by the fused SDF kernels (hm_sdf.hip: exact fp32; hm_sdf_bf16.hip: bf16
-// coarse-search variant).  Included inside each file's anonymous namespace.
+// coarse-search variant; hm_sdf_split.hip: split-operand variant).  Included inside each file's anonymous namespace.
 #pragma once
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -77,17 +77,55 @@ __device__ __forceinline__ float sdf_clamp(float s, float beta) {
     return tanhf(s / (2.0f + rho));
 }
 
-template <int FRAC>
-__device__ __forceinline__ void corner(float x, int32_t res, int bit, uint32_t &u, float &w) {
-    const float xs = __fmul_rn(x, (float)res);
-    if (FRAC == HM_FRAC_REFERENCE) {
-        u = (uint32_t)((int32_t)xs) + (uint32_t)bit;
-        w = bit ? 0.0f : 1.0f;
-    } else {
-        const float fl = floorf(xs);
-        const float xf = __fsub_rn(xs, fl);
-        u = (uint32_t)((int32_t)fl) + (uint32_t)bit;
-        w = bit ? xf : __fsub_rn(1.0f, xf);
+// Encode stage of the fused SDF kernels: the embedding row [x | sin a_c | cos a_c | level features | 0 ... e_pad) of
+// the point (x0, x1, x2), written through put(e, v) so that each kernel keeps its own LDS layout.  The row is cut into
+// 2L + 1 slots: 0 = pass-through + zero padding, 1..L = Fourier channel slot - 1, L+1..2L = hash level slot - L - 1.
+template <class Put>
+__device__ __forceinline__ void embed_passthrough(int E, int e_pad, float x0, float x1, float x2, Put &put) {
+    put(0, x0); put(1, x1); put(2, x2);
+    for (int e = E; e < e_pad; ++e) put(e, 0.0f);
+}
+template <class Put>
+__device__ __forceinline__ void embed_fourier(const float *__restrict__ Bf, int L, int c, float s0, float s1, float s2,
+                                              Put &put) {
+    float sn, cs;
+    sincosf(hm_fourier_arg(Bf, L, c, s0, s1, s2), &sn, &cs);
+    put(3 + c, sn);
+    put(3 + L + c, cs);
+}
+// the thread owns slots first, first + step, ... of its point (Fourier channels and levels walked separately)
+template <int FRAC, class Put>
+__device__ __forceinline__ void embed_point(const HmLevels &lv, const float *__restrict__ table,
+                                            const float *__restrict__ Bf, float x0, float x1, float x2, int first,
+                                            int step, int e_pad, Put &&put) {
+    const int L = lv.L;
+    if (first == 0) embed_passthrough(lv.E, e_pad, x0, x1, x2, put);
+    const float two_pi = 6.283185307179586f;
+    const float s0 = __fmul_rn(two_pi, x0), s1 = __fmul_rn(two_pi, x1), s2 = __fmul_rn(two_pi, x2);
+    for (int c = first; c < L; c += step) embed_fourier(Bf, L, c, s0, s1, s2, put);
+    const int F = lv.F;
+    for (int l = first; l < L; l += step) {
+        float acc[8];
+        hm_level_features<FRAC>(lv, table, l, x0, x1, x2, acc);
+        for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
     }
 }
 
+// one slot of the point
+template <int FRAC, class Put>
+__device__ __forceinline__ void embed_slot(const HmLevels &lv, const float *__restrict__ table,
+                                           const float *__restrict__ Bf, float x0, float x1, float x2, int slot,
+                                           int e_pad, Put &&put) {
+    const int L = lv.L;
+    if (slot == 0) {
+        embed_passthrough(lv.E, e_pad, x0, x1, x2, put);
+    } else if (slot <= L) {
+        const float two_pi = 6.283185307179586f;
+        embed_fourier(Bf, L, slot - 1, __fmul_rn(two_pi, x0), __fmul_rn(two_pi, x1), __fmul_rn(two_pi, x2), put);
+    } else {
+        const int l = slot - L - 1, F = lv.F;
+        float acc[8];
+        hm_level_features<FRAC>(lv, table, l, x0, x1, x2, acc);
+        for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
+    }
+}

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
     const int lane = tid & 63;
     const int j = lane & 31;
     const int h = lane >> 5;
-    const int L = lv.L, F = lv.F, E = lv.E;
+    const int L = lv.L, E = lv.E;
     const int64_t n_tiles = (n + kPS - 1) / kPS;
     const int e_pad = e_oct * 8;
 
@@ -133,43 +133,11 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
                 put(p, e, (p < cnt && e < E) ? x[(base + p) * net.emb_stride + e] : 0.0f);
             }
         } else {
-            const int n_slot = 2 * L + 1;      // slot 0: pass-through + padding, 1..L: Fourier channel, L+1..2L: level
+            const int n_slot = 2 * L + 1;
             for (int idx = tid; idx < kPS * n_slot; idx += kTS) {
                 const int p = idx % kPS, slot = idx / kPS;
-                const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-                if (slot == 0) {
-                    put(p, 0, x0); put(p, 1, x1); put(p, 2, x2);
-                    for (int e = E; e < e_pad; ++e) put(p, e, 0.0f);
-                } else if (slot <= L) {
-                    const int c = slot - 1;
-                    const float two_pi = 6.283185307179586f;
-                    float a = __fmul_rn(__fmul_rn(two_pi, x0), Bf[c]);
-                    a = __fmaf_rn(__fmul_rn(two_pi, x1), Bf[L + c], a);
-                    a = __fmaf_rn(__fmul_rn(two_pi, x2), Bf[2 * L + c], a);
-                    float sn, cs;
-                    sincosf(a, &sn, &cs);
-                    put(p, 3 + c, sn);
-                    put(p, 3 + L + c, cs);
-                } else {
-                    const int l = slot - L - 1;
-                    float acc[8];
-                    for (int f = 0; f < F; ++f) acc[f] = 0.0f;
-                    const float *tl = table + (size_t)lv.row_off[l] * F;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        uint32_t ux, uy, uz;
-                        float wx, wy, wz;
-                        corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
-                        corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
-                        corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
-                        const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
-                        if (w != 0.0f) {
-                            const uint32_t id = hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l]);
-                            for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(tl[(size_t)id * F + f], w));
-                        }
-                    }
-                    for (int f = 0; f < F; ++f) put(p, 3 + 2 * L + l * F + f, acc[f]);
-                }
+                embed_slot<FRAC>(lv, table, Bf, SX[p * 3], SX[p * 3 + 1], SX[p * 3 + 2], slot, e_pad,
+                                 [&](int e, float v) { put(p, e, v); });
             }
         }
         __syncthreads();
