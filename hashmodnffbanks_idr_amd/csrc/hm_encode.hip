@@ -16,8 +16,6 @@
 // full-line coalesced stores.
 #include "hm_common.h"
 
-#include <stdlib.h>
-
 #include <math.h>
 
 namespace {
@@ -46,28 +44,21 @@ __device__ __forceinline__ void dpp_sum8_pair(float &a0, float &a1) {
         : "+v"(a0), "+v"(a1));
 }
 
-// Output-tile store with a cache policy (flags bits 0-1): 0 plain, 1 write-through `sc1` (the line is DROPPED from the
-// XCD's L2 once written: 1.1 GB of output rows per launch no longer push table lines out of the 4 MB L2s), 2 `nt`,
-// 3 `sc0 sc1`.  dst / n_vec describe ONE tile (wave-uniform), i is the lane's float4 index inside it.
+// Output-tile store, non-temporal (`nt`: C2 4.61 -> 4.77 TB/s, C4 3.61 -> 3.73 against plain stores; `sc1` measured
+// equal or slower, profiles/README.md).  dst / tile_bytes describe ONE tile (wave-uniform), i is the
+// lane's float4 index inside it.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_tile_vec(float *dst, unsigned tile_bytes, int i, const float4 &v, int mode) {
-    if (mode == 0) {
-        reinterpret_cast<float4 *>(dst)[i] = v;
-        return;
-    }
+__device__ __forceinline__ void store_tile_vec(float *dst, unsigned tile_bytes, int i, const float4 &v) {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(dst, 0, tile_bytes, 0x00020000);
     const u32x4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-    if (mode == 1) __builtin_amdgcn_raw_buffer_store_b128(u, rsrc, i * 16, 0, 16);        // sc1
-    else if (mode == 2) __builtin_amdgcn_raw_buffer_store_b128(u, rsrc, i * 16, 0, 2);    // nt
-    else __builtin_amdgcn_raw_buffer_store_b128(u, rsrc, i * 16, 0, 17);                  // sc0 sc1
+    __builtin_amdgcn_raw_buffer_store_b128(u, rsrc, i * 16, 0, 2);    // nt
 }
 
 template <int FRAC>
 __global__ __launch_bounds__(kThreads) void encode_fwd_f2_kernel(HmLevels lv, const float *__restrict__ x, int64_t n,
                                                                  const float2 *__restrict__ table,
                                                                  const float *__restrict__ Bf,
-                                                                 float *__restrict__ out, int64_t out_stride,
-                                                                 int flags) {
+                                                                 float *__restrict__ out, int64_t out_stride) {
     extern __shared__ __align__(16) float smem[];
     const int L = lv.L;
     const bool fourier = (Bf != nullptr);
@@ -152,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void encode_fwd_f2_kernel(HmLevels lv, co
         const int total = cnt * E;
         const int nvec = total >> 2;
         const float4 *s4 = reinterpret_cast<const float4 *>(s_out);
-        for (int i = tid; i < nvec; i += kThreads) store_tile_vec(dst, (unsigned)total * 4u, i, s4[i], flags & 3);
+        for (int i = tid; i < nvec; i += kThreads) store_tile_vec(dst, (unsigned)total * 4u, i, s4[i]);
         for (int i = (nvec << 2) + tid; i < total; i += kThreads) dst[i] = s_out[i];
     } else {
         for (int i = tid; i < cnt * E; i += kThreads) {
@@ -175,12 +166,12 @@ __global__ __launch_bounds__(kThreads) void encode_fwd_f2_kernel(HmLevels lv, co
 constexpr int kTileS = 256, kThreadsS = 512;   // two workgroups per CU: one gathers while the other stores
                                                // (one of 512 points: 4.53 TB/s, two of 256: 4.65, four of 128: 4.45)   // two workgroups per CU: one gathers while the other stores
 
-template <int FRAC, int KL>   // KL = levels gathered per sweep step (2: one (coarse, fine) pair; 4: more loads in flight)
+template <int FRAC>
 __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_sweep_kernel(HmLevels lv, const float *__restrict__ x,
                                                                         int64_t n, const float2 *__restrict__ table,
                                                                         const float *__restrict__ Bf,
-                                                                        float *__restrict__ out, int64_t out_stride,
-                                                                        int flags) {
+                                                                        float *__restrict__ out, int64_t out_stride) {
+    constexpr int KL = 2;   // levels gathered per sweep step: one (coarse, fine) pair (4: measured equal or slower)
     extern __shared__ __align__(16) float smem[];
     const int L = lv.L;
     const bool fourier = (Bf != nullptr);
@@ -199,11 +190,7 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_sweep_kernel(HmLevels
         const int64_t base = tile * kTileS;
         const int cnt = (int)min((int64_t)kTileS, n - base);
         __syncthreads();   // the previous tile's rows have left s_out
-        if (flags & 4)
-            for (int i = tid; i < kTileS * 3; i += kThreadsS)
-                s_x[i] = (i < cnt * 3) ? __builtin_nontemporal_load(x + base * 3 + i) : 0.0f;
-        else
-            for (int i = tid; i < kTileS * 3; i += kThreadsS) s_x[i] = (i < cnt * 3) ? x[base * 3 + i] : 0.0f;
+        for (int i = tid; i < kTileS * 3; i += kThreadsS) s_x[i] = (i < cnt * 3) ? x[base * 3 + i] : 0.0f;
         __syncthreads();
         if (fourier) {
             const int p = tid & (kTileS - 1);
@@ -270,7 +257,7 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_sweep_kernel(HmLevels
             const int total = cnt * E;
             const int nvec = total >> 2;
             const float4 *s4 = reinterpret_cast<const float4 *>(s_out);
-            for (int i = tid; i < nvec; i += kThreadsS) store_tile_vec(dst, (unsigned)total * 4u, i, s4[i], flags & 3);
+            for (int i = tid; i < nvec; i += kThreadsS) store_tile_vec(dst, (unsigned)total * 4u, i, s4[i]);
             for (int i = (nvec << 2) + tid; i < total; i += kThreadsS) dst[i] = s_out[i];
         } else {
             for (int i = tid; i < cnt * E; i += kThreadsS) {
@@ -294,6 +281,7 @@ __global__ __launch_bounds__(kThreadsS) void encode_fwd_f2_sweep_kernel(HmLevels
 // traffic; see DESIGN.md / profiles for the measured numbers.
 constexpr int kSlabs = 512;
 constexpr int kSortChunk = 16384;   // points per workgroup of the bucketing passes
+constexpr int kZGrid = 512;         // persistent workgroups of the gather kernel (two per CU)
 
 __device__ __forceinline__ int z_slab(float z) {
     const float t = (z + 1.0f) * (0.5f * kSlabs);          // [-1, 1] -> [0, kSlabs); everything outside clamps
@@ -1069,19 +1057,12 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
     HM_CHECK_ARG(out_stride >= width, "hm_encode_fwd: out_stride < row width");
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && table && out, "hm_encode_fwd: NULL pointer");
-    static const int sweep_cfg = [] { const char *e = getenv("HM_ENCODE_SWEEP"); return e ? atoi(e) : 1; }();
-    // cache policy of the output-row stores / x loads (see store_tile_vec); HM_ENCODE_FLAGS overrides for experiments
-    // default: nt stores of the output rows (C2 4.61 -> 4.77 TB/s, C4 3.61 -> 3.73; sc1 / nt loads / 4 levels per
-    // step measured equal or slower, profiles/README.md); tables beyond 64 MiB run ONE workgroup per CU (C4: 3.89)
-    static const int enc_flags = [] { const char *e = getenv("HM_ENCODE_FLAGS"); return e ? atoi(e) : 2; }();
-    static const int sweep_grid_env = [] { const char *e = getenv("HM_ENCODE_GRID"); return e ? atoi(e) : 0; }();
-    const int sweep_grid = sweep_grid_env > 0 ? sweep_grid_env
-                                              : (desc->total_rows * (uint64_t)lv.F * 4u > (64u << 20) ? 256 : 512);
+    // sweep kernel: tables beyond 64 MiB run ONE workgroup per CU (C4: 3.89 TB/s)
+    const int sweep_grid = desc->total_rows * (uint64_t)lv.F * 4u > (64u << 20) ? 256 : 512;
     const size_t lds_sweep = sizeof(float) * (size_t)(kTileS * width + kTileS * 3);
     const bool table_exceeds_l2 = desc->total_rows * (uint64_t)lv.F * 4u > (8u << 20);   // (C1's 0.9 MiB: tile kernel)
-    static const int zorder_cfg = [] { const char *e = getenv("HM_ENCODE_ZORDER"); return e ? atoi(e) : 1; }();
     const size_t lds_z = sizeof(float) * (size_t)(kTileS * ((width + 3) & ~3) + kTileS * 3 + kTileS);
-    if (lv.F == 2 && zorder_cfg != 0 && workspace && table_exceeds_l2 && n >= (int64_t)131072 && n < ((int64_t)1 << 32) &&
+    if (lv.F == 2 && workspace && table_exceeds_l2 && n >= (int64_t)131072 && n < ((int64_t)1 << 32) &&
         lds_z <= 160 * 1024 && workspace_bytes >= (int64_t)sizeof(uint32_t) * (n + 2 * kSlabs)) {
         static thread_local bool attr_z = false;
         if (!attr_z) {
@@ -1107,38 +1088,35 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
         hipLaunchKernelGGL(zsort_scatter_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, order,
                            static_cast<const uint16_t *>(slab));
         const int64_t tiles = (n + kTileS - 1) / kTileS;
-        static const int z_grid = [] { const char *e = getenv("HM_ENCODE_ZGRID"); return e ? atoi(e) : 512; }();
-        const unsigned grid = (unsigned)(tiles < z_grid ? ((tiles + 7) / 8) * 8 : z_grid);
+        const unsigned grid = (unsigned)(tiles < kZGrid ? ((tiles + 7) / 8) * 8 : kZGrid);
         if (frac_mode == HM_FRAC_REFERENCE)
             hipLaunchKernelGGL(encode_fwd_f2_zorder_kernel<HM_FRAC_REFERENCE>, dim3(grid), dim3(kThreadsS), lds_z, st,
                                lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out, out_stride, order);
         else
             hipLaunchKernelGGL(encode_fwd_f2_zorder_kernel<HM_FRAC_TRILINEAR>, dim3(grid), dim3(kThreadsS), lds_z, st,
                                lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out, out_stride, order);
-    } else if (lv.F == 2 && sweep_cfg != 0 && table_exceeds_l2 && n >= (int64_t)131072 && lds_sweep <= 160 * 1024) {
+    } else if (lv.F == 2 && table_exceeds_l2 && n >= (int64_t)131072 && lds_sweep <= 160 * 1024) {
         // big launches over big tables: level-synchronous persistent kernel (two workgroups per CU)
         static thread_local bool attr_done = false;
         if (!attr_done) {
-            hipError_t e = hipSuccess;
-            const void *fns[4] = {reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_REFERENCE, 2>),
-                                  reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_TRILINEAR, 2>),
-                                  reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_REFERENCE, 4>),
-                                  reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_TRILINEAR, 4>)};
-            for (int i = 0; i < 4 && e == hipSuccess; ++i)
-                e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_REFERENCE>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_TRILINEAR>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
             attr_done = true;
         }
         const int64_t tiles = (n + kTileS - 1) / kTileS;
         const unsigned grid = (unsigned)(tiles < sweep_grid ? tiles : sweep_grid);
-        const bool kl4 = (enc_flags & 8) != 0;
-#define HM_SWEEP_LAUNCH(FR, KLV)                                                                                    \
-    hipLaunchKernelGGL((encode_fwd_f2_sweep_kernel<FR, KLV>), dim3(grid), dim3(kThreadsS), lds_sweep,               \
-                       as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,        \
-                       out_stride, enc_flags)
-        if (frac_mode == HM_FRAC_REFERENCE) { if (kl4) HM_SWEEP_LAUNCH(HM_FRAC_REFERENCE, 4); else HM_SWEEP_LAUNCH(HM_FRAC_REFERENCE, 2); }
-        else { if (kl4) HM_SWEEP_LAUNCH(HM_FRAC_TRILINEAR, 4); else HM_SWEEP_LAUNCH(HM_FRAC_TRILINEAR, 2); }
-#undef HM_SWEEP_LAUNCH
+        if (frac_mode == HM_FRAC_REFERENCE)
+            hipLaunchKernelGGL(encode_fwd_f2_sweep_kernel<HM_FRAC_REFERENCE>, dim3(grid), dim3(kThreadsS), lds_sweep,
+                               as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
+                               out_stride);
+        else
+            hipLaunchKernelGGL(encode_fwd_f2_sweep_kernel<HM_FRAC_TRILINEAR>, dim3(grid), dim3(kThreadsS), lds_sweep,
+                               as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
+                               out_stride);
     } else if (lv.F == 2) {
         const int64_t tiles = (n + kTile - 1) / kTile;
         HM_CHECK_ARG(tiles <= 0x7fffffffLL, "hm_encode_fwd: n too large for one launch");
@@ -1146,11 +1124,11 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
         if (frac_mode == HM_FRAC_REFERENCE)
             hipLaunchKernelGGL(encode_fwd_f2_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)tiles), dim3(kThreads), lds,
                                as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
-                               out_stride, enc_flags);
+                               out_stride);
         else
             hipLaunchKernelGGL(encode_fwd_f2_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)tiles), dim3(kThreads), lds,
                                as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
-                               out_stride, enc_flags);
+                               out_stride);
     } else {
         const int64_t threads = n * (lv.L + 1);
         const int64_t grid = (threads + kThreads - 1) / kThreads;

@@ -10,13 +10,9 @@
 // v_mfma_f32_32x32x2_f32 (exact fp32 fma chain); 4 waves per workgroup as 2 x 2, each owning
 // TM x TN tiles of 32 x 32; both operands are staged through LDS in the k-grouped image
 // [k/4][row][4] (rows XOR-swizzled by the k-group) so that both the 16-B staging stores and the
-// MFMA operand fetches (ds_read_b128) are bank-conflict free; K is staged 64 deep for the 64x64
-// tile so that one stage of MFMAs (~0.85 us) covers the L2 latency of the next stage's loads.
+// MFMA operand fetches (ds_read_b128) are bank-conflict free; K is staged 128 deep for the 64x64
+// tile so that one stage of MFMAs covers the L2 latency of the next stage's loads.
 #include "hm_common.h"
-
-#include <stdio.h>
-
-#include <stdlib.h>
 
 namespace {
 
@@ -171,8 +167,7 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 
 // EP: compiled with the fused epilogues (kept out of the plain instantiation: its extra registers would drop the
 // 64x64 configuration from two resident workgroups per CU to one).  The 8-wave configuration is held to 128 VGPRs
 // (4 waves per SIMD = two workgroups per CU).
-// WM: wave rows of the tile (2 -> 64*TM rows; 1 -> 32*TM rows for row counts that would leave the 64-row grid
-// with fewer than two workgroups per CU); the wave columns are always 2.
+// WM: wave rows of the tile (2 -> 64*TM rows); the wave columns are always 2.
 template <int TM, int TN, int BK, int KS, bool VA, bool VB, bool EP, int WM = 2>
 __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f32_kernel(GemmArgs g) {
     constexpr int BM = 32 * WM * TM, BN = 64 * TN, NT = 128 * WM * KS, WG = 2 * WM;  // WG = waves per k part
@@ -270,29 +265,16 @@ __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f3
 // a register ring, two LDS buffers, and the MFMA operands of a stage held in registers (two sets) so that the LDS
 // round trip of stage s+1 - store, the ONE barrier of the stage, fragment reads - is issued in the middle of stage
 // s's MFMAs.  (A wave that has passed the barrier of stage s has read the fragments of stage s-1's buffer long
-// before, so that buffer is free to refill.)  The loop body has NO conditionals - the host launches this kernel
-// only when the K range is a whole number of kPipeD-stage groups, partial edge tiles clamp their row pointers once,
+// before, so that buffer is free to refill.)  The loop body has NO conditionals - the K range is a whole number of
+// kPipeD-stage groups (a K tail is rounded up, see gemm_pipe2_body), partial edge tiles clamp their offsets once,
 // before the loop - because with the
 // generic kernel's guards in it hipcc keeps the accumulators in VGPRs across the back edge and copies all 32 of
 // them to AGPRs and back every stage.
-// AKC / BKC: operand is k-contiguous and 16-B aligned (one dwordx4 per k-group), else row-contiguous (four dwords).
+// AKC / BKC: operand is k-contiguous (one dwordx4 per k-group), else row-contiguous (four dwords).
 constexpr int kPipeBK = 32, kPipeD = 4;
 
-template <bool KC, int PER>
-__device__ __forceinline__ void pipe_fetch(const float *const (&p)[PER], int64_t step, int64_t ld, int sc,
-                                           float4 (&x)[PER]) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const float *q = p[i] + sc * step;
-        if (KC) {   // (component-wise: a whole-struct float4 copy into the array keeps it in scratch memory)
-            const float4 t = *reinterpret_cast<const float4 *>(q);
-            x[i] = make_float4(t.x, t.y, t.z, t.w);
-        } else {
-            x[i] = make_float4(q[0], q[ld], q[2 * ld], q[3 * ld]);
-        }
-    }
-}
-// buffer-load form of pipe_fetch: voff = the thread's byte offset (loop invariant), soff = the stage's byte offset (scalar)
+// one stage's operand k-groups through a buffer descriptor: voff = the thread's byte offset (loop invariant), soff = the
+// stage's byte offset (scalar)
 template <bool KC, int PER>
 __device__ __forceinline__ void pipe_fetch_buf(const __amdgpu_buffer_rsrc_t &rs, const int (&voff)[PER], int soff, int ld4,
                                                float4 (&x)[PER]) {
@@ -310,7 +292,7 @@ __device__ __forceinline__ void pipe_fetch_buf(const __amdgpu_buffer_rsrc_t &rs,
     }
 }
 
-template <int OCT, int AROWS = 64>
+template <int OCT, int AROWS>
 __device__ __forceinline__ void pipe_read_ops(const float *as, const float *bs, int arow, int brow, int h,
                                               float4 (&xa)[OCT], float4 (&xb)[OCT]) {
 #pragma unroll
@@ -328,83 +310,7 @@ __device__ __forceinline__ void pipe_mfma_oct(const float4 &a, const float4 &b, 
 }
 
 
-template <bool AKC, bool BKC, bool EP>
-__global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(GemmArgs g) {
-    constexpr int BM = 64, BN = 64, BK = kPipeBK, NT = 256, PER = BM * BK / 4 / NT, KG = BK / 4, OCT = BK / 8;
-    __shared__ __align__(16) float As[2][BK * BM];
-    __shared__ __align__(16) float Bs[2][BK * BN];
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int j = lane & 31, h = lane >> 5;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int kbeg = blockIdx.z * g.k_chunk;
-    const int stages = g.k_chunk / BK;   // multiple of kPipeD (host)
-
-    const float *pa[PER], *pb[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int e = tid + NT * i;
-        // rows / columns past the edge of a partial tile are clamped HERE, once (they compute values nobody stores)
-        const int am = min(m0 + (AKC ? e / KG : e % BM), g.M - 1), bn = min(n0 + (BKC ? e / KG : e % BN), g.N - 1);
-        pa[i] = AKC ? g.A + (int64_t)am * g.lda + kbeg + (e % KG) * 4
-                    : g.A + (int64_t)(kbeg + (e / BM) * 4) * g.lda + am;
-        pb[i] = BKC ? g.B + (int64_t)bn * g.ldb + kbeg + (e % KG) * 4
-                    : g.B + (int64_t)(kbeg + (e / BN) * 4) * g.ldb + bn;
-    }
-    const int64_t sa = AKC ? BK : (int64_t)BK * g.lda, sb = BKC ? BK : (int64_t)BK * g.ldb;
-    const int64_t lda = g.lda, ldb = g.ldb;
-    f32x16 acc, acc2;   // even / odd k-octets: two independent MFMA chains for the one wave on each SIMD
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.0f;
-    // the four ring slots and the two operand sets are separate named arrays (an array indexed by (u+3)%4 inside
-    // the unrolled loop was demoted to scratch memory by hipcc)
-    static_assert(kPipeD == 4, "the stage macro below is written out for a 4-deep ring (8-deep measured no faster)");
-    float4 ra0[PER], ra1[PER], ra2[PER], ra3[PER], rb0[PER], rb1[PER], rb2[PER], rb3[PER];
-    float4 opa0[OCT], opa1[OCT], opb0[OCT], opb1[OCT];
-#define HM_PIPE_FETCH(S_, RA_, RB_)                                                                 \
-    do {                                                                                            \
-        const int sc_ = min((S_), stages - 1); /* past the end: re-read the last stage, never multiplied */ \
-        pipe_fetch<AKC, PER>(pa, sa, lda, sc_, RA_);                                                \
-        pipe_fetch<BKC, PER>(pb, sb, ldb, sc_, RB_);                                                \
-    } while (0)
-    HM_PIPE_FETCH(0, ra0, rb0);
-    HM_PIPE_FETCH(1, ra1, rb1);
-    HM_PIPE_FETCH(2, ra2, rb2);
-    store_tile<BM, BK, NT>(As[0], AKC, tid, ra0);
-    store_tile<BN, BK, NT>(Bs[0], BKC, tid, rb0);
-    __syncthreads();
-    pipe_read_ops<OCT>(As[0], Bs[0], wm * 32 + j, wn * 32 + j, h, opa0, opb0);
-// one stage: multiply from operand set C, meanwhile fetch stage s+D-1 into ring slot F and move ring slot N (stage
-// s+1) through LDS buffer NB into operand set X
-#define HM_PIPE_STAGE(S_, F_, N_, C_, X_, NB_)                                                      \
-    do {                                                                                            \
-        HM_PIPE_FETCH((S_) + kPipeD - 1, ra##F_, rb##F_);                                                    \
-        pipe_mfma_oct(opa##C_[0], opb##C_[0], acc);                                                 \
-        pipe_mfma_oct(opa##C_[1], opb##C_[1], acc2);                                                \
-        store_tile<BM, BK, NT>(As[NB_], AKC, tid, ra##N_);                                          \
-        store_tile<BN, BK, NT>(Bs[NB_], BKC, tid, rb##N_);                                          \
-        __syncthreads();                                                                            \
-        pipe_read_ops<OCT>(As[NB_], Bs[NB_], wm * 32 + j, wn * 32 + j, h, opa##X_, opb##X_);        \
-        pipe_mfma_oct(opa##C_[2], opb##C_[2], acc);                                                 \
-        pipe_mfma_oct(opa##C_[3], opb##C_[3], acc2);                                                \
-    } while (0)
-    static_assert(OCT == 4, "HM_PIPE_STAGE is written for 4 octets per stage");
-    for (int s0 = 0; s0 < stages; s0 += kPipeD) {
-        HM_PIPE_STAGE(s0 + 0, 3, 1, 0, 1, 1);
-        HM_PIPE_STAGE(s0 + 1, 0, 2, 1, 0, 0);
-        HM_PIPE_STAGE(s0 + 2, 1, 3, 0, 1, 1);
-        HM_PIPE_STAGE(s0 + 3, 2, 0, 1, 0, 0);
-    }
-#undef HM_PIPE_STAGE
-#undef HM_PIPE_FETCH
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
-    const int n = n0 + wn * 32 + j;
-    if (n < g.N) gemm_store_tile<EP>(g, acc, n, m0 + wm * 32 + 4 * h, (g.bias != nullptr) && (blockIdx.z == 0));
-}
-
-// Same pipeline with EIGHT waves: two wave groups split the octets of every stage (two waves per SIMD hide each
+// The pipeline runs on EIGHT waves: two wave groups split the octets of every stage (two waves per SIMD hide each
 // other's barrier / LDS turnarounds), partial tiles are summed through LDS at the end.
 // WM = 3: a 96 x 64 tile on TWELVE waves (two groups of 3 x 2), for row counts whose 64-row grid is between one and two
 // rounds of the chip: M = 3072, N = 512 are 384 tiles of 64 x 64 - a CU with two of them takes twice as long as the one
@@ -567,6 +473,8 @@ __global__ __launch_bounds__(256) void zero_window_kernel(float *C, int64_t ldc,
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+constexpr int64_t kSplitTarget = 512;   // split-K: workgroups to aim for when the tile grid alone leaves the chip idle
+
 }  // namespace
 
 static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
@@ -607,50 +515,40 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     g.vecB = (b_kc && K % 4 == 0 && ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15u) == 0) ? 1 : 0;
     // tile choice: big tiles only when they still fill the chip
     const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
-    static const int small_cfg = [] { const char *e = getenv("HM_GEMM_CFG"); return e ? atoi(e) : 0; }();
     const bool big = t128 >= 256;
-    // (128x64 / 64x128 tiles and a forced 128x128 tile were measured too: 30-45 % slower on M = 1750...4822)
-    // 32-row tiles (HM_GEMM_HALF=1) for row counts whose 64-row grid gives a CU fewer than two workgroups
-    // (M = 2048...3072, N = 512).  Measured: the training step is 2 % SLOWER with them (10.50 vs 10.28 ms) -
-    // twice the B-panel traffic outweighs the extra overlap - so they stay off.
+    // (128x64 / 64x128 tiles and a forced 128x128 tile were measured too: 30-45 % slower on M = 1750...4822; 32-row tiles
+    // for row counts whose 64-row grid gives a CU fewer than two workgroups made the training step 2 % SLOWER - twice the
+    // B-panel traffic outweighs the extra overlap)
     const int64_t t64 = ((M + 63) / 64) * ((N + 63) / 64);
-    static const int half_cfg = [] { const char *e = getenv("HM_GEMM_HALF"); return e ? atoi(e) : 0; }();
-    const bool half_rows = !big && small_cfg == 0 && half_cfg != 0 && t64 >= 128 && t64 < 512 && M >= 256;
-    static const int pipe_cfg = [] { const char *e = getenv("HM_GEMM_PIPE"); return e ? atoi(e) : 2; }();   // 2 = eight-wave variant
-    // the pipelined kernel takes K ranges that are a whole number of 128-deep groups per split and operands that are
-    // either k-contiguous + 16-B aligned or row-contiguous (partial edge tiles are fine: clamped rows, guarded stores)
-    // pipe_cfg 2 fetches through buffer descriptors with 32-bit offsets (operands below 2 GB); its 16-byte loads need
-    // dword alignment only (probed: unaligned buffer_load_dwordx4 returns the right dwords), so k-contiguous operands with
-    // any leading dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K range
-    // runs to the next multiple of the stage group, that operand's descriptor returns zeros beyond its end (K = 445 and
-    // 257 of the backward sweeps: 27 - 43 us on the generic kernel).  HM_GEMM_KTAIL=0: generic kernel for those (A/B).
+    // the pipelined kernel fetches through buffer descriptors with 32-bit offsets, so it takes operands below 2 GB only
+    // (every other operand runs on the generic kernel, which addresses rows in 64 bits), and K ranges that are a whole
+    // number of 128-deep groups per split (partial edge tiles are fine: clamped rows, guarded stores).  Its 16-byte loads
+    // need dword alignment only (probed: unaligned buffer_load_dwordx4 returns the right dwords), so k-contiguous operands
+    // with any leading dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K
+    // range runs to the next multiple of the stage group, that operand's descriptor returns zeros beyond its end (K = 445
+    // and 257 of the backward sweeps: 27 - 43 us on the generic kernel).
     const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
                   bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
-    static const int ktail_cfg = [] { const char *e = getenv("HM_GEMM_KTAIL"); return e ? atoi(e) : 1; }();
-    const bool buf_ok = pipe_cfg == 2 && bytesA < (1ll << 31) && bytesB < (1ll << 31);
+    const bool buf_ok = bytesA < (1ll << 31) && bytesB < (1ll << 31);
     const bool k_whole = K % (kPipeBK * kPipeD) == 0;
     // (K >= 192: below that the rounded-up range costs more than the generic kernel's guards - K = 72 of the filter banks)
     // (and only where the generic kernel would not split K over workgroups: a tail runs as ONE chunk, so the small
     //  M x N weight-gradient shapes of the eager path - K = number of points - keep their split-K launch)
-    const bool k_tail_ok = buf_ok && ktail_cfg != 0 && (!a_kc || !b_kc) && K >= 192 &&
-                           (g.ep.mode != HM_EPI_NONE || t64 >= 256);
-    const bool use_pipe = !big && small_cfg == 0 && !half_rows && pipe_cfg != 0 && K > 0 &&
-                          (buf_ok ? (k_whole || k_tail_ok) : (k_whole && (!a_kc || g.vecA) && (!b_kc || g.vecB)));
+    const bool k_tail_ok = (!a_kc || !b_kc) && K >= 192 && (g.ep.mode != HM_EPI_NONE || t64 >= 256);
+    const bool use_pipe = !big && K > 0 && buf_ok && (k_whole || k_tail_ok);
     g.nrecA = (int32_t)(bytesA < 0x7fffffff ? bytesA : 0x7fffffff);
     g.nrecB = (int32_t)(bytesB < 0x7fffffff ? bytesB : 0x7fffffff);
     // 96-row tiles when they need fewer rounds of the chip per row of the tile (M = 3072, N = 512: 384 tiles of 64 rows -
-    // the slowest CU runs two = 128 rows' worth - against 256 tiles of 96).  HM_GEMM_M96=0: always 64-row tiles (A/B).
-    static const int m96_cfg = [] { const char *e = getenv("HM_GEMM_M96"); return e ? atoi(e) : 1; }();
+    // the slowest CU runs two = 128 rows' worth - against 256 tiles of 96)
     const int64_t t96 = ((M + 95) / 96) * ((N + 63) / 64);
-    const bool m96 = use_pipe && pipe_cfg == 2 && m96_cfg != 0 && ((t96 + 255) / 256) * 96 < ((t64 + 255) / 256) * 64;
-    const int64_t bm = big ? 128 : (half_rows ? 32 : (m96 ? 96 : 64)), bn = big ? 128 : 64;
-    const int64_t kBK = big ? 32 : (use_pipe ? kPipeBK * kPipeD : (small_cfg == 1 || small_cfg == 2 ? 64 : 128));
+    const bool m96 = use_pipe && ((t96 + 255) / 256) * 96 < ((t64 + 255) / 256) * 64;
+    const int64_t bm = big ? 128 : (m96 ? 96 : 64), bn = big ? 128 : 64;
+    const int64_t kBK = big ? 32 : (use_pipe ? kPipeBK * kPipeD : 128);
     const int64_t tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
     int64_t split = 1;
     if (tiles < 256 && K >= 256 && g.ep.mode == HM_EPI_NONE && !(use_pipe && !k_whole)) {   // (a nonlinear epilogue needs the
                                                                                           // full sum; a K tail is not split)
-        static const int split_target = [] { const char *e = getenv("HM_GEMM_SPLIT_TARGET"); return e ? atoi(e) : 512; }();
-        split = (split_target + tiles - 1) / tiles;
+        split = (kSplitTarget + tiles - 1) / tiles;
         const int64_t max_split = K / 128;
         if (split > max_split) split = max_split;
         if (split < 1) split = 1;
@@ -695,12 +593,6 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     hipStream_t st = as_stream(stream);
     if (big)
         HM_GEMM_LAUNCH(2, 2, 32, 1, 2);
-    else if (small_cfg == 1)
-        HM_GEMM_LAUNCH(1, 1, 64, 1, 2);
-    else if (small_cfg == 2)
-        HM_GEMM_LAUNCH(1, 1, 64, 2, 2);
-    else if (half_rows)
-        HM_GEMM_LAUNCH(1, 1, 128, 4, 1);
     else if (pipe_ok) {
 #define HM_PIPE_LAUNCH(AKC_, BKC_)                                                                                \
     do {                                                                                                          \
@@ -709,29 +601,18 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
                 hipLaunchKernelGGL((gemm_f32_pipe2_m96_kernel<AKC_, BKC_, true>), grid, dim3(768), 0, st, g);     \
             else                                                                                                  \
                 hipLaunchKernelGGL((gemm_f32_pipe2_m96_kernel<AKC_, BKC_, false>), grid, dim3(768), 0, st, g);    \
-        } else if (pipe_cfg == 2) {                                                                               \
-            if (g.ep.mode != HM_EPI_NONE)                                                                         \
-                hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, true>), grid, dim3(512), 0, st, g);         \
-            else                                                                                                  \
-                hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, false>), grid, dim3(512), 0, st, g);        \
         } else if (g.ep.mode != HM_EPI_NONE)                                                                      \
-            hipLaunchKernelGGL((gemm_f32_pipe_kernel<AKC_, BKC_, true>), grid, dim3(256), 0, st, g);              \
+            hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, true>), grid, dim3(512), 0, st, g);             \
         else                                                                                                      \
-            hipLaunchKernelGGL((gemm_f32_pipe_kernel<AKC_, BKC_, false>), grid, dim3(256), 0, st, g);             \
+            hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, false>), grid, dim3(512), 0, st, g);            \
     } while (0)
         if (a_kc && b_kc) HM_PIPE_LAUNCH(true, true);
         else if (a_kc) HM_PIPE_LAUNCH(true, false);
         else if (b_kc) HM_PIPE_LAUNCH(false, true);
         else HM_PIPE_LAUNCH(false, false);
 #undef HM_PIPE_LAUNCH
-    } else {
-        static const int log_cfg = [] { const char *e = getenv("HM_GEMM_LOG"); return e ? atoi(e) : 0; }();
-        if (log_cfg)   // debugging: which shapes miss the pipelined kernel
-            fprintf(stderr, "hm_gemm_f32 generic: tA %d tB %d M %lld N %lld K %lld lda %lld ldb %lld ep %d vecA %d vecB %d split %lld\n",
-                    transA, transB, (long long)M, (long long)N, (long long)K, (long long)lda, (long long)ldb, g.ep.mode,
-                    g.vecA, g.vecB, (long long)split);
+    } else
         HM_GEMM_LAUNCH(1, 1, 128, 2, 2);
-    }
 #undef HM_GEMM_LAUNCH
     HM_CHECK_LAUNCH("hm_gemm_f32");
     return HM_OK;

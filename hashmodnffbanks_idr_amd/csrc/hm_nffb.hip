@@ -21,16 +21,14 @@
 #include "hm_common.h"
 
 #include <math.h>
-#include <stdlib.h>
 
 namespace {
 
 constexpr int kNT = 256;   // threads per workgroup
 // LP = lanes per point (template value): each lane owns ceil(W / LP) of every layer's outputs (W = 56 / 72).
-//   LP = 8  (32 points per workgroup): big launches, throughput
 //   LP = 32 (8 points per workgroup): the tracer's march / secant rounds (<= 8192 live points).  A call is one serial
 //           chain per point - ~14 matrix-vector products whose weight rows are loaded through the L1 - and took ~92 us
-//           whatever its size; four times fewer rows per lane cut that chain, and every row is still one lane's k-ordered
+//           whatever its size at LP = 8; four times fewer rows per lane cut that chain, and every row is still one lane's k-ordered
 //           fma chain, so the values do not depend on LP.
 constexpr int kSmallCount = 8192;
 
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(kNT) void nffb_fwd_kernel(HmLevels lv, NffbArgs a, 
     __shared__ __align__(16) float T[kPP * WP];    // per point: the vector being exchanged between its lanes
     __shared__ float G[kPP * NG];                  // per point: the consumed part of the grid row
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));
-    if (n < run_min || n > run_max) return;      // the other lanes-per-point variant owns this batch size
+    if (n < run_min || n > run_max) return;      // the matrix-core kernel owns this batch size
     const int tid = threadIdx.x;
     const int pt = tid / kLP, sub = tid % kLP;
     float *prow = T + pt * WP;
@@ -236,7 +234,7 @@ __global__ __launch_bounds__(kNT) void nffb_fwd_kernel(HmLevels lv, NffbArgs a, 
 // encoding, StyleAttention's per-row normalisation (two lane exchanges over the point's four lanes) and the feature
 // accumulation all run on the accumulator layout.  Waves share nothing: no workgroup barrier anywhere.
 typedef float nf_f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kMfmaWaves = 4;      // waves per workgroup (16 points each) of the big-batch launch; 1 for the tracer's rounds
+constexpr int kMfmaWaves = 4;      // waves per workgroup (16 points each) of the big-batch launch
 
 template <int W, int NT>
 __device__ __forceinline__ void nffb_matvec_mfma(const float *__restrict__ Wm, const float *src, nf_f32x4 (&acc)[NT],
@@ -476,30 +474,17 @@ int launch_nffb1(hipStream_t st, const HmLevels &lv, const NffbArgs &a, const fl
     // once unless the live count falls in its range (like the fused SDF kernels)
     const bool small = n <= kSmallCount, big = n_dev ? n > kSmallCount : !small;
     const int64_t kBig = (int64_t)1 << 62;
-    static const int mfma_cfg = [] { const char *e = getenv("HM_NFFB_MFMA"); return e ? atoi(e) : 1; }();
     if (small || n_dev) {
         const int64_t cap = n < kSmallCount ? n : kSmallCount;
-        if (mfma_cfg == 2) {   // (experiment: the matrix-core kernel for the tracer's rounds too, one wave per workgroup)
-            const int64_t blocks = (cap + 15) / 16;
-            hipLaunchKernelGGL((nffb_fwd_mfma_kernel<FRAC, LV, STYLE, 1>), dim3((unsigned)blocks), dim3(64), 0, st, lv, a, x, n,
-                               table, Bf, out, out_stride, n_dev, (int64_t)0, (int64_t)kSmallCount);
-        } else {
-            const int64_t blocks = (cap + kNT / 32 - 1) / (kNT / 32);
-            hipLaunchKernelGGL((nffb_fwd_kernel<FRAC, LV, STYLE, 32>), dim3((unsigned)blocks), dim3(kNT), 0, st, lv, a, x, n,
-                               table, Bf, out, out_stride, n_dev, (int64_t)0, (int64_t)kSmallCount);
-        }
+        const int64_t blocks = (cap + kNT / 32 - 1) / (kNT / 32);
+        hipLaunchKernelGGL((nffb_fwd_kernel<FRAC, LV, STYLE, 32>), dim3((unsigned)blocks), dim3(kNT), 0, st, lv, a, x, n,
+                           table, Bf, out, out_stride, n_dev, (int64_t)0, (int64_t)kSmallCount);
     }
-    if (big) {
-        if (mfma_cfg) {     // matrix-core tiles, a wave per 16 points
-            const int64_t blocks = (n + 16 * kMfmaWaves - 1) / (16 * kMfmaWaves);
-            hipLaunchKernelGGL((nffb_fwd_mfma_kernel<FRAC, LV, STYLE, kMfmaWaves>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)),
-                               dim3(64 * kMfmaWaves), 0, st, lv, a, x, n, table, Bf, out, out_stride, n_dev,
-                               (int64_t)kSmallCount + 1, kBig);
-        } else {            // (HM_NFFB_MFMA=0: the 8-lanes-per-point VALU kernel, for A/B measurements)
-            const int64_t blocks = (n + kNT / 8 - 1) / (kNT / 8);
-            hipLaunchKernelGGL((nffb_fwd_kernel<FRAC, LV, STYLE, 8>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kNT),
-                               0, st, lv, a, x, n, table, Bf, out, out_stride, n_dev, (int64_t)kSmallCount + 1, kBig);
-        }
+    if (big) {   // matrix-core tiles, a wave per 16 points
+        const int64_t blocks = (n + 16 * kMfmaWaves - 1) / (16 * kMfmaWaves);
+        hipLaunchKernelGGL((nffb_fwd_mfma_kernel<FRAC, LV, STYLE, kMfmaWaves>), dim3((unsigned)(blocks < 2048 ? blocks : 2048)),
+                           dim3(64 * kMfmaWaves), 0, st, lv, a, x, n, table, Bf, out, out_stride, n_dev,
+                           (int64_t)kSmallCount + 1, kBig);
     }
     return HM_OK;
 }

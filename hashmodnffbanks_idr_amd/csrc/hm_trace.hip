@@ -435,8 +435,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     // launch and the secant runs behind it on a few dozen workgroups (A/B).
     const char *e_ov = getenv("HM_TRACE_OVERLAP");      // (read per call: the tests compare both forms in one process)
     const bool overlap_ok = !(e_ov && atoi(e_ov) == 0);
-    static const bool persistent_ok = [] { const char *e = getenv("HM_TRACE_PERSISTENT"); return !(e && atoi(e) == 0); }();
-    const bool overlap = overlap_ok && persistent_ok && cfg->training && !nffb && !cfg->coarse_bf16 && tile_points == 0 &&
+    const bool overlap = overlap_ok && cfg->training && !nffb && !cfg->coarse_bf16 && tile_points == 0 &&
                          cfg->n_secant_steps > 0 && n_rays <= 8192;
     a.sel_off = overlap ? 2 * L.cap : -1;
 
@@ -492,9 +491,8 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     // iteration.  Hash-grid networks with the tile size left to the library (or fixed at 16) run the surplus rounds as
     // ONE persistent launch in which every workgroup carries eight rays to the end (hm_sdf.hip: trace_march_tail_kernel;
     // it returns at once when no ray is left) instead of 30 (empty SDF launch, empty update launch) pairs.
-    // HM_TRACE_PERSISTENT=0: every round a launch pair (A/B).
     const int rounds = 1 + cfg->sphere_tracing_iters * (1 + cfg->line_step_iters);
-    const bool tail = persistent_ok && !nffb && (tile_points == 0 || tile_points == 16) &&
+    const bool tail = !nffb && (tile_points == 0 || tile_points == 16) &&
                       a.w.cap >= ((n_rays + 7) / 8) * 16 && cfg->line_step_iters > 0;
     int launched = tail ? 1 + cfg->sphere_tracing_iters : rounds;
     if (tail) {   // HM_TRACE_TAIL_FIRST=k (tests): hand over to the persistent kernel after k rounds already (read per call)
@@ -564,7 +562,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
                                                 n_rays * cfg->n_steps, c_first, grid_p1, (int)C_TAIL_PTS, grid_p2, stream);
             if (rc != HM_OK) return rc;
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-        } else if (persistent_ok && !nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
+        } else if (!nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
             (tile_points != 0 || n_rays <= 8192)) {
             const int rc = hm_trace_secant_persistent(desc, mlp, table, B_fourier, frac_mode, tile_points, &a,
                                                       cfg->n_secant_steps, stream);

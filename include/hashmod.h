@@ -256,7 +256,7 @@ HM_API int hm_pack_mlp_layer_bf16(const float *W, int64_t ldw, int out_dim, int 
 
 /* x [n,3] -> out.  out_cols == 1: only the clamped sdf, out[i*out_stride];  out_cols == last
  * layer's out_dim: the whole [sdf | feature vector] row.
- * tile_points: 32 (two 4-wave workgroups per CU: throughput), 64 (one 8-wave workgroup per CU), 16 (small batches),
+ * tile_points: 64 (one 8-wave workgroup per CU), 16 (small batches),
  * 8 or 4 (<= 2048 / 1024 points: bound by the weight stream alone), 0 = choose by n (on the device when n_dev is given),
  * -1 = like 0 but ONLY for n <= 8192 (larger batches are left to another launch, e.g. hm_sdf_fwd_bf16 with run_min 8193).
  * n_dev: optional DEVICE int32; when non-NULL the kernel evaluates min(n, *n_dev) points, so a

@@ -1,4 +1,4 @@
-"""Which grad-path GEMMs miss the pipelined kernel, and what do they cost?  (HM_GEMM_LOG=1 lists them on stderr.)"""
+"""Which grad-path GEMMs miss the pipelined kernel, and what do they cost?"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [R, R + "/tests", R + "/tests/golden"]

@@ -114,3 +114,20 @@ def test_grouped_weight_gradient_gemm_matches_torch():
     ops.gemm_group_tn([])                                             # empty list is a no-op
     with pytest.raises(ValueError):
         ops.gemm_group_tn([(T(8, 4), T(9, 4), T(4, 4))])              # inner dimensions differ
+
+
+def test_gemm_operand_beyond_2gb_matches_torch():
+    """hm_gemm_f32 with an A view whose span exceeds 2 GB: the pipelined kernel addresses its operands with 32-bit
+    buffer offsets, so such an operand has to run on the generic kernel (64-bit row addressing) - every row, not just
+    the ones within the first 2 GB"""
+    from hashmodnffbanks_idr_amd import ops
+    g = torch.Generator(device="cpu").manual_seed(29)
+    ld = 2 ** 29 + 128                                                   # row stride: row 1 starts 2 GB + 512 B in
+    store = torch.empty(ld + 128, device="cuda")
+    a = store.as_strided((2, 128), (ld, 1))
+    a.copy_(torch.randn(2, 128, generator=g))
+    b = torch.randn(128, 64, generator=g).cuda()
+    bias = torch.randn(64, generator=g).cuda()
+    c = ops.gemm(a, b, bias)
+    ref = a.double() @ b.double() + bias.double()
+    _close(c, ref, "A spanning more than 2 GB")
