@@ -80,6 +80,16 @@ SIGNATURES = {
     "hm_rows_clear": (_int, [_p, _i64, _int, _p, _i64, _i64, _int, _p, _p]),
     "hm_multi_copy_f32": (_int, [_p, _int, _p]),
     "hm_gemm_f32_group_tn": (_int, [_p, _int, _p]),
+    "hm_gemm_f32_det_workspace_bytes": (_i64, [_int, _int, _i64, _i64, _i64, _i64, _i64]),
+    "hm_gemm_f32_det": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _int, _p, _i64, _p]),
+    "hm_gemm_f32_group_tn_det_workspace_bytes": (_i64, [_p, _int]),
+    "hm_gemm_f32_group_tn_det": (_int, [_p, _int, _p, _i64, _p]),
+    "hm_colsum_det_workspace_bytes": (_i64, [_i64, _i64]),
+    "hm_colsum_det": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p]),
+    "hm_colsum_acc_det": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p]),
+    "hm_colsum_acc_multi_det_workspace_bytes": (_i64, [_p, _int]),
+    "hm_colsum_acc_multi_det": (_int, [_p, _int, _p, _i64, _p]),
+    "hm_encode_bwd_table_sorted_tracked": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "hm_gemm_f32_ep": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     "hm_gemm_f32": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _int, _p]),
 }

@@ -70,14 +70,8 @@ __global__ __launch_bounds__(kET) void softplus_bwd_bwd_kernel(const float *__re
     }
 }
 
-// out[n] += sum_m x[m, n]   (bias gradient); rows are split over blockIdx.y, fp32 atomics combine slabs
-__global__ __launch_bounds__(kET) void colsum_kernel(const float *__restrict__ x, int64_t M, int64_t N, int64_t ld,
-                                                     float *__restrict__ out, int rows_per_block) {
-    const int64_t n = (int64_t)blockIdx.x * kET + threadIdx.x;
-    if (n >= N) return;
-    const int64_t m0 = (int64_t)blockIdx.y * rows_per_block;
-    const int64_t m1 = min(M, m0 + rows_per_block);
-    // eight independent row streams per thread keep the loads of a slab in flight together
+// sum of column n over rows [m0, m1): eight independent row streams per thread keep the loads of a slab in flight together
+__device__ __forceinline__ float colsum_slab(const float *__restrict__ x, int64_t ld, int64_t n, int64_t m0, int64_t m1) {
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
     const float *p = x + m0 * ld + n;
     int64_t m = m0;
@@ -86,7 +80,17 @@ __global__ __launch_bounds__(kET) void colsum_kernel(const float *__restrict__ x
         a4 += p[4 * ld]; a5 += p[5 * ld]; a6 += p[6 * ld]; a7 += p[7 * ld];
     }
     for (; m < m1; ++m, p += ld) a0 += *p;
-    atomicAdd(out + n, ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)));
+    return ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
+}
+
+// out[n] += sum_m x[m, n]   (bias gradient); rows are split over blockIdx.y, fp32 atomics combine slabs
+__global__ __launch_bounds__(kET) void colsum_kernel(const float *__restrict__ x, int64_t M, int64_t N, int64_t ld,
+                                                     float *__restrict__ out, int rows_per_block) {
+    const int64_t n = (int64_t)blockIdx.x * kET + threadIdx.x;
+    if (n >= N) return;
+    const int64_t m0 = (int64_t)blockIdx.y * rows_per_block;
+    const int64_t m1 = min(M, m0 + rows_per_block);
+    atomicAdd(out + n, colsum_slab(x, ld, n, m0, m1));
 }
 
 
@@ -110,6 +114,38 @@ __global__ __launch_bounds__(kET) void colsum_multi_kernel(ColsumTable t, int ro
     }
     for (; m < m1; ++m, p += ld) a0 += *p;
     atomicAdd(I.out + n, ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)));
+}
+
+// Deterministic column sums (no atomics): pass 1 writes every slab's partial to a caller-owned workspace,
+// ws[off + s * N + n]; pass 2 gives out[n] = out_old[n] + (((p0 + p1) + p2) + ...) (acc) or ((p0 + p1) + ...), in slab
+// order.  The slab height depends on M only, so the summation order is a function of the shape.  Item z of a table is
+// blockIdx.z; a single call is a table of one.
+constexpr int64_t kColsumDetSlabs = 512;   // slabs per matrix at most: pass 2 reads them serially, one thread per column
+struct ColsumDetItem {
+    const float *x;
+    float *out;
+    int64_t M, N, ld, off;   // off: first workspace float of the item
+    int32_t rows, slabs, acc;
+};
+struct ColsumDetTable {
+    ColsumDetItem it[HM_COLSUM_MAX_ITEMS];
+};
+__global__ __launch_bounds__(kET) void colsum_part_kernel(ColsumDetTable t, float *__restrict__ ws) {
+    const ColsumDetItem &I = t.it[blockIdx.z];
+    const int64_t n = (int64_t)blockIdx.x * kET + threadIdx.x;
+    if (n >= I.N || (int)blockIdx.y >= I.slabs) return;
+    const int64_t m0 = (int64_t)blockIdx.y * I.rows;
+    const int64_t m1 = min(I.M, m0 + I.rows);
+    ws[I.off + (int64_t)blockIdx.y * I.N + n] = colsum_slab(I.x, I.ld, n, m0, m1);
+}
+__global__ __launch_bounds__(kET) void colsum_part_reduce_kernel(ColsumDetTable t, const float *__restrict__ ws) {
+    const ColsumDetItem &I = t.it[blockIdx.z];
+    const int64_t n = (int64_t)blockIdx.x * kET + threadIdx.x;
+    if (n >= I.N) return;
+    const float *p = ws + I.off + n;
+    float s = I.slabs > 0 ? p[0] : 0.0f;
+    for (int k = 1; k < I.slabs; ++k) s = __fadd_rn(s, p[(int64_t)k * I.N]);
+    I.out[n] = I.acc ? __fadd_rn(I.out[n], s) : s;
 }
 
 // ---- soft clamp of the SDF column (implicit_differentiable_renderer.py:112, density_net.py:20-30) ----------------
@@ -498,6 +534,52 @@ static int colsum_impl(const float *x, int64_t M, int64_t N, int64_t ld, float *
     return HM_OK;
 }
 
+// slab height / count of the deterministic column sum of an M-row matrix
+static void colsum_det_slabs(int64_t M, int32_t &rows, int32_t &slabs) {
+    int64_t r = 32;
+    if ((M + r - 1) / r > kColsumDetSlabs) r = (M + kColsumDetSlabs - 1) / kColsumDetSlabs;
+    rows = (int32_t)r;
+    slabs = (int32_t)((M + r - 1) / r);
+}
+
+// deterministic colsum over a list of items (zero_first: out = sum instead of out += sum); with ws == nullptr and
+// need != nullptr only the workspace need is computed.  Tables of HM_COLSUM_MAX_ITEMS run one after another on the
+// stream and share the workspace.
+static int colsum_det_impl(const hm_colsum_item *items, int n_items, bool zero_first, float *ws, int64_t ws_bytes,
+                           int64_t *need, void *stream, const char *name) {
+    HM_CHECK_ARG(n_items >= 0 && (n_items == 0 || items), name);
+    if (need) *need = 0;
+    for (int first = 0; first < n_items; first += HM_COLSUM_MAX_ITEMS) {
+        const int cnt = n_items - first < HM_COLSUM_MAX_ITEMS ? n_items - first : HM_COLSUM_MAX_ITEMS;
+        ColsumDetTable t;
+        int64_t off = 0, max_n = 0, max_slabs = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const hm_colsum_item &I = items[first + i];
+            HM_CHECK_ARG(I.M >= 0 && I.N >= 0 && I.ld >= I.N, name);
+            HM_CHECK_ARG(need || I.N == 0 || (I.out && (I.M == 0 || I.x)), name);
+            ColsumDetItem &D = t.it[i];
+            D.x = I.x; D.out = I.out; D.M = I.M; D.N = I.N; D.ld = I.ld; D.off = off;
+            D.acc = zero_first ? 0 : 1;
+            colsum_det_slabs(I.M, D.rows, D.slabs);
+            off += (int64_t)D.slabs * I.N;
+            max_n = I.N > max_n ? I.N : max_n;
+            max_slabs = D.slabs > max_slabs ? D.slabs : max_slabs;
+        }
+        for (int i = cnt; i < HM_COLSUM_MAX_ITEMS; ++i) t.it[i] = ColsumDetItem{nullptr, nullptr, 0, 0, 0, 0, 1, 0, 1};
+        if (need && 4 * off > *need) *need = 4 * off;
+        if (!ws && need) continue;
+        if (max_n == 0) continue;
+        HM_CHECK_ARG(off == 0 || (ws && ws_bytes >= 4 * off), name);
+        hipStream_t st = as_stream(stream);
+        const unsigned gx = (unsigned)((max_n + kET - 1) / kET);
+        if (max_slabs > 0)
+            hipLaunchKernelGGL(colsum_part_kernel, dim3(gx, (unsigned)max_slabs, (unsigned)cnt), dim3(kET), 0, st, t, ws);
+        hipLaunchKernelGGL(colsum_part_reduce_kernel, dim3(gx, 1, (unsigned)cnt), dim3(kET), 0, st, t, ws);
+        HM_CHECK_LAUNCH(name);
+    }
+    return HM_OK;
+}
+
 // 2-D copy as a KERNEL (hipMemcpy2DAsync / hipMemcpyAsync would become MEMCPY nodes of a captured graph)
 __global__ __launch_bounds__(256) void copy2d_kernel(float *__restrict__ dst, int64_t ldd,
                                                      const float *__restrict__ src, int64_t lds_, int64_t rows,
@@ -536,6 +618,40 @@ int hm_colsum(const float *x, int64_t M, int64_t N, int64_t ld, float *out, void
 
 int hm_colsum_acc(const float *x, int64_t M, int64_t N, int64_t ld, float *out, void *stream) {
     return colsum_impl(x, M, N, ld, out, false, stream);
+}
+
+int64_t hm_colsum_det_workspace_bytes(int64_t M, int64_t N) {
+    if (M <= 0 || N <= 0) return 0;
+    int32_t rows, slabs;
+    colsum_det_slabs(M, rows, slabs);
+    return 4 * (int64_t)slabs * N;
+}
+
+int hm_colsum_det(const float *x, int64_t M, int64_t N, int64_t ld, float *out, void *workspace, int64_t workspace_bytes,
+                  void *stream) {
+    const hm_colsum_item it{x, out, M, N, ld};
+    return colsum_det_impl(&it, 1, true, static_cast<float *>(workspace), workspace_bytes, nullptr, stream,
+                           "hm_colsum_det: bad argument or workspace");
+}
+
+int hm_colsum_acc_det(const float *x, int64_t M, int64_t N, int64_t ld, float *out, void *workspace,
+                      int64_t workspace_bytes, void *stream) {
+    const hm_colsum_item it{x, out, M, N, ld};
+    return colsum_det_impl(&it, 1, false, static_cast<float *>(workspace), workspace_bytes, nullptr, stream,
+                           "hm_colsum_acc_det: bad argument or workspace");
+}
+
+int64_t hm_colsum_acc_multi_det_workspace_bytes(const hm_colsum_item *items, int n_items) {
+    int64_t need = 0;
+    if (colsum_det_impl(items, n_items, false, nullptr, 0, &need, nullptr, "hm_colsum_acc_multi_det: bad item") != HM_OK)
+        return -1;
+    return need;
+}
+
+int hm_colsum_acc_multi_det(const hm_colsum_item *items, int n_items, void *workspace, int64_t workspace_bytes,
+                            void *stream) {
+    return colsum_det_impl(items, n_items, false, static_cast<float *>(workspace), workspace_bytes, nullptr, stream,
+                           "hm_colsum_acc_multi_det: bad item or workspace");
 }
 
 int hm_colsum_acc_multi(const hm_colsum_item *items, int n_items, void *stream) {

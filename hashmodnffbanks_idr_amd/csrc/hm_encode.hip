@@ -825,6 +825,30 @@ __global__ __launch_bounds__(kThreads) void encode_rows_kernel(HmLevels lv, cons
     if (wts) wts[gid] = w;
 }
 
+// the run of row `key` that starts at sorted position k, summed in sorted order and added to its row; returns whether
+// any contribution of the run has a nonzero weight
+__device__ __forceinline__ bool segment_run_add(const int32_t *__restrict__ keys, const int64_t *__restrict__ perm,
+                                                int64_t K, int L, int F, int C, const float *__restrict__ d_feat,
+                                                int64_t d_feat_stride, const float *__restrict__ wts,
+                                                float *__restrict__ d_table, int64_t k, int32_t key) {
+    float acc[8];
+    bool nz = false;
+    for (int f = 0; f < F; ++f) acc[f] = 0.0f;
+    for (int64_t m = k; m < K && keys[m] == key; ++m) {
+        const int64_t jx = perm[m];
+        const int64_t pl = jx / C;
+        const int64_t i = pl / L;
+        const int l = (int)(pl - i * L);
+        const float w = wts ? wts[jx] : 1.0f;
+        nz |= w != 0.0f;
+        const float *g = d_feat + i * d_feat_stride + l * F;
+        for (int f = 0; f < F; ++f) acc[f] = __fadd_rn(acc[f], __fmul_rn(w, g[f]));
+    }
+    float *row = d_table + (int64_t)key * F;
+    for (int f = 0; f < F; ++f) row[f] = __fadd_rn(row[f], acc[f]);
+    return nz;
+}
+
 __global__ __launch_bounds__(kThreads) void segment_scatter_kernel(const int32_t *__restrict__ keys,
                                                                    const int64_t *__restrict__ perm, int64_t K, int L,
                                                                    int F, int C, const float *__restrict__ d_feat,
@@ -847,6 +871,46 @@ __global__ __launch_bounds__(kThreads) void segment_scatter_kernel(const int32_t
     }
     float *row = d_table + (int64_t)key * F;
     for (int f = 0; f < F; ++f) row[f] = __fadd_rn(row[f], acc[f]);
+}
+
+// Deterministic form of encode_bwd_table_tracked_kernel for the data-parallel exchange: the run sums of
+// segment_scatter_kernel, and the head of every run with a nonzero weight claims its row bit and a slot of rows_out
+// with the same workgroup-counter protocol (bits, count, cap as there).  The dense values do not depend on scheduling;
+// the order of the list does, and hm_rows_apply does not care (rows are unique within a rank's list).
+__global__ __launch_bounds__(kThreads) void segment_scatter_tracked_kernel(
+    const int32_t *__restrict__ keys, const int64_t *__restrict__ perm, int64_t K, int L, int F, int C,
+    const float *__restrict__ d_feat, int64_t d_feat_stride, const float *__restrict__ wts, float *__restrict__ d_table,
+    uint32_t *__restrict__ bits, int32_t *__restrict__ count, int32_t *__restrict__ rows_out, int64_t cap) {
+    __shared__ int32_t s_cnt[kThreads / 64], s_base;
+    const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    bool claimed = false;
+    int32_t key = 0;
+    if (k < K) {
+        key = keys[k];
+        if ((k == 0 || keys[k - 1] != key) &&
+            segment_run_add(keys, perm, K, L, F, C, d_feat, d_feat_stride, wts, d_table, k, key)) {
+            const uint32_t bit = 1u << ((uint32_t)key & 31u);
+            claimed = (atomicOr(bits + ((uint32_t)key >> 5), bit) & bit) == 0u;
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t m = __ballot(claimed);
+    if (lane == 0) s_cnt[wave] = (int32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t tot = 0;
+        for (int w = 0; w < kThreads / 64; ++w) {
+            const int32_t v = s_cnt[w];
+            s_cnt[w] = tot;
+            tot += v;
+        }
+        s_base = tot > 0 ? atomicAdd(count, tot) : 0;
+    }
+    __syncthreads();
+    if (claimed) {
+        const int64_t slot = (int64_t)s_base + s_cnt[wave] + __popcll(m & ((1ull << lane) - 1ull));
+        if (slot < cap) rows_out[slot] = key;     // (slot >= cap: reported by hm_rows_pack through `status`)
+    }
 }
 
 // Counter calibration for 8-byte row gathers (diagnostic; bench.py --only gather_calib).  Every group of `group`
@@ -991,6 +1055,28 @@ int hm_encode_bwd_table_sorted(const hm_grid_desc *desc, const int32_t *keys_sor
     hipLaunchKernelGGL(segment_scatter_kernel, dim3((unsigned)grid), dim3(kThreads), 0, as_stream(stream), keys_sorted,
                        perm, n_keys, desc->lv.L, desc->lv.F, corners, d_feat, d_feat_stride, weights, d_table);
     HM_CHECK_LAUNCH("hm_encode_bwd_table_sorted");
+    return HM_OK;
+}
+
+int hm_encode_bwd_table_sorted_tracked(const hm_grid_desc *desc, const int32_t *keys_sorted, const int64_t *perm,
+                                       int64_t n_keys, int corners, const float *d_feat, int64_t d_feat_stride,
+                                       const float *weights, float *d_table, uint32_t *touched_bits,
+                                       int32_t *touched_count, int32_t *touched_rows, int64_t cap, void *stream) {
+    HM_CHECK_ARG(desc != nullptr && n_keys >= 0 && cap >= 0 && (corners == 1 || corners == 8),
+                 "hm_encode_bwd_table_sorted_tracked: bad argument");
+    HM_CHECK_ARG(d_feat_stride >= desc->lv.L * desc->lv.F && desc->lv.F <= 8,
+                 "hm_encode_bwd_table_sorted_tracked: bad stride / F");
+    HM_CHECK_ARG(desc->total_rows < ((uint64_t)1 << 31), "hm_encode_bwd_table_sorted_tracked: table too large");
+    if (n_keys == 0) return HM_OK;
+    HM_CHECK_ARG(keys_sorted && perm && d_feat && d_table && touched_bits && touched_count && touched_rows,
+                 "hm_encode_bwd_table_sorted_tracked: NULL pointer");
+    HM_CHECK_ARG(corners == 1 || weights, "hm_encode_bwd_table_sorted_tracked: trilinear mode needs the weights");
+    const int64_t grid = (n_keys + kThreads - 1) / kThreads;
+    HM_CHECK_ARG(grid <= 0x7fffffffLL, "hm_encode_bwd_table_sorted_tracked: too many contributions for one launch");
+    hipLaunchKernelGGL(segment_scatter_tracked_kernel, dim3((unsigned)grid), dim3(kThreads), 0, as_stream(stream),
+                       keys_sorted, perm, n_keys, desc->lv.L, desc->lv.F, corners, d_feat, d_feat_stride, weights,
+                       d_table, touched_bits, touched_count, touched_rows, cap);
+    HM_CHECK_LAUNCH("hm_encode_bwd_table_sorted_tracked");
     return HM_OK;
 }
 

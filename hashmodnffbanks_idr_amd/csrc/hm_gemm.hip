@@ -98,8 +98,11 @@ __device__ __forceinline__ void store_tile(float *__restrict__ S, bool kcontig, 
 
 // Store one 32x32 accumulator tile: lane holds column n, registers hold rows mrow0 + (r&3) + 8(r>>2)
 // (mrow0 already includes the lane half's +4).  EP selects the fused Softplus epilogues (include/hashmod.h).
-template <bool EP>
-__device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 &acc, int n, int mrow0, bool add_bias) {
+// PART: deterministic split-K - the tile is k part kz's partial and goes with plain stores to the workspace slab
+// g.C + kz * M * ldc (ldc = N); gemm_part_reduce_kernel sums the slabs in k-part order.
+template <bool EP, bool PART = false>
+__device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 &acc, int n, int mrow0, bool add_bias,
+                                                int kz = 0) {
     const float bv = add_bias ? g.bias[n] : 0.0f;
     const int mode = EP ? g.ep.mode : (int)HM_EPI_NONE;
     // epilogue operands first, all 16 (+16) loads in flight together on clamped addresses: a load under
@@ -134,7 +137,9 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 
         if (m >= g.M) continue;
         float v = acc[r] + bv;
         if (mode != HM_EPI_NONE) v *= g.ep.scale;
-        if (g.C) {
+        if (PART) {
+            g.C[((int64_t)kz * g.M + m) * g.ldc + n] = v;
+        } else if (g.C) {
             float *dst = g.C + (int64_t)m * g.ldc + n;
             if (g.atomic)
                 atomicAdd(dst, v);
@@ -258,6 +263,99 @@ __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f3
         }
 }
 
+// Deterministic split-K form of gemm_f32_kernel (no epilogue): the same main loop, k part blockIdx.z's partial tile goes
+// to its workspace slab (gemm_store_tile<false, true>).  A separate kernel rather than a template parameter of the one
+// above: hipcc schedules that kernel differently once its body is shared, and the default path keeps its instructions.
+template <int TM, int TN, int BK, int KS, bool VA, bool VB, int WM = 2>
+__global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f32_part_kernel(GemmArgs g) {
+    constexpr int BM = 32 * WM * TM, BN = 64 * TN, NT = 128 * WM * KS, WG = 2 * WM;  // WG = waves per k part
+    __shared__ __align__(16) float smem[BK * (BM + BN)];
+    float *As = smem, *Bs = smem + BK * BM;
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int kpart = wave / WG, wsub = wave % WG;
+    const int wm = wsub >> 1, wn = wsub & 1;
+    const int j = lane & 31, h = lane >> 5;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    const int kbeg = blockIdx.z * g.k_chunk;
+    const int kend = min(g.K, kbeg + g.k_chunk);
+    const bool a_kc = (g.transA == 0);  // A[m*lda + k]
+    const bool b_kc = (g.transB != 0);  // B stored [N,K]: B[n*ldb + k]
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+
+    float4 ra[BM * BK / 4 / NT], rb[BN * BK / 4 / NT];
+    load_tile<BM, BK, NT, VA>(g.A, g.lda, a_kc, m0, g.M, kbeg, kend, tid, ra);
+    load_tile<BN, BK, NT, VB>(g.B, g.ldb, b_kc, n0, g.N, kbeg, kend, tid, rb);
+    for (int k0 = kbeg; k0 < kend; k0 += BK) {
+        __syncthreads();  // previous stage fully consumed
+        store_tile<BM, BK, NT>(As, a_kc, tid, ra);
+        store_tile<BN, BK, NT>(Bs, b_kc, tid, rb);
+        __syncthreads();
+        if (k0 + BK < kend) {  // prefetch the next stage into registers while this one is multiplied
+            load_tile<BM, BK, NT, VA>(g.A, g.lda, a_kc, m0, g.M, k0 + BK, kend, tid, ra);
+            load_tile<BN, BK, NT, VB>(g.B, g.ldb, b_kc, n0, g.N, k0 + BK, kend, tid, rb);
+        }
+        constexpr int OCT = BK / 8 / KS;
+#pragma unroll
+        for (int oo = 0; oo < OCT; ++oo) {
+            float4 a[TM], b[TN];
+            const int kg = 2 * (kpart * OCT + oo) + h;
+#pragma unroll
+            for (int t = 0; t < TM; ++t)
+                a[t] = *reinterpret_cast<const float4 *>(As + lds_slot<BM>(kg, wm * 32 * TM + t * 32 + j));
+#pragma unroll
+            for (int t = 0; t < TN; ++t)
+                b[t] = *reinterpret_cast<const float4 *>(Bs + lds_slot<BN>(kg, wn * 32 * TN + t * 32 + j));
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                    for (int tn = 0; tn < TN; ++tn) {
+                        const float av = s == 0 ? a[tm].x : s == 1 ? a[tm].y : s == 2 ? a[tm].z : a[tm].w;
+                        const float bv = s == 0 ? b[tn].x : s == 1 ? b[tn].y : s == 2 ? b[tn].z : b[tn].w;
+                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[tm][tn], 0, 0, 0);
+                    }
+        }
+    }
+
+    if (KS > 1) {
+        // sum the wave groups' partial tiles through LDS (the staging buffers are free now)
+        static_assert(KS == 1 || (TM == 1 && TN == 1), "intra-workgroup K split is built for the 64x64 tile");
+        __syncthreads();
+        float *red = smem;  // (KS-1) * WG waves * 16 regs * 64 lanes floats
+        static_assert((KS - 1) * WG * 16 * 64 <= BK * (BM + BN), "K-split reduction does not fit the staging buffers");
+        if (kpart > 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) red[(((kpart - 1) * WG + wsub) * 16 + r) * 64 + lane] = acc[0][0][r];
+        }
+        __syncthreads();
+        if (kpart > 0) return;
+#pragma unroll
+        for (int p = 0; p < KS - 1; ++p)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[0][0][r] += red[((p * WG + wsub) * 16 + r) * 64 + lane];
+    }
+
+    // epilogue: lane holds column n, registers hold rows (r&3) + 8(r>>2) + 4h
+    const bool add_bias = (g.bias != nullptr) && (blockIdx.z == 0);
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            const int n = n0 + wn * 32 * TN + tn * 32 + j;
+            if (n >= g.N) continue;
+            gemm_store_tile<false, true>(g, acc[tm][tn], n, m0 + wm * 32 * TM + tm * 32 + 4 * h, add_bias, blockIdx.z);
+        }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Pipelined 64x64 tile for the training shapes (M = 2048...4096 rows, N = K = 512: 256-512 tiles, i.e. ONE or two
 // workgroups per CU, 6.8 us of matrix work each).  With so little work per tile the steady state of the software
@@ -315,7 +413,7 @@ __device__ __forceinline__ void pipe_mfma_oct(const float4 &a, const float4 &b, 
 // WM = 3: a 96 x 64 tile on TWELVE waves (two groups of 3 x 2), for row counts whose 64-row grid is between one and two
 // rounds of the chip: M = 3072, N = 512 are 384 tiles of 64 x 64 - a CU with two of them takes twice as long as the one
 // with one - but exactly 256 of 96 x 64.  The B panel is staged by the first 512 threads.
-template <bool AKC, bool BKC, bool EP, int WM = 2>
+template <bool AKC, bool BKC, bool EP, int WM = 2, bool PART = false>
 __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int by, int bz) {
     constexpr int BM = 32 * WM, BN = 64, BK = kPipeBK, NT = 256 * WM, NTB = 512, PER = BM * BK / 4 / NT, KG = BK / 4,
                   OCT = BK / 8 / 2;   // OCT: octets of a stage per wave group
@@ -413,7 +511,7 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
         for (int r = 0; r < 16; ++r) acc[r] += red[(wsub * 16 + r) * 64 + lane];
     }
     const int n = n0 + wn * 32 + j;
-    if (n < g.N) gemm_store_tile<EP>(g, acc, n, m0 + wm * 32 + 4 * h, (g.bias != nullptr) && (bz == 0));
+    if (n < g.N) gemm_store_tile<EP, PART>(g, acc, n, m0 + wm * 32 + 4 * h, (g.bias != nullptr) && (bz == 0), bz);
 }
 
 template <bool AKC, bool BKC, bool EP>
@@ -423,6 +521,14 @@ __global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_kernel(GemmArgs g) {
 template <bool AKC, bool BKC, bool EP>
 __global__ __launch_bounds__(768, 3) void gemm_f32_pipe2_m96_kernel(GemmArgs g) {
     gemm_pipe2_body<AKC, BKC, EP, 3>(g, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <bool AKC, bool BKC>
+__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_part_kernel(GemmArgs g) {
+    gemm_pipe2_body<AKC, BKC, false, 2, true>(g, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <bool AKC, bool BKC>
+__global__ __launch_bounds__(768, 3) void gemm_f32_pipe2_m96_part_kernel(GemmArgs g) {
+    gemm_pipe2_body<AKC, BKC, false, 3, true>(g, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // Grouped form for the weight gradients of one backward pass: C_p += A_p^T B_p for up to HM_GEMM_GROUP_MAX problems in ONE
@@ -441,7 +547,10 @@ struct GemmGroupTable {
     int32_t start[HM_GEMM_GROUP_MAX + 1];
     int32_t n;
 };
-__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_kernel(GemmGroupTable t) {
+// PART: deterministic form - every problem's E.C is its workspace slab base (E.ldc = N), partials go there with plain
+// stores and gemm_part_reduce_kernel adds them to the real C in k-part order.
+template <bool PART>
+__device__ __forceinline__ void gemm_group_body(const GemmGroupTable &t) {
     int p = 0;
     while (p + 1 < t.n && (int)blockIdx.x >= t.start[p + 1]) ++p;       // (uniform: <= 16 problems)
     const GemmGroupEntry &E = t.e[p];
@@ -459,7 +568,41 @@ __global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_kernel(GemmGroupT
     g.vecA = g.vecB = 0;
     g.nrecA = g.nrecB = 0x7fffffff;
     g.ep.mode = HM_EPI_NONE;
-    gemm_pipe2_body<false, false, false>(g, bx, by, bz);
+    gemm_pipe2_body<false, false, false, 2, PART>(g, bx, by, bz);
+}
+__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_kernel(GemmGroupTable t) {
+    gemm_group_body<false>(t);
+}
+__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_part_kernel(GemmGroupTable t) {
+    gemm_group_body<true>(t);
+}
+
+// Deterministic split-K, second pass: C = C_old + (((p0 + p1) + p2) + ...) (accumulate) or C = ((p0 + p1) + ...),
+// the partials p_k read from the workspace slabs of gemm_*_part_kernel in k-part order - the summation order depends
+// on the shape only.  One launch serves every problem of a call: thread i of problem p owns element i - start[p].
+struct GemmReduceEntry {
+    const float *P;   // split slabs of M x N floats
+    float *C;
+    int64_t ldc, start;   // start: first flat element of this problem in the launch
+    int32_t M, N, split, accumulate;
+};
+struct GemmReduceTable {
+    GemmReduceEntry e[HM_GEMM_GROUP_MAX];
+    int64_t end;
+    int32_t n;
+};
+__global__ __launch_bounds__(256) void gemm_part_reduce_kernel(GemmReduceTable t) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.end) return;
+    int p = 0;
+    while (p + 1 < t.n && i >= t.e[p + 1].start) ++p;
+    const GemmReduceEntry &E = t.e[p];
+    const int64_t e = i - E.start, mn = (int64_t)E.M * E.N;
+    const int64_t m = e / E.N, n = e - m * E.N;
+    float s = E.P[e];
+    for (int k = 1; k < E.split; ++k) s = __fadd_rn(s, E.P[k * mn + e]);
+    float *dst = E.C + m * E.ldc + n;
+    *dst = E.accumulate ? __fadd_rn(*dst, s) : s;
 }
 
 // zero an M x N window of C (split-K accumulates with atomics); a plain kernel instead of
@@ -477,9 +620,84 @@ constexpr int64_t kSplitTarget = 512;   // split-K: workgroups to aim for when t
 
 }  // namespace
 
+// Tile, kernel and split-K decomposition of one GEMM: a function of the shape alone, so that the deterministic
+// workspace query (hm_gemm_f32_det_workspace_bytes) and the launch agree.
+struct GemmPlan {
+    bool big, use_pipe, pipe_ok, m96;
+    int64_t bm, bn, split, k_chunk;
+};
+static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool has_ep) {
+    GemmPlan P;
+    const bool a_kc = !transA, b_kc = transB != 0;
+    // tile choice: big tiles only when they still fill the chip
+    const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
+    P.big = t128 >= 256;
+    // (128x64 / 64x128 tiles and a forced 128x128 tile were measured too: 30-45 % slower on M = 1750...4822; 32-row tiles
+    // for row counts whose 64-row grid gives a CU fewer than two workgroups made the training step 2 % SLOWER - twice the
+    // B-panel traffic outweighs the extra overlap)
+    const int64_t t64 = ((M + 63) / 64) * ((N + 63) / 64);
+    // the pipelined kernel fetches through buffer descriptors with 32-bit offsets, so it takes operands below 2 GB only
+    // (every other operand runs on the generic kernel, which addresses rows in 64 bits), and K ranges that are a whole
+    // number of 128-deep groups per split (partial edge tiles are fine: clamped rows, guarded stores).  Its 16-byte loads
+    // need dword alignment only (probed: unaligned buffer_load_dwordx4 returns the right dwords), so k-contiguous operands
+    // with any leading dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K
+    // range runs to the next multiple of the stage group, that operand's descriptor returns zeros beyond its end (K = 445
+    // and 257 of the backward sweeps: 27 - 43 us on the generic kernel).
+    const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
+                  bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
+    const bool buf_ok = bytesA < (1ll << 31) && bytesB < (1ll << 31);
+    const bool k_whole = K % (kPipeBK * kPipeD) == 0;
+    // (K >= 192: below that the rounded-up range costs more than the generic kernel's guards - K = 72 of the filter banks)
+    // (and only where the generic kernel would not split K over workgroups: a tail runs as ONE chunk, so the small
+    //  M x N weight-gradient shapes of the eager path - K = number of points - keep their split-K launch)
+    const bool k_tail_ok = (!a_kc || !b_kc) && K >= 192 && (has_ep || t64 >= 256);
+    P.use_pipe = !P.big && K > 0 && buf_ok && (k_whole || k_tail_ok);
+    // 96-row tiles when they need fewer rounds of the chip per row of the tile (M = 3072, N = 512: 384 tiles of 64 rows -
+    // the slowest CU runs two = 128 rows' worth - against 256 tiles of 96)
+    const int64_t t96 = ((M + 95) / 96) * ((N + 63) / 64);
+    P.m96 = P.use_pipe && ((t96 + 255) / 256) * 96 < ((t64 + 255) / 256) * 64;
+    P.bm = P.big ? 128 : (P.m96 ? 96 : 64);
+    P.bn = P.big ? 128 : 64;
+    const int64_t kBK = P.big ? 32 : (P.use_pipe ? kPipeBK * kPipeD : 128);
+    const int64_t tiles = ((M + P.bm - 1) / P.bm) * ((N + P.bn - 1) / P.bn);
+    int64_t split = 1;
+    if (tiles < 256 && K >= 256 && !has_ep && !(P.use_pipe && !k_whole)) {   // (a nonlinear epilogue needs the
+                                                                             // full sum; a K tail is not split)
+        split = (kSplitTarget + tiles - 1) / tiles;
+        const int64_t max_split = K / 128;
+        if (split > max_split) split = max_split;
+        if (split < 1) split = 1;
+    }
+    int64_t k_chunk = (K + split - 1) / split;
+    k_chunk = ((k_chunk + kBK - 1) / kBK) * kBK;
+    if (k_chunk == 0) k_chunk = kBK;
+    // the pipelined kernel has no K tail: grow the chunk until it divides K (K = 6144 over 10 splits: 640 -> 768)
+    while (P.use_pipe && k_whole && K % k_chunk != 0 && k_chunk < K) k_chunk += kBK;
+    P.split = K > 0 ? (K + k_chunk - 1) / k_chunk : 1;
+    P.k_chunk = k_chunk;
+    // (whole K: the chunks divide it; K tail: ONE chunk of the rounded-up K, zeros beyond the slow operand's end)
+    P.pipe_ok = P.use_pipe && (k_whole ? K % k_chunk == 0 : P.split == 1);
+    return P;
+}
+
+// deterministic split-K: bytes of k-part slabs a call needs (0 when K is not split)
+static int64_t gemm_det_bytes(const GemmPlan &P, int64_t M, int64_t N) {
+    return P.split > 1 ? 4 * P.split * M * N : 0;
+}
+
+static int launch_part_reduce(const GemmReduceTable &t, hipStream_t st) {
+    if (t.end == 0) return HM_OK;
+    HM_CHECK_ARG((t.end + 255) / 256 < (1ll << 31), "hm_gemm_f32_det: too many elements for one reduce launch");
+    hipLaunchKernelGGL(gemm_part_reduce_kernel, dim3((unsigned)((t.end + 255) / 256)), dim3(256), 0, st, t);
+    return HM_OK;
+}
+
+// det: a split K goes through k-part slabs in ws (ws_bytes >= gemm_det_bytes) and gemm_part_reduce_kernel instead of
+// atomics; an unsplit K is the default launch (one adder per element)
 static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
                      const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
-                     const hm_gemm_epilogue *ep, void *stream) {
+                     const hm_gemm_epilogue *ep, void *stream, bool det = false, float *ws = nullptr,
+                     int64_t ws_bytes = 0) {
     HM_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "hm_gemm_f32: negative dimension");
     HM_CHECK_ARG(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "hm_gemm_f32: dimension too large");
     if (M == 0 || N == 0) return HM_OK;
@@ -513,57 +731,22 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     // (and the K range ends on a multiple of 4, so no k-group straddles the end)
     g.vecA = (a_kc && K % 4 == 0 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0) ? 1 : 0;
     g.vecB = (b_kc && K % 4 == 0 && ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15u) == 0) ? 1 : 0;
-    // tile choice: big tiles only when they still fill the chip
-    const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
-    const bool big = t128 >= 256;
-    // (128x64 / 64x128 tiles and a forced 128x128 tile were measured too: 30-45 % slower on M = 1750...4822; 32-row tiles
-    // for row counts whose 64-row grid gives a CU fewer than two workgroups made the training step 2 % SLOWER - twice the
-    // B-panel traffic outweighs the extra overlap)
-    const int64_t t64 = ((M + 63) / 64) * ((N + 63) / 64);
-    // the pipelined kernel fetches through buffer descriptors with 32-bit offsets, so it takes operands below 2 GB only
-    // (every other operand runs on the generic kernel, which addresses rows in 64 bits), and K ranges that are a whole
-    // number of 128-deep groups per split (partial edge tiles are fine: clamped rows, guarded stores).  Its 16-byte loads
-    // need dword alignment only (probed: unaligned buffer_load_dwordx4 returns the right dwords), so k-contiguous operands
-    // with any leading dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K
-    // range runs to the next multiple of the stage group, that operand's descriptor returns zeros beyond its end (K = 445
-    // and 257 of the backward sweeps: 27 - 43 us on the generic kernel).
+    const GemmPlan P = gemm_plan(transA, transB, M, N, K, lda, ldb, g.ep.mode != HM_EPI_NONE);
+    const bool big = P.big, m96 = P.m96, pipe_ok = P.pipe_ok;
+    const int64_t bm = P.bm, bn = P.bn, split = P.split;
     const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
                   bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
-    const bool buf_ok = bytesA < (1ll << 31) && bytesB < (1ll << 31);
-    const bool k_whole = K % (kPipeBK * kPipeD) == 0;
-    // (K >= 192: below that the rounded-up range costs more than the generic kernel's guards - K = 72 of the filter banks)
-    // (and only where the generic kernel would not split K over workgroups: a tail runs as ONE chunk, so the small
-    //  M x N weight-gradient shapes of the eager path - K = number of points - keep their split-K launch)
-    const bool k_tail_ok = (!a_kc || !b_kc) && K >= 192 && (g.ep.mode != HM_EPI_NONE || t64 >= 256);
-    const bool use_pipe = !big && K > 0 && buf_ok && (k_whole || k_tail_ok);
     g.nrecA = (int32_t)(bytesA < 0x7fffffff ? bytesA : 0x7fffffff);
     g.nrecB = (int32_t)(bytesB < 0x7fffffff ? bytesB : 0x7fffffff);
-    // 96-row tiles when they need fewer rounds of the chip per row of the tile (M = 3072, N = 512: 384 tiles of 64 rows -
-    // the slowest CU runs two = 128 rows' worth - against 256 tiles of 96)
-    const int64_t t96 = ((M + 95) / 96) * ((N + 63) / 64);
-    const bool m96 = use_pipe && ((t96 + 255) / 256) * 96 < ((t64 + 255) / 256) * 64;
-    const int64_t bm = big ? 128 : (m96 ? 96 : 64), bn = big ? 128 : 64;
-    const int64_t kBK = big ? 32 : (use_pipe ? kPipeBK * kPipeD : 128);
-    const int64_t tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    int64_t split = 1;
-    if (tiles < 256 && K >= 256 && g.ep.mode == HM_EPI_NONE && !(use_pipe && !k_whole)) {   // (a nonlinear epilogue needs the
-                                                                                          // full sum; a K tail is not split)
-        split = (kSplitTarget + tiles - 1) / tiles;
-        const int64_t max_split = K / 128;
-        if (split > max_split) split = max_split;
-        if (split < 1) split = 1;
+    g.k_chunk = (int)P.k_chunk;
+    const bool part = det && split > 1;
+    if (part) {
+        HM_CHECK_ARG(ws != nullptr && ws_bytes >= gemm_det_bytes(P, M, N), "hm_gemm_f32_det: workspace too small");
+        g.C = ws;
+        g.ldc = N;
     }
-    int64_t k_chunk = (K + split - 1) / split;
-    k_chunk = ((k_chunk + kBK - 1) / kBK) * kBK;
-    if (k_chunk == 0) k_chunk = kBK;
-    // the pipelined kernel has no K tail: grow the chunk until it divides K (K = 6144 over 10 splits: 640 -> 768)
-    while (use_pipe && k_whole && K % k_chunk != 0 && k_chunk < K) k_chunk += kBK;
-    split = K > 0 ? (K + k_chunk - 1) / k_chunk : 1;
-    g.k_chunk = (int)k_chunk;
-    // (whole K: the chunks divide it; K tail: ONE chunk of the rounded-up K, zeros beyond the slow operand's end)
-    const bool pipe_ok = use_pipe && (k_whole ? K % k_chunk == 0 : split == 1);
     g.atomic = (accumulate || split > 1) ? 1 : 0;
-    if (split > 1 && !accumulate) {
+    if (split > 1 && !accumulate && !part) {
         // split-K accumulates with atomics into a zeroed C
         hipLaunchKernelGGL(zero_window_kernel, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, as_stream(stream),
                            C, ldc, M, N);
@@ -591,7 +774,35 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
             hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, false, false, false, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
     } while (0)
     hipStream_t st = as_stream(stream);
-    if (big)
+    if (part) {
+        // (big tiles are never split: they are taken only when the tile grid alone fills the chip)
+        if (pipe_ok) {
+            const bool a_kc = !transA, b_kc = transB != 0;
+#define HM_PART_PIPE(AKC_, BKC_)                                                                                   \
+    do {                                                                                                          \
+        if (m96) hipLaunchKernelGGL((gemm_f32_pipe2_m96_part_kernel<AKC_, BKC_>), grid, dim3(768), 0, st, g);     \
+        else hipLaunchKernelGGL((gemm_f32_pipe2_part_kernel<AKC_, BKC_>), grid, dim3(512), 0, st, g);             \
+    } while (0)
+            if (a_kc && b_kc) HM_PART_PIPE(true, true);
+            else if (a_kc) HM_PART_PIPE(true, false);
+            else if (b_kc) HM_PART_PIPE(false, true);
+            else HM_PART_PIPE(false, false);
+#undef HM_PART_PIPE
+        } else if (g.vecA && g.vecB)
+            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, true, true>), grid, dim3(512), 0, st, g);
+        else if (g.vecA)
+            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, true, false>), grid, dim3(512), 0, st, g);
+        else if (g.vecB)
+            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, false, true>), grid, dim3(512), 0, st, g);
+        else
+            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, false, false>), grid, dim3(512), 0, st, g);
+        GemmReduceTable t;
+        t.n = 1;
+        t.end = M * N;
+        t.e[0] = GemmReduceEntry{ws, C, ldc, 0, (int32_t)M, (int32_t)N, (int32_t)split, accumulate ? 1 : 0};
+        const int rc = launch_part_reduce(t, st);
+        if (rc != HM_OK) return rc;
+    } else if (big)
         HM_GEMM_LAUNCH(2, 2, 32, 1, 2);
     else if (pipe_ok) {
 #define HM_PIPE_LAUNCH(AKC_, BKC_)                                                                                \
@@ -674,6 +885,124 @@ int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, void *str
         ++t.n;
     }
     return flush();
+}
+
+int64_t hm_gemm_f32_det_workspace_bytes(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return gemm_det_bytes(gemm_plan(transA, transB, M, N, K, lda, ldb, false), M, N);
+}
+
+int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
+                    const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
+                    void *workspace, int64_t workspace_bytes, void *stream) {
+    return gemm_impl(transA, transB, M, N, K, A, lda, B, ldb, bias, C, ldc, accumulate, nullptr, stream, true,
+                     static_cast<float *>(workspace), workspace_bytes);
+}
+
+// Deterministic grouped call: the same problem table and k parts as hm_gemm_f32_group_tn, partials to workspace slabs
+// (one launch), then one gemm_part_reduce_kernel launch for all problems of the table.  With run = false only the
+// workspace need is computed (hm_gemm_f32_group_tn_det_workspace_bytes): the largest table's slabs, or the largest need
+// of a problem that goes alone - the launches of a call follow each other on one stream, so they share the buffer.
+static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws, int64_t ws_bytes, void *stream, bool run,
+                        int64_t *need) {
+    HM_CHECK_ARG(n_items >= 0 && (n_items == 0 || items), "hm_gemm_f32_group_tn_det: bad argument");
+    *need = 0;
+    // byte window of a problem's C: the reduce kernel gives every C element ONE thread, so two problems of one table
+    // must not overlap - a problem that overlaps one already in the table starts the next table (the two sums are then
+    // added in item order, by two launches)
+    auto window = [](const hm_gemm_group_item &it, uintptr_t &w0, uintptr_t &w1) {
+        w0 = reinterpret_cast<uintptr_t>(it.C);
+        w1 = w0 + 4 * ((it.M - 1) * it.ldc + it.N);
+    };
+    int in_table[HM_GEMM_GROUP_MAX];   // item index of every table entry
+    GemmGroupTable t;
+    GemmReduceTable r;
+    int64_t off = 0;   // floats of workspace the current table uses
+    t.n = r.n = 0;
+    t.start[0] = 0;
+    r.end = 0;
+    hipStream_t st = as_stream(stream);
+    auto flush = [&]() -> int {
+        if (4 * off > *need) *need = 4 * off;
+        if (t.n > 0 && run) {
+            HM_CHECK_ARG(ws != nullptr && ws_bytes >= 4 * off, "hm_gemm_f32_group_tn_det: workspace too small");
+            for (int p = 0; p < t.n; ++p) t.e[p].C = ws + reinterpret_cast<uintptr_t>(t.e[p].C);   // slab offsets -> pointers
+            for (int p = 0; p < r.n; ++p) r.e[p].P = ws + reinterpret_cast<uintptr_t>(r.e[p].P);
+            hipLaunchKernelGGL(gemm_f32_pipe2_group_part_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
+            const int rc = launch_part_reduce(r, st);
+            if (rc != HM_OK) return rc;
+            HM_CHECK_LAUNCH("hm_gemm_f32_group_tn_det");
+        }
+        t.n = r.n = 0;
+        t.start[0] = 0;
+        r.end = 0;
+        off = 0;
+        return HM_OK;
+    };
+    for (int i = 0; i < n_items; ++i) {
+        const hm_gemm_group_item &it = items[i];
+        HM_CHECK_ARG(it.M >= 0 && it.N >= 0 && it.K >= 0 && it.M < (1ll << 31) && it.N < (1ll << 31) && it.K < (1ll << 31),
+                     "hm_gemm_f32_group_tn_det: bad dimension");
+        if (it.M == 0 || it.N == 0 || it.K == 0) continue;
+        HM_CHECK_ARG(!run || (it.A && it.B && it.C && it.lda >= it.M && it.ldb >= it.N && it.ldc >= it.N),
+                     "hm_gemm_f32_group_tn_det: NULL operand or leading dimension");
+        if (it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31)) {
+            // the same problems as in hm_gemm_f32_group_tn go alone
+            const int64_t b = gemm_det_bytes(gemm_plan(1, 0, it.M, it.N, it.K, it.lda, it.ldb, false), it.M, it.N);
+            if (b > *need) *need = b;
+            if (run) {
+                const int rc = gemm_impl(1, 0, it.M, it.N, it.K, it.A, it.lda, it.B, it.ldb, nullptr, it.C, it.ldc, 1,
+                                         nullptr, stream, true, ws, ws_bytes);
+                if (rc != HM_OK) return rc;
+            }
+            continue;
+        }
+        bool overlap = false;
+        for (int p = 0; p < t.n && !overlap; ++p) {
+            uintptr_t a0, a1, b0, b1;
+            window(it, a0, a1);
+            window(items[in_table[p]], b0, b1);
+            overlap = !(a1 <= b0 || b1 <= a0);
+        }
+        if (t.n == HM_GEMM_GROUP_MAX || overlap) {
+            const int rc = flush();
+            if (rc != HM_OK) return rc;
+        }
+        in_table[t.n] = i;
+        int64_t split = it.K / 1024;     // k parts as in hm_gemm_f32_group_tn
+        if (split < 1) split = 1;
+        if (split > 4) split = 4;
+        while (split > 1 && (it.K % split != 0 || (it.K / split) % (kPipeBK * kPipeD) != 0)) --split;
+        GemmGroupEntry &E = t.e[t.n];
+        E.A = it.A; E.B = it.B;
+        E.C = reinterpret_cast<float *>(static_cast<uintptr_t>(off));   // slab offset until flush
+        E.lda = it.lda; E.ldb = it.ldb; E.ldc = it.N;
+        E.M = (int32_t)it.M; E.N = (int32_t)it.N;
+        E.tiles_m = (int32_t)((it.M + 63) / 64);
+        E.tiles_n = (int32_t)((it.N + 63) / 64);
+        E.split = (int32_t)split;
+        E.k_chunk = (int32_t)(it.K / split);
+        t.start[t.n + 1] = t.start[t.n] + E.tiles_m * E.tiles_n * E.split;
+        r.e[r.n] = GemmReduceEntry{reinterpret_cast<const float *>(static_cast<uintptr_t>(off)), it.C, it.ldc, r.end,
+                                   (int32_t)it.M, (int32_t)it.N, (int32_t)split, 1};
+        r.end += it.M * it.N;
+        off += split * it.M * it.N;
+        ++t.n;
+        ++r.n;
+    }
+    return flush();
+}
+
+int64_t hm_gemm_f32_group_tn_det_workspace_bytes(const hm_gemm_group_item *items, int n_items) {
+    int64_t need = 0;
+    if (group_tn_det(items, n_items, nullptr, 0, nullptr, false, &need) != HM_OK) return -1;
+    return need;
+}
+
+int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void *workspace, int64_t workspace_bytes,
+                             void *stream) {
+    int64_t need = 0;
+    return group_tn_det(items, n_items, static_cast<float *>(workspace), workspace_bytes, stream, true, &need);
 }
 
 int hm_gemm_f32_ep(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,

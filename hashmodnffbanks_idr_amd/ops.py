@@ -15,6 +15,56 @@ from ._lib import check, dptr, lib, require_gpu, stream_ptr
 FRAC_MODES = {"reference": 0, "trilinear": 1}
 
 
+# =========================================================================================
+# deterministic mode (DESIGN.md "Deterministic mode")
+# =========================================================================================
+_DETERMINISTIC = []     # stack of the active deterministic(...) contexts' settings (module-wide, not thread-local:
+                        # autograd runs the backward nodes on a thread of its own)
+
+
+class deterministic:
+    """``with ops.deterministic():`` - every reduction of the library runs without fp32 atomics, in an order that
+    depends on shapes and indices only, so that a training step is bitwise reproducible: gemm / gemm_group_tn split K
+    through k-part workspaces, the column sums through slab workspaces, encode_bwd_table sorts its contributions.
+    Nestable; ``deterministic(False)`` switches the mode off inside an outer context.  Outside every context the mode
+    follows ``torch.are_deterministic_algorithms_enabled()``."""
+
+    def __init__(self, enabled=True):
+        self.enabled = bool(enabled)
+
+    def __enter__(self):
+        _DETERMINISTIC.append(self.enabled)
+        return self
+
+    def __exit__(self, *exc):
+        _DETERMINISTIC.pop()
+
+
+def is_deterministic():
+    """the innermost deterministic(...) setting, else torch's deterministic-algorithms flag"""
+    return _DETERMINISTIC[-1] if _DETERMINISTIC else torch.are_deterministic_algorithms_enabled()
+
+
+_DET_WS = {}        # device -> uint8 workspace of the deterministic reductions (shared: one stream orders their use)
+_DET_WS_OLD = []    # outgrown workspaces stay allocated: a captured graph may still name them
+
+
+def _det_workspace(device, need):
+    """(pointer, bytes) of the per-device workspace, grown to `need` bytes outside a graph capture"""
+    if need <= 0:
+        return None, 0
+    ws = _DET_WS.get(device)
+    if ws is None or ws.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"hashmod deterministic mode: a {need}-byte workspace is needed during graph capture; "
+                               "run the captured work once eagerly first (warm-up) so that it is sized beforehand")
+        if ws is not None:
+            _DET_WS_OLD.append(ws)
+            need = max(need, 2 * ws.numel())
+        ws = _DET_WS[device] = torch.empty(need, dtype=torch.uint8, device=device)
+    return dptr(ws), ws.numel()
+
+
 def level_table(n_levels, log2_hashmap_size, base_resolution, desired_resolution, in_dim=3):
     """res[l], rows[l] in host double precision, the arithmetic of
     reference model/embeddings/hashGridEmbedding.py:126-132 (Python ``math``, not fp32)."""
@@ -108,10 +158,13 @@ def encode_fwd(desc, x, table, B, frac_mode=0, hash_only=False):
     return out
 
 
-def encode_bwd_table(desc, x, d_feat, frac_mode=0, out=None, deterministic=False):
+def encode_bwd_table(desc, x, d_feat, frac_mode=0, out=None, deterministic=None):
     """Scatter-add of the hash-feature gradient d_feat [N,L*F] into a [rows,F] table gradient.
     deterministic: sort the contributions by destination row (sort_pairs: the library's stable radix sort) and sum each row's run in one thread
-    (hm_encode_rows + hm_encode_bwd_table_sorted) instead of fp32 atomics - bitwise reproducible."""
+    (hm_encode_rows + hm_encode_bwd_table_sorted) instead of fp32 atomics - bitwise reproducible.  None follows
+    is_deterministic()."""
+    if deterministic is None:
+        deterministic = is_deterministic()
     x = _prep_x(x)
     require_gpu(x, d_feat)
     n = x.shape[0]
@@ -121,12 +174,8 @@ def encode_bwd_table(desc, x, d_feat, frac_mode=0, out=None, deterministic=False
     if out is None:
         out = torch.zeros((desc.total_rows, desc.F), dtype=torch.float32, device=x.device)
     if deterministic and n > 0:
-        corners = 1 if int(frac_mode) == 0 else 8
-        keys = torch.empty(n * desc.L * corners, dtype=torch.int32, device=x.device)
-        wts = torch.empty(n * desc.L * corners, dtype=torch.float32, device=x.device) if corners == 8 else None
-        check(lib().hm_encode_rows(desc.handle, dptr(x), n, int(frac_mode), dptr(keys), dptr(wts), stream_ptr(x)))
-        skeys, perm = sort_pairs(keys, max(int(desc.total_rows - 1).bit_length(), 1))
-        check(lib().hm_encode_bwd_table_sorted(desc.handle, dptr(skeys), dptr(perm), keys.numel(), corners, dptr(d_feat),
+        corners, skeys, perm, wts = sorted_rows(desc, x, frac_mode)
+        check(lib().hm_encode_bwd_table_sorted(desc.handle, dptr(skeys), dptr(perm), skeys.numel(), corners, dptr(d_feat),
                                                d_feat.stride(0), dptr(wts), dptr(out), stream_ptr(x)))
         return out
     if n >= 131072 and desc.F == 2:     # big launches: z-ordered, LDS-privatised scatter (needs scratch)
@@ -140,6 +189,18 @@ def encode_bwd_table(desc, x, d_feat, frac_mode=0, out=None, deterministic=False
     check(lib().hm_encode_bwd_table(desc.handle, dptr(x), n, dptr(d_feat), d_feat.stride(0), dptr(out),
                                     int(frac_mode), stream_ptr(x)))
     return out
+
+
+def sorted_rows(desc, x, frac_mode=0):
+    """(corners, destination rows sorted, permutation, corner weights or None) of the table-gradient contributions of
+    the points x: hm_encode_rows + sort_pairs, the first half of the deterministic scatter"""
+    n = x.shape[0]
+    corners = 1 if int(frac_mode) == 0 else 8
+    keys = torch.empty(n * desc.L * corners, dtype=torch.int32, device=x.device)
+    wts = torch.empty(n * desc.L * corners, dtype=torch.float32, device=x.device) if corners == 8 else None
+    check(lib().hm_encode_rows(desc.handle, dptr(x), n, int(frac_mode), dptr(keys), dptr(wts), stream_ptr(x)))
+    skeys, perm = sort_pairs(keys, max(int(desc.total_rows - 1).bit_length(), 1))
+    return corners, skeys, perm, wts
 
 
 _SORT_WS = {}
@@ -229,6 +290,9 @@ class _HashInputGrad(torch.autograd.Function):
             check(lib().hm_encode_bwd_input(desc.handle, dptr(x), n, dptr(table), dptr(d_feat), _ld(d_feat),
                                             dptr(gg_x), dptr(d_x), stream_ptr(x)))
         if ctx.needs_input_grad[1]:
+            if is_deterministic():
+                raise NotImplementedError("hashmod deterministic mode: the trilinear encoder's second-order table term "
+                                          "(hm_encode_bwd_table_jvp) scatters with atomics; use frac_mode='reference'")
             d_table = torch.zeros_like(table)
             check(lib().hm_encode_bwd_table_jvp(desc.handle, dptr(x), n, dptr(gg_x), dptr(d_feat), _ld(d_feat),
                                                 dptr(d_table), stream_ptr(x)))
@@ -344,6 +408,12 @@ def gemm(a, b, bias=None, trans_a=False, trans_b=False, out=None, accumulate=Fal
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     if bias is not None:
         bias = bias.contiguous()
+    if is_deterministic():
+        need = check(lib().hm_gemm_f32_det_workspace_bytes(int(trans_a), int(trans_b), M, N, K, _ld(a), _ld(b)))
+        ws, nb = _det_workspace(a.device, need)
+        check(lib().hm_gemm_f32_det(int(trans_a), int(trans_b), M, N, K, dptr(a), _ld(a), dptr(b), _ld(b), dptr(bias),
+                                    dptr(out), _ld(out), int(accumulate), ws, nb, stream_ptr(a)))
+        return out
     check(lib().hm_gemm_f32(int(trans_a), int(trans_b), M, N, K, dptr(a), _ld(a), dptr(b), _ld(b), dptr(bias),
                             dptr(out), _ld(out), int(accumulate), stream_ptr(a)))
     return out
@@ -367,6 +437,12 @@ def gemm_group_tn(problems):
             raise ValueError(f"hashmod gemm_group_tn: shapes {tuple(a.shape)}^T @ {tuple(b.shape)} -> {tuple(c.shape)}")
         keep += [a, b]
         items[i] = _lib.GemmGroupItem(a.data_ptr(), b.data_ptr(), c.data_ptr(), M, N, K, _ld(a), _ld(b), _ld(c))
+    if is_deterministic():
+        need = check(lib().hm_gemm_f32_group_tn_det_workspace_bytes(C.cast(items, C.c_void_p), len(problems)))
+        ws, nb = _det_workspace(problems[0][0].device, need)
+        check(lib().hm_gemm_f32_group_tn_det(C.cast(items, C.c_void_p), len(problems), ws, nb,
+                                             stream_ptr(problems[0][0])))
+        return
     check(lib().hm_gemm_f32_group_tn(C.cast(items, C.c_void_p), len(problems), stream_ptr(problems[0][0])))
 
 
@@ -824,6 +900,11 @@ class _ColSum(torch.autograd.Function):
         if x.stride(-1) != 1:
             x = x.contiguous()
         out = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
+        if is_deterministic():
+            ws, nb = _det_workspace(x.device, check(lib().hm_colsum_det_workspace_bytes(x.shape[0], x.shape[1])))
+            check(lib().hm_colsum_det(dptr(x), x.shape[0], x.shape[1], max(x.stride(0), 1), dptr(out), ws, nb,
+                                      stream_ptr(x)))
+            return out
         check(lib().hm_colsum(dptr(x), x.shape[0], x.shape[1], max(x.stride(0), 1), dptr(out), stream_ptr(x)))
         return out
 
@@ -934,6 +1015,10 @@ def colsum_into(x, out):
     """out += column sums of x (no autograd; `out` zeroed by the caller)."""
     require_gpu(x, out)
     x = _rowmajor(x)
+    if is_deterministic():
+        ws, nb = _det_workspace(x.device, check(lib().hm_colsum_det_workspace_bytes(x.shape[0], x.shape[1])))
+        check(lib().hm_colsum_acc_det(dptr(x), x.shape[0], x.shape[1], _ld(x), dptr(out), ws, nb, stream_ptr(x)))
+        return out
     check(lib().hm_colsum_acc(dptr(x), x.shape[0], x.shape[1], _ld(x), dptr(out), stream_ptr(x)))
     return out
 
@@ -949,6 +1034,11 @@ def colsum_into_multi(pairs):
         x = _rowmajor(x)
         keep.append(x)
         items[i] = _lib.ColsumItem(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], _ld(x))
+    if is_deterministic():
+        need = check(lib().hm_colsum_acc_multi_det_workspace_bytes(C.cast(items, C.c_void_p), len(pairs)))
+        ws, nb = _det_workspace(pairs[0][0].device, need)
+        check(lib().hm_colsum_acc_multi_det(C.cast(items, C.c_void_p), len(pairs), ws, nb, stream_ptr(pairs[0][0])))
+        return
     check(lib().hm_colsum_acc_multi(C.cast(items, C.c_void_p), len(pairs), stream_ptr(pairs[0][0])))
 
 

@@ -198,7 +198,7 @@ class TouchedRowExchange:
         self.rows, self.cap = new, int(new.numel())
 
     def add(self, x, d_feat):
-        from . import _lib
+        from . import _lib, ops
         x = x.detach().reshape(-1, 3)
         d_feat = d_feat.detach()
         if d_feat.stride(-1) != 1:
@@ -209,9 +209,17 @@ class TouchedRowExchange:
         elif self.param.grad.data_ptr() != self.dense.data_ptr():
             raise RuntimeError("TouchedRowExchange: table.grad was re-bound; call attach() after zero_grad()")
         self._ensure(self.cursor + n * self.emb.n_levels)
-        _lib.check(_lib.lib().hm_encode_bwd_table_tracked(
-            self.emb.desc.handle, _lib.dptr(x), n, _lib.dptr(d_feat), d_feat.stride(0), _lib.dptr(self.dense), 0,
-            _lib.dptr(self.bits), _lib.dptr(self.count), _lib.dptr(self.rows), self.cap, _lib.stream_ptr(x)))
+        if ops.is_deterministic() and n > 0:
+            # sorted run sums instead of atomics (ops.deterministic): the same dense values run after run, the same rows
+            corners, skeys, perm, wts = ops.sorted_rows(self.emb.desc, x.contiguous(), 0)
+            _lib.check(_lib.lib().hm_encode_bwd_table_sorted_tracked(
+                self.emb.desc.handle, _lib.dptr(skeys), _lib.dptr(perm), skeys.numel(), corners, _lib.dptr(d_feat),
+                d_feat.stride(0), _lib.dptr(wts), _lib.dptr(self.dense), _lib.dptr(self.bits), _lib.dptr(self.count),
+                _lib.dptr(self.rows), self.cap, _lib.stream_ptr(x)))
+        else:
+            _lib.check(_lib.lib().hm_encode_bwd_table_tracked(
+                self.emb.desc.handle, _lib.dptr(x), n, _lib.dptr(d_feat), d_feat.stride(0), _lib.dptr(self.dense), 0,
+                _lib.dptr(self.bits), _lib.dptr(self.count), _lib.dptr(self.rows), self.cap, _lib.stream_ptr(x)))
         self.cursor += n * self.emb.n_levels
 
 

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from .. import _lib
+from .. import _lib, ops
 from ..model.loss import idr_loss_terms
 
 
@@ -47,7 +47,6 @@ class LocalTableGrad:
         self.param.grad = self.dense
 
     def add(self, x, d_feat):
-        from .. import ops
         if self.param.grad is None:
             self.param.grad = self.dense
         elif self.param.grad.data_ptr() != self.dense.data_ptr():
@@ -72,9 +71,15 @@ def local_table_grads(model):
 
 
 class GraphedTrainStep:
+    """deterministic: run the warm-up, the capture and every eager iteration under ops.deterministic(deterministic), so
+    that the graphs record the library's atomic-free reductions and two runs from the same seeds give the same bits;
+    None takes ops.is_deterministic() at construction (a surrounding ops.deterministic() or
+    torch.use_deterministic_algorithms(True))."""
+
     def __init__(self, model, loss_fn, optimizer, reducer=None, max_norm=1.0, warmup=3, use_graph=True,
-                 sync_each_step=None):
+                 sync_each_step=None, deterministic=None):
         self.model, self.loss_fn, self.opt, self.reducer = model, loss_fn, optimizer, reducer
+        self.deterministic = ops.is_deterministic() if deterministic is None else bool(deterministic)
         # single process: the hash tables' gradients accumulate in one static dense tensor each (LocalTableGrad);
         # HM_LOCAL_TABLE_GRAD=0 keeps autograd's per-node dense gradients (A/B)
         self.local_tables = (local_table_grads(model)
@@ -181,6 +186,10 @@ class GraphedTrainStep:
 
     # -- driver -------------------------------------------------------------------------------
     def step(self, model_input, ground_truth):
+        with ops.deterministic(self.deterministic):
+            return self._step(model_input, ground_truth)
+
+    def _step(self, model_input, ground_truth):
         dev = model_input["uv"].device
         n_rays = model_input["uv"].shape[0] * model_input["uv"].shape[1]
         steps, eik, ev = self._draws(n_rays, dev)

@@ -550,6 +550,38 @@ typedef struct hm_gemm_group_item {
 } hm_gemm_group_item;
 HM_API int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, void *stream);
 
+/* ---- deterministic mode (ops.deterministic; DESIGN.md "Deterministic mode") -------------------------------------
+ * Bitwise reproducible forms of the reductions above: no fp32 atomics, a summation order that depends on shapes and
+ * indices only.  Each takes a caller-owned device workspace of at least the matching *_workspace_bytes() bytes (0 when
+ * nothing is split) and is sync-free and graph-capturable (kernel launches only).
+ *
+ * hm_gemm_f32 (the reference's grad_weight / grad_input / forward products, implicit_differentiable_renderer.py:102,
+ * 116-128,211-221): the same tiles and split-K decomposition; every (tile, k part) stores its partial tile to the
+ * workspace, a second launch forms C = C_old + (((p0 + p1) + p2) + ...) (accumulate) or C = ((p0 + p1) + ...) in k-part
+ * order.  An unsplit K is the plain launch (one adder per element).  (hm_gemm_f32_ep never splits K.)              */
+HM_API int64_t hm_gemm_f32_det_workspace_bytes(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda,
+                                               int64_t ldb);
+HM_API int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
+                           const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+/* hm_gemm_f32_group_tn (the weight gradients of one backward pass): the same problem table and k parts, partials of
+ * every problem to the workspace in one launch, one reduce launch for all problems.  Items whose C windows overlap
+ * (two terms of one weight gradient) go to consecutive launches and are added in item order.  The workspace query
+ * returns -1 on a bad item.                                                                                        */
+HM_API int64_t hm_gemm_f32_group_tn_det_workspace_bytes(const hm_gemm_group_item *items, int n_items);
+HM_API int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void *workspace,
+                                    int64_t workspace_bytes, void *stream);
+/* hm_colsum / hm_colsum_acc / hm_colsum_acc_multi (nn.Linear bias gradients): slab partials to the workspace, then
+ * summed per column in slab order - two launches per call (per HM_COLSUM_MAX_ITEMS items for the list form).       */
+HM_API int64_t hm_colsum_det_workspace_bytes(int64_t M, int64_t N);
+HM_API int hm_colsum_det(const float *x, int64_t M, int64_t N, int64_t ld, float *out, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+HM_API int hm_colsum_acc_det(const float *x, int64_t M, int64_t N, int64_t ld, float *out, void *workspace,
+                             int64_t workspace_bytes, void *stream);
+HM_API int64_t hm_colsum_acc_multi_det_workspace_bytes(const hm_colsum_item *items, int n_items);
+HM_API int hm_colsum_acc_multi_det(const hm_colsum_item *items, int n_items, void *workspace, int64_t workspace_bytes,
+                                   void *stream);
+
 /* ---- data-parallel gradient exchange (device side) ---------------------------------------------------
  * The reference runner is single-GPU (training/idr_train.py:92-93,278-321): there is no interface to
  * replace, the exchange is the build's own addition in the place the north star names - between loss.backward()
@@ -569,6 +601,16 @@ HM_API int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, vo
 HM_API int hm_encode_bwd_table_tracked(const hm_grid_desc *desc, const float *x, int64_t n, const float *d_feat,
                                        int64_t d_feat_stride, float *d_table, int frac_mode, uint32_t *touched_bits,
                                        int32_t *touched_count, int32_t *touched_rows, int64_t cap, void *stream);
+/* Deterministic hm_encode_bwd_table_tracked (the hash-table scatter_add of hashGridEmbedding.py's backward, for the
+ * data-parallel exchange): hm_encode_bwd_table_sorted's run sums over the output of hm_encode_rows ->
+ * hm_sort_pairs_i32, and the head of every run with a nonzero weight claims its row's bit and a slot of touched_rows -
+ * the same bits, count, cap and overflow semantics as hm_encode_bwd_table_tracked.  The dense values are
+ * reproducible; the order of the list is not (hm_rows_apply does not depend on it).                              */
+HM_API int hm_encode_bwd_table_sorted_tracked(const hm_grid_desc *desc, const int32_t *keys_sorted,
+                                              const int64_t *perm, int64_t n_keys, int corners, const float *d_feat,
+                                              int64_t d_feat_stride, const float *weights, float *d_table,
+                                              uint32_t *touched_bits, int32_t *touched_count, int32_t *touched_rows,
+                                              int64_t cap, void *stream);
 HM_API int hm_rows_pack(float *d_table, int n_features, const int32_t *touched_rows, const int32_t *touched_count,
                         int64_t cap, uint32_t *touched_bits, int32_t *payload, int32_t *status, void *stream);
 HM_API int hm_rows_apply(float *d_table, int64_t total_rows, int n_features, const int32_t *lists, int64_t cap,
