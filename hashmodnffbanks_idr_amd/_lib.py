@@ -72,8 +72,10 @@ SIGNATURES = {
     "hm_copy2d_f32": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p]),
     "hm_camera_rays": (_int, [_p, _p, _p, _i64, _i64, C.c_float, _p, _p, _p, _p, _p]),
     "hm_idr_loss": (_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, C.c_float, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
+    "hm_idr_loss_dev": (_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "hm_adam_scratch_floats": (_i64, [_p, _int]),
     "hm_adam_step": (_int, [_p, _int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _p, _p]),
+    "hm_adam_step_dev": (_int, [_p, _int, _p, _int, _p, _p]),
     "hm_encode_bwd_table_tracked": (_int, [_p, _p, _i64, _p, _i64, _p, _int, _p, _p, _p, _i64, _p]),
     "hm_rows_pack": (_int, [_p, _int, _p, _p, _i64, _p, _p, _p, _p]),
     "hm_rows_apply": (_int, [_p, _i64, _int, _p, _i64, _i64, _int, C.c_float, _p]),
@@ -171,6 +173,23 @@ def param_epoch():
 
 def bump_param_epoch():
     _param_epoch[0] += 1
+
+
+class PinnedRing:
+    """Host staging of asynchronous host->device copies: two slots of pinned tensors of the given shapes, each guarded by
+    an event.  slot() returns (*tensors, event) after the copies that last read that slot have completed; the caller
+    fills the tensors, enqueues its copies (non_blocking) and records the event.  A copy engine that reads a source
+    after the host has rewritten it copies the wrong values, and one whose source has been freed faults."""
+
+    def __init__(self, *shapes):
+        self._slots = [([torch.empty(s).pin_memory() for s in shapes], torch.cuda.Event()) for _ in range(2)]
+        self._next = 0
+
+    def slot(self):
+        bufs, ev = self._slots[self._next]
+        self._next ^= 1
+        ev.synchronize()
+        return (*bufs, ev)
 
 
 def lib():

@@ -27,14 +27,22 @@ __device__ __forceinline__ float block_sum(float v, float *red) {
     return s;
 }
 
+// kDevHyper: w_eik, w_mask, alpha are read from hyper_dev[3] when the kernel runs (a captured step follows the
+// runner's alpha schedule); the by-value arguments are ignored.  The same arithmetic either way.
+template <bool kDevHyper>
 __global__ __launch_bounds__(kLT) void idr_loss_kernel(const float *__restrict__ rgb, const float *__restrict__ rgb_gt,
                                                        const float *__restrict__ sdf, const uint8_t *__restrict__ hit,
                                                        const uint8_t *__restrict__ inside, int64_t n,
                                                        const float *__restrict__ grad_theta, int64_t m, float w_eik,
-                                                       float w_mask, float alpha, float *__restrict__ terms,
-                                                       float *__restrict__ d_rgb, float *__restrict__ d_sdf,
-                                                       float *__restrict__ d_grad) {
+                                                       float w_mask, float alpha, const float *__restrict__ hyper_dev,
+                                                       float *__restrict__ terms, float *__restrict__ d_rgb,
+                                                       float *__restrict__ d_sdf, float *__restrict__ d_grad) {
     __shared__ float red[kLT / 64];
+    if constexpr (kDevHyper) {
+        w_eik = hyper_dev[0];
+        w_mask = hyper_dev[1];
+        alpha = hyper_dev[2];
+    }
     const float inv_n = 1.0f / (float)n;
     float s_rgb = 0.0f, s_mask = 0.0f, s_eik = 0.0f;
     for (int64_t i = threadIdx.x; i < n; i += kLT) {
@@ -88,10 +96,24 @@ int hm_idr_loss(const float *rgb, const float *rgb_gt, const float *sdf, const u
     HM_CHECK_ARG(rgb && rgb_gt && sdf && hit && inside && terms && d_rgb && d_sdf, "hm_idr_loss: NULL pointer");
     HM_CHECK_ARG(n_grad == 0 || (grad_theta && d_grad), "hm_idr_loss: NULL grad_theta pointer");
     HM_CHECK_ARG(alpha > 0.0f, "hm_idr_loss: alpha must be positive");
-    hipLaunchKernelGGL(idr_loss_kernel, dim3(1), dim3(kLT), 0, reinterpret_cast<hipStream_t>(stream), rgb, rgb_gt, sdf,
-                       hit, inside, n_rays, grad_theta, n_grad, eikonal_weight, mask_weight, alpha, terms, d_rgb, d_sdf,
-                       d_grad);
+    hipLaunchKernelGGL(idr_loss_kernel<false>, dim3(1), dim3(kLT), 0, reinterpret_cast<hipStream_t>(stream), rgb, rgb_gt,
+                       sdf, hit, inside, n_rays, grad_theta, n_grad, eikonal_weight, mask_weight, alpha, nullptr, terms,
+                       d_rgb, d_sdf, d_grad);
     HM_CHECK_LAUNCH("hm_idr_loss");
+    return HM_OK;
+}
+
+int hm_idr_loss_dev(const float *rgb, const float *rgb_gt, const float *sdf, const uint8_t *hit, const uint8_t *inside,
+                    int64_t n_rays, const float *grad_theta, int64_t n_grad, const float *hyper_dev, float *terms,
+                    float *d_rgb, float *d_sdf, float *d_grad, void *stream) {
+    HM_CHECK_ARG(n_rays >= 1 && n_grad >= 0, "hm_idr_loss_dev: bad row counts");
+    HM_CHECK_ARG(rgb && rgb_gt && sdf && hit && inside && terms && d_rgb && d_sdf, "hm_idr_loss_dev: NULL pointer");
+    HM_CHECK_ARG(n_grad == 0 || (grad_theta && d_grad), "hm_idr_loss_dev: NULL grad_theta pointer");
+    HM_CHECK_ARG(hyper_dev, "hm_idr_loss_dev: NULL hyper-parameter pointer");
+    hipLaunchKernelGGL(idr_loss_kernel<true>, dim3(1), dim3(kLT), 0, reinterpret_cast<hipStream_t>(stream), rgb, rgb_gt,
+                       sdf, hit, inside, n_rays, grad_theta, n_grad, 0.0f, 0.0f, 1.0f, hyper_dev, terms, d_rgb, d_sdf,
+                       d_grad);
+    HM_CHECK_LAUNCH("hm_idr_loss_dev");
     return HM_OK;
 }
 

@@ -91,25 +91,35 @@ struct AdamHyper {
     float lr, beta1, beta2, eps, max_norm;
 };
 
-__global__ __launch_bounds__(kOT) void adam_update_kernel(AdamTable tb, AdamHyper hp, const float *norm_sq,
-                                                          float *norm_out) {
-    __shared__ float sh[3];  // clip coefficient, step size, 1/sqrt(bias_correction2)
+// kDevHyper: lr, beta1, beta2, eps, max_norm are read from hyper_dev[5] when the kernel runs (a captured step follows
+// schedules); the by-value hp is ignored.  Either way the same arithmetic, so equal values give the same bits.
+template <bool kDevHyper>
+__global__ __launch_bounds__(kOT) void adam_update_kernel(AdamTable tb, AdamHyper hp, const float *hyper_dev,
+                                                          const float *norm_sq, float *norm_out) {
+    __shared__ float sh[kDevHyper ? 6 : 3];  // clip coefficient, step size, 1/sqrt(bias_correction2) [, beta1, beta2, eps]
     const int ti = find_tensor(tb, blockIdx.x);
     const hm_adam_tensor T = tb.t[ti];
     if (threadIdx.x == 0) {
+        AdamHyper h = hp;
+        if constexpr (kDevHyper) {
+            h = AdamHyper{hyper_dev[0], hyper_dev[1], hyper_dev[2], hyper_dev[3], hyper_dev[4]};
+            sh[3] = h.beta1;
+            sh[4] = h.beta2;
+            sh[5] = h.eps;
+        }
         const float total = sqrtf(*norm_sq);
         float coef = 1.0f;
-        if (hp.max_norm > 0.0f) coef = fminf(hp.max_norm / (total + 1e-6f), 1.0f);   // clip_grad_norm_
+        if (h.max_norm > 0.0f) coef = fminf(h.max_norm / (total + 1e-6f), 1.0f);   // clip_grad_norm_
         const double t = (double)*T.step;
-        const double bc1 = 1.0 - pow((double)hp.beta1, t), bc2 = 1.0 - pow((double)hp.beta2, t);
+        const double bc1 = 1.0 - pow((double)h.beta1, t), bc2 = 1.0 - pow((double)h.beta2, t);
         sh[0] = coef;
-        sh[1] = (float)((double)hp.lr / bc1);
+        sh[1] = (float)((double)h.lr / bc1);
         sh[2] = (float)(1.0 / sqrt(bc2));
         if (blockIdx.x == 0 && norm_out) *norm_out = total;
     }
     __syncthreads();
     const float coef = sh[0], step_size = sh[1], rsq_bc2 = sh[2];
-    const float b1 = hp.beta1, b2 = hp.beta2, eps = hp.eps;
+    const float b1 = kDevHyper ? sh[3] : hp.beta1, b2 = kDevHyper ? sh[4] : hp.beta2, eps = kDevHyper ? sh[5] : hp.eps;
     const int64_t beg = (int64_t)(blockIdx.x - tb.chunk_start[ti]) * kChunk;
     const int64_t end = min(beg + kChunk, T.numel);
     auto upd = [&](float &p, float &g, float &m, float &v) {
@@ -141,36 +151,20 @@ __global__ __launch_bounds__(kOT) void adam_update_kernel(AdamTable tb, AdamHype
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-}  // namespace
-
-extern "C" {
-
-int64_t hm_adam_scratch_floats(const hm_adam_tensor *tensors, int n_tensors) {
-    if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return hm_fail(HM_ERR_INVALID, "hm_adam_scratch_floats: bad argument");
-    int64_t chunks = 0;
+// hyper_dev == NULL: the by-value hp, clipping when hp.max_norm > 0.  Otherwise the kernels read hyper_dev and the norm
+// kernels run when `clip` is set.
+int adam_step(const char *who, const hm_adam_tensor *tensors, int n_tensors, const AdamHyper &hp,
+              const float *hyper_dev, bool clip, float *scratch_dev, hipStream_t st) {
+    HM_CHECK_ARG(n_tensors >= 0, std::string(who) + ": negative tensor count");
+    HM_CHECK_ARG(scratch_dev, std::string(who) + ": NULL scratch pointer");
+    HM_CHECK_ARG(n_tensors == 0 || tensors, std::string(who) + ": NULL tensor table");
     for (int i = 0; i < n_tensors; ++i) {
-        if (tensors[i].numel < 0) return hm_fail(HM_ERR_INVALID, "hm_adam_scratch_floats: negative numel");
-        chunks += (tensors[i].numel + kChunk - 1) / kChunk;
-    }
-    return 2 + chunks;
-}
-
-int hm_adam_step(const hm_adam_tensor *tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
-                 float max_norm, float *scratch_dev, void *stream) {
-    HM_CHECK_ARG(n_tensors >= 0, "hm_adam_step: negative tensor count");
-    HM_CHECK_ARG(scratch_dev, "hm_adam_step: NULL scratch pointer");
-    HM_CHECK_ARG(n_tensors == 0 || tensors, "hm_adam_step: NULL tensor table");
-    HM_CHECK_ARG(lr >= 0.0f && beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f,
-                 "hm_adam_step: invalid hyper-parameter");
-    for (int i = 0; i < n_tensors; ++i) {
-        HM_CHECK_ARG(tensors[i].numel >= 0, "hm_adam_step: negative numel");
+        HM_CHECK_ARG(tensors[i].numel >= 0, std::string(who) + ": negative numel");
         HM_CHECK_ARG(tensors[i].numel == 0 || (tensors[i].param && tensors[i].grad && tensors[i].exp_avg &&
                                                tensors[i].exp_avg_sq && tensors[i].step),
-                     "hm_adam_step: NULL tensor pointer");
-        HM_CHECK_ARG(tensors[i].numel < ((int64_t)1 << 40), "hm_adam_step: tensor too large");
+                     std::string(who) + ": NULL tensor pointer");
+        HM_CHECK_ARG(tensors[i].numel < ((int64_t)1 << 40), std::string(who) + ": tensor too large");
     }
-    hipStream_t st = as_stream(stream);
-    const AdamHyper hp{lr, beta1, beta2, eps, max_norm};
     auto fill = [&](int first, AdamTable &tb) {  // table of up to kMaxT non-empty tensors starting at `first`
         tb.n = 0;
         tb.chunk_start[0] = 0;
@@ -189,34 +183,68 @@ int hm_adam_step(const hm_adam_tensor *tensors, int n_tensors, float lr, float b
     if (n_tensors == 0) return HM_OK;
     for (int first = 0, k = 0; first < n_tensors; ++k) {
         const int next = fill(first, tb);
-        HM_CHECK_ARG(next > first, "hm_adam_step: tensor too large for one launch");
+        HM_CHECK_ARG(next > first, std::string(who) + ": tensor too large for one launch");
         hipLaunchKernelGGL(adam_begin_kernel, dim3(1), dim3(128), 0, st, tb, scratch_dev, k == 0 ? 1 : 0);
         first = next;
     }
-    if (max_norm > 0.0f) {
+    if (clip) {
         int64_t n_part = 0;
         for (int first = 0; first < n_tensors;) {
             const int next = fill(first, tb);
-            HM_CHECK_ARG(next > first, "hm_adam_step: tensor too large for one launch");
+            HM_CHECK_ARG(next > first, std::string(who) + ": tensor too large for one launch");
             if (tb.n > 0)
                 hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)tb.chunk_start[tb.n]), dim3(kOT), 0, st, tb,
                                    scratch_dev + 2 + n_part);
             n_part += tb.chunk_start[tb.n];
             first = next;
         }
-        HM_CHECK_ARG(n_part < 0x7fffffff, "hm_adam_step: too many chunks");
+        HM_CHECK_ARG(n_part < 0x7fffffff, std::string(who) + ": too many chunks");
         hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(1024), 0, st, scratch_dev + 2, (int)n_part, scratch_dev);
     }
     for (int first = 0; first < n_tensors;) {
         const int next = fill(first, tb);
-        HM_CHECK_ARG(next > first, "hm_adam_step: tensor too large for one launch");
-        if (tb.n > 0)
-            hipLaunchKernelGGL(adam_update_kernel, dim3((unsigned)tb.chunk_start[tb.n]), dim3(kOT), 0, st, tb, hp,
-                               scratch_dev, scratch_dev + 1);
+        HM_CHECK_ARG(next > first, std::string(who) + ": tensor too large for one launch");
+        if (tb.n > 0) {
+            if (hyper_dev)
+                hipLaunchKernelGGL(adam_update_kernel<true>, dim3((unsigned)tb.chunk_start[tb.n]), dim3(kOT), 0, st, tb,
+                                   hp, hyper_dev, scratch_dev, scratch_dev + 1);
+            else
+                hipLaunchKernelGGL(adam_update_kernel<false>, dim3((unsigned)tb.chunk_start[tb.n]), dim3(kOT), 0, st,
+                                   tb, hp, hyper_dev, scratch_dev, scratch_dev + 1);
+        }
         first = next;
     }
-    HM_CHECK_LAUNCH("hm_adam_step");
+    HM_CHECK_LAUNCH(who);
     return HM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t hm_adam_scratch_floats(const hm_adam_tensor *tensors, int n_tensors) {
+    if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return hm_fail(HM_ERR_INVALID, "hm_adam_scratch_floats: bad argument");
+    int64_t chunks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (tensors[i].numel < 0) return hm_fail(HM_ERR_INVALID, "hm_adam_scratch_floats: negative numel");
+        chunks += (tensors[i].numel + kChunk - 1) / kChunk;
+    }
+    return 2 + chunks;
+}
+
+int hm_adam_step(const hm_adam_tensor *tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
+                 float max_norm, float *scratch_dev, void *stream) {
+    HM_CHECK_ARG(lr >= 0.0f && beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f,
+                 "hm_adam_step: invalid hyper-parameter");
+    return adam_step("hm_adam_step", tensors, n_tensors, AdamHyper{lr, beta1, beta2, eps, max_norm}, nullptr,
+                     max_norm > 0.0f, scratch_dev, as_stream(stream));
+}
+
+int hm_adam_step_dev(const hm_adam_tensor *tensors, int n_tensors, const float *hyper_dev, int clip,
+                     float *scratch_dev, void *stream) {
+    HM_CHECK_ARG(hyper_dev, "hm_adam_step_dev: NULL hyper-parameter pointer");
+    return adam_step("hm_adam_step_dev", tensors, n_tensors, AdamHyper{}, hyper_dev, clip != 0, scratch_dev,
+                     as_stream(stream));
 }
 
 }  // extern "C"

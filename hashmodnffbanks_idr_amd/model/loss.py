@@ -6,7 +6,9 @@
 Formulated with ray masks instead of the reference's boolean gathers: the selected-subset sums become
 masked sums over all N rays.  Same terms and values (an empty selection contributes an exact 0, which is
 what the reference's `.sum() == 0` guards return), but no data-dependent shapes and no device->host
-reads, so the loss can sit inside a captured HIP graph (training/graph_step.py).
+reads, so the loss can sit inside a captured HIP graph (training/graph_step.py).  There the weights and alpha come
+as a device array (hyper, staged before each replay: see loss_hyper_values), so the graph follows the runner's
+alpha schedule.
 """
 import torch
 from torch import nn
@@ -15,10 +17,11 @@ from torch.nn import functional as F
 
 class _IdrLossHip(torch.autograd.Function):
     """terms = [loss, rgb_loss, eikonal_loss, mask_loss] from one HIP launch (csrc/hm_loss.hip) that also leaves
-    d loss / d (rgb_values, sdf_output, grad_theta); only terms[0] carries gradient."""
+    d loss / d (rgb_values, sdf_output, grad_theta); only terms[0] carries gradient.  hyper: None, or a device
+    float[3] {w_eik, w_mask, alpha} the kernel reads when it runs (hm_idr_loss_dev) instead of the three numbers."""
 
     @staticmethod
-    def forward(ctx, rgb, sdf, grad_theta, rgb_gt, hit, inside, w_eik, w_mask, alpha):
+    def forward(ctx, rgb, sdf, grad_theta, rgb_gt, hit, inside, w_eik, w_mask, alpha, hyper):
         from .. import _lib
         rgb, sdf_c, rgb_gt = rgb.contiguous(), sdf.reshape(-1).contiguous(), rgb_gt.reshape(-1, 3).contiguous()
         n = rgb.shape[0]
@@ -28,10 +31,19 @@ class _IdrLossHip(torch.autograd.Function):
         terms = torch.empty(4, dtype=torch.float32, device=rgb.device)
         d_rgb, d_sdf = torch.empty_like(rgb), torch.empty_like(sdf_c)
         d_grad = torch.empty_like(gt_c) if m else None
-        _lib.check(_lib.lib().hm_idr_loss(_lib.dptr(rgb), _lib.dptr(rgb_gt), _lib.dptr(sdf_c), _lib.dptr(hit8),
-                                          _lib.dptr(in8), n, _lib.dptr(gt_c), m, float(w_eik), float(w_mask),
-                                          float(alpha), _lib.dptr(terms), _lib.dptr(d_rgb), _lib.dptr(d_sdf),
-                                          _lib.dptr(d_grad), _lib.stream_ptr(rgb)))
+        if hyper is None:
+            _lib.check(_lib.lib().hm_idr_loss(_lib.dptr(rgb), _lib.dptr(rgb_gt), _lib.dptr(sdf_c), _lib.dptr(hit8),
+                                              _lib.dptr(in8), n, _lib.dptr(gt_c), m, float(w_eik), float(w_mask),
+                                              float(alpha), _lib.dptr(terms), _lib.dptr(d_rgb), _lib.dptr(d_sdf),
+                                              _lib.dptr(d_grad), _lib.stream_ptr(rgb)))
+        else:
+            if (hyper.dtype != torch.float32 or hyper.numel() != 3 or hyper.device != rgb.device
+                    or not hyper.is_contiguous()):
+                raise ValueError("idr_loss_terms: hyper must be a contiguous float32[3] tensor on the outputs' device")
+            _lib.check(_lib.lib().hm_idr_loss_dev(_lib.dptr(rgb), _lib.dptr(rgb_gt), _lib.dptr(sdf_c), _lib.dptr(hit8),
+                                                  _lib.dptr(in8), n, _lib.dptr(gt_c), m, _lib.dptr(hyper),
+                                                  _lib.dptr(terms), _lib.dptr(d_rgb), _lib.dptr(d_sdf),
+                                                  _lib.dptr(d_grad), _lib.stream_ptr(rgb)))
         ctx.save_for_backward(d_rgb, d_sdf, d_grad)
         ctx.sdf_shape = sdf.shape
         # the loss leaves as its OWN tensor: indexing terms[0] outside would put a SelectBackward node in front of this
@@ -47,18 +59,32 @@ class _IdrLossHip(torch.autograd.Function):
         d_rgb, d_sdf, d_grad = ctx.saved_tensors
         g = d_loss
         return (d_rgb * g, (d_sdf * g).reshape(ctx.sdf_shape), d_grad * g if d_grad is not None else None,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
-def idr_loss_terms(model_outputs, rgb_gt, eikonal_weight, mask_weight, alpha):
+def loss_hyper_values(eikonal_weight, mask_weight, alpha):
+    """[eikonal_weight, mask_weight, alpha] as the hyper array of idr_loss_terms holds them.  The kernel cannot report an
+    error, so they are checked here, where they are staged (ValueError)."""
+    vals = [float(eikonal_weight), float(mask_weight), float(alpha)]
+    if not vals[2] > 0 or vals[0] != vals[0] or vals[1] != vals[1]:
+        raise ValueError(f"IDRLoss: alpha must be positive and the weights numbers (got eikonal_weight={vals[0]}, "
+                         f"mask_weight={vals[1]}, alpha={vals[2]})")
+    return vals
+
+
+def idr_loss_terms(model_outputs, rgb_gt, eikonal_weight=None, mask_weight=None, alpha=None, hyper=None):
+    """the IDRLoss terms; the weights and alpha are numbers, or (hyper) a device float32[3] {eikonal_weight,
+    mask_weight, alpha} read when the loss kernel runs, so that a captured step follows changes of them"""
     if model_outputs['rgb_values'].is_cuda:
         gt = model_outputs['grad_theta']
         loss, terms = _IdrLossHip.apply(model_outputs['rgb_values'], model_outputs['sdf_output'],
                                   gt if (gt is not None and gt.shape[0] > 0) else None, rgb_gt,
                                   model_outputs['network_object_mask'], model_outputs['object_mask'],
-                                  eikonal_weight, mask_weight, alpha)
+                                  eikonal_weight, mask_weight, alpha, hyper)
         det = terms.detach()
         return {'loss': loss, 'rgb_loss': det[1], 'eikonal_loss': det[2], 'mask_loss': det[3]}
+    if hyper is not None:
+        eikonal_weight, mask_weight, alpha = hyper.tolist()
     return idr_loss_terms_torch(model_outputs, rgb_gt, eikonal_weight, mask_weight, alpha)
 
 

@@ -7,7 +7,13 @@ masks instead of boolean gathers, the whole ray search enqueued by one C call) s
 depends on a device->host read.  The first calls run eagerly (warm-up on a side stream), then the
 kernels of [forward + loss + backward] and of [clip + Adam] are captured once with
 torch.cuda.CUDAGraph (hipGraph underneath) and replayed; only the two CPU-generator draws the reference
-makes per iteration (eikonal samples, closest-approach fractions) are copied in before each replay.
+makes per iteration (eikonal samples, closest-approach fractions) and the hyper-parameters are copied in before each
+replay.  The replayed kernels read the hyper-parameters a schedule changes from device arrays: ClipAdam's lr, betas,
+eps and max_norm, and the loss's eikonal_weight, mask_weight and alpha (the runner's MultiStepLR and alpha milestones,
+training/idr_train.py:131,175-179,227-228,330).  What a replay cannot follow raises RuntimeError before the replay:
+a torch.optim.Adam(capturable=True) hyper-parameter held as a Python number (torch bakes it into the captured kernels;
+a tensor lr, which torch's schedulers update in place, is followed), and ClipAdam's max_norm turned on after a capture
+without clipping.
 With more than one rank the gradient exchange sits between the two graphs: parallel.StaticGradExchange has its device
 work (payload packing, flat bucket, dense-gradient assembly) captured INTO the two graphs, so only its two collectives
 run eagerly; a plain parallel.GradAllReducer (dense all-reduce) runs eagerly as a whole.
@@ -17,7 +23,19 @@ import os
 import torch
 
 from .. import _lib, ops
-from ..model.loss import idr_loss_terms
+from ..model.loss import idr_loss_terms, loss_hyper_values
+
+# the torch.optim.Adam group entries its captured kernels take by value (a tensor lr / betas is read when they run)
+_ADAM_BAKED = ("lr", "betas", "eps", "weight_decay", "amsgrad", "maximize")
+
+
+def _same_value(a, b):
+    """a tensor hyper-parameter is followed while it is the same tensor (schedulers fill_ it in place)"""
+    if torch.is_tensor(a) or torch.is_tensor(b):
+        return a is b
+    if isinstance(a, (tuple, list)) and isinstance(b, (tuple, list)):
+        return len(a) == len(b) and all(_same_value(x, y) for x, y in zip(a, b))
+    return a == b
 
 
 class LocalTableGrad:
@@ -104,6 +122,7 @@ class GraphedTrainStep:
         self._stage = None
         self.static = None
         self.out = self.loss_out = None
+        self._baked = None     # torch.optim.Adam: (group values, max_norm) at capture time (_check_baked)
         for grp in optimizer.param_groups:
             if use_graph and not (grp.get("capturable", False) or getattr(optimizer, "fused_clip", False)):
                 raise ValueError("GraphedTrainStep needs training.optim.ClipAdam or torch.optim.Adam(..., capturable=True)")
@@ -113,21 +132,18 @@ class GraphedTrainStep:
         """the reference's two CPU-generator draws of an iteration, in its order (ray_tracing.py:277 first,
         then implicit_differentiable_renderer.py:279).
 
-        They are written into PINNED staging buffers owned by this object (a ring of two, each guarded by an
-        event): the host->device copies are asynchronous, and a copy whose pageable source tensor has
-        already been freed by the time the copy engine runs is a GPU memory-access fault."""
+        They are written into PINNED staging buffers owned by this object (_lib.PinnedRing): the host->device
+        copies are asynchronous, and a copy whose pageable source tensor has already been freed by the time the
+        copy engine runs is a GPU memory-access fault.  The steps buffer has 3 more floats at its end for the loss
+        hyper-parameters, which so travel in the same copy."""
         rt = self.model.ray_tracer
         if self._stage is None:
-            self._stage = [(torch.empty(rt.n_steps).pin_memory(), torch.empty(n_rays // 2, 3).pin_memory(),
-                            torch.cuda.Event()) for _ in range(2)]
-            self._slot = 0
-        steps, eik, ev = self._stage[self._slot]
-        self._slot ^= 1
-        ev.synchronize()          # the copy that last read this slot has completed
-        steps.uniform_(0.0, 1.0)
+            self._stage = _lib.PinnedRing((rt.n_steps + 3,), (n_rays // 2, 3))
+        steps_hyp, eik, ev = self._stage.slot()
+        steps_hyp[:rt.n_steps].uniform_(0.0, 1.0)
         bb = self.model.object_bounding_sphere
         eik.uniform_(-bb, bb)
-        return steps, eik, ev
+        return steps_hyp, eik, ev
 
     def _sparse(self):
         return getattr(self.reducer, "sparse", ()) if self.reducer is not None else self.local_tables
@@ -139,7 +155,7 @@ class GraphedTrainStep:
             self.reducer.begin_step()
         s = self.static
         out = self.model.forward_static(s["input"], s["eik"], s["steps"])
-        lo = idr_loss_terms(out, s["rgb"], self.loss_fn.eikonal_weight, self.loss_fn.mask_weight, self.loss_fn.alpha)
+        lo = idr_loss_terms(out, s["rgb"], hyper=s["loss_hyper"])
         lo["loss"].backward()
         for ex in self.local_tables:
             ex.end_step()
@@ -189,21 +205,51 @@ class GraphedTrainStep:
         with ops.deterministic(self.deterministic):
             return self._step(model_input, ground_truth)
 
+    def _hyper_snapshot(self):
+        return [{k: grp.get(k) for k in _ADAM_BAKED} for grp in self.opt.param_groups], self.max_norm
+
+    def _check_baked(self):
+        """torch.optim.Adam(capturable=True) after capture: RuntimeError for a hyper-parameter the graphs hold by value
+        that has changed since (as GraphedTrainStep's own max_norm, which clip_grad_norm_ takes by value)"""
+        (groups, max_norm), (now, now_norm) = self._baked, self._hyper_snapshot()
+        for i, (g0, g1) in enumerate(zip(groups, now)):
+            for k in _ADAM_BAKED:
+                if not _same_value(g0[k], g1[k]):
+                    raise RuntimeError(
+                        f"GraphedTrainStep: param_groups[{i}]['{k}'] of the optimizer changed from {g0[k]} to {g1[k]} "
+                        f"after the step was captured, and torch.optim.Adam's captured kernels hold it by value.  Use "
+                        f"training.optim.ClipAdam (its kernels read lr, betas, eps and max_norm when they run), or for a "
+                        f"schedule of lr alone pass lr as a tensor: torch.optim.Adam(..., lr=torch.tensor(lr), "
+                        f"capturable=True), which torch's schedulers update in place")
+        if not _same_value(max_norm, now_norm):
+            raise RuntimeError(f"GraphedTrainStep: max_norm changed from {max_norm} to {now_norm} after the step was "
+                               f"captured; clip_grad_norm_ holds it by value (training.optim.ClipAdam reads it at run time)")
+
     def _step(self, model_input, ground_truth):
+        # every value the replayed kernels read from a staged array is checked before anything is enqueued
+        loss_hyper = loss_hyper_values(self.loss_fn.eikonal_weight, self.loss_fn.mask_weight, self.loss_fn.alpha)
+        fused = getattr(self.opt, "fused_clip", False)
+        opt_hyper = self.opt.hyper_values(captured=self.g_fb is not None) if fused else None
+        if self._baked is not None:
+            self._check_baked()
         dev = model_input["uv"].device
         n_rays = model_input["uv"].shape[0] * model_input["uv"].shape[1]
-        steps, eik, ev = self._draws(n_rays, dev)
+        steps_hyp, eik, ev = self._draws(n_rays, dev)
         if self.static is None:
             self.static = {"input": {k: v.to(dev).clone() for k, v in model_input.items()},
                            "rgb": ground_truth["rgb"].to(dev).clone(),
-                           "eik": torch.empty(eik.shape, device=dev), "steps": torch.empty(steps.shape, device=dev)}
+                           "eik": torch.empty(eik.shape, device=dev),
+                           "steps_hyper": torch.empty(steps_hyp.shape, device=dev)}
+            self.static["steps"], self.static["loss_hyper"] = self.static["steps_hyper"].split(
+                [steps_hyp.numel() - 3, 3])
         s = self.static
         for k, v in model_input.items():
             if v.data_ptr() != s["input"][k].data_ptr():
                 s["input"][k].copy_(v, non_blocking=v.is_cuda)   # host sources are copied synchronously
         s["rgb"].copy_(ground_truth["rgb"], non_blocking=ground_truth["rgb"].is_cuda)
         s["eik"].copy_(eik, non_blocking=True)
-        s["steps"].copy_(steps, non_blocking=True)
+        steps_hyp[-3:] = torch.tensor(loss_hyper, dtype=torch.float32)
+        s["steps_hyper"].copy_(steps_hyp, non_blocking=True)
         ev.record()
 
         if not self.use_graph or self.warmup_left > 0:
@@ -266,6 +312,8 @@ class GraphedTrainStep:
                     self.reducer.freeze()                # bucket / payload layout is what the graphs were captured on
                 if hasattr(self.opt, "frozen_grads"):
                     self.opt.frozen_grads = True
+                if not fused:
+                    self._baked = self._hyper_snapshot()
                 if dump:
                     g_fb.debug_dump(os.path.join(dump, "g_fb.dot"))
                     g_opt.debug_dump(os.path.join(dump, "g_opt.dot"))
@@ -282,6 +330,8 @@ class GraphedTrainStep:
                 self._eager_iteration()
                 return self.out, self.loss_out
 
+        if fused:
+            self.opt.stage_hyper(self.opt.param_groups[0]["params"][0].device, opt_hyper)   # read by g_opt's update
         self.g_fb.replay()
         self._exchange()
         self.g_opt.replay()

@@ -508,6 +508,13 @@ HM_API int hm_idr_loss(const float *rgb, const float *rgb_gt, const float *sdf, 
                        const uint8_t *inside, int64_t n_rays, const float *grad_theta, int64_t n_grad,
                        float eikonal_weight, float mask_weight, float alpha, float *terms, float *d_rgb, float *d_sdf,
                        float *d_grad, void *stream);
+/* IDRLoss.forward with eikonal_weight, mask_weight, alpha read from hyper_dev[3] (device) when the kernel runs, so a
+ * captured training step follows a schedule of them (training/idr_train.py:175-179,227-228: alpha doubled at its
+ * milestones).  Equal values give bit-identical terms and gradients to hm_idr_loss.  The caller validates the values
+ * (alpha > 0) where it writes them: device code cannot report an error.                                     */
+HM_API int hm_idr_loss_dev(const float *rgb, const float *rgb_gt, const float *sdf, const uint8_t *hit,
+                           const uint8_t *inside, int64_t n_rays, const float *grad_theta, int64_t n_grad,
+                           const float *hyper_dev, float *terms, float *d_rgb, float *d_sdf, float *d_grad, void *stream);
 
 /* ---- camera rays + bounding-sphere intersections --------------------------------------------------
  * Replaces rend_util.get_camera_params for 4x4 poses (utils/rend_util.py:48-75: lift, pose x pixel, normalise) and
@@ -536,6 +543,13 @@ typedef struct hm_adam_tensor {
 HM_API int64_t hm_adam_scratch_floats(const hm_adam_tensor *tensors, int n_tensors);
 HM_API int hm_adam_step(const hm_adam_tensor *tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
                         float max_norm, float *scratch_dev, void *stream);
+/* torch.optim.Adam.step (after clip_grad_norm_) as hm_adam_step, with lr, beta1, beta2, eps, max_norm read from
+ * hyper_dev[5] (device) when the kernels run, so a captured step follows lr / momentum schedules
+ * (torch.optim.lr_scheduler).  The norm kernels run when clip != 0; a device max_norm <= 0 then gives clip
+ * coefficient 1.  Equal values give bit-identical results to hm_adam_step.  The caller validates the values
+ * (lr >= 0, 0 <= beta < 1, eps >= 0) where it writes them: device code cannot report an error.            */
+HM_API int hm_adam_step_dev(const hm_adam_tensor *tensors, int n_tensors, const float *hyper_dev, int clip,
+                            float *scratch_dev, void *stream);
 
 /* Weight gradients of one backward pass in ONE launch: C_p += A_p^T B_p for every item (A_p [K, M] and B_p [K, N]
  * row-major with leading dimensions, C_p [M, N] accumulated with fp32 atomics - the caller zeroes it, like the
