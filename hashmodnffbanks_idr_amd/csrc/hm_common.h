@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../include/hashmod.h"
 
@@ -37,6 +38,33 @@ int hm_fail(int code, const std::string &msg);
         hipError_t e__ = hipGetLastError();                                                       \
         if (e__ != hipSuccess) return hm_fail(HM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e__)); \
     } while (0)
+
+inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Opts Kernel in to `bytes` of dynamic LDS (above the 64 KB default), once per host thread (not a stream operation).
+template <auto Kernel>
+int hm_allow_dynamic_lds(int bytes) {
+    static thread_local bool done = false;
+    if (done) return HM_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
+    done = true;
+    return HM_OK;
+}
+
+// f(std::integral_constant<int, FRAC>{}) for the run-time frac_mode (HM_FRAC_REFERENCE or HM_FRAC_TRILINEAR): each
+// launch is written once, with FRAC as its kernel's template value
+template <class F>
+auto hm_frac_dispatch(int frac_mode, F &&f) {
+    if (frac_mode == HM_FRAC_REFERENCE) return f(std::integral_constant<int, HM_FRAC_REFERENCE>{});
+    return f(std::integral_constant<int, HM_FRAC_TRILINEAR>{});
+}
+
+// Small-batch rule of the fused SDF forward (hm_sdf.hip): up to kSdfSmall live points run on the small-tile launch -
+// 8-point tiles up to kSdfTiny, 4-point tiles up to kSdfMini - more on 64-point tiles.  hm_trace.hip picks its launch
+// forms by the same bound: a launch that takes only counts above it passes run_min = kSdfSmall + 1.
+constexpr int64_t kSdfSmall = 8192, kSdfTiny = 2048, kSdfMini = 1024;
 
 #ifdef __HIPCC__
 // Small device-side fills / copies as ordinary KERNELS.  hipMemsetAsync / hipMemcpyAsync become MEMSET / MEMCPY

@@ -190,8 +190,6 @@ __global__ __launch_bounds__(kET) void sdf_head_bwd_kernel(const float *__restri
     zb[i] = v;
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 // ---- SIREN activation sin(w0 x) (embeddings/Sine.py:10-12) and NeRF positional encoding (frequency_enc.py:6-51) with

@@ -932,8 +932,6 @@ __global__ __launch_bounds__(256) void gather_calib_kernel(const float2 *__restr
     out[i] = v.x + v.y;
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" {
@@ -974,25 +972,16 @@ int hm_encode_bwd_table_ws(const hm_grid_desc *desc, const float *x, int64_t n, 
                        static_cast<const uint16_t *>(slab));
     hipLaunchKernelGGL(zsort_pack_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, x, d_feat, d_feat_stride,
                        order, n, lv.L * lv.F, xs, dfs);
-    static thread_local bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_bwd_table_zorder_kernel<HM_FRAC_REFERENCE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_bwd_table_zorder_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_done = true;
-    }
     const size_t lds = sizeof(float) * kBwdSlots * kBwdBlockRows * 2 + sizeof(uint32_t) * kBwdSlots;
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(encode_bwd_table_zorder_kernel<HM_FRAC_REFERENCE>, dim3(kSlabs, lv.L), dim3(kBwdThreads), lds, st,
-                           lv, xs, reinterpret_cast<const float2 *>(dfs), n, hist + kSlabs, d_table);
-    else
-        hipLaunchKernelGGL(encode_bwd_table_zorder_kernel<HM_FRAC_TRILINEAR>, dim3(kSlabs, lv.L), dim3(kBwdThreads), lds, st,
-                           lv, xs, reinterpret_cast<const float2 *>(dfs), n, hist + kSlabs, d_table);
-    HM_CHECK_LAUNCH("hm_encode_bwd_table_ws");
-    return HM_OK;
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        constexpr auto kernel = encode_bwd_table_zorder_kernel<decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(kSlabs, lv.L), dim3(kBwdThreads), lds, st, lv, xs,
+                           reinterpret_cast<const float2 *>(dfs), n, hist + kSlabs, d_table);
+        HM_CHECK_LAUNCH("hm_encode_bwd_table_ws");
+        return HM_OK;
+    });
 }
 
 int hm_encode_bwd_table_tracked(const hm_grid_desc *desc, const float *x, int64_t n, const float *d_feat,
@@ -1150,16 +1139,6 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
     const size_t lds_z = sizeof(float) * (size_t)(kTileS * ((width + 3) & ~3) + kTileS * 3 + kTileS);
     if (lv.F == 2 && workspace && table_exceeds_l2 && n >= (int64_t)131072 && n < ((int64_t)1 << 32) &&
         lds_z <= 160 * 1024 && workspace_bytes >= (int64_t)sizeof(uint32_t) * (n + 2 * kSlabs)) {
-        static thread_local bool attr_z = false;
-        if (!attr_z) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_fwd_f2_zorder_kernel<HM_FRAC_REFERENCE>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_fwd_f2_zorder_kernel<HM_FRAC_TRILINEAR>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-            attr_z = true;
-        }
         hipStream_t st = as_stream(stream);
         uint32_t *hist = static_cast<uint32_t *>(workspace);        // [kSlabs] counts -> start offsets -> cursors
         uint32_t *order = hist + 2 * kSlabs;                          // [n]
@@ -1175,34 +1154,28 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
                            static_cast<const uint16_t *>(slab));
         const int64_t tiles = (n + kTileS - 1) / kTileS;
         const unsigned grid = (unsigned)(tiles < kZGrid ? ((tiles + 7) / 8) * 8 : kZGrid);
-        if (frac_mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(encode_fwd_f2_zorder_kernel<HM_FRAC_REFERENCE>, dim3(grid), dim3(kThreadsS), lds_z, st,
-                               lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out, out_stride, order);
-        else
-            hipLaunchKernelGGL(encode_fwd_f2_zorder_kernel<HM_FRAC_TRILINEAR>, dim3(grid), dim3(kThreadsS), lds_z, st,
-                               lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out, out_stride, order);
+        const int rc = hm_frac_dispatch(frac_mode, [&](auto frac) {
+            constexpr auto kernel = encode_fwd_f2_zorder_kernel<decltype(frac)::value>;
+            const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
+            if (rc == HM_OK)
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsS), lds_z, st, lv, x, n,
+                                   reinterpret_cast<const float2 *>(table), B_fourier, out, out_stride, order);
+            return rc;
+        });
+        if (rc != HM_OK) return rc;
     } else if (lv.F == 2 && table_exceeds_l2 && n >= (int64_t)131072 && lds_sweep <= 160 * 1024) {
         // big launches over big tables: level-synchronous persistent kernel (two workgroups per CU)
-        static thread_local bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_REFERENCE>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(encode_fwd_f2_sweep_kernel<HM_FRAC_TRILINEAR>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-            attr_done = true;
-        }
         const int64_t tiles = (n + kTileS - 1) / kTileS;
         const unsigned grid = (unsigned)(tiles < sweep_grid ? tiles : sweep_grid);
-        if (frac_mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(encode_fwd_f2_sweep_kernel<HM_FRAC_REFERENCE>, dim3(grid), dim3(kThreadsS), lds_sweep,
-                               as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
-                               out_stride);
-        else
-            hipLaunchKernelGGL(encode_fwd_f2_sweep_kernel<HM_FRAC_TRILINEAR>, dim3(grid), dim3(kThreadsS), lds_sweep,
-                               as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
-                               out_stride);
+        const int rc = hm_frac_dispatch(frac_mode, [&](auto frac) {
+            constexpr auto kernel = encode_fwd_f2_sweep_kernel<decltype(frac)::value>;
+            const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
+            if (rc == HM_OK)
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsS), lds_sweep, as_stream(stream), lv, x, n,
+                                   reinterpret_cast<const float2 *>(table), B_fourier, out, out_stride);
+            return rc;
+        });
+        if (rc != HM_OK) return rc;
     } else if (lv.F == 2) {
         const int64_t tiles = (n + kTile - 1) / kTile;
         HM_CHECK_ARG(tiles <= 0x7fffffffLL, "hm_encode_fwd: n too large for one launch");

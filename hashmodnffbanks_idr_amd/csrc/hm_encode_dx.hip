@@ -227,8 +227,6 @@ __global__ __launch_bounds__(kThreads) void fourier_bwd_input_bwd_kernel(const f
     }
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 bool grid_ok(int64_t threads, int64_t &grid) {
     grid = (threads + kThreads - 1) / kThreads;
     return grid <= 0x7fffffffLL;

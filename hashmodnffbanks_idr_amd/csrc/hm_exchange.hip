@@ -95,8 +95,6 @@ __global__ __launch_bounds__(kT) void rows_clear_kernel(float *__restrict__ d_ta
     for (int f = 0; f < F; ++f) dst[f] = 0.0f;
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" {

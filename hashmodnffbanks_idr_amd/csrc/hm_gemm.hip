@@ -614,8 +614,6 @@ __global__ __launch_bounds__(256) void zero_window_kernel(float *C, int64_t ldc,
     C[m * ldc + n] = 0.0f;
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int64_t kSplitTarget = 512;   // split-K: workgroups to aim for when the tile grid alone leaves the chip idle
 
 }  // namespace

@@ -465,8 +465,6 @@ __global__ __launch_bounds__(64 * WAVES) void nffb_fwd_mfma_kernel(HmLevels lv, 
     }
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 template <int FRAC, int LV, bool STYLE>
 int launch_nffb1(hipStream_t st, const HmLevels &lv, const NffbArgs &a, const float *x, int64_t n, const float *table,
                  const float *Bf, float *out, int64_t out_stride, const int32_t *n_dev) {

@@ -149,8 +149,6 @@ __global__ __launch_bounds__(kOT) void adam_update_kernel(AdamTable tb, AdamHype
     }
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 // hyper_dev == NULL: the by-value hp, clipping when hp.max_norm > 0.  Otherwise the kernels read hyper_dev and the norm
 // kernels run when `clip` is set.
 int adam_step(const char *who, const hm_adam_tensor *tensors, int n_tensors, const AdamHyper &hp,

@@ -1086,7 +1086,48 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevel
                           lds, reinterpret_cast<unsigned *>(a.w.cnt + C_TILE_CURSOR), none);
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+// network descriptor -> kernel argument for the exact-fp32 kernels (sdf_net_from_desc)
+static int sdf_net_fp32(const char *who, const HmLevels &lv, const hm_mlp_desc *mlp, int64_t emb_stride, SdfImage img,
+                        SdfNet &net, bool *all_m16 = nullptr) {
+    return sdf_net_from_desc(who, mlp, lv.E, emb_stride, img, 1, (lv.E + 7) / 8 * 2, false, net, all_m16);
+}
+
+// dynamic LDS of the 16-point tile bodies: two activation images + the embedding (the 8-point layout needs half of it)
+static size_t sdf_lds16(const SdfNet &net, int E) {
+    return sizeof(float) * ((size_t)(2 * net.x_groups + (E + 15) / 16 * 4) * kGroupFloats16 + kPts16 * 4 +
+                            kWaves * kPts16);
+}
+// dynamic LDS of the 64-point tile
+static size_t sdf_lds64(const SdfNet &net) {
+    return sizeof(float) * ((size_t)(net.x_groups + net.emb_groups) * kGroupFloats + kPts * 4 + kWaves * kPts);
+}
+
+// tile-size thresholds of the small-tile kernels: 8-point tiles up to m8_max live points, 4-point tiles up to m4_max,
+// 16-point tiles above.  tile_points 0 / -1: by the live count (kSdfTiny, kSdfMini); 4, 8, 16: that size only.
+struct SmallTiles {
+    int64_t m8_max, m4_max;
+};
+static SmallTiles sdf_small_tiles(int tile_points) {
+    const int64_t kBig = (int64_t)1 << 62;
+    if (tile_points == 16) return {0, 0};
+    if (tile_points == 8) return {kBig, 0};
+    if (tile_points == 4) return {kBig, kBig};
+    return {kSdfTiny, kSdfMini};
+}
+// workgroups of a small-tile launch over up to n live points: one tile each, at most `cap`
+static unsigned sdf_small_grid(int64_t n, SmallTiles t, int64_t cap) {
+    int64_t tiles = t.m8_max >= n ? 0 : (n + kPts16 - 1) / kPts16;
+    if (t.m8_max > 0) tiles = max(tiles, ((n < t.m8_max ? n : t.m8_max) + kPts8 - 1) / kPts8);
+    if (t.m4_max > 0) tiles = max(tiles, ((n < t.m4_max ? n : t.m4_max) + 3) / 4);
+    return (unsigned)(tiles < cap ? tiles : cap);
+}
+
+// hm_frac_dispatch + the precomputed-embedding form of the kernels (mode kFracEmb)
+template <class F>
+int sdf_dispatch(int mode, F &&f) {
+    if (mode == kFracEmb) return f(std::integral_constant<int, kFracEmb>{});
+    return hm_frac_dispatch(mode, f);
+}
 
 }  // namespace
 
@@ -1145,48 +1186,6 @@ int hm_sdf_fwd_emb(const hm_mlp_desc *mlp, const float *emb, int64_t emb_stride,
                         tile_points, n_dev, max_workgroups, stream);
 }
 
-// kernel-side image of the network descriptor (+ the checks every fused SDF launch makes on it)
-static int sdf_net_from_desc(const HmLevels &lv, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, bool &have16) {
-    HM_CHECK_ARG(mlp && mlp->n_layers >= 1 && mlp->n_layers <= HM_MAX_LAYERS, "hm_sdf_fwd: n_layers out of range");
-    net.n_layers = mlp->n_layers;
-    net.beta = mlp->beta;
-    net.emb_stride = emb_stride;
-    const int emb_oct = (lv.E + 7) / 8;
-    const int emb_b16 = (lv.E + 15) / 16;
-    net.emb_groups = emb_oct * 2;
-    int x_groups = 0;
-    have16 = true;
-    for (int l = 0; l < mlp->n_layers; ++l) {
-        const hm_mlp_layer &Ly = mlp->layer[l];
-        HM_CHECK_ARG(Ly.w_packed && Ly.bias, "hm_sdf_fwd: layer has NULL weights/bias");
-        HM_CHECK_ARG(Ly.n_tiles >= 1 && Ly.n_tiles <= 2 * kWaves, "hm_sdf_fwd: layer wider than 512 features");
-        HM_CHECK_ARG(Ly.out_dim >= 1 && Ly.out_dim <= Ly.n_tiles * 32, "hm_sdf_fwd: out_dim / n_tiles mismatch");
-        HM_CHECK_ARG(Ly.seg_octets[0] >= 1 && Ly.seg_octets[1] >= 0, "hm_sdf_fwd: bad segment length");
-        if (!Ly.w_packed_m16) have16 = false;
-        for (int s = 0; s < 2; ++s) {
-            if (Ly.seg_octets[s] == 0) continue;
-            if (Ly.seg_src[s] == 1) {
-                HM_CHECK_ARG(Ly.seg_octets[s] == emb_oct, "hm_sdf_fwd: embedding segment must span ceil(E/8) octets");
-                HM_CHECK_ARG(!Ly.w_packed_m16 || Ly.seg_blocks16[s] == emb_b16,
-                             "hm_sdf_fwd: embedding segment must span ceil(E/16) 16-blocks");
-            } else {
-                HM_CHECK_ARG(Ly.seg_src[s] == 0 && l > 0, "hm_sdf_fwd: layer 0 must read the embedding");
-                HM_CHECK_ARG(Ly.seg_octets[s] * 8 <= mlp->layer[l - 1].n_tiles * 32,
-                             "hm_sdf_fwd: layer reads more inputs than the previous layer produces");
-                HM_CHECK_ARG(Ly.seg_octets[s] * 8 >= mlp->layer[l - 1].out_dim,
-                             "hm_sdf_fwd: layer reads fewer inputs than the previous layer produces");
-                HM_CHECK_ARG(!Ly.w_packed_m16 || (Ly.seg_blocks16[s] * 16 <= mlp->layer[l - 1].n_tiles * 32 &&
-                                                  Ly.seg_blocks16[s] * 16 >= mlp->layer[l - 1].out_dim),
-                             "hm_sdf_fwd: 16-block segment length does not match the previous layer");
-            }
-        }
-        x_groups = max(x_groups, Ly.n_tiles * 8);
-        net.layer[l] = Ly;
-    }
-    net.x_groups = x_groups;
-    return HM_OK;
-}
-
 // internal entry of the ray search (hm_trace.hip, not exported): rounds [first, rounds) of the sphere-tracing march as
 // ONE launch (trace_march_tail_kernel).  `trace_args` = a TraceArgs of hm_trace_dev.h.
 int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
@@ -1196,35 +1195,23 @@ int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const 
     HM_CHECK_ARG(first >= 1 && first < 64 && rounds <= 64, "hm_trace_march_tail: bad round range");
     const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
     SdfNet net;
-    bool have16 = false;
-    const int rc = sdf_net_from_desc(desc->lv, mlp, 0, net, have16);
+    const int rc = sdf_net_fp32("hm_trace_march_tail", desc->lv, mlp, 0, kImgM16, net);
     if (rc != HM_OK) return rc;
-    HM_CHECK_ARG(have16, "hm_trace_march_tail: needs w_packed_m16 in every layer");
     if (a.n == 0 || first >= rounds) return HM_OK;
     HM_CHECK_ARG(a.w.cap >= ((a.n + 7) / 8) * 16, "hm_trace_march_tail: point buffer too small");
-    const int emb_b16 = (desc->lv.E + 15) / 16;
-    const int lds_floats = (2 * net.x_groups + emb_b16 * 4) * kGroupFloats16 + kPts16 * 4 + kWaves * kPts16;   // two activation images
+    const int lds_floats = (int)(sdf_lds16(net, desc->lv.E) / sizeof(float));
     const size_t lds = sizeof(float) * (size_t)lds_floats + 64;
     HM_CHECK_ARG(lds <= 96 * 1024, "hm_trace_march_tail: network does not fit the 16-point LDS tile");
-    static thread_local bool attr_tail_done = false;
-    if (!attr_tail_done) {  // opt in to >64 KB dynamic LDS once (not a stream operation)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(trace_march_tail_kernel<HM_FRAC_REFERENCE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(trace_march_tail_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_tail_done = true;
-    }
     const unsigned grid = (unsigned)((a.n + 7) / 8);
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(trace_march_tail_kernel<HM_FRAC_REFERENCE>, dim3(grid), dim3(kThreadsSdf), lds,
-                           as_stream(stream), desc->lv, net, table, B_fourier, a, first, rounds, lds_floats, body16);
-    else
-        hipLaunchKernelGGL(trace_march_tail_kernel<HM_FRAC_TRILINEAR>, dim3(grid), dim3(kThreadsSdf), lds,
-                           as_stream(stream), desc->lv, net, table, B_fourier, a, first, rounds, lds_floats, body16);
-    HM_CHECK_LAUNCH("hm_trace_march_tail");
-    return HM_OK;
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        constexpr auto kernel = trace_march_tail_kernel<decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(96 * 1024);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table,
+                           B_fourier, a, first, rounds, lds_floats, body16);
+        HM_CHECK_LAUNCH("hm_trace_march_tail");
+        return HM_OK;
+    });
 }
 
 // internal entry of the ray search (hm_trace.hip, not exported): all secant iterations as ONE launch
@@ -1237,48 +1224,27 @@ int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
                  "hm_trace_secant_persistent: tile_points must be 0, 4, 8 or 16");
     const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
     SdfNet net;
-    bool have16 = false;
-    const int rc = sdf_net_from_desc(desc->lv, mlp, 0, net, have16);
+    const int rc = sdf_net_fp32("hm_trace_secant_persistent", desc->lv, mlp, 0, kImgM16, net);
     if (rc != HM_OK) return rc;
-    HM_CHECK_ARG(have16, "hm_trace_secant_persistent: needs w_packed_m16 in every layer");
     if (a.n == 0 || n_iters <= 0) return HM_OK;
-    const int64_t kBig = (int64_t)1 << 62;
-    int64_t m8_max = 0, m4_max = 0;      // (the thresholds of hm_sdf_fwd's small-tile launch)
-    if (tile_points == 0) { m8_max = 2048; m4_max = 1024; }
-    else if (tile_points == 8) m8_max = kBig;
-    else if (tile_points == 4) { m8_max = kBig; m4_max = kBig; }
-    const int emb_b16 = (desc->lv.E + 15) / 16;
-    const size_t lds = sizeof(float) * ((size_t)(2 * net.x_groups + emb_b16 * 4) * kGroupFloats16 + kPts16 * 4 +
-                                        kWaves * kPts16);
+    const size_t lds = sdf_lds16(net, desc->lv.E);
     HM_CHECK_ARG(lds <= 96 * 1024, "hm_trace_secant_persistent: network does not fit the 16-point LDS tile");
-    static thread_local bool attr_sec_done = false;
-    if (!attr_sec_done) {  // opt in to >64 KB dynamic LDS once (not a stream operation)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(trace_secant_kernel<HM_FRAC_REFERENCE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(trace_secant_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_sec_done = true;
-    }
+    const SmallTiles t = sdf_small_tiles(tile_points);
     // workgroups for the longest list the call can see (every ray a secant ray), one tile each up to one per CU
-    const int64_t nmax = a.n;
-    int64_t tiles = m8_max >= nmax ? 0 : (nmax + kPts16 - 1) / kPts16;
-    if (m8_max > 0) tiles = max(tiles, ((nmax < m8_max ? nmax : m8_max) + kPts8 - 1) / kPts8);
-    if (m4_max > 0) tiles = max(tiles, ((nmax < m4_max ? nmax : m4_max) + 3) / 4);
-    const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(trace_secant_kernel<HM_FRAC_REFERENCE>, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream),
-                           desc->lv, net, table, B_fourier, a, n_iters, m8_max, m4_max);
-    else
-        hipLaunchKernelGGL(trace_secant_kernel<HM_FRAC_TRILINEAR>, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream),
-                           desc->lv, net, table, B_fourier, a, n_iters, m8_max, m4_max);
-    HM_CHECK_LAUNCH("hm_trace_secant_persistent");
-    return HM_OK;
+    const unsigned grid = sdf_small_grid(a.n, t, 256);
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        constexpr auto kernel = trace_secant_kernel<decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(96 * 1024);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier,
+                           a, n_iters, t.m8_max, t.m4_max);
+        HM_CHECK_LAUNCH("hm_trace_secant_persistent");
+        return HM_OK;
+    });
 }
 
 // Closest-approach scan (points at pts + scan_off, count cnt[C_NSEL_PTS]) and the secant refinement in one launch
-// (sdf_scan_secant_kernel); scans of <= 8192 points run on the small-tile launch in front of it.  tile_points = 0 only.
+// (sdf_scan_secant_kernel); scans of <= kSdfSmall points run on the small-tile launch in front of it.  tile_points = 0 only.
 int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
                          int frac_mode, const void *trace_args, int n_iters, int64_t scan_off, int64_t scan_capacity,
                          int c_prev1, int grid1, int c_prev2, int grid2, void *stream) {
@@ -1286,68 +1252,49 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_scan_secant: bad frac_mode");
     const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
     SdfNet net;
-    bool have16 = false;
-    int rc = sdf_net_from_desc(desc->lv, mlp, 0, net, have16);
+    int rc = sdf_net_fp32("hm_trace_scan_secant", desc->lv, mlp, 0, kImgM16, net);
     if (rc != HM_OK) return rc;
-    HM_CHECK_ARG(have16, "hm_trace_scan_secant: needs w_packed_m16 in every layer");
     if (a.n == 0) return HM_OK;
-    constexpr int64_t kSmall = 8192;
-    // the scan's small-count form (tile_points -1: returns at once above kSmall live points)
+    // the scan's small-count form (tile_points -1: returns at once above kSdfSmall live points)
     rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1, frac_mode,
                     -1, a.w.cnt + C_NSEL_PTS, 0, stream);
     if (rc != HM_OK) return rc;
-    const int emb_b16 = (desc->lv.E + 15) / 16;
-    const size_t lds16 = sizeof(float) * ((size_t)(2 * net.x_groups + emb_b16 * 4) * kGroupFloats16 + kPts16 * 4 +
-                                          kWaves * kPts16);
-    const size_t lds64 = sizeof(float) * ((size_t)(net.x_groups + net.emb_groups) * kGroupFloats + kPts * 4 + kWaves * kPts);
+    const size_t lds16 = sdf_lds16(net, desc->lv.E), lds64 = sdf_lds64(net);
     HM_CHECK_ARG(lds16 <= 96 * 1024 && lds64 <= 160 * 1024 - 64, "hm_trace_scan_secant: network does not fit the LDS tiles");
     const size_t lds = lds16 > lds64 ? lds16 : lds64;
-    static thread_local bool attr_done = false;
-    if (!attr_done) {  // opt in to >64 KB dynamic LDS once (not a stream operation)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_scan_secant_kernel<HM_FRAC_REFERENCE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_scan_secant_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_done = true;
-    }
     // 16-point secant tiles once the scan keeps the chip busy for longer than their chain takes (8 x 131 us ~ 2.3 rounds
     // of 64-point tiles: 3 rounds = 49 152 points)
     const int64_t scan_hide = 3 * 256 * kPts;
     // c_prev*: counters holding the own-point counts of the sampler launches that took filler tiles of this scan (-1: none)
     const int p1 = grid1 > 0 ? c_prev1 : -1, p2 = grid2 > 0 ? c_prev2 : -1;
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(sdf_scan_secant_kernel<HM_FRAC_REFERENCE>, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream),
-                           desc->lv, net, table, B_fourier, a, n_iters, (int64_t)2048, (int64_t)1024, scan_off, kSmall + 1,
-                           scan_hide, p1, grid1, p2, grid2);
-    else
-        hipLaunchKernelGGL(sdf_scan_secant_kernel<HM_FRAC_TRILINEAR>, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream),
-                           desc->lv, net, table, B_fourier, a, n_iters, (int64_t)2048, (int64_t)1024, scan_off, kSmall + 1,
-                           scan_hide, p1, grid1, p2, grid2);
-    HM_CHECK_LAUNCH("hm_trace_scan_secant");
-    return HM_OK;
+    const SmallTiles t = sdf_small_tiles(0);
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        constexpr auto kernel = sdf_scan_secant_kernel<decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier, a,
+                           n_iters, t.m8_max, t.m4_max, scan_off, kSdfSmall + 1, scan_hide, p1, grid1, p2, grid2);
+        HM_CHECK_LAUNCH("hm_trace_scan_secant");
+        return HM_OK;
+    });
 }
 
 static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,
                         const float *table, const float *B_fourier, float *out, int64_t out_stride, int out_cols,
                         int frac_mode, int tile_points, const int32_t *n_dev, int max_workgroups, void *stream,
                         const SdfFillArgs *fill, int *grid64_out) {
-    HM_CHECK_ARG(mlp, "hm_sdf_fwd: NULL descriptor");
     HM_CHECK_ARG(n >= 0, "hm_sdf_fwd: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_sdf_fwd: bad frac_mode");
-    HM_CHECK_ARG(mlp->n_layers >= 1 && mlp->n_layers <= HM_MAX_LAYERS, "hm_sdf_fwd: n_layers out of range");
     HM_CHECK_ARG(tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16 || tile_points == 64 ||
                      tile_points == -1,
                  "hm_sdf_fwd: tile_points must be -1, 0, 4, 8, 16 or 64");
     SdfNet net;
     bool have16 = true;
     {
-        const int rc = sdf_net_from_desc(lv, mlp, emb_stride, net, have16);
+        const int rc = sdf_net_fp32("hm_sdf_fwd", lv, mlp, emb_stride, kImgM16Optional, net, &have16);
         if (rc != HM_OK) return rc;
     }
     const int mode = emb_stride > 0 ? kFracEmb : frac_mode;    // kernel template value
-    const int emb_b16 = (lv.E + 15) / 16;
     const hm_mlp_layer &last = mlp->layer[mlp->n_layers - 1];
     HM_CHECK_ARG(out_cols == 1 || out_cols == last.out_dim, "hm_sdf_fwd: out_cols must be 1 or the last layer's out_dim");
     HM_CHECK_ARG(out_stride >= out_cols, "hm_sdf_fwd: out_stride < out_cols");
@@ -1355,104 +1302,58 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
                  "hm_sdf_fwd: tile_points 4 / 8 / 16 need w_packed_m16 in every layer");
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && out && (emb_stride > 0 || (table && B_fourier)), "hm_sdf_fwd: NULL pointer");
-    // small batches: 16-point tiles spread the call over the whole chip (see sdf_m16_body / sdf_m8_body).
+    // small batches: 16-point tiles spread the call over the whole chip (see sdf_m16_body / sdf_m8_body), 8- and 4-point
+    // tiles below kSdfTiny / kSdfMini live points (one tile per CU), 64-point tiles above kSdfSmall.
     // With a device-side count the host cannot know the batch size: both kernels are enqueued and
     // each returns at once unless the live count falls in its range.
-    constexpr int64_t kSmall = 8192;
     const int64_t kBig = (int64_t)1 << 62;
     bool run16 = false, run64 = false;
     int64_t lo16 = 0, hi16 = kBig, lo64 = 0, hi64 = kBig;
-    // 8-point tiles below kTiny live points (one tile per CU), 16-point tiles up to kSmall, 64 above
-    // (4-point tiles below kMini: same weight stream, a quarter of the 16-point tile's matrix work)
-    constexpr int64_t kTiny = 2048, kMini = 1024;
-    int64_t m8_max = 0, m4_max = 0;
-    if (tile_points == -1) {   // small counts only: n > kSmall is another launch's job (bf16 coarse kernel)
+    if (tile_points == -1) {   // small counts only: n > kSdfSmall is another launch's job (bf16 coarse kernel)
         HM_CHECK_ARG(have16, "hm_sdf_fwd: tile_points -1 needs w_packed_m16 in every layer");
-        run16 = true; hi16 = kSmall; m8_max = kTiny; m4_max = kMini;
+        run16 = true; hi16 = kSdfSmall;
     }
-    else if (tile_points == 8) { run16 = true; m8_max = kBig; }
-    else if (tile_points == 4) { run16 = true; m8_max = kBig; m4_max = kBig; }
-    else if (tile_points == 16) run16 = true;
+    else if (tile_points == 4 || tile_points == 8 || tile_points == 16) run16 = true;
     else if (tile_points == 64 || !have16) run64 = true;
-    else if (!n_dev) { run16 = n <= kSmall; run64 = !run16; m8_max = kTiny; m4_max = kMini; }
-    else if (n <= kSmall) { run16 = true; m8_max = kTiny; m4_max = kMini; }
-    else { run16 = run64 = true; hi16 = kSmall; lo64 = kSmall + 1; m8_max = kTiny; m4_max = kMini; }
-    static thread_local bool attr_done = false;
-    if (!attr_done) {  // opt in to >64 KB dynamic LDS once (not a stream operation)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_kernel<HM_FRAC_REFERENCE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_kernel<kFracEmb>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        // (small tiles: two activation images of 32 KB + the embedding = 70 KB at 512-wide layers)
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_small_kernel<HM_FRAC_REFERENCE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_small_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_small_kernel<kFracEmb>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_done = true;
-    }
+    else if (!n_dev) { run16 = n <= kSdfSmall; run64 = !run16; }
+    else if (n <= kSdfSmall) run16 = true;
+    else { run16 = run64 = true; hi16 = kSdfSmall; lo64 = kSdfSmall + 1; }
+    const int64_t cap = max_workgroups > 0 ? max_workgroups : 256;  // one resident workgroup per CU
     if (run16) {
-        const size_t lds = sizeof(float) * ((size_t)(2 * net.x_groups + emb_b16 * 4) * kGroupFloats16 + kPts16 * 4 +
-                                            kWaves * kPts16);   // two activation images (the 8-point layout needs half of this)
+        const size_t lds = sdf_lds16(net, lv.E);
         HM_CHECK_ARG(lds <= 96 * 1024, "hm_sdf_fwd: network does not fit the 16-point LDS tile");
-        const int64_t nmax = n < hi16 ? n : hi16;
-        int64_t tiles = m8_max >= nmax ? 0 : (nmax + kPts16 - 1) / kPts16;
-        if (m8_max > 0) {
-            const int64_t n8 = nmax < m8_max ? nmax : m8_max;
-            tiles = max(tiles, (n8 + kPts8 - 1) / kPts8);
-        }
-        if (m4_max > 0) {
-            const int64_t n4 = nmax < m4_max ? nmax : m4_max;
-            tiles = max(tiles, (n4 + 3) / 4);
-        }
-        const int64_t cap = max_workgroups > 0 ? max_workgroups : 256;  // one resident workgroup per CU
-        const int64_t grid = tiles < cap ? tiles : cap;
-        if (mode == kFracEmb)
-            hipLaunchKernelGGL(sdf_fwd_small_kernel<kFracEmb>, dim3((unsigned)grid), dim3(kThreadsSdf), lds,
-                               as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, out_cols, n_dev,
-                               lo16, hi16, m8_max, m4_max);
-        else if (mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(sdf_fwd_small_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kThreadsSdf), lds,
-                               as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, out_cols, n_dev,
-                               lo16, hi16, m8_max, m4_max);
-        else
-            hipLaunchKernelGGL(sdf_fwd_small_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kThreadsSdf), lds,
-                               as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, out_cols, n_dev,
-                               lo16, hi16, m8_max, m4_max);
+        const SmallTiles t = sdf_small_tiles(tile_points);
+        const unsigned grid = sdf_small_grid(n < hi16 ? n : hi16, t, cap);
+        const int rc = sdf_dispatch(mode, [&](auto frac) {
+            // (two activation images of 32 KB + the embedding = 70 KB at 512-wide layers)
+            constexpr auto kernel = sdf_fwd_small_kernel<decltype(frac)::value>;
+            const int rc = hm_allow_dynamic_lds<kernel>(96 * 1024);
+            if (rc == HM_OK)
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), lv, net, x, n, table,
+                                   B_fourier, out, out_stride, out_cols, n_dev, lo16, hi16, t.m8_max, t.m4_max);
+            return rc;
+        });
+        if (rc != HM_OK) return rc;
     }
     // big batches: one 64-point workgroup per CU
     if (run64) {
-        const size_t lds = sizeof(float) * ((size_t)(net.x_groups + net.emb_groups) * kGroupFloats + kPts * 4 +
-                                            kWaves * kPts);
+        const size_t lds = sdf_lds64(net);
         HM_CHECK_ARG(lds <= 160 * 1024, "hm_sdf_fwd: network does not fit the 160 KB LDS tile");
         const int64_t tiles = (n + 31) / 32;      // (up to cap * 32 points: one 32-point half tile per workgroup)
-        const int64_t cap = max_workgroups > 0 ? max_workgroups : 256;
         const int64_t grid = tiles < cap ? tiles : cap;
         // filler tiles only where every launch of the chain applies the same lower bound (fill_quota's run_min)
         const SdfFillArgs none = {nullptr, nullptr, nullptr, nullptr, 0, 0};
-        const SdfFillArgs fa = (fill && lo64 == kSmall + 1 && out_cols == 1 && out_stride == 1) ? *fill : none;
+        const SdfFillArgs fa = (fill && lo64 == kSdfSmall + 1 && out_cols == 1 && out_stride == 1) ? *fill : none;
         if (grid64_out && fa.n_dev) *grid64_out = (int)grid;
-        if (mode == kFracEmb)
-            hipLaunchKernelGGL(sdf_fwd_kernel<kFracEmb>, dim3((unsigned)grid), dim3(kThreadsSdf), lds,
-                               as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, out_cols, n_dev,
-                               lo64, hi64, none);
-        else if (mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(sdf_fwd_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kThreadsSdf), lds,
-                               as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, out_cols, n_dev,
-                               lo64, hi64, fa);
-        else
-            hipLaunchKernelGGL(sdf_fwd_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kThreadsSdf), lds,
-                               as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, out_cols, n_dev,
-                               lo64, hi64, fa);
+        const int rc = sdf_dispatch(mode, [&](auto frac) {
+            constexpr auto kernel = sdf_fwd_kernel<decltype(frac)::value>;
+            const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
+            if (rc == HM_OK)
+                hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kThreadsSdf), lds, as_stream(stream), lv, net, x, n,
+                                   table, B_fourier, out, out_stride, out_cols, n_dev, lo64, hi64, fa);
+            return rc;
+        });
+        if (rc != HM_OK) return rc;
     }
     HM_CHECK_LAUNCH("hm_sdf_fwd");
     return HM_OK;

@@ -30,7 +30,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPB = 96;            // points per workgroup tile
 constexpr int kTB16 = 512;         // threads
-constexpr int kWB = 8;             // waves
 constexpr int kPT = kPB / 32;      // point tiles per wave (3)
 constexpr int kEmbGF = kPB * 4;    // floats per k-group row of the fp32 embedding image
 constexpr int kXOct = kPB * 8;     // bf16 elements per k-octet row of X
@@ -238,69 +237,30 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
     }
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 static int sdf_bf16_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,
                          const float *table, const float *B_fourier, float *out, int64_t out_stride, int frac_mode,
                          const int32_t *n_dev, int64_t run_min, void *stream) {
-    HM_CHECK_ARG(mlp, "hm_sdf_fwd_bf16: NULL descriptor");
     HM_CHECK_ARG(n >= 0, "hm_sdf_fwd_bf16: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_sdf_fwd_bf16: bad frac_mode");
-    HM_CHECK_ARG(mlp->n_layers >= 2 && mlp->n_layers <= HM_MAX_LAYERS, "hm_sdf_fwd_bf16: n_layers out of range");
     SdfNet net;
-    net.n_layers = mlp->n_layers;
-    net.beta = mlp->beta;
-    net.emb_stride = emb_stride;
-    const int emb_oct = (lv.E + 7) / 8, emb_b16 = (lv.E + 15) / 16;
-    net.emb_groups = emb_oct * 2;
-    int x_groups = 0;
-    for (int l = 0; l < mlp->n_layers; ++l) {
-        const hm_mlp_layer &Ly = mlp->layer[l];
-        HM_CHECK_ARG(Ly.w_packed && Ly.bias && Ly.w_packed_bf16, "hm_sdf_fwd_bf16: layer lacks the fp32 or the bf16 image");
-        HM_CHECK_ARG(Ly.n_tiles >= 1 && Ly.n_tiles <= 2 * kWB, "hm_sdf_fwd_bf16: layer wider than 512 features");
-        HM_CHECK_ARG(Ly.seg_octets[0] >= 1 && Ly.seg_octets[1] >= 0, "hm_sdf_fwd_bf16: bad segment length");
-        for (int s = 0; s < 2; ++s) {
-            if (Ly.seg_octets[s] == 0) continue;
-            if (Ly.seg_src[s] == 1) {
-                HM_CHECK_ARG(Ly.seg_octets[s] == emb_oct && Ly.seg_blocks16[s] == emb_b16,
-                             "hm_sdf_fwd_bf16: embedding segment must span ceil(E/8) octets / ceil(E/16) blocks");
-            } else {
-                HM_CHECK_ARG(l > 0 && Ly.seg_blocks16[s] * 16 <= mlp->layer[l - 1].n_tiles * 32 &&
-                                 Ly.seg_blocks16[s] * 16 >= mlp->layer[l - 1].out_dim,
-                             "hm_sdf_fwd_bf16: hidden segment does not match the previous layer");
-            }
-        }
-        x_groups = max(x_groups, Ly.n_tiles * 8);
-        net.layer[l] = Ly;
-    }
-    const hm_mlp_layer &last = mlp->layer[mlp->n_layers - 1];
-    HM_CHECK_ARG(last.seg_octets[1] == 0 && last.seg_src[0] == 0, "hm_sdf_fwd_bf16: the last layer must read the previous layer only");
-    net.x_groups = x_groups;
+    const int rc = sdf_net_from_desc("hm_sdf_fwd_bf16", mlp, lv.E, emb_stride, kImgBf16, 2, (lv.E + 7) / 8 * 2, true, net);
+    if (rc != HM_OK) return rc;
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && out && (emb_stride > 0 || (table && B_fourier)), "hm_sdf_fwd_bf16: NULL pointer");
-    const size_t lds = (size_t)(x_groups / 2) * kXOct * 2 + sizeof(float) * ((size_t)net.emb_groups * kEmbGF + kPB * 4 + 5 * kPB);
+    const size_t lds = (size_t)(net.x_groups / 2) * kXOct * 2 + sizeof(float) * ((size_t)net.emb_groups * kEmbGF + kPB * 4 + 5 * kPB);
     HM_CHECK_ARG(lds <= 160 * 1024, "hm_sdf_fwd_bf16: network does not fit the 160 KB LDS tile");
-    static thread_local bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_bf16_kernel<HM_FRAC_REFERENCE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_bf16_kernel<HM_FRAC_TRILINEAR>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_done = true;
-    }
     const int64_t tiles = (n + kPB - 1) / kPB;
     const int64_t grid = tiles < 256 ? tiles : 256;
     const int64_t big = (int64_t)1 << 62;
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(sdf_fwd_bf16_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kTB16), lds,
-                           as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, big);
-    else
-        hipLaunchKernelGGL(sdf_fwd_bf16_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kTB16), lds,
-                           as_stream(stream), lv, net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, big);
-    HM_CHECK_LAUNCH("hm_sdf_fwd_bf16");
-    return HM_OK;
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        constexpr auto kernel = sdf_fwd_bf16_kernel<decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kTB16), lds, as_stream(stream), lv, net, x, n, table,
+                           B_fourier, out, out_stride, n_dev, run_min, big);
+        HM_CHECK_LAUNCH("hm_sdf_fwd_bf16");
+        return HM_OK;
+    });
 }
 
 }  // namespace

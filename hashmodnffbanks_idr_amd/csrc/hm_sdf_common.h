@@ -129,3 +129,64 @@ __device__ __forceinline__ void embed_slot(const HmLevels &lv, const float *__re
         for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
     }
 }
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+// the weight image a fused SDF kernel reads from every layer besides the fp32 one (w_packed): the fp32 16-point image
+// (w_packed_m16; optional for hm_sdf_fwd, which runs the small tiles only when every layer carries it), the bf16 image or
+// the split-operand image
+enum SdfImage { kImgM16Optional, kImgM16, kImgBf16, kImgSplit };
+
+// Kernel-side image of the network descriptor + the checks every fused SDF launch makes on it.  The kernel families
+// differ in the image they read (img), their minimum layer count, the k-groups of their EMB region (emb_groups:
+// 2 ceil(E/8) for the fp32 and bf16 kernels, 4 ceil(E/16) for the split kernel) and whether the last layer may read
+// nothing but the previous layer (last_prev_only).  *all_m16: every layer carries w_packed_m16 (kImgM16Optional).
+static int sdf_net_from_desc(const char *who, const hm_mlp_desc *mlp, int E, int64_t emb_stride, SdfImage img,
+                             int min_layers, int emb_groups, bool last_prev_only, SdfNet &net, bool *all_m16 = nullptr) {
+    const auto bad = [who](const char *what) { return hm_fail(HM_ERR_INVALID, std::string(who) + ": " + what); };
+    if (!mlp) return bad("NULL descriptor");
+    if (mlp->n_layers < min_layers || mlp->n_layers > HM_MAX_LAYERS) return bad("n_layers out of range");
+    if (img == kImgSplit && mlp->split_kind != HM_SPLIT_BF16X2 && mlp->split_kind != HM_SPLIT_F16X2)
+        return bad("the descriptor carries no split image (split_kind)");
+    const int emb_oct = (E + 7) / 8, emb_b16 = (E + 15) / 16;
+    net.n_layers = mlp->n_layers;
+    net.x_groups = 0;
+    net.emb_groups = emb_groups;
+    net.beta = mlp->beta;
+    net.emb_stride = emb_stride;
+    if (all_m16) *all_m16 = true;
+    for (int l = 0; l < mlp->n_layers; ++l) {
+        const hm_mlp_layer &Ly = mlp->layer[l];
+        // the layer's 16-block image (segment lengths in seg_blocks16), if it has the one the kernel reads
+        const void *img16 = img == kImgBf16 ? Ly.w_packed_bf16 : img == kImgSplit ? Ly.w_packed_split : Ly.w_packed_m16;
+        if (!Ly.w_packed || !Ly.bias) return bad("layer has NULL weights/bias");
+        if (!img16 && img != kImgM16Optional) return bad("layer lacks the weight image of this kernel");
+        if (!img16 && all_m16) *all_m16 = false;
+        // (every kernel has 8 waves of up to 64 output features each)
+        if (Ly.n_tiles < 1 || Ly.n_tiles > 16) return bad("layer wider than 512 features");
+        if (Ly.out_dim < 1 || Ly.out_dim > Ly.n_tiles * 32) return bad("out_dim / n_tiles mismatch");
+        if (Ly.seg_octets[0] < 1 || Ly.seg_octets[1] < 0) return bad("bad segment length");
+        for (int s = 0; s < 2; ++s) {
+            if (Ly.seg_octets[s] == 0 && !(img16 && Ly.seg_blocks16[s] != 0)) continue;
+            if (Ly.seg_src[s] == 1) {
+                if (Ly.seg_octets[s] != emb_oct) return bad("embedding segment must span ceil(E/8) octets");
+                if (img16 && Ly.seg_blocks16[s] != emb_b16) return bad("embedding segment must span ceil(E/16) 16-blocks");
+            } else {
+                if (Ly.seg_src[s] != 0 || l == 0)
+                    return bad("a segment reads the embedding (1) or, after layer 0, the previous layer (0)");
+                const hm_mlp_layer &prev = mlp->layer[l - 1];
+                if (Ly.seg_octets[s] * 8 > prev.n_tiles * 32)
+                    return bad("layer reads more inputs than the previous layer produces");
+                if (Ly.seg_octets[s] * 8 < prev.out_dim)
+                    return bad("layer reads fewer inputs than the previous layer produces");
+                if (img16 && (Ly.seg_blocks16[s] * 16 > prev.n_tiles * 32 || Ly.seg_blocks16[s] * 16 < prev.out_dim))
+                    return bad("16-block segment length does not match the previous layer");
+            }
+        }
+        net.x_groups = max(net.x_groups, Ly.n_tiles * 8);
+        net.layer[l] = Ly;
+    }
+    const hm_mlp_layer &last = mlp->layer[mlp->n_layers - 1];
+    if (last_prev_only && (last.seg_octets[1] != 0 || last.seg_src[0] != 0))
+        return bad("the last layer must read the previous layer only");
+    return HM_OK;
+}

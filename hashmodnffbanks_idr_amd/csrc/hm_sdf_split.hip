@@ -342,77 +342,35 @@ __global__ __launch_bounds__(256) void pack_layer_split_kernel(PackSplitArgs a, 
     img[o + 512] = lo;
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
-template <int KIND, int FRAC>
-static int launch_split(const HmLevels &lv, const SdfNet &net, const float *x, int64_t n, const float *table,
-                        const float *B_fourier, float *out, int64_t out_stride, const int32_t *n_dev, int64_t run_min,
-                        size_t lds, void *stream) {
-    static thread_local bool attr_done = false;
-    if (!attr_done) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sdf_fwd_split_kernel<KIND, FRAC>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return hm_fail(HM_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-        attr_done = true;
-    }
-    const int64_t tiles = (n + kPS - 1) / kPS;
-    const int64_t grid = tiles < 256 ? tiles : 256;
-    const int64_t big = (int64_t)1 << 62;
-    hipLaunchKernelGGL((sdf_fwd_split_kernel<KIND, FRAC>), dim3((unsigned)grid), dim3(kTS), lds, as_stream(stream), lv,
-                       net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, big);
-    HM_CHECK_LAUNCH("hm_sdf_fwd_split");
-    return HM_OK;
-}
-
 static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,
                           const float *table, const float *B_fourier, float *out, int64_t out_stride, int frac_mode,
                           const int32_t *n_dev, int64_t run_min, void *stream) {
-    HM_CHECK_ARG(mlp, "hm_sdf_fwd_split: NULL descriptor");
     HM_CHECK_ARG(n >= 0, "hm_sdf_fwd_split: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_sdf_fwd_split: bad frac_mode");
-    HM_CHECK_ARG(mlp->n_layers >= 2 && mlp->n_layers <= HM_MAX_LAYERS, "hm_sdf_fwd_split: n_layers out of range");
-    HM_CHECK_ARG(mlp->split_kind == HM_SPLIT_BF16X2 || mlp->split_kind == HM_SPLIT_F16X2,
-                 "hm_sdf_fwd_split: the descriptor carries no split image (split_kind)");
-    SdfNet net;
-    net.n_layers = mlp->n_layers;
-    net.beta = mlp->beta;
-    net.emb_stride = emb_stride;
-    const int emb_b16 = (lv.E + 15) / 16;
-    net.emb_groups = emb_b16 * 4;      // k-groups of 4 = 2 octets per 16-block
-    int x_groups = 0;
-    for (int l = 0; l < mlp->n_layers; ++l) {
-        const hm_mlp_layer &Ly = mlp->layer[l];
-        HM_CHECK_ARG(Ly.w_packed && Ly.bias && Ly.w_packed_split, "hm_sdf_fwd_split: layer lacks the fp32 or the split image");
-        HM_CHECK_ARG(Ly.n_tiles >= 1 && Ly.n_tiles <= 2 * kWS, "hm_sdf_fwd_split: layer wider than 512 features");
-        HM_CHECK_ARG(Ly.seg_blocks16[0] >= 1 && Ly.seg_blocks16[1] >= 0, "hm_sdf_fwd_split: bad segment length");
-        for (int s = 0; s < 2; ++s) {
-            if (Ly.seg_blocks16[s] == 0) continue;
-            if (Ly.seg_src[s] == 1) {
-                HM_CHECK_ARG(Ly.seg_blocks16[s] == emb_b16, "hm_sdf_fwd_split: embedding segment must span ceil(E/16) blocks");
-            } else {
-                HM_CHECK_ARG(l > 0 && Ly.seg_blocks16[s] * 16 <= mlp->layer[l - 1].n_tiles * 32 &&
-                                 Ly.seg_blocks16[s] * 16 >= mlp->layer[l - 1].out_dim,
-                             "hm_sdf_fwd_split: hidden segment does not match the previous layer");
-            }
-        }
-        x_groups = max(x_groups, Ly.n_tiles * 8);
-        net.layer[l] = Ly;
-    }
-    const hm_mlp_layer &last = mlp->layer[mlp->n_layers - 1];
-    HM_CHECK_ARG(last.seg_octets[1] == 0 && last.seg_src[0] == 0, "hm_sdf_fwd_split: the last layer must read the previous layer only");
-    net.x_groups = x_groups;
+    SdfNet net;   // (EMB region: k-groups of 4 = 2 octets per 16-block)
+    const int rc =
+        sdf_net_from_desc("hm_sdf_fwd_split", mlp, lv.E, emb_stride, kImgSplit, 2, (lv.E + 15) / 16 * 4, true, net);
+    if (rc != HM_OK) return rc;
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && out && (emb_stride > 0 || (table && B_fourier)), "hm_sdf_fwd_split: NULL pointer");
-    const size_t lds = (size_t)(x_groups / 2 + net.emb_groups / 2) * kOctE * 2 * 2 + sizeof(float) * (kPS * 4 + kWS * kPS);
+    const size_t lds = (size_t)(net.x_groups / 2 + net.emb_groups / 2) * kOctE * 2 * 2 + sizeof(float) * (kPS * 4 + kWS * kPS);
     HM_CHECK_ARG(lds <= 160 * 1024, "hm_sdf_fwd_split: network does not fit the 160 KB LDS tile");
-    if (mlp->split_kind == HM_SPLIT_BF16X2) {
-        if (frac_mode == HM_FRAC_REFERENCE)
-            return launch_split<HM_SPLIT_BF16X2, HM_FRAC_REFERENCE>(lv, net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, lds, stream);
-        return launch_split<HM_SPLIT_BF16X2, HM_FRAC_TRILINEAR>(lv, net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, lds, stream);
-    }
-    if (frac_mode == HM_FRAC_REFERENCE)
-        return launch_split<HM_SPLIT_F16X2, HM_FRAC_REFERENCE>(lv, net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, lds, stream);
-    return launch_split<HM_SPLIT_F16X2, HM_FRAC_TRILINEAR>(lv, net, x, n, table, B_fourier, out, out_stride, n_dev, run_min, lds, stream);
+    const int64_t tiles = (n + kPS - 1) / kPS;
+    const int64_t grid = tiles < 256 ? tiles : 256;
+    const int64_t big = (int64_t)1 << 62;
+    const auto launch = [&](auto kind, auto frac) {
+        constexpr auto kernel = sdf_fwd_split_kernel<decltype(kind)::value, decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kTS), lds, as_stream(stream), lv, net, x, n, table,
+                           B_fourier, out, out_stride, n_dev, run_min, big);
+        HM_CHECK_LAUNCH("hm_sdf_fwd_split");
+        return HM_OK;
+    };
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
+        return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
+    });
 }
 
 }  // namespace

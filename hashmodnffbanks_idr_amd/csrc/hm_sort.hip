@@ -99,7 +99,6 @@ __global__ __launch_bounds__(kST) void radix_scatter_kernel(const int32_t *__res
     }
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 inline int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace

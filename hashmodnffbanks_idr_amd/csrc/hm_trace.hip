@@ -307,8 +307,6 @@ __global__ void count_evals_kernel(int32_t *cnt, int rounds, int n_secant) {
     cnt[C_EVALS] = (int32_t)tot;
 }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct Layout {
@@ -436,7 +434,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     const char *e_ov = getenv("HM_TRACE_OVERLAP");      // (read per call: the tests compare both forms in one process)
     const bool overlap_ok = !(e_ov && atoi(e_ov) == 0);
     const bool overlap = overlap_ok && cfg->training && !nffb && !cfg->coarse_bf16 && tile_points == 0 &&
-                         cfg->n_secant_steps > 0 && n_rays <= 8192;
+                         cfg->n_secant_steps > 0 && n_rays <= kSdfSmall;
     a.sel_off = overlap ? 2 * L.cap : -1;
 
     hm_zero_u32_async(a.w.cnt, C_COUNT, st);
@@ -459,6 +457,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     auto coarse = [&](int64_t off, int64_t capacity, const int32_t *n_dev) -> int {
         const float *p = a.w.pts + off * 3;
         float *v = a.w.vals + off;
+        const int64_t run_min = kSdfSmall + 1;   // (16-bit coarse kernels: the counts the small-tile launch leaves)
         int rc;
         if (!cfg->coarse_bf16) {
             if (nffb) {
@@ -468,20 +467,20 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             } else {
                 rc = hm_sdf_fwd(desc, mlp, p, capacity, table, B_fourier, v, 1, 1, frac_mode, tile_points, n_dev, 0, stream);
             }
-        } else if (nffb) {   // coarse scans on the 16-bit matrix cores above 8192 live points, exact fp32 small tiles below
+        } else if (nffb) {   // coarse scans on the 16-bit matrix cores above kSdfSmall live points, exact fp32 small tiles below
             rc = hm_nffb_fwd(desc, nffb, p, capacity, table, B_fourier, emb_ws, emb_width, frac_mode, n_dev, stream);
             if (rc == HM_OK)
                 rc = hm_sdf_fwd_emb(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, 1, -1, n_dev, 0, stream);
             if (rc == HM_OK)
                 rc = cfg->coarse_bf16 == 2
-                         ? hm_sdf_fwd_emb_split(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, 8193, stream)
-                         : hm_sdf_fwd_emb_bf16(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, 8193, stream);
+                         ? hm_sdf_fwd_emb_split(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, stream)
+                         : hm_sdf_fwd_emb_bf16(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, stream);
         } else {
             rc = hm_sdf_fwd(desc, mlp, p, capacity, table, B_fourier, v, 1, 1, frac_mode, -1, n_dev, 0, stream);
             if (rc == HM_OK)
                 rc = cfg->coarse_bf16 == 2
-                         ? hm_sdf_fwd_split(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, 8193, stream)
-                         : hm_sdf_fwd_bf16(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, 8193, stream);
+                         ? hm_sdf_fwd_split(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, run_min, stream)
+                         : hm_sdf_fwd_bf16(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, run_min, stream);
         }
         return rc;
     };
@@ -563,7 +562,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             if (rc != HM_OK) return rc;
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         } else if (!nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
-            (tile_points != 0 || n_rays <= 8192)) {
+            (tile_points != 0 || n_rays <= kSdfSmall)) {
             const int rc = hm_trace_secant_persistent(desc, mlp, table, B_fourier, frac_mode, tile_points, &a,
                                                       cfg->n_secant_steps, stream);
             if (rc != HM_OK) return rc;

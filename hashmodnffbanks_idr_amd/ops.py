@@ -715,55 +715,52 @@ def sdf_fwd(desc, packed, x, table, B, frac_mode=0, sdf_only=False, max_workgrou
     return out[:, 0] if sdf_only else out
 
 
+def _sdf_fwd_coarse(name, kind, packed, x, n_dev, run_min, grid=None):
+    """sdf-only values [N] from the 16-bit coarse-search kernels (kind "bf16": hm_sdf_fwd_bf16, "split":
+    hm_sdf_fwd_split; packed.split names the split kind) on points x with grid = (desc, table, B, frac_mode), or on
+    precomputed embedding rows x when grid is None (the _emb_ entry points)"""
+    if grid is None:
+        require_gpu(x)
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        n, width = x.shape
+    else:
+        desc, table, B, frac_mode = grid
+        x = _prep_x(x)
+        require_gpu(x, table, B)
+        n = x.shape[0]
+    if not (packed.has_bf16 if kind == "bf16" else packed.split is not None):
+        raise ValueError(f"hashmod {name}: the packed weights carry no {kind} image")
+    out = torch.empty((n, 1), dtype=torch.float32, device=x.device)
+    if grid is None:
+        fn = lib().hm_sdf_fwd_emb_bf16 if kind == "bf16" else lib().hm_sdf_fwd_emb_split
+        check(fn(C.byref(packed.desc), dptr(x), x.stride(0), width, n, dptr(out), 1, dptr(n_dev), int(run_min),
+                 stream_ptr(x)))
+    else:
+        fn = lib().hm_sdf_fwd_bf16 if kind == "bf16" else lib().hm_sdf_fwd_split
+        check(fn(desc.handle, C.byref(packed.desc), dptr(x), n, dptr(table), dptr(B.contiguous()), dptr(out), 1,
+                 int(frac_mode), dptr(n_dev), int(run_min), stream_ptr(x)))
+    return out[:, 0]
+
+
 def sdf_fwd_bf16(desc, packed, x, table, B, frac_mode=0, n_dev=None, run_min=0):
     """sdf-only values [N] from the bf16 variant of the fused kernel (hm_sdf_fwd_bf16; coarse-search precision)."""
-    x = _prep_x(x)
-    require_gpu(x, table, B)
-    if not packed.has_bf16:
-        raise ValueError("hashmod sdf_fwd_bf16: the packed weights carry no bf16 image")
-    n = x.shape[0]
-    out = torch.empty((n, 1), dtype=torch.float32, device=x.device)
-    check(lib().hm_sdf_fwd_bf16(desc.handle, C.byref(packed.desc), dptr(x), n, dptr(table), dptr(B.contiguous()),
-                                dptr(out), 1, int(frac_mode), dptr(n_dev), int(run_min), stream_ptr(x)))
-    return out[:, 0]
+    return _sdf_fwd_coarse("sdf_fwd_bf16", "bf16", packed, x, n_dev, run_min, (desc, table, B, frac_mode))
 
 
 def sdf_fwd_split(desc, packed, x, table, B, frac_mode=0, n_dev=None, run_min=0):
     """sdf-only values [N] from the split-operand kernel (hm_sdf_fwd_split; kind = packed.split)."""
-    x = _prep_x(x)
-    require_gpu(x, table, B)
-    if packed.split is None:
-        raise ValueError("hashmod sdf_fwd_split: the packed weights carry no split image")
-    n = x.shape[0]
-    out = torch.empty((n, 1), dtype=torch.float32, device=x.device)
-    check(lib().hm_sdf_fwd_split(desc.handle, C.byref(packed.desc), dptr(x), n, dptr(table), dptr(B.contiguous()),
-                                 dptr(out), 1, int(frac_mode), dptr(n_dev), int(run_min), stream_ptr(x)))
-    return out[:, 0]
+    return _sdf_fwd_coarse("sdf_fwd_split", "split", packed, x, n_dev, run_min, (desc, table, B, frac_mode))
 
 
 def sdf_fwd_emb_split(packed, emb, n_dev=None, run_min=0):
     """the same on precomputed embedding rows (hm_sdf_fwd_emb_split)"""
-    require_gpu(emb)
-    if packed.split is None:
-        raise ValueError("hashmod sdf_fwd_emb_split: the packed weights carry no split image")
-    if emb.stride(-1) != 1:
-        emb = emb.contiguous()
-    n, width = emb.shape
-    out = torch.empty((n, 1), dtype=torch.float32, device=emb.device)
-    check(lib().hm_sdf_fwd_emb_split(C.byref(packed.desc), dptr(emb), emb.stride(0), width, n, dptr(out), 1,
-                                     dptr(n_dev), int(run_min), stream_ptr(emb)))
-    return out[:, 0]
+    return _sdf_fwd_coarse("sdf_fwd_emb_split", "split", packed, emb, n_dev, run_min)
 
 
 def sdf_fwd_emb_bf16(packed, emb, n_dev=None, run_min=0):
-    require_gpu(emb)
-    if emb.stride(-1) != 1:
-        emb = emb.contiguous()
-    n, width = emb.shape
-    out = torch.empty((n, 1), dtype=torch.float32, device=emb.device)
-    check(lib().hm_sdf_fwd_emb_bf16(C.byref(packed.desc), dptr(emb), emb.stride(0), width, n, dptr(out), 1,
-                                    dptr(n_dev), int(run_min), stream_ptr(emb)))
-    return out[:, 0]
+    """sdf_fwd_bf16 on precomputed embedding rows (hm_sdf_fwd_emb_bf16)"""
+    return _sdf_fwd_coarse("sdf_fwd_emb_bf16", "bf16", packed, emb, n_dev, run_min)
 
 
 def sdf_fwd_emb(packed, emb, sdf_only=False, tile_points=0, n_dev=None, max_workgroups=0):

@@ -258,6 +258,41 @@ def test_colsum_matches_torch():
     assert torch.equal(x.grad[5], torch.arange(445, device="cuda").float())
 
 
+@pytest.mark.parametrize("entry", ["sdf_fwd", "sdf_fwd_emb", "sdf_fwd_bf16", "sdf_fwd_emb_bf16", "sdf_fwd_split",
+                                   "sdf_fwd_emb_split"])
+def test_every_sdf_family_validates_the_descriptor(entry):
+    """The six fused SDF entry points check the network descriptor in one place (sdf_net_from_desc): an embedding
+    segment of the wrong length and a layer without the family's weight image both fail with ValueError."""
+    from hashmodnffbanks_idr_amd import ops
+    net = make_implicit("tiny", (64,) * 8, 16, 3, 0.5, 0.5)
+    net.bf16_coarse_search = True
+    net.coarse_split = "bf16x2"
+    emb = net.embed_model.embedder_obj
+    x = torch.from_numpy(P.make_points(2, 100)).cuda()
+    with torch.no_grad():
+        e = ops.encode_fwd(emb.desc, x, emb.table.detach(), emb.freq_encoding.B, 0)
+        pk = net.packed_weights()
+    fn = getattr(ops, entry)
+
+    def run():
+        if "_emb" in entry:
+            return fn(pk, e)
+        return fn(emb.desc, pk, x, emb.table.detach(), emb.freq_encoding.B)
+
+    assert torch.isfinite(run()).all()
+    ly = pk.desc.layer[0]
+    ly.seg_octets[0] += 1
+    ly.seg_blocks16[0] += 1
+    with pytest.raises(ValueError, match="embedding segment"):
+        run()
+    ly.seg_octets[0] -= 1
+    ly.seg_blocks16[0] -= 1
+    image = "w_packed_bf16" if "bf16" in entry else "w_packed_split" if "split" in entry else "w_packed"
+    setattr(pk.desc.layer[1], image, None)
+    with pytest.raises(ValueError, match="weights|image"):
+        run()
+
+
 def test_pack_kernel_matches_layout_contract():
     """hm_pack_mlp_layer vs the torch expression of the layout contract (ops.pack_mlp_layer)."""
     from hashmodnffbanks_idr_amd import ops
