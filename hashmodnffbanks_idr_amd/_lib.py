@@ -94,6 +94,10 @@ SIGNATURES = {
     "hm_encode_bwd_table_sorted_tracked": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "hm_gemm_f32_ep": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     "hm_gemm_f32": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _int, _p]),
+    "hm_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "hm_mc_count": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _i64, _p, _p]),
+    "hm_mc_emit": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _p, _i64, _i64, _i64, _p, _p, _p,
+                          _p]),
 }
 
 

@@ -1,0 +1,342 @@
+// hm_mesh.hip - marching cubes of a device fp32 volume (reference: skimage.measure.marching_cubes as plots.py:122-128
+// calls it; topology from the generated case table hm_mc_table.h, see scripts/gen_mc_table.py).
+//
+// The output size depends on the data, so there are two phases around one host read of the totals:
+//   hm_mc_count  mc_classify   per lattice point: the sign-changing lattice edges it owns (+x, +y, +z) and the case of
+//                              the cell it is the lowest corner of -> a uint16 code; per 4096-point block: vertex and
+//                              triangle sums and a NaN bit
+//                mc_scan       one workgroup: exclusive prefix of the block sums, the int64 totals and the NaN flag
+//   hm_mc_emit   mc_verts      per point: vertex base = block offset + in-block prefix (-> vbase, int32), its vertices
+//                              (linear interpolation on the edge) and normals (interpolated central differences)
+//                mc_faces      per cell: face base likewise; each edge of a table triangle is the vertex
+//                              vbase[q] + (its axis' rank among q's crossing axes) of one of the cell's 8 points q
+// Order of the outputs: vertices by owning point (linear index (i*ny + j)*nz + k), then axis x < y < z; faces by cell
+// linear index, then table order - independent of the volume's strides.  No atomics: two calls give the same bits.
+// Workspace: 2 B (code) + 4 B (vbase) per lattice point + 32 B per block.
+#include "hm_common.h"
+#include "hm_mc_table.h"
+
+namespace {
+
+constexpr int kMT = 256;                  // threads per workgroup
+constexpr int kMRounds = 16;              // rounds of kMT consecutive points per workgroup
+constexpr int kMBlock = kMT * kMRounds;   // 4096 lattice points per workgroup
+constexpr int kScanT = 1024;
+
+struct McVol {
+    const float *v;
+    int32_t nx, ny, nz;
+    int64_t sx, sy, sz;
+    __device__ __forceinline__ float at(int i, int j, int k) const {
+        return v[(int64_t)i * sx + (int64_t)j * sy + (int64_t)k * sz];
+    }
+};
+
+struct McWs {
+    uint16_t *code;      // [n] bits 0-7 cell case (0 on the upper faces), bits 8-10 crossing axes
+    int32_t *vbase;      // [n]
+    int32_t *bsum;       // [3][nb] vertex sum, triangle sum, NaN bit per block
+    int64_t *boff;       // [2][nb] exclusive block offsets of vertices and triangles
+};
+
+inline int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
+
+McWs carve(void *ws, int64_t n) {
+    const int64_t nb = (n + kMBlock - 1) / kMBlock;
+    char *p = static_cast<char *>(ws);
+    McWs w;
+    w.code = reinterpret_cast<uint16_t *>(p);
+    p += up256(2 * n);
+    w.vbase = reinterpret_cast<int32_t *>(p);
+    p += up256(4 * n);
+    w.bsum = reinterpret_cast<int32_t *>(p);
+    p += up256(12 * nb);
+    w.boff = reinterpret_cast<int64_t *>(p);
+    return w;
+}
+
+__device__ __forceinline__ void mc_point(int64_t q, const McVol &V, int &i, int &j, int &k) {
+    const uint32_t u = (uint32_t)q;
+    k = (int)(u % (uint32_t)V.nz);
+    const uint32_t r = u / (uint32_t)V.nz;
+    j = (int)(r % (uint32_t)V.ny);
+    i = (int)(r / (uint32_t)V.ny);
+}
+
+// exclusive prefix of x over the workgroup's threads (in thread order) and the workgroup total
+__device__ __forceinline__ int block_excl_scan(int x, int *lds_waves, int &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int s = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(s, o, 64);
+        if (lane >= o) s += y;
+    }
+    if (lane == 63) lds_waves[wave] = s;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kMT / 64; ++w) {
+        const int t = lds_waves[w];
+        before += w < wave ? t : 0;
+        total += t;
+    }
+    __syncthreads();
+    return before + s - x;
+}
+
+__global__ __launch_bounds__(kMT) void mc_classify_kernel(McVol V, float level, int64_t n, uint16_t *__restrict__ code,
+                                                          int32_t *__restrict__ bsum, int64_t nb) {
+    __shared__ int red[3][kMT / 64];
+    const int64_t beg = (int64_t)blockIdx.x * kMBlock;
+    int nv = 0, nt = 0, nan = 0;
+    for (int r = 0; r < kMRounds; ++r) {
+        const int64_t q = beg + (int64_t)r * kMT + threadIdx.x;
+        if (q >= n) break;
+        int i, j, k;
+        mc_point(q, V, i, j, k);
+        const float c0 = V.at(i, j, k);
+        nan |= c0 != c0;
+        const bool in0 = c0 < level;
+        const bool hx = i + 1 < V.nx, hy = j + 1 < V.ny, hz = k + 1 < V.nz;
+        // corner values of the cell (i, j, k) .. (i+1, j+1, k+1); only the ones that exist are read
+        const float c1 = hx ? V.at(i + 1, j, k) : c0;
+        const float c2 = hy ? V.at(i, j + 1, k) : c0;
+        const float c4 = hz ? V.at(i, j, k + 1) : c0;
+        const int mask = ((hx && (c1 < level) != in0) ? 1 : 0) | ((hy && (c2 < level) != in0) ? 2 : 0) |
+                         ((hz && (c4 < level) != in0) ? 4 : 0);
+        int cs = 0;
+        if (hx && hy && hz) {
+            const float c3 = V.at(i + 1, j + 1, k), c5 = V.at(i + 1, j, k + 1);
+            const float c6 = V.at(i, j + 1, k + 1), c7 = V.at(i + 1, j + 1, k + 1);
+            cs = (int)in0 | (int)(c1 < level) << 1 | (int)(c2 < level) << 2 | (int)(c3 < level) << 3 |
+                 (int)(c4 < level) << 4 | (int)(c5 < level) << 5 | (int)(c6 < level) << 6 | (int)(c7 < level) << 7;
+        }
+        code[q] = (uint16_t)(cs | mask << 8);
+        nv += __popc(mask);
+        nt += hm_mc_tris[cs][0];
+    }
+    // workgroup sums (fixed order: wave reduction, then the waves in order)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        nv += __shfl_xor(nv, o, 64);
+        nt += __shfl_xor(nt, o, 64);
+        nan |= __shfl_xor(nan, o, 64);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][wave] = nv;
+        red[1][wave] = nt;
+        red[2][wave] = nan;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        int s = 0;
+        for (int w = 0; w < kMT / 64; ++w) s = threadIdx.x == 2 ? (s | red[2][w]) : s + red[threadIdx.x][w];
+        bsum[threadIdx.x * nb + blockIdx.x] = s;
+    }
+}
+
+// exclusive prefix of the block sums (int64), totals[0..2] = vertices, triangles, NaN flag
+__global__ __launch_bounds__(kScanT) void mc_scan_kernel(const int32_t *__restrict__ bsum, int64_t nb,
+                                                         int64_t *__restrict__ boff, int64_t *__restrict__ totals) {
+    __shared__ int64_t pv[kScanT], pt[kScanT];
+    __shared__ int pn[kScanT];
+    const int64_t per = (nb + kScanT - 1) / kScanT;
+    const int64_t beg = min((int64_t)threadIdx.x * per, nb), end = min(beg + per, nb);
+    int64_t sv = 0, st = 0;
+    int nan = 0;
+    for (int64_t b = beg; b < end; ++b) {
+        sv += bsum[b];
+        st += bsum[nb + b];
+        nan |= bsum[2 * nb + b];
+    }
+    pv[threadIdx.x] = sv;
+    pt[threadIdx.x] = st;
+    pn[threadIdx.x] = nan;
+    __syncthreads();
+    for (int o = 1; o < kScanT; o <<= 1) {
+        const int64_t av = (int)threadIdx.x >= o ? pv[threadIdx.x - o] : 0;
+        const int64_t at = (int)threadIdx.x >= o ? pt[threadIdx.x - o] : 0;
+        const int an = (int)threadIdx.x >= o ? pn[threadIdx.x - o] : 0;
+        __syncthreads();
+        pv[threadIdx.x] += av;
+        pt[threadIdx.x] += at;
+        pn[threadIdx.x] |= an;
+        __syncthreads();
+    }
+    int64_t rv = pv[threadIdx.x] - sv, rt = pt[threadIdx.x] - st;
+    for (int64_t b = beg; b < end; ++b) {
+        boff[b] = rv;
+        boff[nb + b] = rt;
+        rv += bsum[b];
+        rt += bsum[nb + b];
+    }
+    if (threadIdx.x == kScanT - 1) {
+        totals[0] = pv[kScanT - 1];
+        totals[1] = pt[kScanT - 1];
+        totals[2] = pn[kScanT - 1];
+    }
+}
+
+// central difference along each axis (one-sided at the border) over the spacing: numpy.gradient's rule
+__device__ __forceinline__ void mc_grad(const McVol &V, int i, int j, int k, const float (&sp)[3], float (&g)[3]) {
+    const int n[3] = {V.nx, V.ny, V.nz};
+    const int p[3] = {i, j, k};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int lo = p[a] > 0 ? p[a] - 1 : p[a], hi = p[a] + 1 < n[a] ? p[a] + 1 : p[a];
+        const float vlo = V.at(a == 0 ? lo : i, a == 1 ? lo : j, a == 2 ? lo : k);
+        const float vhi = V.at(a == 0 ? hi : i, a == 1 ? hi : j, a == 2 ? hi : k);
+        g[a] = (vhi - vlo) / ((float)(hi - lo) * sp[a]);
+    }
+}
+
+__global__ __launch_bounds__(kMT) void mc_verts_kernel(McVol V, float level, float spx, float spy, float spz, int64_t n,
+                                                       const uint16_t *__restrict__ code, int32_t *__restrict__ vbase,
+                                                       const int64_t *__restrict__ boff, int64_t cap_v,
+                                                       float *__restrict__ verts, float *__restrict__ normals) {
+    __shared__ int lds_waves[kMT / 64];
+    const float sp[3] = {spx, spy, spz};
+    const int64_t beg = (int64_t)blockIdx.x * kMBlock;
+    int64_t base = boff[blockIdx.x];
+    for (int r = 0; r < kMRounds; ++r) {
+        if (beg + (int64_t)r * kMT >= n) break;  // uniform over the workgroup
+        const int64_t q = beg + (int64_t)r * kMT + threadIdx.x;
+        const int mask = q < n ? code[q] >> 8 : 0;
+        int total;
+        const int pre = block_excl_scan(__popc(mask), lds_waves, total);
+        if (q < n) {
+            int64_t vi = base + pre;
+            vbase[q] = (int32_t)vi;
+            if (mask) {
+                int i, j, k;
+                mc_point(q, V, i, j, k);
+                const float a = V.at(i, j, k);
+                float g0[3];
+                mc_grad(V, i, j, k, sp, g0);
+                for (int ax = 0; ax < 3; ++ax) {
+                    if (!((mask >> ax) & 1)) continue;
+                    const int i1 = i + (ax == 0), j1 = j + (ax == 1), k1 = k + (ax == 2);
+                    const float b = V.at(i1, j1, k1);
+                    const float t = (level - a) / (b - a);
+                    float g1[3], nn[3];
+                    mc_grad(V, i1, j1, k1, sp, g1);
+#pragma unroll
+                    for (int m = 0; m < 3; ++m) nn[m] = g0[m] + t * (g1[m] - g0[m]);
+                    const float d = nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2];
+                    const float s = sqrtf(d);
+                    if (vi < cap_v) {
+                        const int id[3] = {i, j, k};
+#pragma unroll
+                        for (int m = 0; m < 3; ++m) {
+                            verts[vi * 3 + m] = (m == ax ? (float)id[m] + t : (float)id[m]) * sp[m];
+                            normals[vi * 3 + m] = d > 0.0f ? nn[m] / s : 0.0f;
+                        }
+                    }
+                    ++vi;
+                }
+            }
+        }
+        base += total;
+    }
+}
+
+__global__ __launch_bounds__(kMT) void mc_faces_kernel(McVol V, int64_t n, const uint16_t *__restrict__ code,
+                                                       const int32_t *__restrict__ vbase,
+                                                       const int64_t *__restrict__ boff, int64_t cap_f,
+                                                       int32_t *__restrict__ faces) {
+    __shared__ int lds_waves[kMT / 64];
+    const int64_t beg = (int64_t)blockIdx.x * kMBlock;
+    const int64_t sj = V.nz, si = (int64_t)V.ny * V.nz;
+    int64_t base = boff[blockIdx.x];
+    for (int r = 0; r < kMRounds; ++r) {
+        if (beg + (int64_t)r * kMT >= n) break;
+        const int64_t q = beg + (int64_t)r * kMT + threadIdx.x;
+        const int cs = q < n ? code[q] & 255 : 0;
+        const int nt = hm_mc_tris[cs][0];
+        int total;
+        const int pre = block_excl_scan(nt, lds_waves, total);
+        int64_t f = base + pre;
+        for (int t = 0; t < nt; ++t, ++f) {
+            if (f >= cap_f) break;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                const int e = hm_mc_tris[cs][1 + 3 * t + m];
+                const int c = hm_mc_edge_corner[e], ax = hm_mc_edge_axis[e];
+                const int64_t p = q + (c & 1) * si + ((c >> 1) & 1) * sj + ((c >> 2) & 1);
+                const int pmask = code[p] >> 8;
+                faces[f * 3 + m] = vbase[p] + __popc(pmask & ((1 << ax) - 1));
+            }
+        }
+        base += total;
+    }
+}
+
+int mc_check_volume(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy, int64_t sz,
+                    const char *what) {
+    const std::string w(what);
+    HM_CHECK_ARG(nx >= 2 && ny >= 2 && nz >= 2, w + ": every volume dimension must be >= 2");
+    HM_CHECK_ARG(nx * ny * nz < ((int64_t)1 << 31), w + ": nx*ny*nz must be < 2^31");
+    HM_CHECK_ARG(sx >= 0 && sy >= 0 && sz >= 0, w + ": negative stride");
+    HM_CHECK_ARG(vol != nullptr, w + ": volume is NULL");
+    return HM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t hm_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || nx * ny * nz >= ((int64_t)1 << 31))
+        return hm_fail(HM_ERR_INVALID, "hm_mc_workspace_bytes: dimensions must be >= 2 and nx*ny*nz < 2^31");
+    const int64_t n = nx * ny * nz, nb = (n + kMBlock - 1) / kMBlock;
+    return up256(2 * n) + up256(4 * n) + up256(12 * nb) + up256(16 * nb);
+}
+
+int hm_mc_count(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy, int64_t sz, float level,
+                void *workspace, int64_t workspace_bytes, int64_t *counts, void *stream) {
+    if (int rc = mc_check_volume(vol, nx, ny, nz, sx, sy, sz, "hm_mc_count")) return rc;
+    HM_CHECK_ARG(workspace && counts, "hm_mc_count: NULL workspace or counts");
+    HM_CHECK_ARG(workspace_bytes >= hm_mc_workspace_bytes(nx, ny, nz), "hm_mc_count: workspace too small");
+    HM_CHECK_ARG(level == level, "hm_mc_count: level is NaN");
+    const int64_t n = nx * ny * nz, nb = (n + kMBlock - 1) / kMBlock;
+    const McVol V{vol, (int32_t)nx, (int32_t)ny, (int32_t)nz, sx, sy, sz};
+    const McWs w = carve(workspace, n);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, V, level, n, w.code, w.bsum, nb);
+    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kScanT), 0, st, static_cast<const int32_t *>(w.bsum), nb, w.boff,
+                       counts);
+    HM_CHECK_LAUNCH("hm_mc_count");
+    return HM_OK;
+}
+
+int hm_mc_emit(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy, int64_t sz, float level,
+               const float *spacing, void *workspace, int64_t workspace_bytes, int64_t n_verts, int64_t n_faces,
+               float *verts, float *normals, int32_t *faces, void *stream) {
+    if (int rc = mc_check_volume(vol, nx, ny, nz, sx, sy, sz, "hm_mc_emit")) return rc;
+    HM_CHECK_ARG(workspace && spacing, "hm_mc_emit: NULL workspace or spacing");
+    HM_CHECK_ARG(workspace_bytes >= hm_mc_workspace_bytes(nx, ny, nz), "hm_mc_emit: workspace too small");
+    HM_CHECK_ARG(n_verts >= 0 && n_faces >= 0, "hm_mc_emit: negative count");
+    HM_CHECK_ARG(n_verts <= INT32_MAX && n_faces <= INT32_MAX,
+                 "hm_mc_emit: " + std::to_string(n_verts) + " vertices / " + std::to_string(n_faces) +
+                     " faces do not fit int32 indices");
+    HM_CHECK_ARG(n_verts == 0 || (verts && normals), "hm_mc_emit: NULL verts or normals");
+    HM_CHECK_ARG(n_faces == 0 || faces, "hm_mc_emit: NULL faces");
+    const int64_t n = nx * ny * nz, nb = (n + kMBlock - 1) / kMBlock;
+    const McVol V{vol, (int32_t)nx, (int32_t)ny, (int32_t)nz, sx, sy, sz};
+    const McWs w = carve(workspace, n);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(mc_verts_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, V, level, spacing[0], spacing[1],
+                       spacing[2], n, static_cast<const uint16_t *>(w.code), w.vbase,
+                       static_cast<const int64_t *>(w.boff), n_verts, verts, normals);
+    if (n_faces > 0)
+        hipLaunchKernelGGL(mc_faces_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, V, n,
+                           static_cast<const uint16_t *>(w.code), static_cast<const int32_t *>(w.vbase),
+                           static_cast<const int64_t *>(w.boff + nb), n_faces, faces);
+    HM_CHECK_LAUNCH("hm_mc_emit");
+    return HM_OK;
+}
+
+}  // extern "C"

@@ -1280,3 +1280,37 @@ def softplus(z, beta=100.0, threshold=20.0):
     """nn.Softplus(beta, threshold) with fused backward and double backward (third order is not provided)."""
     require_gpu(z)
     return _Softplus.apply(z, float(beta), float(threshold))
+
+
+# =========================================================================================
+# mesh extraction (csrc/hm_mesh.hip)
+# =========================================================================================
+def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0)):
+    """(verts [V,3] fp32, faces [F,3] int32, normals [V,3] fp32) of the `level` isosurface of a device fp32 volume
+    [nx, ny, nz] - skimage.measure.marching_cubes(volume, level, spacing) as plots.py:122-128 calls it, with the
+    normals pointing toward increasing values (the reference's -normals) and the triangulation of the generated case
+    table (csrc/hm_mc_table.h).  Any element strides (the transposed meshgrid view of sdf_volume needs no copy).
+    One host read of the counts between the two phases; not graph-capturable.  Empty outputs when nothing crosses."""
+    require_gpu(volume)
+    if volume.dtype != torch.float32 or volume.dim() != 3:
+        raise ValueError("hashmod marching_cubes: a 3-D fp32 volume expected")
+    nx, ny, nz = (int(s) for s in volume.shape)
+    sx, sy, sz = (int(s) for s in volume.stride())
+    dev = volume.device
+    L = lib()
+    ws = torch.empty(check(L.hm_mc_workspace_bytes(nx, ny, nz)), dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    st = stream_ptr(volume)
+    args = (dptr(volume), nx, ny, nz, sx, sy, sz, float(level))
+    check(L.hm_mc_count(*args, dptr(ws), ws.numel(), dptr(counts), st))
+    n_verts, n_faces, has_nan = counts.tolist()
+    if has_nan:
+        raise _lib.HashmodError("hashmod marching_cubes: the volume contains NaN")
+    verts = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    if n_verts > 0:
+        sp = (C.c_float * 3)(*(float(s) for s in spacing))
+        check(L.hm_mc_emit(*args, sp, dptr(ws), ws.numel(), n_verts, n_faces, dptr(verts), dptr(normals), dptr(faces),
+                           st))
+    return verts, faces, normals

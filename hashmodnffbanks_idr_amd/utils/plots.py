@@ -1,4 +1,5 @@
-"""SDF-on-a-grid callers of the fused no-grad kernel (reference: code/utils/plots.py:110-238).
+"""SDF-on-a-grid callers of the fused no-grad kernel and the mesh procedure on top of them (reference:
+code/utils/plots.py:110-271).
 
 The reference's mesh extraction evaluates the SDF on resolution^3 points in 10 000-point chunks, each a
 9-GEMM eager forward plus a device->host copy (64 M evaluations at resolution 400), then hands the volume to
@@ -6,9 +7,15 @@ skimage's marching cubes.  Here the volume is produced by the fused kernel (csrc
 one MI355X) in a few large launches and comes back in exactly the layout the reference passes to
 ``measure.marching_cubes`` (axis order, spacing, origin), so the CPU part (marching cubes / trimesh export -
 third-party, not part of the hot path) is unchanged.
+
+get_surface_high_res_mesh (plots.py:146-224) runs entirely on this library: the SDF volumes come from the fused kernel
+on device-generated lattices, the meshes from ops.marching_cubes (csrc/hm_mesh.hip), and TriMesh stands in for the
+part of trimesh.Trimesh the reference's callers use.
 """
 import numpy as np
 import torch
+
+from .. import ops
 
 
 def get_grid_uniform(resolution, device=None):
@@ -23,8 +30,8 @@ def get_grid_uniform(resolution, device=None):
     return {"grid_points": grid_points, "shortest_axis_length": 2.0, "xyz": [x, y, z], "shortest_axis_index": 0}
 
 
-def get_grid(points, resolution, device=None, eps=0.2):
-    """plots.py:240-271: lattice around a point cloud, `resolution` samples along its shortest axis."""
+def _grid_axes(points, resolution, eps=0.2):
+    """the axes of get_grid's lattice: (x, y, z, shortest axis length, shortest axis index)"""
     pts = points.detach().cpu()
     input_min = torch.min(pts, dim=0)[0].squeeze().numpy()
     input_max = torch.max(pts, dim=0)[0].squeeze().numpy()
@@ -35,7 +42,12 @@ def get_grid(points, resolution, device=None, eps=0.2):
     axes = [None, None, None]
     for a in range(3):
         axes[a] = lin if a == shortest_axis else np.arange(input_min[a] - eps, input_max[a] + step + eps, step)
-    x, y, z = axes
+    return axes[0], axes[1], axes[2], length, shortest_axis
+
+
+def get_grid(points, resolution, device=None, eps=0.2):
+    """plots.py:240-271: lattice around a point cloud, `resolution` samples along its shortest axis."""
+    x, y, z, length, shortest_axis = _grid_axes(points, resolution, eps)
     xx, yy, zz = np.meshgrid(x, y, z)
     grid_points = torch.tensor(np.vstack([xx.ravel(), yy.ravel(), zz.ravel()]).T, dtype=torch.float)
     if device is not None:
@@ -77,3 +89,193 @@ def get_surface_mesh(sdf, resolution=100, device="cuda"):
                           "use sdf_volume() to get the SDF volume without it") from err
     verts, faces, normals, _ = measure.marching_cubes(volume=vol["volume"], level=0, spacing=vol["spacing"])
     return verts + vol["origin"], faces, -normals
+
+
+# =========================================================================================
+# mesh object and the reference's high-resolution mesh procedure
+# =========================================================================================
+class TriMesh:
+    """The part of trimesh.Trimesh the reference's mesh callers use (eval.py: world transform, largest component,
+    .ply export; plots.py: .ply export): vertices [V,3] float64, faces [F,3] int64, vertex_normals [V,3] (the given
+    ones, else area-weighted face normals), area, apply_transform, split, export."""
+
+    def __init__(self, vertices, faces, vertex_normals=None):
+        self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+        self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+        self._normals = None if vertex_normals is None else np.asarray(vertex_normals, np.float64).reshape(-1, 3)
+
+    def _cross(self):
+        v = self.vertices[self.faces]
+        return np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+
+    @property
+    def area_faces(self):
+        return 0.5 * np.linalg.norm(self._cross(), axis=1)
+
+    @property
+    def area(self):
+        return float(self.area_faces.sum())
+
+    @property
+    def vertex_normals(self):
+        if self._normals is None:
+            acc = np.zeros_like(self.vertices)
+            cr = self._cross()
+            for m in range(3):
+                np.add.at(acc, self.faces[:, m], cr)
+            nrm = np.linalg.norm(acc, axis=1, keepdims=True)
+            self._normals = np.divide(acc, nrm, out=np.zeros_like(acc), where=nrm > 0)
+        return self._normals
+
+    @property
+    def is_watertight(self):
+        """every undirected edge in exactly two faces"""
+        e = np.sort(np.concatenate([self.faces[:, [0, 1]], self.faces[:, [1, 2]], self.faces[:, [2, 0]]]), axis=1)
+        _, cnt = np.unique(e[:, 0] * (len(self.vertices) + 1) + e[:, 1], return_counts=True)
+        return len(self.faces) > 0 and bool(np.all(cnt == 2))
+
+    def apply_transform(self, matrix):
+        """x -> M[:3,:3] x + M[:3,3]; normals by the inverse transpose; a reflection reverses the winding"""
+        m = np.asarray(matrix, dtype=np.float64)
+        if m.shape != (4, 4):
+            raise ValueError("TriMesh.apply_transform: a 4x4 matrix expected")
+        lin = m[:3, :3]
+        normals = None if self._normals is None else self._normals @ np.linalg.inv(lin)
+        self.vertices = self.vertices @ lin.T + m[:3, 3]
+        if normals is not None:
+            nrm = np.linalg.norm(normals, axis=1, keepdims=True)
+            self._normals = np.divide(normals, nrm, out=np.zeros_like(normals), where=nrm > 0)
+        if np.linalg.det(lin) < 0:
+            self.faces = np.ascontiguousarray(self.faces[:, ::-1])
+        return self
+
+    def split(self, only_watertight=False):
+        """connected components through shared vertices, in the order of their lowest vertex"""
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        f = self.faces
+        nv = len(self.vertices)
+        if len(f) == 0:
+            return []
+        rows = np.concatenate([f[:, 0], f[:, 1]])
+        cols = np.concatenate([f[:, 1], f[:, 2]])
+        graph = coo_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=(nv, nv))
+        _, label = connected_components(graph, directed=False)
+        face_label = label[f[:, 0]]
+        out = []
+        for lab in np.unique(label[np.unique(f)]):
+            ff = f[face_label == lab]
+            used, inv = np.unique(ff, return_inverse=True)
+            normals = None if self._normals is None else self._normals[used]
+            part = TriMesh(self.vertices[used], inv.reshape(-1, 3), normals)
+            if not only_watertight or part.is_watertight:
+                out.append(part)
+        return out
+
+    def export(self, file_obj=None, file_type="ply"):
+        """binary little-endian PLY: float32 x y z (+ nx ny nz), faces as (uchar 3, int32 x3); bytes when file_obj
+        is None, else written to the path or binary file object"""
+        if file_type != "ply":
+            raise ValueError("TriMesh.export: only file_type='ply' is supported")
+        names = ["x", "y", "z", "nx", "ny", "nz"]
+        vdt = np.dtype([(n, "<f4") for n in names])
+        vert = np.empty(len(self.vertices), vdt)
+        cols = np.concatenate([self.vertices, self.vertex_normals], axis=1)
+        for c, n in enumerate(names):
+            vert[n] = cols[:, c]
+        face = np.empty(len(self.faces), np.dtype([("count", "u1"), ("index", "<i4", (3,))]))
+        face["count"] = 3
+        face["index"] = self.faces
+        head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(vert)}"]
+        head += [f"property float {n}" for n in names]
+        head += [f"element face {len(face)}", "property list uchar int vertex_indices", "end_header", ""]
+        data = "\n".join(head).encode("ascii") + vert.tobytes() + face.tobytes()
+        if file_obj is None:
+            return data
+        if hasattr(file_obj, "write"):
+            file_obj.write(data)
+        else:
+            with open(file_obj, "wb") as fh:
+                fh.write(data)
+        return None
+
+
+@torch.no_grad()
+def _lattice_sdf(sdf, axes, device, rot=None, shift=None, chunk=1 << 22):
+    """sdf on the meshgrid('xy') lattice of the numpy axes (x, y, z), points generated on the device chunk by chunk
+    (no host lattice): a flat [ny*nx*nz] tensor in get_grid's point order.  rot / shift: the points are rotated into
+    world space as p @ rot + shift (fp32, the reference's bmm(vecs^T, p) + s_mean)."""
+    ax = [torch.as_tensor(np.asarray(a), dtype=torch.float32, device=device) for a in axes]
+    nx, ny, nz = (a.numel() for a in ax)
+    n = nx * ny * nz
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    for s in range(0, n, chunk):
+        q = torch.arange(s, min(s + chunk, n), dtype=torch.int64, device=device)
+        k = q % nz
+        i = (q // nz) % nx
+        j = q // (nz * nx)
+        p = torch.stack([ax[0][i], ax[1][j], ax[2][k]], dim=1)
+        if rot is not None:
+            p = p @ rot + shift
+        out[s:s + chunk] = sdf(p).reshape(-1)
+    return out
+
+
+def _mesh_on_lattice(sdf, axes, device, rot=None, shift=None):
+    """marching cubes of sdf's zero set on the lattice (vertices in lattice coordinates from the first point), or None
+    without a sign change"""
+    x, y, z = axes
+    z_flat = _lattice_sdf(sdf, axes, device, rot, shift)
+    lo, hi = torch.aminmax(z_flat)
+    if lo.item() > 0 or hi.item() < 0:
+        return None
+    volume = z_flat.view(len(y), len(x), len(z)).permute(1, 0, 2)    # [nx, ny, nz] view, as sdf_volume's transpose
+    d = float(x[2] - x[1])
+    return ops.marching_cubes(volume, 0.0, (d, d, d))
+
+
+def _surface_moments(mesh):
+    """(mean [3], covariance [3,3]) of the uniform distribution on the mesh surface, exact from its triangles"""
+    v = mesh.vertices[mesh.faces]
+    a = mesh.area_faces
+    s = v.sum(axis=1)
+    mean = (a[:, None] * s).sum(0) / (3.0 * a.sum())
+    second = np.einsum("t,tmi,tmj->ij", a, v, v) + np.einsum("t,ti,tj->ij", a, s, s)
+    cov = second / (12.0 * a.sum()) - np.outer(mean, mean)
+    return mean, cov
+
+
+def get_surface_high_res_mesh(sdf, resolution=100, device="cuda"):
+    """plots.py:146-224: the zero level set of `sdf` on a lattice aligned with the principal axes of a coarse mesh's
+    largest component, `resolution` samples along its shortest axis; a TriMesh in world space, or None without a
+    sign change.  Two deliberate deviations (mesh extraction): the principal axes come from the exact
+    area-weighted surface moments of the coarse component (the reference: 10 000 random trimesh.sample points), and
+    the lattices are generated on the device chunk by chunk (no host lattice)."""
+    lin = np.linspace(-1.0, 1.0, 100)      # the coarse 100^3 grid of get_grid_uniform(100)
+    coarse = _mesh_on_lattice(sdf, (lin, lin, lin), device)
+    if coarse is None:
+        return None
+    verts, faces, normals = (t.cpu().numpy() for t in coarse)
+    mesh_low_res = TriMesh(verts + np.array([lin[0], lin[0], lin[0]]), faces, normals)
+    components = mesh_low_res.split(only_watertight=False)
+    areas = np.array([c.area for c in components], dtype=np.float64)
+    mesh_low_res = components[int(areas.argmax())]
+
+    # center and align
+    s_mean, s_cov = _surface_moments(mesh_low_res)
+    vecs = torch.linalg.eigh(torch.from_numpy(s_cov))[1].transpose(0, 1)
+    if torch.det(vecs) < 0:
+        vecs = torch.mm(torch.tensor([[1, 0, 0], [0, 0, 1], [0, 1, 0]], dtype=vecs.dtype), vecs)
+    helper = (torch.from_numpy(mesh_low_res.vertices) - torch.from_numpy(s_mean)) @ vecs.transpose(0, 1)
+    x, y, z, _, _ = _grid_axes(helper, resolution)
+
+    rot = vecs.to(device=device, dtype=torch.float32)
+    shift = torch.from_numpy(s_mean).to(device=device, dtype=torch.float32)
+    fine = _mesh_on_lattice(sdf, (x, y, z), device, rot, shift)
+    if fine is None:
+        return None
+    verts, faces, normals = fine
+    origin = torch.tensor([[x[0], y[0], z[0]]], dtype=torch.float32, device=device) @ rot + shift  # grid_points[0]
+    verts = verts @ rot + origin
+    normals = normals @ rot
+    return TriMesh(verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy())

@@ -642,6 +642,30 @@ typedef struct hm_copy_item {
 } hm_copy_item;
 HM_API int hm_multi_copy_f32(const hm_copy_item *items, int n_items, void *stream);
 
+/* ---- mesh extraction: marching cubes ------------------------------------------------------------
+ * Replaces skimage.measure.marching_cubes(volume, level, spacing) as plots.py:122-128 (and
+ * get_surface_high_res_mesh, plots.py:146-224) call it: vertices on the sign-changing lattice edges by linear
+ * interpolation, t = (level - a)/(b - a), at ((i,j,k) + t e_axis) * spacing in the volume's axis order; triangles from
+ * the generated case table (csrc/hm_mc_table.h; ambiguous faces cut every inside corner off on its own, so the
+ * triangulation inside ambiguous cells may differ from marching_cubes_lewiner); normals = central differences
+ * (one-sided at the border) over the spacing, interpolated with t and normalised, pointing toward increasing values
+ * (the reference's -normals; (0,0,0) where the gradient is zero).
+ * vol is fp32 [nx, ny, nz] with element strides sx, sy, sz >= 0 (a transposed view works without a copy); every
+ * dimension >= 2 and nx*ny*nz < 2^31.  Output order does not depend on the strides: vertices by owning lattice point
+ * ((i*ny + j)*nz + k), then axis x < y < z; faces by cell linear index, then table order.  No atomics: repeated calls
+ * give the same bits.
+ *   hm_mc_count: classifies the lattice into the workspace; counts [3] int64 (device) receive the number of vertices,
+ *                the number of faces and 1 if any volume value is NaN (else 0).
+ *   hm_mc_emit:  after hm_mc_count on the same stream, volume and workspace: verts [n_verts, 3], normals [n_verts, 3]
+ *                fp32 and faces [n_faces, 3] int32 (vertex ids); n_verts / n_faces are the counts hm_mc_count wrote
+ *                (read by the caller) and must fit int32 indices.  spacing is [host] [3].                          */
+HM_API int64_t hm_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+HM_API int hm_mc_count(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy, int64_t sz,
+                       float level, void *workspace, int64_t workspace_bytes, int64_t *counts, void *stream);
+HM_API int hm_mc_emit(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy, int64_t sz,
+                      float level, const float *spacing, void *workspace, int64_t workspace_bytes, int64_t n_verts,
+                      int64_t n_faces, float *verts, float *normals, int32_t *faces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
