@@ -94,6 +94,7 @@ SIGNATURES = {
     "hm_encode_bwd_table_sorted_tracked": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "hm_gemm_f32_ep": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     "hm_gemm_f32": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _int, _p]),
+    "hm_diag_gemm_plan": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _int, _int, _p]),
     "hm_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "hm_mc_count": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _i64, _p, _p]),
     "hm_mc_emit": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _p, _i64, _i64, _i64, _p, _p, _p,
@@ -113,6 +114,11 @@ class GemmEpilogue(C.Structure):
                 ("threshold", C.c_float), ("z", C.c_void_p), ("ldz", C.c_int64), ("g", C.c_void_p), ("ldg", C.c_int64),
                 ("out1", C.c_void_p), ("ld1", C.c_int64), ("out2", C.c_void_p), ("ld2", C.c_int64),
                 ("out3", C.c_void_p), ("ld3", C.c_int64)]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("k_tail", C.c_int32), ("vec_a", C.c_int32), ("vec_b", C.c_int32),
+                ("part", C.c_int32), ("pad_", C.c_int32), ("split", C.c_int64), ("k_chunk", C.c_int64)]
 
 
 class AdamTensor(C.Structure):

@@ -198,8 +198,10 @@ __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f3
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
 
     float4 ra[BM * BK / 4 / NT], rb[BN * BK / 4 / NT];
-    load_tile<BM, BK, NT, VA>(g.A, g.lda, a_kc, m0, g.M, kbeg, kend, tid, ra);
-    load_tile<BN, BK, NT, VB>(g.B, g.ldb, b_kc, n0, g.N, kbeg, kend, tid, rb);
+    if (kbeg < kend) {   // (K = 0: the clamped prologue addresses would lie before the operands, which may be NULL)
+        load_tile<BM, BK, NT, VA>(g.A, g.lda, a_kc, m0, g.M, kbeg, kend, tid, ra);
+        load_tile<BN, BK, NT, VB>(g.B, g.ldb, b_kc, n0, g.N, kbeg, kend, tid, rb);
+    }
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
         __syncthreads();  // previous stage fully consumed
         store_tile<BM, BK, NT>(As, a_kc, tid, ra);
@@ -390,6 +392,22 @@ __device__ __forceinline__ void pipe_fetch_buf(const __amdgpu_buffer_rsrc_t &rs,
     }
 }
 
+// K tail: zero the elements k >= K of a k-contiguous operand's k-groups (klim = K - the group's first k within the chunk,
+// k0 = the stage's first k).  Applied when the ring slot goes to LDS - its loads have landed by then - not at the fetch,
+// where the select would wait for them.
+template <bool KC, int PER>
+__device__ __forceinline__ void pipe_mask_tail(float4 (&x)[PER], const int (&klim)[PER], int k0) {
+    if (!KC) return;   // k is the slow dimension: the buffer descriptor returns zeros beyond K
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int l = klim[i] - k0;
+        x[i].x = l > 0 ? x[i].x : 0.0f;
+        x[i].y = l > 1 ? x[i].y : 0.0f;
+        x[i].z = l > 2 ? x[i].z : 0.0f;
+        x[i].w = l > 3 ? x[i].w : 0.0f;
+    }
+}
+
 template <int OCT, int AROWS>
 __device__ __forceinline__ void pipe_read_ops(const float *as, const float *bs, int arow, int brow, int h,
                                               float4 (&xa)[OCT], float4 (&xb)[OCT]) {
@@ -413,7 +431,9 @@ __device__ __forceinline__ void pipe_mfma_oct(const float4 &a, const float4 &b, 
 // WM = 3: a 96 x 64 tile on TWELVE waves (two groups of 3 x 2), for row counts whose 64-row grid is between one and two
 // rounds of the chip: M = 3072, N = 512 are 384 tiles of 64 x 64 - a CU with two of them takes twice as long as the one
 // with one - but exactly 256 of 96 x 64.  The B panel is staged by the first 512 threads.
-template <bool AKC, bool BKC, bool EP, int WM = 2, bool PART = false>
+// KT: the K range has a tail (see the descriptors below); the k-contiguous operand's k >= K elements are zeroed before
+// they go to LDS.  A separate instantiation, so that the K-whole loop keeps its instructions.
+template <bool AKC, bool BKC, bool EP, int WM = 2, bool PART = false, bool KT = false>
 __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int by, int bz) {
     constexpr int BM = 32 * WM, BN = 64, BK = kPipeBK, NT = 256 * WM, NTB = 512, PER = BM * BK / 4 / NT, KG = BK / 4,
                   OCT = BK / 8 / 2;   // OCT: octets of a stage per wave group
@@ -434,11 +454,13 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
     // serial with the MFMAs of every wave on the SIMD; the fused SDF kernels gained 3 - 11 % from the same change).
     // The host takes this kernel only for operands below 2 GB.
     // The descriptors end at the operands' last element: a K range that is no multiple of the stage group (K = 445, 257)
-    // runs to the next multiple, the operand whose k is the SLOW dimension returns zeros beyond its end and cancels what the
-    // k-contiguous one reads from its following rows (the host admits a K tail only when there is such an operand).
+    // runs to the next multiple, the operand whose k is the SLOW dimension returns zeros beyond its end.  The k-contiguous
+    // one reads on into its pad columns or its next row - values that may be NaN or Inf, and 0 * NaN is NaN - so the KT
+    // instantiation zeroes them (the host admits a K tail only with split == 1 and at most one k-contiguous operand).
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.A), 0, g.nrecA, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.B), 0, g.nrecB, 0x00020000);
     int va[PER], vb[PER];
+    int kla[PER], klb[PER];   // KT only (the grouped kernels set g.K = 0 and never reach it)
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const int e = tid + NT * i;
@@ -449,7 +471,18 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
                                : (int64_t)(kbeg + (e / BM) * 4) * g.lda + am));
         vb[i] = (int)(4 * (BKC ? (int64_t)bn * g.ldb + kbeg + (eb % KG) * 4
                                : (int64_t)(kbeg + (eb / BN) * 4) * g.ldb + bn));
+        if (KT) {
+            kla[i] = g.K - kbeg - (e % KG) * 4;
+            klb[i] = g.K - kbeg - (eb % KG) * 4;
+        }
     }
+#define HM_PIPE_MASK(S_, RA_, RB_)                                                                  \
+    do {                                                                                            \
+        if (KT) {                                                                                   \
+            pipe_mask_tail<AKC, PER>(RA_, kla, (S_) * BK);                                          \
+            pipe_mask_tail<BKC, PER>(RB_, klb, (S_) * BK);                                          \
+        }                                                                                           \
+    } while (0)
     const bool stage_b = NT == NTB || tid < NTB;
     const int sa = 4 * (AKC ? BK : BK * (int)g.lda), sb = 4 * (BKC ? BK : BK * (int)g.ldb);   // bytes per stage
     const int lda4 = 4 * (int)g.lda, ldb4 = 4 * (int)g.ldb;
@@ -470,6 +503,7 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
     HM_PIPE_FETCH(0, ra0, rb0);
     HM_PIPE_FETCH(1, ra1, rb1);
     HM_PIPE_FETCH(2, ra2, rb2);
+    HM_PIPE_MASK(0, ra0, rb0);
     store_tile<BM, BK, NT>(As[0], AKC, tid, ra0);
     if (stage_b) store_tile<BN, BK, NTB>(Bs[0], BKC, tid, rb0);
     __syncthreads();
@@ -480,6 +514,7 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
     do {                                                                                            \
         HM_PIPE_FETCH((S_) + kPipeD - 1, ra##F_, rb##F_);                                                    \
         pipe_mfma_oct(opa##C_[0], opb##C_[0], acc);                                                 \
+        HM_PIPE_MASK((S_) + 1, ra##N_, rb##N_);                                                     \
         store_tile<BM, BK, NT>(As[NB_], AKC, tid, ra##N_);                                          \
         if (stage_b) store_tile<BN, BK, NTB>(Bs[NB_], BKC, tid, rb##N_);                            \
         __syncthreads();                                                                            \
@@ -494,6 +529,7 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
         HM_PIPE_STAGE(s0 + 3, 2, 0, 1, 0, 0);
     }
 #undef HM_PIPE_STAGE
+#undef HM_PIPE_MASK
 #undef HM_PIPE_FETCH
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
@@ -521,6 +557,14 @@ __global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_kernel(GemmArgs g) {
 template <bool AKC, bool BKC, bool EP>
 __global__ __launch_bounds__(768, 3) void gemm_f32_pipe2_m96_kernel(GemmArgs g) {
     gemm_pipe2_body<AKC, BKC, EP, 3>(g, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <bool AKC, bool BKC, bool EP>
+__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_ktail_kernel(GemmArgs g) {
+    gemm_pipe2_body<AKC, BKC, EP, 2, false, true>(g, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <bool AKC, bool BKC, bool EP>
+__global__ __launch_bounds__(768, 3) void gemm_f32_pipe2_m96_ktail_kernel(GemmArgs g) {
+    gemm_pipe2_body<AKC, BKC, EP, 3, false, true>(g, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 template <bool AKC, bool BKC>
 __global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_part_kernel(GemmArgs g) {
@@ -618,15 +662,23 @@ constexpr int64_t kSplitTarget = 512;   // split-K: workgroups to aim for when t
 
 }  // namespace
 
-// Tile, kernel and split-K decomposition of one GEMM: a function of the shape alone, so that the deterministic
-// workspace query (hm_gemm_f32_det_workspace_bytes) and the launch agree.
+// Tile, kernel and split-K decomposition of one GEMM: a function of the shape (and, for the 16-byte loads of the
+// generic and big kernels, of the operands' alignment), so that the deterministic workspace query
+// (hm_gemm_f32_det_workspace_bytes), the launch and hm_diag_gemm_plan agree.
 struct GemmPlan {
     bool big, use_pipe, pipe_ok, m96;
+    bool k_tail;        // pipelined kernel on a K that is no multiple of the stage group (KT instantiation)
+    bool vecA, vecB;    // generic / big kernel: 16-byte operand loads
     int64_t bm, bn, split, k_chunk;
 };
-static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool has_ep) {
+static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
+                          const void *B, int64_t ldb, bool has_ep) {
     GemmPlan P;
     const bool a_kc = !transA, b_kc = transB != 0;
+    // operands may be fetched with 16-B loads when every k-group of every row is 16-B aligned
+    // (and the K range ends on a multiple of 4, so no k-group straddles the end)
+    P.vecA = a_kc && K % 4 == 0 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0;
+    P.vecB = b_kc && K % 4 == 0 && ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15u) == 0;
     // tile choice: big tiles only when they still fill the chip
     const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
     P.big = t128 >= 256;
@@ -637,10 +689,11 @@ static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t 
     // the pipelined kernel fetches through buffer descriptors with 32-bit offsets, so it takes operands below 2 GB only
     // (every other operand runs on the generic kernel, which addresses rows in 64 bits), and K ranges that are a whole
     // number of 128-deep groups per split (partial edge tiles are fine: clamped rows, guarded stores).  Its 16-byte loads
-    // need dword alignment only (probed: unaligned buffer_load_dwordx4 returns the right dwords), so k-contiguous operands
-    // with any leading dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K
-    // range runs to the next multiple of the stage group, that operand's descriptor returns zeros beyond its end (K = 445
-    // and 257 of the backward sweeps: 27 - 43 us on the generic kernel).
+    // need dword alignment only (unaligned buffer_load_dwordx4 returns the right dwords: the misaligned and padded operand
+    // views of tests/test_gemm_paths_gpu.py run here and are bit-exact), so k-contiguous operands with any leading
+    // dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K range runs to the
+    // next multiple of the stage group, that operand's descriptor returns zeros beyond its end and the KT instantiation
+    // zeroes the other's k >= K elements (K = 445 and 257 of the backward sweeps: 27 - 43 us on the generic kernel).
     const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
                   bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
     const bool buf_ok = bytesA < (1ll << 31) && bytesB < (1ll << 31);
@@ -675,6 +728,7 @@ static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t 
     P.k_chunk = k_chunk;
     // (whole K: the chunks divide it; K tail: ONE chunk of the rounded-up K, zeros beyond the slow operand's end)
     P.pipe_ok = P.use_pipe && (k_whole ? K % k_chunk == 0 : P.split == 1);
+    P.k_tail = P.pipe_ok && !k_whole;
     return P;
 }
 
@@ -724,12 +778,10 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     g.M = (int)M; g.N = (int)N; g.K = (int)K;
     g.transA = transA; g.transB = transB;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    // operands may be fetched with 16-B loads when every k-group of every row is 16-B aligned
     const bool a_kc = !transA, b_kc = transB != 0;
-    // (and the K range ends on a multiple of 4, so no k-group straddles the end)
-    g.vecA = (a_kc && K % 4 == 0 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15u) == 0) ? 1 : 0;
-    g.vecB = (b_kc && K % 4 == 0 && ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15u) == 0) ? 1 : 0;
-    const GemmPlan P = gemm_plan(transA, transB, M, N, K, lda, ldb, g.ep.mode != HM_EPI_NONE);
+    const GemmPlan P = gemm_plan(transA, transB, M, N, K, A, lda, B, ldb, g.ep.mode != HM_EPI_NONE);
+    g.vecA = P.vecA ? 1 : 0;
+    g.vecB = P.vecB ? 1 : 0;
     const bool big = P.big, m96 = P.m96, pipe_ok = P.pipe_ok;
     const int64_t bm = P.bm, bn = P.bn, split = P.split;
     const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
@@ -775,7 +827,6 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     if (part) {
         // (big tiles are never split: they are taken only when the tile grid alone fills the chip)
         if (pipe_ok) {
-            const bool a_kc = !transA, b_kc = transB != 0;
 #define HM_PART_PIPE(AKC_, BKC_)                                                                                   \
     do {                                                                                                          \
         if (m96) hipLaunchKernelGGL((gemm_f32_pipe2_m96_part_kernel<AKC_, BKC_>), grid, dim3(768), 0, st, g);     \
@@ -815,10 +866,26 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
         else                                                                                                      \
             hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, false>), grid, dim3(512), 0, st, g);            \
     } while (0)
+#define HM_PIPE_KTAIL_LAUNCH(AKC_, BKC_)                                                                          \
+    do {                                                                                                          \
+        if (m96) {                                                                                                \
+            if (g.ep.mode != HM_EPI_NONE)                                                                         \
+                hipLaunchKernelGGL((gemm_f32_pipe2_m96_ktail_kernel<AKC_, BKC_, true>), grid, dim3(768), 0, st, g); \
+            else                                                                                                  \
+                hipLaunchKernelGGL((gemm_f32_pipe2_m96_ktail_kernel<AKC_, BKC_, false>), grid, dim3(768), 0, st, g); \
+        } else if (g.ep.mode != HM_EPI_NONE)                                                                      \
+            hipLaunchKernelGGL((gemm_f32_pipe2_ktail_kernel<AKC_, BKC_, true>), grid, dim3(512), 0, st, g);       \
+        else                                                                                                      \
+            hipLaunchKernelGGL((gemm_f32_pipe2_ktail_kernel<AKC_, BKC_, false>), grid, dim3(512), 0, st, g);      \
+    } while (0)
+        // (a K tail has at most one k-contiguous operand; with none, the descriptors alone zero the k >= K products)
         if (a_kc && b_kc) HM_PIPE_LAUNCH(true, true);
+        else if (a_kc && P.k_tail) HM_PIPE_KTAIL_LAUNCH(true, false);
         else if (a_kc) HM_PIPE_LAUNCH(true, false);
+        else if (b_kc && P.k_tail) HM_PIPE_KTAIL_LAUNCH(false, true);
         else if (b_kc) HM_PIPE_LAUNCH(false, true);
         else HM_PIPE_LAUNCH(false, false);
+#undef HM_PIPE_KTAIL_LAUNCH
 #undef HM_PIPE_LAUNCH
     } else
         HM_GEMM_LAUNCH(1, 1, 128, 2, 2);
@@ -887,7 +954,25 @@ int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, void *str
 
 int64_t hm_gemm_f32_det_workspace_bytes(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    return gemm_det_bytes(gemm_plan(transA, transB, M, N, K, lda, ldb, false), M, N);
+    return gemm_det_bytes(gemm_plan(transA, transB, M, N, K, nullptr, lda, nullptr, ldb, false), M, N);
+}
+
+int hm_diag_gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
+                      const float *B, int64_t ldb, int has_epilogue, int deterministic, hm_gemm_plan_info *info) {
+    HM_CHECK_ARG(info != nullptr, "hm_diag_gemm_plan: info is NULL");
+    HM_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "hm_diag_gemm_plan: negative dimension");
+    *info = hm_gemm_plan_info{};
+    if (M == 0 || N == 0) return HM_OK;   // HM_GEMM_KERNEL_NONE: gemm_impl launches nothing
+    const GemmPlan P = gemm_plan(transA, transB, M, N, K, A, lda, B, ldb, has_epilogue != 0);
+    info->kernel = P.big ? HM_GEMM_KERNEL_BIG
+                 : P.pipe_ok ? (P.m96 ? HM_GEMM_KERNEL_PIPE96 : HM_GEMM_KERNEL_PIPE64) : HM_GEMM_KERNEL_GENERIC;
+    info->k_tail = P.k_tail ? 1 : 0;
+    info->vec_a = P.vecA ? 1 : 0;
+    info->vec_b = P.vecB ? 1 : 0;
+    info->part = (deterministic && P.split > 1) ? 1 : 0;
+    info->split = P.split;
+    info->k_chunk = P.k_chunk;
+    return HM_OK;
 }
 
 int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
@@ -946,7 +1031,7 @@ static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws,
                      "hm_gemm_f32_group_tn_det: NULL operand or leading dimension");
         if (it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31)) {
             // the same problems as in hm_gemm_f32_group_tn go alone
-            const int64_t b = gemm_det_bytes(gemm_plan(1, 0, it.M, it.N, it.K, it.lda, it.ldb, false), it.M, it.N);
+            const int64_t b = gemm_det_bytes(gemm_plan(1, 0, it.M, it.N, it.K, nullptr, it.lda, nullptr, it.ldb, false), it.M, it.N);
             if (b > *need) *need = b;
             if (run) {
                 const int rc = gemm_impl(1, 0, it.M, it.N, it.K, it.A, it.lda, it.B, it.ldb, nullptr, it.C, it.ldc, 1,

@@ -391,19 +391,38 @@ def encode_table_grad(x, table, B, desc, frac_mode=0, collector=None):
 # =========================================================================================
 # exact-fp32 MFMA GEMM (csrc/hm_gemm.hip) as an any-order differentiable torch op
 # =========================================================================================
+def _check_gemm_out(buf, M, cols, dev, what):
+    """a caller-owned GEMM destination: fp32 [M, cols] on `dev`, unit column stride, any row stride"""
+    if buf.dtype != torch.float32 or tuple(buf.shape) != (M, cols) or buf.device != dev or \
+            (cols > 1 and buf.stride(1) != 1):
+        raise ValueError(f"hashmod {what}: bad output buffer (need fp32 [{M}, {cols}] with unit column stride on {dev}; "
+                         f"got {buf.dtype} {tuple(buf.shape)} strides {tuple(buf.stride())} on {buf.device})")
+
+
+def _check_gemm_bias(bias, N, dev, what):
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or bias.device != dev):
+        raise ValueError(f"hashmod {what}: bias must be fp32 with N = {N} elements on {dev}")
+
+
 def gemm(a, b, bias=None, trans_a=False, trans_b=False, out=None, accumulate=False):
-    """C = op(a) @ op(b) (+ bias) on the HIP kernel; no autograd."""
-    require_gpu(a, b, bias)
+    """C = op(a) @ op(b) (+ bias) on the HIP kernel; no autograd.  out: optional caller-owned fp32 [M, N] destination
+    with unit column stride (a row-strided view is fine); accumulate=True adds into it (and needs it)."""
+    require_gpu(a, b, bias, out)
     if a.dtype != torch.float32 or b.dtype != torch.float32:
         raise TypeError("hashmod gemm: fp32 only")
-    if a.stride(-1) != 1:
-        a = a.contiguous()
-    if b.stride(-1) != 1:
-        b = b.contiguous()
     M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
     Kb, N = (b.shape[1], b.shape[0]) if trans_b else (b.shape[0], b.shape[1])
     if K != Kb:
         raise ValueError(f"hashmod gemm: inner dimensions differ ({K} vs {Kb})")
+    _check_gemm_bias(bias, N, a.device, "gemm")
+    if out is not None:
+        _check_gemm_out(out, M, N, a.device, "gemm")
+    elif accumulate:
+        raise ValueError("hashmod gemm: accumulate=True adds into out, which is missing")
+    if a.stride(-1) != 1:
+        a = a.contiguous()
+    if b.stride(-1) != 1:
+        b = b.contiguous()
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     if bias is not None:
@@ -474,6 +493,7 @@ def gemm_ep(a, b, bias, trans_a, trans_b, mode, beta, thr, scale=1.0, z=None, g=
     if K != Kb:
         raise ValueError(f"hashmod gemm: inner dimensions differ ({K} vs {Kb})")
     dev = a.device
+    _check_gemm_bias(bias, N, dev, "gemm_ep")
     new = lambda cols: torch.empty((M, cols), dtype=torch.float32, device=dev)  # noqa: E731
     ep = _lib.GemmEpilogue()
     ep.mode, ep.scale, ep.beta, ep.threshold = mode, float(scale), float(beta), float(thr)
@@ -483,8 +503,7 @@ def gemm_ep(a, b, bias, trans_a, trans_b, mode, beta, thr, scale=1.0, z=None, g=
     def dest(buf, cols):
         if buf is None:
             return new(cols)
-        if buf.shape != (M, cols) or buf.stride(1) != 1 or buf.dtype != torch.float32:
-            raise ValueError("hashmod gemm_ep: bad output buffer")
+        _check_gemm_out(buf, M, cols, dev, "gemm_ep")
         return buf
 
     if mode in (EPI_SOFTPLUS, EPI_RELU):
@@ -497,20 +516,20 @@ def gemm_ep(a, b, bias, trans_a, trans_b, mode, beta, thr, scale=1.0, z=None, g=
         if z.shape[0] != M or z.shape[1] < ncol or (g is not None and (g.shape[0] != M or g.shape[1] < ncol)):
             raise ValueError("hashmod gemm_ep: epilogue operand shape")
         ep.nz = ncol
-        ep.z, ep.ldz = z.data_ptr(), z.stride(0)
+        ep.z, ep.ldz = z.data_ptr(), _ld(z)
         if g is not None:
-            ep.g, ep.ldg = g.data_ptr(), g.stride(0)
+            ep.g, ep.ldg = g.data_ptr(), _ld(g)
         o1 = dest(out1, ncol)
         if masked:
             outs = (c, o1)
         else:
             o2 = new(N)
             o3 = dest(out3, N) if (want_out3 or out3 is not None) else None
-            ep.out2, ep.ld2 = o2.data_ptr(), o2.stride(0)
+            ep.out2, ep.ld2 = o2.data_ptr(), _ld(o2)
             if o3 is not None:
-                ep.out3, ep.ld3 = o3.data_ptr(), o3.stride(0)
+                ep.out3, ep.ld3 = o3.data_ptr(), _ld(o3)
             outs = (o1, o2, o3)
-    ep.out1, ep.ld1 = o1.data_ptr(), o1.stride(0)
+    ep.out1, ep.ld1 = o1.data_ptr(), _ld(o1)
     if bias is not None:
         bias = bias.contiguous()
     check(lib().hm_gemm_f32_ep(int(trans_a), int(trans_b), M, N, K, dptr(a), _ld(a), dptr(b), _ld(b), dptr(bias),

@@ -395,7 +395,8 @@ HM_API int hm_trace_forward_nffb(const hm_grid_desc *desc, const hm_nffb_desc *n
  * dY*W and dY^T*X, and the same shapes again under create_graph=True.
  *   C[M,N] (+)= op(A)[M,K] * op(B)[K,N] (+ bias[N]);  row-major, leading dimensions in floats;
  *   transA: A is stored [K,M];  transB: B is stored [N,K];  bias may be NULL;
- *   accumulate != 0 adds into C (fp32 atomics), otherwise C is overwritten.                      */
+ *   accumulate != 0 adds into C (fp32 atomics), otherwise C is overwritten.
+ *   K = 0 gives C = bias (or 0), C += bias with accumulate; A and B are not read (they may be NULL).  */
 HM_API int hm_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
                        const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
                        void *stream);
@@ -409,7 +410,7 @@ HM_API int hm_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, 
  *   HM_EPI_S1MUL     C = v;  out1[:, :nz] = v[:, :nz] * s1(z) (+ g)               (gradient sweeps: u = v * s1(z))
  *   HM_EPI_ADJOINT   out1 = v * s1(z);  out2 = v * g * s2(z);  out3 = g * s1(z)    (adjoint of u = g * s1(z); out3 optional)
  *   HM_EPI_RELU      C = v;  out1 = max(v, 0)                                     (rendering MLP forward, :214-219)
- *   HM_EPI_RELUMASK  C = v;  out1[:, :nz] = z > 0 ? v : 0                        (its backward; z = the layer's ReLU output) */
+ *   HM_EPI_RELUMASK  C = v;  out1[:, :nz] = (z > 0 ? v : 0) (+ g)                (its backward; z = the layer's ReLU output) */
 enum { HM_EPI_NONE = 0, HM_EPI_SOFTPLUS = 1, HM_EPI_S1MUL = 2, HM_EPI_ADJOINT = 3, HM_EPI_RELU = 4, HM_EPI_RELUMASK = 5 };
 typedef struct hm_gemm_epilogue {
     int32_t mode;
@@ -424,6 +425,24 @@ typedef struct hm_gemm_epilogue {
 HM_API int hm_gemm_f32_ep(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
                           const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
                           const hm_gemm_epilogue *ep, void *stream);
+
+/* ---- diagnostic: the kernel hm_gemm_f32 / _ep / _det would launch ------------------------------------------------
+ * Not part of the reference's interface.  Host only, reads no memory (A and B are used for their alignment alone, so
+ * any pointer values will do): the same plan the launch uses - the kernel family, the K tail of the pipelined kernel,
+ * the 16-byte operand loads of the generic / big kernel, the split-K decomposition and, with deterministic != 0,
+ * whether the k-part kernels and their reduce launch run.  kernel = HM_GEMM_KERNEL_NONE (all zeros) when M or N is 0.  */
+enum { HM_GEMM_KERNEL_NONE = 0, HM_GEMM_KERNEL_GENERIC = 1, HM_GEMM_KERNEL_BIG = 2, HM_GEMM_KERNEL_PIPE64 = 3,
+       HM_GEMM_KERNEL_PIPE96 = 4 };
+typedef struct hm_gemm_plan_info {
+    int32_t kernel;           /* HM_GEMM_KERNEL_*: generic 64x64, big 128x128, pipelined 64x64 or 96x64        */
+    int32_t k_tail;           /* pipelined: K is no multiple of 128 and runs to the next one (k >= K read as 0)  */
+    int32_t vec_a, vec_b;     /* generic / big: operand fetched with 16-byte loads                              */
+    int32_t part;             /* deterministic split-K: k-part slabs + reduce launch instead of atomics          */
+    int32_t pad_;
+    int64_t split, k_chunk;   /* workgroups along K and the K range of one                                       */
+} hm_gemm_plan_info;
+HM_API int hm_diag_gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
+                             const float *B, int64_t ldb, int has_epilogue, int deterministic, hm_gemm_plan_info *info);
 
 /* ---- fused activation passes of the grad-enabled MLP path ------------------------------------
  * nn.Softplus(beta, threshold) (implicit_differentiable_renderer.py:84) over n contiguous floats:
