@@ -1101,6 +1101,24 @@ static size_t sdf_lds16(const SdfNet &net, int E) {
 static size_t sdf_lds64(const SdfNet &net) {
     return sizeof(float) * ((size_t)(net.x_groups + net.emb_groups) * kGroupFloats + kPts * 4 + kWaves * kPts);
 }
+// LDS limits of the small-tile (16 / 8 / 4-point) and 64-point launches; the tracer's persistent kernels keep 64 bytes of
+// their own on top of the tile
+constexpr size_t kLds16Max = 96 * 1024, kLds64Max = 160 * 1024, kLdsTrace = 64;
+
+// The checks of every fp32 launch that can evaluate the network - hm_sdf_fwd / hm_sdf_fwd_emb at any tile size and the
+// tracer's march, secant and scan-secant kernels - at their tightest bounds (hm_sdf_net_fits, HM_SDF_FP32).
+static int sdf_fp32_fits(const hm_mlp_desc *mlp, int E) {
+    HmLevels lv = {};
+    lv.E = E;
+    SdfNet net;
+    bool have16 = true;
+    const int rc = sdf_net_fp32("hm_sdf_net_fits", lv, mlp, 0, kImgM16Optional, net, &have16);
+    if (rc != HM_OK) return rc;
+    HM_CHECK_ARG(sdf_lds64(net) + kLdsTrace <= kLds64Max, "hm_sdf_net_fits: network does not fit the 160 KB LDS tile");
+    HM_CHECK_ARG(!have16 || sdf_lds16(net, E) + kLdsTrace <= kLds16Max,
+                 "hm_sdf_net_fits: network does not fit the 16-point LDS tile");
+    return HM_OK;
+}
 
 // tile-size thresholds of the small-tile kernels: 8-point tiles up to m8_max live points, 4-point tiles up to m4_max,
 // 16-point tiles above.  tile_points 0 / -1: by the live count (kSdfTiny, kSdfMini); 4, 8, 16: that size only.
@@ -1150,6 +1168,9 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
                         const float *table, const float *B_fourier, float *out, int64_t out_stride, int out_cols,
                         int frac_mode, int tile_points, const int32_t *n_dev, int max_workgroups, void *stream,
                         const SdfFillArgs *fill = nullptr, int *grid64_out = nullptr);
+// hm_sdf_bf16.hip / hm_sdf_split.hip: the network and LDS checks of their launches (hm_sdf_net_fits)
+int sdf_bf16_fits(const hm_mlp_desc *mlp, int E);
+int sdf_split_fits(const hm_mlp_desc *mlp, int E);
 
 // hm_sdf_fwd for the ray search's sampler launches (not exported): the 64-point launch completes its last round with
 // tiles of a second point set (fill_quota; x_fill / out_fill / n_fill_dev: the closest-approach scan's points, values and
@@ -1200,8 +1221,8 @@ int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const 
     if (a.n == 0 || first >= rounds) return HM_OK;
     HM_CHECK_ARG(a.w.cap >= ((a.n + 7) / 8) * 16, "hm_trace_march_tail: point buffer too small");
     const int lds_floats = (int)(sdf_lds16(net, desc->lv.E) / sizeof(float));
-    const size_t lds = sizeof(float) * (size_t)lds_floats + 64;
-    HM_CHECK_ARG(lds <= 96 * 1024, "hm_trace_march_tail: network does not fit the 16-point LDS tile");
+    const size_t lds = sizeof(float) * (size_t)lds_floats + kLdsTrace;
+    HM_CHECK_ARG(lds <= kLds16Max, "hm_trace_march_tail: network does not fit the 16-point LDS tile");
     const unsigned grid = (unsigned)((a.n + 7) / 8);
     return hm_frac_dispatch(frac_mode, [&](auto frac) {
         constexpr auto kernel = trace_march_tail_kernel<decltype(frac)::value>;
@@ -1228,7 +1249,7 @@ int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
     if (rc != HM_OK) return rc;
     if (a.n == 0 || n_iters <= 0) return HM_OK;
     const size_t lds = sdf_lds16(net, desc->lv.E);
-    HM_CHECK_ARG(lds <= 96 * 1024, "hm_trace_secant_persistent: network does not fit the 16-point LDS tile");
+    HM_CHECK_ARG(lds <= kLds16Max, "hm_trace_secant_persistent: network does not fit the 16-point LDS tile");
     const SmallTiles t = sdf_small_tiles(tile_points);
     // workgroups for the longest list the call can see (every ray a secant ray), one tile each up to one per CU
     const unsigned grid = sdf_small_grid(a.n, t, 256);
@@ -1260,7 +1281,7 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
                     -1, a.w.cnt + C_NSEL_PTS, 0, stream);
     if (rc != HM_OK) return rc;
     const size_t lds16 = sdf_lds16(net, desc->lv.E), lds64 = sdf_lds64(net);
-    HM_CHECK_ARG(lds16 <= 96 * 1024 && lds64 <= 160 * 1024 - 64, "hm_trace_scan_secant: network does not fit the LDS tiles");
+    HM_CHECK_ARG(lds16 <= kLds16Max && lds64 <= kLds64Max - kLdsTrace, "hm_trace_scan_secant: network does not fit the LDS tiles");
     const size_t lds = lds16 > lds64 ? lds16 : lds64;
     // 16-point secant tiles once the scan keeps the chip busy for longer than their chain takes (8 x 131 us ~ 2.3 rounds
     // of 64-point tiles: 3 rounds = 49 152 points)
@@ -1321,7 +1342,7 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
     const int64_t cap = max_workgroups > 0 ? max_workgroups : 256;  // one resident workgroup per CU
     if (run16) {
         const size_t lds = sdf_lds16(net, lv.E);
-        HM_CHECK_ARG(lds <= 96 * 1024, "hm_sdf_fwd: network does not fit the 16-point LDS tile");
+        HM_CHECK_ARG(lds <= kLds16Max, "hm_sdf_fwd: network does not fit the 16-point LDS tile");
         const SmallTiles t = sdf_small_tiles(tile_points);
         const unsigned grid = sdf_small_grid(n < hi16 ? n : hi16, t, cap);
         const int rc = sdf_dispatch(mode, [&](auto frac) {
@@ -1338,7 +1359,7 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
     // big batches: one 64-point workgroup per CU
     if (run64) {
         const size_t lds = sdf_lds64(net);
-        HM_CHECK_ARG(lds <= 160 * 1024, "hm_sdf_fwd: network does not fit the 160 KB LDS tile");
+        HM_CHECK_ARG(lds <= kLds64Max, "hm_sdf_fwd: network does not fit the 160 KB LDS tile");
         const int64_t tiles = (n + 31) / 32;      // (up to cap * 32 points: one 32-point half tile per workgroup)
         const int64_t grid = tiles < cap ? tiles : cap;
         // filler tiles only where every launch of the chain applies the same lower bound (fill_quota's run_min)
@@ -1357,6 +1378,15 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
     }
     HM_CHECK_LAUNCH("hm_sdf_fwd");
     return HM_OK;
+}
+
+int hm_sdf_net_fits(const hm_mlp_desc *mlp, int emb_width, int family) {
+    HM_CHECK_ARG(mlp && emb_width >= 1 && emb_width <= 512, "hm_sdf_net_fits: bad descriptor or embedding width");
+    HM_CHECK_ARG(family == HM_SDF_FP32 || family == HM_SDF_BF16 || family == HM_SDF_SPLIT, "hm_sdf_net_fits: bad family");
+    const int rc = family == HM_SDF_FP32   ? sdf_fp32_fits(mlp, emb_width)
+                   : family == HM_SDF_BF16 ? sdf_bf16_fits(mlp, emb_width)
+                                           : sdf_split_fits(mlp, emb_width);
+    return rc == HM_OK ? 1 : 0;
 }
 
 }  // extern "C"

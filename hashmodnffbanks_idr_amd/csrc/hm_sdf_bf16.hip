@@ -237,18 +237,26 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
     }
 }
 
+// the network and LDS checks of every launch of this kernel (hm_sdf_net_fits asks the same): *lds = its dynamic LDS
+static int sdf_bf16_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, size_t *lds) {
+    const int rc = sdf_net_from_desc(who, mlp, E, emb_stride, kImgBf16, 2, (E + 7) / 8 * 2, true, net);
+    if (rc != HM_OK) return rc;
+    *lds = (size_t)(net.x_groups / 2) * kXOct * 2 + sizeof(float) * ((size_t)net.emb_groups * kEmbGF + kPB * 4 + 5 * kPB);
+    if (*lds > 160 * 1024) return hm_fail(HM_ERR_INVALID, std::string(who) + ": network does not fit the 160 KB LDS tile");
+    return HM_OK;
+}
+
 static int sdf_bf16_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,
                          const float *table, const float *B_fourier, float *out, int64_t out_stride, int frac_mode,
                          const int32_t *n_dev, int64_t run_min, void *stream) {
     HM_CHECK_ARG(n >= 0, "hm_sdf_fwd_bf16: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_sdf_fwd_bf16: bad frac_mode");
     SdfNet net;
-    const int rc = sdf_net_from_desc("hm_sdf_fwd_bf16", mlp, lv.E, emb_stride, kImgBf16, 2, (lv.E + 7) / 8 * 2, true, net);
+    size_t lds = 0;
+    const int rc = sdf_bf16_net("hm_sdf_fwd_bf16", lv.E, mlp, emb_stride, net, &lds);
     if (rc != HM_OK) return rc;
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && out && (emb_stride > 0 || (table && B_fourier)), "hm_sdf_fwd_bf16: NULL pointer");
-    const size_t lds = (size_t)(net.x_groups / 2) * kXOct * 2 + sizeof(float) * ((size_t)net.emb_groups * kEmbGF + kPB * 4 + 5 * kPB);
-    HM_CHECK_ARG(lds <= 160 * 1024, "hm_sdf_fwd_bf16: network does not fit the 160 KB LDS tile");
     const int64_t tiles = (n + kPB - 1) / kPB;
     const int64_t grid = tiles < 256 ? tiles : 256;
     const int64_t big = (int64_t)1 << 62;
@@ -266,6 +274,13 @@ static int sdf_bf16_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float
 }  // namespace
 
 extern "C" {
+
+// (internal: hm_sdf_net_fits, HM_SDF_BF16)
+int sdf_bf16_fits(const hm_mlp_desc *mlp, int E) {
+    SdfNet net;
+    size_t lds = 0;
+    return sdf_bf16_net("hm_sdf_net_fits", E, mlp, 0, net, &lds);
+}
 
 int hm_sdf_fwd_bf16(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n, const float *table,
                     const float *B_fourier, float *out, int64_t out_stride, int frac_mode, const int32_t *n_dev,

@@ -342,19 +342,27 @@ __global__ __launch_bounds__(256) void pack_layer_split_kernel(PackSplitArgs a, 
     img[o + 512] = lo;
 }
 
+// the network and LDS checks of every launch of this kernel (hm_sdf_net_fits asks the same): *lds = its dynamic LDS
+static int sdf_split_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, size_t *lds) {
+    // (EMB region: k-groups of 4 = 2 octets per 16-block)
+    const int rc = sdf_net_from_desc(who, mlp, E, emb_stride, kImgSplit, 2, (E + 15) / 16 * 4, true, net);
+    if (rc != HM_OK) return rc;
+    *lds = (size_t)(net.x_groups / 2 + net.emb_groups / 2) * kOctE * 2 * 2 + sizeof(float) * (kPS * 4 + kWS * kPS);
+    if (*lds > 160 * 1024) return hm_fail(HM_ERR_INVALID, std::string(who) + ": network does not fit the 160 KB LDS tile");
+    return HM_OK;
+}
+
 static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,
                           const float *table, const float *B_fourier, float *out, int64_t out_stride, int frac_mode,
                           const int32_t *n_dev, int64_t run_min, void *stream) {
     HM_CHECK_ARG(n >= 0, "hm_sdf_fwd_split: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_sdf_fwd_split: bad frac_mode");
-    SdfNet net;   // (EMB region: k-groups of 4 = 2 octets per 16-block)
-    const int rc =
-        sdf_net_from_desc("hm_sdf_fwd_split", mlp, lv.E, emb_stride, kImgSplit, 2, (lv.E + 15) / 16 * 4, true, net);
+    SdfNet net;
+    size_t lds = 0;
+    const int rc = sdf_split_net("hm_sdf_fwd_split", lv.E, mlp, emb_stride, net, &lds);
     if (rc != HM_OK) return rc;
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && out && (emb_stride > 0 || (table && B_fourier)), "hm_sdf_fwd_split: NULL pointer");
-    const size_t lds = (size_t)(net.x_groups / 2 + net.emb_groups / 2) * kOctE * 2 * 2 + sizeof(float) * (kPS * 4 + kWS * kPS);
-    HM_CHECK_ARG(lds <= 160 * 1024, "hm_sdf_fwd_split: network does not fit the 160 KB LDS tile");
     const int64_t tiles = (n + kPS - 1) / kPS;
     const int64_t grid = tiles < 256 ? tiles : 256;
     const int64_t big = (int64_t)1 << 62;
@@ -376,6 +384,13 @@ static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const floa
 }  // namespace
 
 extern "C" {
+
+// (internal: hm_sdf_net_fits, HM_SDF_SPLIT)
+int sdf_split_fits(const hm_mlp_desc *mlp, int E) {
+    SdfNet net;
+    size_t lds = 0;
+    return sdf_split_net("hm_sdf_net_fits", E, mlp, 0, net, &lds);
+}
 
 int hm_pack_mlp_layer_split(const float *W, int64_t ldw, int out_dim, int seg_width0, int seg_width1, float seg_scale0,
                             float seg_scale1, int split_kind, void *w_packed_split, void *stream) {

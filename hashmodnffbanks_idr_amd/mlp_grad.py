@@ -67,8 +67,13 @@ class _SdfMlp(torch.autograd.Function):
         # - the product with s1 is the epilogue of the GEMM that makes v_l
         v_list = [None] * L
         v = c.unsqueeze(-1) * Ws[L - 1][0:1, :]          # u_{L-1} is c on column 0 only: rank-1, no GEMM
-        v_list[L - 1] = v
         ge_skip = None
+        if skip_layer == L - 1:     # the last layer reads cat[h, e] / sqrt2: split v as the loop does at the skip
+            v = v.div_(_SQRT2)
+            dh = z_list[L - 2].shape[1]
+            ge_skip = v[:, dh:]
+            v = v[:, :dh].contiguous()
+        v_list[L - 1] = v
         u = _softplus_call(1, z_list[L - 2], v, None, beta_sp, thr_sp)[0] if L > 1 else None
         for l in range(L - 2, -1, -1):
             scale = 1.0 / _SQRT2 if l == skip_layer else 1.0

@@ -125,10 +125,13 @@ class ImplicitNetwork(nn.Module):
         self.coarse_split = None
 
     def coarse_mode(self):
-        """hm_trace_cfg.coarse_bf16 value of this network: 0 exact fp32, 1 bf16, 2 split operands"""
+        """hm_trace_cfg.coarse_bf16 value of this network: 0 exact fp32, 1 bf16, 2 split operands.  A 16-bit mode is
+        used only where its kernel accepts the network (hm_sdf_net_fits); the coarse scans stay exact fp32 otherwise."""
         if self.coarse_split is not None:
-            return 2
-        return 1 if self.bf16_coarse_search else 0
+            return 2 if self.packed_weights().fits(ops.SDF_SPLIT) else 0
+        if self.bf16_coarse_search:
+            return 1 if self.packed_weights().fits(ops.SDF_BF16) else 0
+        return 0
 
     def __getstate__(self):  # the packed-weight cache holds raw device pointers: never copied / pickled
         d = self.__dict__.copy()
@@ -163,7 +166,10 @@ class ImplicitNetwork(nn.Module):
         if emb is None or not emb.table.is_cuda or emb.n_features != 2:
             return False
         widths = [getattr(self, "lin" + str(l)).bias.shape[0] for l in range(self.num_layers - 1)]
-        return max(widths) <= 512 and 0 not in self.skip_in and (self.num_layers - 1) <= 16
+        if not (max(widths) <= 512 and 0 not in self.skip_in and (self.num_layers - 1) <= 16):
+            return False      # (no operand images for such a network)
+        # the rest is decided by the kernels' own host-side checks (LDS tiles: embedding width x layer width)
+        return self.packed_weights().fits(ops.SDF_FP32)
 
     def packed_weights(self):
         """Fold weight-norm and pack the MFMA operand images; cached until a parameter changes."""

@@ -628,6 +628,9 @@ def pack_mlp_layer(W, segs, kblock=8):
     return Wp, n_tiles, octs, srcs
 
 
+SDF_FP32, SDF_BF16, SDF_SPLIT = 0, 1, 2     # kernel families of hm_sdf_net_fits (HM_SDF_*)
+
+
 class PackedSdf:
     """Device-resident packed weights + the [host] hm_mlp_desc for hm_sdf_fwd.
 
@@ -690,7 +693,17 @@ class PackedSdf:
             ly.post_div_sqrt2 = 1 if (l + 1) in skip_in else 0
             prev_out = out_dim
         self.out_dim = prev_out
+        self.E = E
+        self._fits = {}
         self.update(weights, biases, beta)
+
+    def fits(self, family):
+        """whether the fused kernels of `family` (SDF_FP32 / SDF_BF16 / SDF_SPLIT) accept this network: the host-side
+        checks of their launches (hm_sdf_net_fits), asked once per family - update() never changes a layer's shape"""
+        r = self._fits.get(family)
+        if r is None:
+            r = self._fits[family] = check(lib().hm_sdf_net_fits(C.byref(self.desc), int(self.E), int(family))) == 1
+        return r
 
     def update(self, weights, biases, beta):
         self.desc.beta = float(beta)

@@ -307,6 +307,16 @@ HM_API int hm_sdf_fwd_emb(const hm_mlp_desc *mlp, const float *emb, int64_t emb_
                           float *out, int64_t out_stride, int out_cols, int tile_points, const int32_t *n_dev,
                           int max_workgroups, void *stream);
 
+/* Whether the fused SDF kernels of one family accept the network mlp over embedding rows of width emb_width, decided by
+ * the host-side checks their launches make (descriptor, layer shapes, LDS tiles); host only, nothing is enqueued.
+ *   HM_SDF_FP32:  hm_sdf_fwd / hm_sdf_fwd_emb at every tile size and the ray tracer's fp32 kernels;
+ *   HM_SDF_BF16:  hm_sdf_fwd_bf16 / hm_sdf_fwd_emb_bf16;   HM_SDF_SPLIT: hm_sdf_fwd_split / hm_sdf_fwd_emb_split.
+ * Returns 1 (accepted), 0 (refused: hm_last_error() says why) or -1 (bad argument).                              */
+#define HM_SDF_FP32 0
+#define HM_SDF_BF16 1
+#define HM_SDF_SPLIT 2
+HM_API int hm_sdf_net_fits(const hm_mlp_desc *mlp, int emb_width, int family);
+
 /* ---- Fourier-filter-bank embedders ('FFB', 'StyleModNFFB') forward, no grad ------------------------------------
  * Replaces FourierFilterBanks.forward (model/embeddings/nffb3d.py:122-194, registry settings PositionalEncodingNET /
  * SIREN / has_out=False) with PositionalEncoding (frequency_enc.py:6-51), Sine (Sine.py:5-25) and StyleAttention

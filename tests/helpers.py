@@ -80,22 +80,48 @@ def load_embedder(emb, levels, B):
     emb.load_state_dict(sd)
 
 
-def make_implicit(cfg, hidden, fvs, seed, perturb, table_scale, g_jitter=0.1, device="cuda", bias=0.6):
+def make_implicit(cfg, hidden, fvs, seed, perturb, table_scale, g_jitter=0.1, device="cuda", bias=0.6, skip_in=(4,)):
+    """cfg: a name of params.CONFIGS or an (L, T, base, desired) tuple"""
     from hashmodnffbanks_idr_amd.model.implicit_differentiable_renderer import ImplicitNetwork
-    L, Tt, b, d = P.CONFIGS[cfg]
-    net = ImplicitNetwork(fvs, 3, 1, list(hidden), True, 0.6, [4], True, multires=L, embed_type="HashGrid",
+    L, Tt, b, d = P.CONFIGS[cfg] if isinstance(cfg, str) else cfg
+    net = ImplicitNetwork(fvs, 3, 1, list(hidden), True, 0.6, list(skip_in), True, multires=L, embed_type="HashGrid",
                           log2_max_hash_size=Tt, max_points_per_entry=2, base_resolution=b, desired_resolution=d,
                           bound=1.0)
     levels, B, res, rows = P.make_embedder_state(seed, cfg, table_scale)
     load_embedder(net.embed_model.embedder_obj, levels, B)
     E = 3 + 4 * L
-    prm = P.make_sdf_params(seed + 7, E, hidden, 1 + fvs, (4,), bias, perturb, g_jitter)
+    prm = P.make_sdf_params(seed + 7, E, hidden, 1 + fvs, tuple(skip_in), bias, perturb, g_jitter)
     sd = net.state_dict()
     for k, v in prm.items():
         assert sd[k].shape == v.shape, (k, sd[k].shape, v.shape)
         sd[k] = torch.from_numpy(v)
     net.load_state_dict(sd)
     return net.to(device)
+
+
+def mlp_fp64(net, e):
+    """ImplicitNetwork.forward (implicit_differentiable_renderer.py:96-113) in float64 on the embedding rows e, for any
+    skip_in: Softplus(100, threshold 20), skip concat / sqrt(2), Laplace soft clamp of column 0.  The weights are the
+    fp32 weight-norm folds the fused kernels pack (ImplicitNetwork.packed_weights), taken as W.double(): the rounding of
+    the fold is not the kernels' error.  Returns (out [N, 1 + fvs] with the clamped sdf in column 0, s = the pre-clamp
+    column 0)."""
+    from hashmodnffbanks_idr_amd.model.implicit_differentiable_renderer import _folded_weight
+    e = e.double()
+    x = e
+    n_lin = net.num_layers - 1
+    for l in range(n_lin):
+        lin = getattr(net, "lin" + str(l))
+        if l in net.skip_in:
+            x = torch.cat([x, e], 1) / np.sqrt(2.0)
+        with torch.no_grad():
+            W = _folded_weight(lin).detach().double()
+        x = x @ W.t() + lin.bias.detach().double()
+        if l < n_lin - 1:
+            x = torch.where(x * 100.0 > 20.0, x, torch.log1p(torch.exp(torch.clamp(x * 100.0, max=20.0))) / 100.0)
+    s = x[:, 0]
+    beta = net.dencity_net.beta.detach().abs().double() + 1e-4
+    rho = (1.0 / beta) * (0.5 + 0.5 * torch.sign(s) * torch.expm1(-s.abs() / beta))
+    return torch.cat([torch.tanh(s / (2.0 + rho)).unsqueeze(1), x[:, 1:]], 1), s
 
 
 def make_idr(cfg, seed, bias=0.6, device="cuda"):

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import make_implicit
+from helpers import make_implicit, mlp_fp64
 
 pytestmark = pytest.mark.gpu
 
@@ -14,32 +14,6 @@ pytestmark = pytest.mark.gpu
 def _c2_net(g, bias=1.0):
     return make_implicit("C2", (512,) * 8, 256, int(g["seed"]), float(g["perturb"]), float(g["table_scale"]),
                          bias=float(g["bias"]) if "bias" in g.files else bias)
-
-
-def _mlp_fp64(net, e):
-    """the SDF column of ImplicitNetwork.forward (implicit_differentiable_renderer.py:96-113) in float64 on the fp32
-    embedding rows e: folded weights g v / ||v||, Softplus(100, threshold 20), skip concat / sqrt(2), Laplace clamp"""
-    from hashmodnffbanks_idr_amd.model.implicit_differentiable_renderer import _folded_weight
-    e = e.double()
-    x = e
-    n_lin = net.num_layers - 1
-    for l in range(n_lin):
-        lin = getattr(net, "lin" + str(l))
-        if l in net.skip_in:
-            x = torch.cat([x, e], 1) / np.sqrt(2.0)
-        with torch.no_grad():
-            if hasattr(lin, "weight_g"):
-                v, gg = lin.weight_v.double(), lin.weight_g.double()
-                W = gg * v / v.norm(dim=1, keepdim=True)
-            else:
-                W = lin.weight.double()
-        x = x @ W.t() + lin.bias.double()
-        if l < n_lin - 1:
-            x = torch.where(x * 100.0 > 20.0, x, torch.log1p(torch.exp(torch.clamp(x * 100.0, max=20.0))) / 100.0)
-    s = x[:, 0]
-    beta = net.dencity_net.beta.detach().abs().double() + 1e-4
-    rho = (1.0 / beta) * (0.5 + 0.5 * torch.sign(s) * torch.expm1(-s.abs() / beta))
-    return torch.tanh(s / (2.0 + rho))
 
 
 @pytest.mark.parametrize("kind", ["bf16x2", "f16x2"])
@@ -52,7 +26,7 @@ def test_split_kernel_against_fp32_and_fp64(golden, kind):
     with torch.no_grad():
         ref32 = net.sdf(x)                                   # exact-fp32 MFMA kernel
         e = ops.encode_fwd(emb.desc, x, emb.table.detach(), emb.freq_encoding.B, 0)
-        ref64 = _mlp_fp64(net, e)
+        ref64 = mlp_fp64(net, e)[0][:, 0]
         net.coarse_split = kind
         pk = net.packed_weights()
         assert pk.split == kind
@@ -126,7 +100,7 @@ def test_split_emb_kernel_on_stylemod(golden, kind):
     with torch.no_grad():
         e = ops.nffb_fwd(net._nffb_embedder(), x)
         ref32 = ops.sdf_fwd_emb(net.packed_weights(), e, sdf_only=True)
-        ref64 = _mlp_fp64(net, e)
+        ref64 = mlp_fp64(net, e)[0][:, 0]
         net.coarse_split = kind
         pk = net.packed_weights()
         got = ops.sdf_fwd_emb_split(pk, e)
