@@ -51,6 +51,7 @@ SIGNATURES = {
     "hm_nffb_fwd": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _int, _p, _p]),
     "hm_sdf_fwd_emb": (_int, [_p, _p, _i64, _int, _i64, _p, _i64, _int, _int, _p, _int, _p]),
     "hm_sdf_net_fits": (_int, [_p, _int, _int]),
+    "hm_diag_sdf_lds": (_int, [_p, _int, _int, _int, _p]),
     "hm_trace_workspace_bytes": (_i64, [_i64, _p]),
     "hm_trace_forward": (_int, [_p, _p, _p, _p, _int, _int, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
                                 _i64, _p, _p]),

@@ -19,7 +19,9 @@
 //     optional /sqrt(2)) writes it back with ds_write_b128 - no transpose, no shuffles.
 // Small batches (the ray search issues ~30 dependent calls of 1...4096 points per iteration) use 16-, 8- and
 // 4-point tiles so that every call is ONE tile per CU; the tile size is chosen on the device from the live
-// point count (sdf_fwd_small_kernel -> sdf_m16_body / sdf_m8_body<8|4>).
+// point count (sdf_fwd_small_kernel -> sdf_small_body<Tile16 | Tile8<8> | Tile8<4>>).
+// The stages all tile bodies share - point load, weight stream (WeightRing), quad epilogue, embedding rescale, last-layer
+// finish, output rows, LDS layout (SdfLds) - are in hm_sdf_common.h; sdf64_run below is the 64-point body.
 #include "hm_common.h"
 
 #include <math.h>
@@ -65,6 +67,16 @@ constexpr int kThreadsSdf = 512;
 constexpr int kWaves = 8;
 constexpr int kGroupFloats = kPts * 4;  // floats per k-group row of X: [point][4]
 
+// dynamic LDS of the 64-point tile: X, the embedding (kept for the skip connection), 8 partial sums per point
+__host__ __device__ inline SdfLds sdf_lds64(const SdfNet &net) {
+    return sdf_lds(kPts, 1, net.x_groups * kGroupFloats, 1, net.emb_groups * kGroupFloats, kWaves);
+}
+// ... of the small tiles (pts = 16 or 8 points in the LDS image): two activation images + the embedding in whole
+// 16-blocks.  (The 8-point layout needs half of the 16-point one, which is what every launch asks for.)
+__host__ __device__ inline SdfLds sdf_lds_small(const SdfNet &net, int E, int pts) {
+    return sdf_lds(pts, 2, net.x_groups * pts * 4, 1, (E + 15) / 16 * 4 * pts * 4, kWaves);
+}
+
 // Filler tiles.  A launch whose own points end in a partly filled last round can take the 64-point tiles that complete
 // the round from a SECOND point set that has to be evaluated anyway (the ray search: the closest-approach scan, whose
 // values nothing in the sampler's launches waits for).  Which of that set's tiles a launch takes follows from the
@@ -102,10 +114,11 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
                                           float *__restrict__ out, int64_t out_stride, int out_cols, float *lds,
                                           unsigned *cursor, const SdfFill &fb) {
     __shared__ unsigned s_next_tile;
+    const SdfLds at = sdf_lds64(net);
     float *X = lds;
-    float *EMB = lds + (size_t)net.x_groups * kGroupFloats;
-    float *SX = EMB + (size_t)net.emb_groups * kGroupFloats;  // [64][3] raw points
-    float *RED = SX + kPts * 4;                                // [8][64] cross-wave partial sums
+    float *EMB = lds + at.emb;
+    float *SX = lds + at.sx;     // [64][3] raw points
+    float *RED = lds + at.red;   // [8][64] cross-wave partial sums
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: the weight pointers below stay in SGPRs)
@@ -164,7 +177,7 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
         const bool half = cnt <= 32;   // (also a ragged last tile of <= 32 points)
         HM_PROBE(0);
         __syncthreads();  // previous tile's output stage is done with X
-        if (FRAC != kFracEmb && tid < kPts * 3) SX[tid] = (tid < cnt * 3) ? xs[base * 3 + tid] : 0.0f;
+        load_points(FRAC != kFracEmb, SX, xs, base, cnt, kPts, tid);
         __syncthreads();
 
         // ---------------- encode -> EMB[(e/4)][p][e%4] ------------------------------------
@@ -181,29 +194,18 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
         HM_PROBE(1);
 
         // ---------------- layers ------------------------------------------------------------
-        // weight ring (4 slots per feature tile) lives across layers: the first three octets of layer l+1 are
-        // requested before layer l's epilogue (weights do not depend on the activations), so the stream does not
-        // restart from an empty pipe behind the two barriers of every layer
-        float4 r0[4], r1[4];
+        // weight ring (WeightRing, hm_sdf_common.h: 4 slots, 3 octets = 6 KB per wave in flight); it lives across layers
+        WeightRing<4, 2> ring;
+        ring.voff = lane * 16;
         bool ring_ready = false;
-        const int lane16 = lane * 16;
-        auto ldw = [&](const __amdgpu_buffer_rsrc_t &rs, int soff) -> float4 { return ld_w16(rs, lane16, soff); };
         auto prefetch64 = [&](int l) {
             const hm_mlp_layer &Lp = net.layer[l];
             const int nop = Lp.seg_octets[0] + Lp.seg_octets[1];
             const int ntp = max(0, min(2, Lp.n_tiles - 2 * wave));
-            // buffer loads: descriptor (SGPRs) on the wave's first feature tile, lane * 16 as the one loop-invariant VGPR
-            // offset, the octet / tile offset as the scalar offset - no per-load 64-bit address arithmetic on the VALU,
-            // whose instructions are serial with the MFMAs of both waves on the SIMD
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float *>(Lp.w_packed) + ((size_t)(2 * wave) * nop) * 256, 0, 0x7fffffff, 0x00020000);
-            const int t1 = ntp > 1 ? nop * 1024 : 0;
-#pragma unroll
-            for (int st = 0; st < 3; ++st) {
-                const int off = min(st, nop - 1) * 1024;
-                r0[st] = ldw(rs, off);
-                r1[st] = ldw(rs, t1 + off);
-            }
+            // descriptor on the wave's first feature tile; the second one is nop KB on
+            const __amdgpu_buffer_rsrc_t rs = w_rsrc(Lp.w_packed + ((size_t)(2 * wave) * nop) * 256);
+            const int so[2] = {0, ntp > 1 ? nop * 1024 : 0};
+            ring.fill(rs, so, nop);
         };
         for (int li = 0; li < net.n_layers; ++li) {
             const hm_mlp_layer &Ly = net.layer[li];
@@ -230,12 +232,7 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
                     kg0 += ng;
                 }
                 RED[wave * kPts + lane] = part;
-                __syncthreads();
-                if (tid < cnt) {
-                    float sacc = Ly.bias[0];
-                    for (int w8 = 0; w8 < kWaves; ++w8) sacc += RED[w8 * kPts + tid];
-                    os[(base + tid) * out_stride] = sdf_clamp(sacc, net.beta);
-                }
+                sdf_last_finish(RED, kWaves, kPts, cnt, Ly.bias, net.beta, os, base, out_stride, tid);
                 break;
             }
             const int nt = Ly.n_tiles;
@@ -243,11 +240,8 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
             const int ntw = max(0, min(2, nt - t0));
             f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
             if (ntw > 0) {
-                // weight stream: 4-deep register ring (3 octets = 6 KB per wave in flight), unconditional
-                // clamped loads so that hipcc emits counted vmcnt waits instead of draining per octet
-                const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<float *>(Ly.w_packed) + ((size_t)t0 * n_oct) * 256, 0, 0x7fffffff, 0x00020000);
-                const int tA1 = ntw > 1 ? n_oct * 1024 : 0;     // byte offset of the wave's second feature tile
+                const __amdgpu_buffer_rsrc_t rsA = w_rsrc(Ly.w_packed + ((size_t)t0 * n_oct) * 256);
+                const int so[2] = {0, ntw > 1 ? n_oct * 1024 : 0};     // byte offsets of the wave's two feature tiles
                 const int no0 = Ly.seg_octets[0];
                 const float *src0 = (Ly.seg_src[0] == 0) ? X : EMB;
                 const float *src1 = (Ly.seg_src[1] == 0) ? X : EMB;
@@ -283,9 +277,6 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
                 //  LDS round trip.  Alone this changed nothing - one wave's k-loop 62.4 -> 54.2 us per layer, but then 11 us
                 //  at the barrier, scripts/sdf_phase_probe.py; on top of the buffer-load weight stream: 132.0 -> 134.2
                 //  TFLOP/s)
-                // whole groups of four octets run without an exit test: with a `break` inside the unrolled group
-                // hipcc cannot count the loads in flight across the back edge and drains them (vmcnt(0)) at every
-                // loop head; the 1-3 left-over octets are already in ring slots 0..2
                 // half tile: the same stream, point block 0 only (8 MFMAs per octet)
                 auto octet_h = [&](int gg, const float4 &a0, const float4 &a1) {
                     const float *src = (gg < no0) ? src0 + (2 * gg + h) * kGroupFloats
@@ -300,44 +291,16 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
                     acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc00, 0, 0, 0);
                     acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b0.w, acc10, 0, 0, 0);
                 };
-                const int n_full = n_oct & ~3;
                 if (!half) {
                     float4 bA0, bA1, bB0, bB1;      // B fragments: even octets in set A, odd octets in set B
                     loadB(0, bA0, bA1);
-                    for (int gg0 = 0; gg0 < n_full; gg0 += 4) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int gg = gg0 + u;
-                            {
-                                const int off = min(gg + 3, n_oct - 1) * 1024;
-                                r0[(u + 3) & 3] = ldw(rsA, off);
-                                r1[(u + 3) & 3] = ldw(rsA, tA1 + off);
-                            }
-                            if (u & 1) loadB(gg + 1, bA0, bA1); else loadB(gg + 1, bB0, bB1);
-                            __builtin_amdgcn_sched_barrier(0);   // (loads stay ahead of this octet's MFMAs; see the 16-point body)
-                            if (u & 1) mfma16(r0[u], r1[u], bB0, bB1); else mfma16(r0[u], r1[u], bA0, bA1);
-                        }
-                    }
-                    if (n_full + 0 < n_oct) { loadB(n_full + 1, bB0, bB1); mfma16(r0[0], r1[0], bA0, bA1); }
-                    if (n_full + 1 < n_oct) { loadB(n_full + 2, bA0, bA1); mfma16(r0[1], r1[1], bB0, bB1); }
-                    if (n_full + 2 < n_oct) mfma16(r0[2], r1[2], bA0, bA1);
+                    ring.run(rsA, so, n_oct,
+                             [&](int gg, int u) { if (u & 1) loadB(gg + 1, bA0, bA1); else loadB(gg + 1, bB0, bB1); },
+                             [&](int, int u, const float4 (&w)[2]) {
+                                 if (u & 1) mfma16(w[0], w[1], bB0, bB1); else mfma16(w[0], w[1], bA0, bA1);
+                             });
                 } else {
-                    for (int gg0 = 0; gg0 < n_full; gg0 += 4) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int gg = gg0 + u;
-                            {
-                                const int off = min(gg + 3, n_oct - 1) * 1024;
-                                r0[(u + 3) & 3] = ldw(rsA, off);
-                                r1[(u + 3) & 3] = ldw(rsA, tA1 + off);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            octet_h(gg, r0[u], r1[u]);
-                        }
-                    }
-                    if (n_full + 0 < n_oct) octet_h(n_full + 0, r0[0], r1[0]);
-                    if (n_full + 1 < n_oct) octet_h(n_full + 1, r0[1], r1[1]);
-                    if (n_full + 2 < n_oct) octet_h(n_full + 2, r0[2], r1[2]);
+                    ring.run(rsA, so, n_oct, no_pre, [&](int gg, int, const float4 (&w)[2]) { octet_h(gg, w[0], w[1]); });
                 }
             }
             if (li + 1 < net.n_layers && !(li + 1 == net.n_layers - 1 && out_cols == 1) &&
@@ -354,24 +317,16 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
             // epilogue: registers 4q..4q+3 of a tile = features 8q+4h+{0..3} = one k-group of the next layer
             const bool act = Ly.activation != 0;
             const bool div = Ly.post_div_sqrt2 != 0;
-            const float sqrt2 = 1.41421356237309515f;
             auto store_tile = [&](const f32x16 &acc, int ft, int pt) {
                 const int fbase = 32 * (t0 + ft);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int f = fbase + 8 * q + 4 * h;
                     const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
-                    float v0 = acc[4 * q + 0] + bb.x, v1 = acc[4 * q + 1] + bb.y, v2 = acc[4 * q + 2] + bb.z,
-                          v3 = acc[4 * q + 3] + bb.w;
-                    if (act) {
-                        softplus100_4(v0, v1, v2, v3);
-                    }
-                    if (div) {
-                        v0 = __fdiv_rn(v0, sqrt2); v1 = __fdiv_rn(v1, sqrt2); v2 = __fdiv_rn(v2, sqrt2);
-                        v3 = __fdiv_rn(v3, sqrt2);
-                    }
+                    float v[4] = {acc[4 * q + 0] + bb.x, acc[4 * q + 1] + bb.y, acc[4 * q + 2] + bb.z, acc[4 * q + 3] + bb.w};
+                    act_quads(v, act, div);
                     *reinterpret_cast<float4 *>(X + (f >> 2) * kGroupFloats + (32 * pt + j) * 4) =
-                        make_float4(v0, v1, v2, v3);
+                        make_float4(v[0], v[1], v[2], v[3]);
                 }
             };
             if (ntw > 0) {
@@ -382,11 +337,7 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
                 store_tile(acc10, 1, 0);
                 if (!half) store_tile(acc11, 1, 1);
             }
-            if (li == 0 && net.emb_groups > 0) {
-                // the skip layer consumes cat[x, emb]/sqrt(2): rescale the kept embedding once, in place
-                for (int i = tid; i < net.emb_groups * kGroupFloats; i += kThreadsSdf)
-                    EMB[i] = __fdiv_rn(EMB[i], sqrt2);
-            }
+            if (li == 0 && net.emb_groups > 0) rescale_emb(EMB, net.emb_groups * kGroupFloats, tid, kThreadsSdf);
             HM_PROBE(4 + 4 * li);
             __syncthreads();
             HM_PROBE(5 + 4 * li);
@@ -395,15 +346,7 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
 
         // ---------------- output: X[(f/4)][p][f%4] -> out[p][f] -----------------------------
         const hm_mlp_layer &last = net.layer[net.n_layers - 1];
-        if (out_cols != 1) {
-            const int od = last.out_dim;
-            for (int i = tid; i < cnt * od; i += kThreadsSdf) {
-                const int p = i / od, f = i - p * od;
-                float v = X[(f >> 2) * kGroupFloats + p * 4 + (f & 3)];
-                if (f == 0) v = sdf_clamp(v, net.beta);
-                os[(base + p) * out_stride + f] = v;
-            }
-        }
+        if (out_cols != 1) store_rows(X, kGroupFloats, cnt, last.out_dim, net.beta, os, base, out_stride, tid, kThreadsSdf);
     }
 }
 
@@ -431,230 +374,96 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_fwd_kernel(HmLevels lv, Sd
 
 
 // ------------------------------------------------------------------------------------------------
-// 16-point tile variant for SMALL batches (sphere-tracing rounds evaluate only 2 points per ray):
-// with 64-point tiles a 4096-point call occupies 64 of the 256 CUs for a full 9-layer latency.
-// Here a workgroup owns 16 points (v_mfma_f32_16x16x4_f32, 4 feature tiles of 16 per wave), so
-// the same call spreads over 256 workgroups; the price is 4x the weight traffic per point, which
-// L2 absorbs at this size.  Same LDS image X[k/4][point][4] (64 floats per k-group), same epilogue
-// identity: lane (point j, quarter q) holds features 4q..4q+3 of a tile = one k-group.
+// Small tiles for SMALL batches (sphere-tracing rounds evaluate only 2 points per ray): with 64-point tiles a
+// 4096-point call occupies 64 of the 256 CUs for a full 9-layer latency.  sdf_small_body is the tile loop and layer
+// skeleton of the 16-, 8- and 4-point forms; a Tile (Tile16, Tile8<8>, Tile8<4>) supplies what differs: the MFMA block of
+// one 16-wide k-block, the reduction over k quarters of the 8-point form, the epilogue's lane -> (feature quad, point)
+// mapping and the lane mapping of the sdf-only last layer.  Every wave owns 4 feature tiles of 16.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kPts16 = 16;
-constexpr int kRing16 = 4;   // weight ring depth of the 16-point kernel (k-blocks)
-constexpr int kGroupFloats16 = kPts16 * 4;
+constexpr int kRing16 = 4;   // weight ring depth of the 16-point tile (k-blocks)
+constexpr int kPts8 = 8;
+constexpr int kRing8 = 5;    // weight ring depth of the 8-point tile (k-blocks)
 
-template <int FRAC>
-__device__ __forceinline__ void sdf_m16_body(const HmLevels &lv, const SdfNet &net, const float *__restrict__ x,
-                                             int64_t n, const float *__restrict__ table,
-                                             const float *__restrict__ Bf, float *__restrict__ out,
-                                             int64_t out_stride, int out_cols, float *lds, int64_t tile_first,
-                                             int64_t tile_step) {
-    const int emb_groups16 = ((lv.E + 15) / 16) * 4;
-    // two activation images, used alternately (layer l reads one, its epilogue writes the other): no barrier between a
-    // layer's k-loop and its epilogue - a wave that finishes early does not wait for the others before its Softplus
-    float *X0 = lds;
-    float *X1 = lds + (size_t)net.x_groups * kGroupFloats16;
-    float *EMB = X1 + (size_t)net.x_groups * kGroupFloats16;
-    float *SX = EMB + (size_t)emb_groups16 * kGroupFloats16;  // [16][3]
-    float *RED = SX + kPts16 * 4;                              // [8][16]
-
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: descriptors / scalar offsets of the weight stream)
-    const int lane = tid & 63;
-    const int lane16 = lane * 16;
-    const int j = lane & 15;  // point
-    const int q = lane >> 4;  // k quarter / feature quarter
-    const int E = lv.E;
-    const int64_t n_tiles = (n + kPts16 - 1) / kPts16;
-
-    for (int64_t tile = tile_first; tile < n_tiles; tile += tile_step) {
-        const int64_t base = tile * kPts16;
-        const int cnt = (int)min((int64_t)kPts16, n - base);
-        float *X = X0, *Xn = X1;     // X: the image the current layer reads; Xn: the one its epilogue fills
-        __syncthreads();
-        if (FRAC != kFracEmb && tid < kPts16 * 3) SX[tid] = (tid < cnt * 3) ? x[base * 3 + tid] : 0.0f;
-        __syncthreads();
-
-        // ---- encode: thread -> (point p, slot c); 32 slots cover channels / levels
-        if constexpr (FRAC == kFracEmb) {
-            load_emb_tile(EMB, x, net.emb_stride, base, cnt, E, emb_groups16, kPts16, kGroupFloats16, tid, kThreadsSdf);
-        } else {
-            const int p = tid & (kPts16 - 1);
-            const int c0 = tid >> 4;  // 0..31
-            const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, c0, 32, emb_groups16 * 4,
-                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats16 + p * 4 + (e & 3)] = v; });
-        }
-        __syncthreads();
-
-        float4 ring[kRing16][4];
-        bool ring_ready = false;
-        auto prefetch16 = [&](int l) {
-            const hm_mlp_layer &Lp = net.layer[l];
-            const int nbp = Lp.seg_blocks16[0] + Lp.seg_blocks16[1];
-            const int ntp = max(0, min(4, Lp.n_tiles * 2 - 4 * wave));
-            const __amdgpu_buffer_rsrc_t rp = w_rsrc(Lp.w_packed_m16 + ((size_t)(4 * wave) * nbp) * 256);
-            const int ts = nbp * 1024;     // bytes to the next feature tile
-            const int p1 = (1 < ntp ? 1 : 0) * ts, p2 = (2 < ntp ? 2 : 0) * ts, p3 = (3 < ntp ? 3 : 0) * ts;
+// 16-point tile: a workgroup owns 16 points (v_mfma_f32_16x16x4_f32), so a 4096-point call spreads over 256
+// workgroups; the price is 4x the weight traffic per point, which L2 absorbs at this size.  Same LDS image
+// X[k/4][point][4] (64 floats per k-group), same epilogue identity as the 64-point tile: lane (point j, quarter q) holds
+// features 4q..4q+3 of a tile = one k-group.
+struct Tile16 {
+    static constexpr int kTile = 16, kStride = 16, kDepth = kRing16, kGF = 64;
+    static_assert(kDepth % 2 == 0, "the B double buffer alternates with the parity of the block in the group");
+    int j, q;      // point; k quarter / feature quarter
+    f32x4 acc[4];
+    __device__ __forceinline__ Tile16(int lane) : j(lane & 15), q(lane >> 4) {}
+    __device__ __forceinline__ void zero() {
 #pragma unroll
-            for (int st = 0; st < kRing16 - 1; ++st) {
-                const int off = min(st, nbp - 1) * 1024;
-                ring[st][0] = ld_w16(rp, lane16, off); ring[st][1] = ld_w16(rp, lane16, p1 + off);
-                ring[st][2] = ld_w16(rp, lane16, p2 + off); ring[st][3] = ld_w16(rp, lane16, p3 + off);
-            }
+        for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    // acc = W[this wave's tiles][k-blocks 0 .. nb) * X.  A small batch is bound by the round trip of the packed weights
+    // (7.9 MB per workgroup, served from the Infinity Cache at ~2 us), not by the MFMAs: bytes in flight per CU set the
+    // rate - kDepth-1 k-blocks of 4 KB per wave.
+    __device__ __forceinline__ void products(WeightRing<kDepth, 4> &ring, const __amdgpu_buffer_rsrc_t &rA,
+                                             const int (&so)[4], int nb, int nb0, const float *src0, const float *src1) {
+        // B fragment of k-block t (LDS), requested one block ahead of its MFMAs (two registers sets, as in the
+        // 64-point kernel)
+        auto loadB16 = [&](int t) -> float4 {
+            const int tc = min(t, nb - 1);
+            const float *src = (tc < nb0) ? src0 + (4 * tc + q) * kGF : src1 + (4 * (tc - nb0) + q) * kGF;
+            return *reinterpret_cast<const float4 *>(src + j * 4);
         };
-        for (int li = 0; li < net.n_layers; ++li) {
-            const hm_mlp_layer &Ly = net.layer[li];
-            const int nb = Ly.seg_blocks16[0] + Ly.seg_blocks16[1];  // 16-wide k blocks
-            if (li == net.n_layers - 1 && out_cols == 1) {
-                // sdf-only last layer: VALU dot product, lane (point j, quarter q) walks k-groups == q (mod 4)
-                const float4 *W0 = reinterpret_cast<const float4 *>(Ly.w_packed_m16);
-                float part = 0.0f;
-                int t0 = 0;
-                for (int seg = 0; seg < 2; ++seg) {
-                    const float *src = (Ly.seg_src[seg] == 0) ? X : EMB;
-                    const int nbs = Ly.seg_blocks16[seg];
-                    for (int t = wave; t < nbs; t += kWaves) {
-                        const float4 xv = *reinterpret_cast<const float4 *>(src + (4 * t + q) * kGroupFloats16 + j * 4);
-                        const float4 wv = W0[(size_t)(t0 + t) * 64 + q * 16];
-                        part = __fmaf_rn(xv.x, wv.x, part);
-                        part = __fmaf_rn(xv.y, wv.y, part);
-                        part = __fmaf_rn(xv.z, wv.z, part);
-                        part = __fmaf_rn(xv.w, wv.w, part);
-                    }
-                    t0 += nbs;
-                }
-                part += __shfl_xor(part, 16);
-                part += __shfl_xor(part, 32);
-                if (q == 0) RED[wave * kPts16 + j] = part;
-                __syncthreads();
-                if (tid < cnt) {
-                    float sacc = Ly.bias[0];
-                    for (int w8 = 0; w8 < kWaves; ++w8) sacc += RED[w8 * kPts16 + tid];
-                    out[(base + tid) * out_stride] = sdf_clamp(sacc, net.beta);
-                }
-                break;
-            }
-            const int nt16 = Ly.n_tiles * 2;
-            const int u0 = 4 * wave;
-            const int ntw = max(0, min(4, nt16 - u0));
-            f32x4 acc[4];
+        auto block16 = [&](const float4 &b, const float4 (&w)[4]) {
+            // component-major order: four INDEPENDENT accumulators between two uses of the same one
 #pragma unroll
-            for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (ntw > 0) {
-                // Weight stream: a kRing16-deep register ring (kRing16-1 k-blocks of 4 KB per wave in flight).
-                // A small batch is bound by the round trip of the packed weights (7.9 MB per workgroup, served
-                // from the Infinity Cache at ~2 us), not by the MFMAs: bytes in flight per CU set the rate.
-                // The first kRing16-1 blocks of a layer were requested before the previous layer's epilogue
-                // (`prefetch16` below), so the pipeline does not drain at layer boundaries.
-                // All loads are unconditional (clamped index) so hipcc emits counted vmcnt waits.
-                const __amdgpu_buffer_rsrc_t rA = w_rsrc(Ly.w_packed_m16 + ((size_t)u0 * nb) * 256);
-                const int tstride = nb * 1024;  // bytes to the next feature tile
-                const int o1 = (1 < ntw ? 1 : 0) * tstride, o2 = (2 < ntw ? 2 : 0) * tstride,
-                          o3 = (3 < ntw ? 3 : 0) * tstride;
-                const int nb0 = Ly.seg_blocks16[0];
-                const float *src0 = (Ly.seg_src[0] == 0) ? X : EMB;
-                const float *src1 = (Ly.seg_src[1] == 0) ? X : EMB;
-                if (!ring_ready) prefetch16(li);
-                ring_ready = false;
-                // B fragment of k-block t (LDS), requested one block ahead of its MFMAs (two registers sets, as in the
-                // 64-point kernel)
-                auto loadB16 = [&](int t) -> float4 {
-                    const int tc = min(t, nb - 1);
-                    const float *src = (tc < nb0) ? src0 + (4 * tc + q) * kGroupFloats16
-                                                  : src1 + (4 * (tc - nb0) + q) * kGroupFloats16;
-                    return *reinterpret_cast<const float4 *>(src + j * 4);
-                };
-                auto block16 = [&](const float4 &b, const float4 (&w)[4]) {
-                    // component-major order: four INDEPENDENT accumulators between two uses of the same one
+            for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].x, b.x, acc[a], 0, 0, 0);
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].x, b.x, acc[a], 0, 0, 0);
+            for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].y, b.y, acc[a], 0, 0, 0);
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].y, b.y, acc[a], 0, 0, 0);
+            for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].z, b.z, acc[a], 0, 0, 0);
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].z, b.z, acc[a], 0, 0, 0);
+            for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].w, b.w, acc[a], 0, 0, 0);
+        };
+        float4 bE = loadB16(0), bO;      // even / odd blocks (kDepth is even: block t has the parity of u)
+        ring.run(rA, so, nb, [&](int t, int u) { if (u & 1) bE = loadB16(t + 1); else bO = loadB16(t + 1); },
+                 [&](int, int u, const float4 (&w)[4]) { if (u & 1) block16(bO, w); else block16(bE, w); });
+    }
+    __device__ __forceinline__ void reduce() {}
+    // bias, activation and store of the wave's ntw feature tiles (first: u0) -> Xn
+    __device__ __forceinline__ void epilogue(const float *__restrict__ bias, int u0, int ntw, bool act, bool div, float *Xn) {
 #pragma unroll
-                    for (int a = 0; a < 4; ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[a].w, b.w, acc[a], 0, 0, 0);
-                };
-                // whole groups of kRing16 blocks run without an exit test (with a `break` inside the unrolled group
-                // hipcc drains all loads in flight - vmcnt(0) - at every loop head); the left-over blocks are
-                // already in ring slots 0 .. kRing16-2
-                const int nb_full = (nb / kRing16) * kRing16;
-                static_assert(kRing16 % 2 == 0, "the B double buffer alternates with the parity of the block in the group");
-                float4 bE = loadB16(0), bO;      // even / odd blocks
-                for (int tt = 0; tt < nb_full; tt += kRing16) {
-#pragma unroll
-                    for (int u = 0; u < kRing16; ++u) {
-                        const int t = tt + u;
-                        {
-                            const int off = min(t + kRing16 - 1, nb - 1) * 1024;
-                            ring[(u + kRing16 - 1) % kRing16][0] = ld_w16(rA, lane16, off);
-                            ring[(u + kRing16 - 1) % kRing16][1] = ld_w16(rA, lane16, o1 + off);
-                            ring[(u + kRing16 - 1) % kRing16][2] = ld_w16(rA, lane16, o2 + off);
-                            ring[(u + kRing16 - 1) % kRing16][3] = ld_w16(rA, lane16, o3 + off);
-                        }
-                        // keep the four loads HERE: left to itself hipcc sinks them below this block's MFMAs (their
-                        // destination registers double as MFMA temporaries), which halves the bytes in flight
-                        if (u & 1) bE = loadB16(t + 1); else bO = loadB16(t + 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (u & 1) block16(bO, ring[u]); else block16(bE, ring[u]);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < kRing16 - 1; ++u)      // (nb_full is even: block nb_full + u has the parity of u)
-                    if (nb_full + u < nb) {
-                        if (u & 1) { bE = loadB16(nb_full + u + 1); block16(bO, ring[u]); }
-                        else { bO = loadB16(nb_full + u + 1); block16(bE, ring[u]); }
-                    }
-            }
-            // request the next layer's first blocks now: they travel while this layer's epilogue and the two
-            // barriers run (weights do not depend on the activations)
-            if (li + 1 < net.n_layers && !(li + 1 == net.n_layers - 1 && out_cols == 1)) {
-                if (2 * net.layer[li + 1].n_tiles - 4 * wave > 0) {
-                    prefetch16(li + 1);
-                    ring_ready = true;
-                }
-            }
-            if (li == 0) __syncthreads();   // (layer 0 only: its epilogue rescales EMB in place, which every wave has read)
-            const bool act = Ly.activation != 0;
-            const bool div = Ly.post_div_sqrt2 != 0;
-            const float sqrt2 = 1.41421356237309515f;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                if (a >= ntw) continue;
-                const int f = 16 * (u0 + a) + 4 * q;
-                const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
-                float v0 = acc[a][0] + bb.x, v1 = acc[a][1] + bb.y, v2 = acc[a][2] + bb.z, v3 = acc[a][3] + bb.w;
-                if (act) {
-                    softplus100_4(v0, v1, v2, v3);
-                }
-                if (div) {
-                    v0 = __fdiv_rn(v0, sqrt2); v1 = __fdiv_rn(v1, sqrt2); v2 = __fdiv_rn(v2, sqrt2);
-                    v3 = __fdiv_rn(v3, sqrt2);
-                }
-                *reinterpret_cast<float4 *>(Xn + (f >> 2) * kGroupFloats16 + j * 4) = make_float4(v0, v1, v2, v3);
-            }
-            if (li == 0) {
-                for (int i = tid; i < emb_groups16 * kGroupFloats16; i += kThreadsSdf) EMB[i] = __fdiv_rn(EMB[i], sqrt2);
-            }
-            __syncthreads();
-            { float *t_ = X; X = Xn; Xn = t_; }
-        }
-
-        const hm_mlp_layer &last = net.layer[net.n_layers - 1];
-        if (out_cols != 1) {
-            const int od = last.out_dim;
-            for (int i = tid; i < cnt * od; i += kThreadsSdf) {
-                const int p = i / od, f = i - p * od;
-                float v = X[(f >> 2) * kGroupFloats16 + p * 4 + (f & 3)];
-                if (f == 0) v = sdf_clamp(v, net.beta);
-                out[(base + p) * out_stride + f] = v;
-            }
+        for (int a = 0; a < 4; ++a) {
+            if (a >= ntw) continue;
+            const int f = 16 * (u0 + a) + 4 * q;
+            const float4 bb = *reinterpret_cast<const float4 *>(bias + f);
+            float v[4] = {acc[a][0] + bb.x, acc[a][1] + bb.y, acc[a][2] + bb.z, acc[a][3] + bb.w};
+            act_quads(v, act, div);
+            *reinterpret_cast<float4 *>(Xn + (f >> 2) * kGF + j * 4) = make_float4(v[0], v[1], v[2], v[3]);
         }
     }
-}
+    // sdf-only last layer: VALU dot product, lane (point j, quarter q) walks k-groups == q (mod 4); partial sums -> RED
+    __device__ __forceinline__ void last_layer(const hm_mlp_layer &Ly, const float *X, const float *EMB, int wave, int lane,
+                                               float *RED) {
+        const float4 *W0 = reinterpret_cast<const float4 *>(Ly.w_packed_m16);
+        float part = 0.0f;
+        int t0 = 0;
+        for (int seg = 0; seg < 2; ++seg) {
+            const float *src = (Ly.seg_src[seg] == 0) ? X : EMB;
+            const int nbs = Ly.seg_blocks16[seg];
+            for (int t = wave; t < nbs; t += kWaves) {
+                const float4 xv = *reinterpret_cast<const float4 *>(src + (4 * t + q) * kGF + j * 4);
+                const float4 wv = W0[(size_t)(t0 + t) * 64 + q * 16];
+                part = __fmaf_rn(xv.x, wv.x, part);
+                part = __fmaf_rn(xv.y, wv.y, part);
+                part = __fmaf_rn(xv.z, wv.z, part);
+                part = __fmaf_rn(xv.w, wv.w, part);
+            }
+            t0 += nbs;
+        }
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        if (q == 0) RED[wave * kPts16 + j] = part;
+    }
+};
 
-
-// ---------------------------------------------------------------------------------------------------------
 // 8-point tiles for the smallest batches (late sphere-tracing rounds, secant steps: <= 2048 live points).
 // A 16-point tile costs the same MFMA time however few of its points are live (8 x 13.6 us per network on
 // one CU); with 8 points per workgroup the matrix work halves and the call is bound by the weight stream
@@ -664,37 +473,128 @@ __device__ __forceinline__ void sdf_m16_body(const HmLevels &lv, const SdfNet &n
 // and block (q, j / 4) accumulates, for its four features and four points, the partial sum over the k of
 // quarter q; the four quarters are added with two lane exchanges at the end of the layer, which also hand
 // each lane exactly one (feature quad, point) of the next layer's X image.
-constexpr int kPts8 = 8;
-constexpr int kRing8 = 5;    // weight ring depth of the 8-point body (k-blocks)
-constexpr int kGroupFloats8 = kPts8 * 4;
-
 // PTS = 8: two point groups per tile; PTS = 4: one (<= 1024 live points: the second group's MFMAs are skipped,
 // the LDS image keeps its 8-point stride)
-template <int FRAC, int PTS>
-__device__ __forceinline__ void sdf_m8_body(const HmLevels &lv, const SdfNet &net, const float *__restrict__ x,
-                                            int64_t n, const float *__restrict__ table,
-                                            const float *__restrict__ Bf, float *__restrict__ out,
-                                            int64_t out_stride, int out_cols, float *lds, int64_t tile_first,
-                                            int64_t tile_step) {
+template <int PTS>
+struct Tile8 {
+    // (a ring one block deeper for the 4-point variant measured the same: 94 vs 93 us)
+    static constexpr int kTile = PTS, kStride = kPts8, kDepth = kRing8, kGF = 32;
+    static constexpr bool TWO = PTS == 8;
+    int q, jj, p4;            // k quarter of the A operand; feature quad within the 16-feature tile; point within a group of four
+    f32x4 acc0[4], acc1[4];   // points 0-3 / 4-7
+    f32x4 r0, r1;             // the lane's complete sums after reduce()
+    __device__ __forceinline__ Tile8(int lane) : q(lane >> 4), jj((lane & 15) >> 2), p4(lane & 3) {}
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            acc0[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            acc1[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    }
+    __device__ __forceinline__ void products(WeightRing<kDepth, 4> &ring, const __amdgpu_buffer_rsrc_t &rA,
+                                             const int (&so)[4], int nb, int nb0, const float *src0, const float *src1) {
+        ring.run(rA, so, nb, no_pre, [&](int t, int, const float4 (&w)[4]) {
+            const float *src = (t < nb0) ? src0 + (4 * t + q) * kGF : src1 + (4 * (t - nb0) + q) * kGF;
+            const float4 b0 = *reinterpret_cast<const float4 *>(src + p4 * 4);
+            const float4 b1 = TWO ? *reinterpret_cast<const float4 *>(src + (p4 + 4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const float4 av = w[a];
+                acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b0.x, acc0[a], 0, 0, 0);
+                if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b1.x, acc1[a], 0, 0, 0);
+                acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b0.y, acc0[a], 0, 0, 0);
+                if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b1.y, acc1[a], 0, 0, 0);
+                acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b0.z, acc0[a], 0, 0, 0);
+                if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b1.z, acc1[a], 0, 0, 0);
+                acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b0.w, acc0[a], 0, 0, 0);
+                if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b1.w, acc1[a], 0, 0, 0);
+            }
+        });
+    }
+    // add the four k quarters; lane q ends up with the complete sums of feature tile a == q
+    // (exchange across lane bit 5 keeps tiles {0,1} or {2,3}, across bit 4 keeps one of the pair)
+    __device__ __forceinline__ void reduce() {
+        const bool hi2 = (q & 2) != 0, hi1 = (q & 1) != 0;
+        f32x4 k0[2], k1[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float keep0 = hi2 ? acc0[a + 2][r] : acc0[a][r], send0 = hi2 ? acc0[a][r] : acc0[a + 2][r];
+                const float keep1 = hi2 ? acc1[a + 2][r] : acc1[a][r], send1 = hi2 ? acc1[a][r] : acc1[a + 2][r];
+                k0[a][r] = keep0 + __shfl_xor(send0, 32);
+                k1[a][r] = TWO ? keep1 + __shfl_xor(send1, 32) : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float keep0 = hi1 ? k0[1][r] : k0[0][r], send0 = hi1 ? k0[0][r] : k0[1][r];
+            const float keep1 = hi1 ? k1[1][r] : k1[0][r], send1 = hi1 ? k1[0][r] : k1[1][r];
+            r0[r] = keep0 + __shfl_xor(send0, 16);
+            r1[r] = TWO ? keep1 + __shfl_xor(send1, 16) : 0.0f;
+        }
+    }
+    __device__ __forceinline__ void epilogue(const float *__restrict__ bias, int u0, int ntw, bool act, bool div, float *Xn) {
+        if (q < ntw) {
+            const int f = 16 * (u0 + q) + 4 * jj;
+            const float4 bb = *reinterpret_cast<const float4 *>(bias + f);
+            float v[8] = {r0[0] + bb.x, r0[1] + bb.y, r0[2] + bb.z, r0[3] + bb.w,
+                          r1[0] + bb.x, r1[1] + bb.y, r1[2] + bb.z, r1[3] + bb.w};
+            act_quads(v, act, div);
+            float *dst = Xn + (f >> 2) * kGF;
+            *reinterpret_cast<float4 *>(dst + p4 * 4) = make_float4(v[0], v[1], v[2], v[3]);
+            if (TWO) *reinterpret_cast<float4 *>(dst + (p4 + 4) * 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+    }
+    // sdf-only last layer: VALU dot product.  lane -> (point, k quarter, block parity); partial sums -> RED
+    __device__ __forceinline__ void last_layer(const hm_mlp_layer &Ly, const float *X, const float *EMB, int wave, int lane,
+                                               float *RED) {
+        const float4 *W0 = reinterpret_cast<const float4 *>(Ly.w_packed_m16);
+        const int pp = lane & 7, qq = (lane >> 3) & 3, th = lane >> 5;
+        float part = 0.0f;
+        int t0 = 0;
+        for (int seg = 0; seg < 2; ++seg) {
+            const float *src = (Ly.seg_src[seg] == 0) ? X : EMB;
+            const int nbs = Ly.seg_blocks16[seg];
+            for (int t = 2 * wave + th; t < nbs; t += 2 * kWaves) {
+                const float4 xv = *reinterpret_cast<const float4 *>(src + (4 * t + qq) * kGF + pp * 4);
+                const float4 wv = W0[(size_t)(t0 + t) * 64 + qq * 16];
+                part = __fmaf_rn(xv.x, wv.x, part);
+                part = __fmaf_rn(xv.y, wv.y, part);
+                part = __fmaf_rn(xv.z, wv.z, part);
+                part = __fmaf_rn(xv.w, wv.w, part);
+            }
+            t0 += nbs;
+        }
+        part += __shfl_xor(part, 8);
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        if (lane < kPts8) RED[wave * kPts8 + lane] = part;
+    }
+};
+
+template <int FRAC, class Tile>
+__device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet &net, const float *__restrict__ x,
+                                               int64_t n, const float *__restrict__ table,
+                                               const float *__restrict__ Bf, float *__restrict__ out,
+                                               int64_t out_stride, int out_cols, float *lds, int64_t tile_first,
+                                               int64_t tile_step) {
+    constexpr int PTS = Tile::kTile, ST = Tile::kStride, GF = Tile::kGF;   // live points; points / floats per k-group of the LDS image
     const int emb_groups16 = ((lv.E + 15) / 16) * 4;
     // two activation images, used alternately (layer l reads one, its epilogue writes the other): no barrier between a
     // layer's k-loop and its epilogue - a wave that finishes early does not wait for the others before its Softplus
+    const SdfLds at = sdf_lds_small(net, lv.E, ST);
     float *X0 = lds;
-    float *X1 = lds + (size_t)net.x_groups * kGroupFloats8;
-    float *EMB = X1 + (size_t)net.x_groups * kGroupFloats8;
-    float *SX = EMB + (size_t)emb_groups16 * kGroupFloats8;  // [8][3] (+ pad)
-    float *RED = SX + kPts8 * 4;                              // [8 waves][8 points]
+    float *X1 = lds + at.x1;
+    float *EMB = lds + at.emb;
+    float *SX = lds + at.sx;     // [ST][3] (+ pad)
+    float *RED = lds + at.red;   // [8 waves][ST]
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: descriptors / scalar offsets of the weight stream)
     const int lane = tid & 63;
-    const int lane16 = lane * 16;
-    const int q = lane >> 4;         // k quarter of the A operand
-    const int jj = (lane & 15) >> 2; // feature quad within the 16-feature tile
-    const int p4 = lane & 3;         // point within a group of four
     const int E = lv.E;
-    constexpr bool TWO = PTS == 8;
-    constexpr int RD8 = kRing8;   // (one block deeper for the 4-point variant measured the same: 94 vs 93 us)
+    Tile tl(lane);
     const int64_t n_tiles = (n + PTS - 1) / PTS;
 
     for (int64_t tile = tile_first; tile < n_tiles; tile += tile_step) {
@@ -703,185 +603,72 @@ __device__ __forceinline__ void sdf_m8_body(const HmLevels &lv, const SdfNet &ne
         HM_PROBE_S(0);
         float *X = X0, *Xn = X1;     // X: the image the current layer reads; Xn: the one its epilogue fills
         __syncthreads();
-        if (FRAC != kFracEmb && tid < kPts8 * 3) SX[tid] = (tid < cnt * 3) ? x[base * 3 + tid] : 0.0f;
+        load_points(FRAC != kFracEmb, SX, x, base, cnt, ST, tid);
         __syncthreads();
 
-        // ---- encode: thread -> (point p, slot c0); 64 slots cover channels / levels
+        // ---- encode: thread -> (point p, slot c0); 512 / ST slots cover channels / levels
         if constexpr (FRAC == kFracEmb) {
-            load_emb_tile(EMB, x, net.emb_stride, base, cnt, E, emb_groups16, PTS, kGroupFloats8, tid, kThreadsSdf);
+            load_emb_tile(EMB, x, net.emb_stride, base, cnt, E, emb_groups16, PTS, GF, tid, kThreadsSdf);
         } else {
-            const int p = tid & (kPts8 - 1);
-            const int c0 = tid >> 3;  // 0..63
+            const int p = tid & (ST - 1);
+            const int c0 = tid / ST;
             const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, c0, 64, emb_groups16 * 4,
-                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats8 + p * 4 + (e & 3)] = v; });
+            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, c0, kThreadsSdf / ST, emb_groups16 * 4,
+                              [&](int e, float v) { EMB[(e >> 2) * GF + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
         HM_PROBE_S(1);
 
-        float4 ring[RD8][4];
+        // weight ring (WeightRing, hm_sdf_common.h); streams: the wave's four 16-feature tiles, clamped to the live ones
+        WeightRing<Tile::kDepth, 4> ring;
+        ring.voff = lane * 16;
         bool ring_ready = false;
-        auto prefetch8 = [&](int l) {
+        auto prefetch = [&](int l) {
             const hm_mlp_layer &Lp = net.layer[l];
             const int nbp = Lp.seg_blocks16[0] + Lp.seg_blocks16[1];
             const int ntp = max(0, min(4, Lp.n_tiles * 2 - 4 * wave));
             const __amdgpu_buffer_rsrc_t rp = w_rsrc(Lp.w_packed_m16 + ((size_t)(4 * wave) * nbp) * 256);
             const int ts = nbp * 1024;     // bytes to the next feature tile
-            const int p1 = (1 < ntp ? 1 : 0) * ts, p2 = (2 < ntp ? 2 : 0) * ts, p3 = (3 < ntp ? 3 : 0) * ts;
-#pragma unroll
-            for (int st = 0; st < RD8 - 1; ++st) {
-                const int off = min(st, nbp - 1) * 1024;
-                ring[st][0] = ld_w16(rp, lane16, off); ring[st][1] = ld_w16(rp, lane16, p1 + off);
-                ring[st][2] = ld_w16(rp, lane16, p2 + off); ring[st][3] = ld_w16(rp, lane16, p3 + off);
-            }
+            const int so[4] = {0, (1 < ntp ? 1 : 0) * ts, (2 < ntp ? 2 : 0) * ts, (3 < ntp ? 3 : 0) * ts};
+            ring.fill(rp, so, nbp);
         };
         for (int li = 0; li < net.n_layers; ++li) {
             const hm_mlp_layer &Ly = net.layer[li];
-            const int nb = Ly.seg_blocks16[0] + Ly.seg_blocks16[1];  // 16-wide k blocks
             if (li == net.n_layers - 1 && out_cols == 1) {
-                // sdf-only last layer: VALU dot product.  lane -> (point, k quarter, block parity)
-                const float4 *W0 = reinterpret_cast<const float4 *>(Ly.w_packed_m16);
-                const int pp = lane & 7, qq = (lane >> 3) & 3, th = lane >> 5;
-                float part = 0.0f;
-                int t0 = 0;
-                for (int seg = 0; seg < 2; ++seg) {
-                    const float *src = (Ly.seg_src[seg] == 0) ? X : EMB;
-                    const int nbs = Ly.seg_blocks16[seg];
-                    for (int t = 2 * wave + th; t < nbs; t += 2 * kWaves) {
-                        const float4 xv = *reinterpret_cast<const float4 *>(src + (4 * t + qq) * kGroupFloats8 + pp * 4);
-                        const float4 wv = W0[(size_t)(t0 + t) * 64 + qq * 16];
-                        part = __fmaf_rn(xv.x, wv.x, part);
-                        part = __fmaf_rn(xv.y, wv.y, part);
-                        part = __fmaf_rn(xv.z, wv.z, part);
-                        part = __fmaf_rn(xv.w, wv.w, part);
-                    }
-                    t0 += nbs;
-                }
-                part += __shfl_xor(part, 8);
-                part += __shfl_xor(part, 16);
-                part += __shfl_xor(part, 32);
-                if (lane < kPts8) RED[wave * kPts8 + lane] = part;
-                __syncthreads();
-                if (tid < cnt) {
-                    float sacc = Ly.bias[0];
-                    for (int w8 = 0; w8 < kWaves; ++w8) sacc += RED[w8 * kPts8 + tid];
-                    out[(base + tid) * out_stride] = sdf_clamp(sacc, net.beta);
-                }
+                tl.last_layer(Ly, X, EMB, wave, lane, RED);
+                sdf_last_finish(RED, kWaves, ST, cnt, Ly.bias, net.beta, out, base, out_stride, tid);
                 break;
             }
+            const int nb = Ly.seg_blocks16[0] + Ly.seg_blocks16[1];  // 16-wide k blocks
             const int nt16 = Ly.n_tiles * 2;
             const int u0 = 4 * wave;
             const int ntw = max(0, min(4, nt16 - u0));
-            f32x4 acc0[4], acc1[4];   // points 0-3 / 4-7
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                acc0[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                acc1[a] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            }
+            tl.zero();
             if (ntw > 0) {
                 const __amdgpu_buffer_rsrc_t rA = w_rsrc(Ly.w_packed_m16 + ((size_t)u0 * nb) * 256);
-                const int tstride = nb * 1024;
-                const int o1 = (1 < ntw ? 1 : 0) * tstride, o2 = (2 < ntw ? 2 : 0) * tstride,
-                          o3 = (3 < ntw ? 3 : 0) * tstride;
-                const int nb0 = Ly.seg_blocks16[0];
+                const int tstride = nb * 1024;  // bytes to the next feature tile
+                const int so[4] = {0, (1 < ntw ? 1 : 0) * tstride, (2 < ntw ? 2 : 0) * tstride, (3 < ntw ? 3 : 0) * tstride};
                 const float *src0 = (Ly.seg_src[0] == 0) ? X : EMB;
                 const float *src1 = (Ly.seg_src[1] == 0) ? X : EMB;
-                if (!ring_ready) prefetch8(li);
+                if (!ring_ready) prefetch(li);
                 ring_ready = false;
-                auto block8 = [&](int t, const float4 (&w)[4]) {
-                    const float *src = (t < nb0) ? src0 + (4 * t + q) * kGroupFloats8
-                                                 : src1 + (4 * (t - nb0) + q) * kGroupFloats8;
-                    const float4 b0 = *reinterpret_cast<const float4 *>(src + p4 * 4);
-                    const float4 b1 = TWO ? *reinterpret_cast<const float4 *>(src + (p4 + 4) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        const float4 av = w[a];
-                        acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b0.x, acc0[a], 0, 0, 0);
-                        if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.x, b1.x, acc1[a], 0, 0, 0);
-                        acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b0.y, acc0[a], 0, 0, 0);
-                        if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.y, b1.y, acc1[a], 0, 0, 0);
-                        acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b0.z, acc0[a], 0, 0, 0);
-                        if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.z, b1.z, acc1[a], 0, 0, 0);
-                        acc0[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b0.w, acc0[a], 0, 0, 0);
-                        if (TWO) acc1[a] = __builtin_amdgcn_mfma_f32_4x4x1f32(av.w, b1.w, acc1[a], 0, 0, 0);
-                    }
-                };
-                const int nb_full = (nb / RD8) * RD8;   // (no exit test inside the unrolled group: see the 16-point body)
-                for (int tt = 0; tt < nb_full; tt += RD8) {
-#pragma unroll
-                    for (int u = 0; u < RD8; ++u) {
-                        const int t = tt + u;
-                        {
-                            const int off = min(t + RD8 - 1, nb - 1) * 1024;
-                            ring[(u + RD8 - 1) % RD8][0] = ld_w16(rA, lane16, off);
-                            ring[(u + RD8 - 1) % RD8][1] = ld_w16(rA, lane16, o1 + off);
-                            ring[(u + RD8 - 1) % RD8][2] = ld_w16(rA, lane16, o2 + off);
-                            ring[(u + RD8 - 1) % RD8][3] = ld_w16(rA, lane16, o3 + off);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);   // loads stay ahead of this block's MFMAs
-                        block8(t, ring[u]);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < RD8 - 1; ++u)
-                    if (nb_full + u < nb) block8(nb_full + u, ring[u]);
+                tl.products(ring, rA, so, nb, Ly.seg_blocks16[0], src0, src1);
             }
+            // request the next layer's first blocks now: they travel while this layer's epilogue and the two
+            // barriers run (weights do not depend on the activations)
             if (li + 1 < net.n_layers && !(li + 1 == net.n_layers - 1 && out_cols == 1)) {
                 if (2 * net.layer[li + 1].n_tiles - 4 * wave > 0) {
-                    prefetch8(li + 1);
+                    prefetch(li + 1);
                     ring_ready = true;
                 }
             }
             HM_PROBE_S(2 + 4 * li);
-            // add the four k quarters; lane q ends up with the complete sums of feature tile a == q
-            // (exchange across lane bit 5 keeps tiles {0,1} or {2,3}, across bit 4 keeps one of the pair)
-            f32x4 r0, r1;
-            {
-                const bool hi2 = (q & 2) != 0, hi1 = (q & 1) != 0;
-                f32x4 k0[2], k1[2];
-#pragma unroll
-                for (int a = 0; a < 2; ++a) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float keep0 = hi2 ? acc0[a + 2][r] : acc0[a][r], send0 = hi2 ? acc0[a][r] : acc0[a + 2][r];
-                        const float keep1 = hi2 ? acc1[a + 2][r] : acc1[a][r], send1 = hi2 ? acc1[a][r] : acc1[a + 2][r];
-                        k0[a][r] = keep0 + __shfl_xor(send0, 32);
-                        k1[a][r] = TWO ? keep1 + __shfl_xor(send1, 32) : 0.0f;
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float keep0 = hi1 ? k0[1][r] : k0[0][r], send0 = hi1 ? k0[0][r] : k0[1][r];
-                    const float keep1 = hi1 ? k1[1][r] : k1[0][r], send1 = hi1 ? k1[0][r] : k1[1][r];
-                    r0[r] = keep0 + __shfl_xor(send0, 16);
-                    r1[r] = TWO ? keep1 + __shfl_xor(send1, 16) : 0.0f;
-                }
-            }
+            tl.reduce();
             HM_PROBE_S(3 + 4 * li);
             if (li == 0) __syncthreads();   // (layer 0 only: its epilogue rescales EMB in place, which every wave has read)
             HM_PROBE_S(4 + 4 * li);
-            const bool act = Ly.activation != 0;
-            const bool div = Ly.post_div_sqrt2 != 0;
-            const float sqrt2 = 1.41421356237309515f;
-            if (q < ntw) {
-                const int f = 16 * (u0 + q) + 4 * jj;
-                const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
-                float v[8] = {r0[0] + bb.x, r0[1] + bb.y, r0[2] + bb.z, r0[3] + bb.w,
-                              r1[0] + bb.x, r1[1] + bb.y, r1[2] + bb.z, r1[3] + bb.w};
-                if (act) {
-                    softplus100_4(v[0], v[1], v[2], v[3]);
-                    softplus100_4(v[4], v[5], v[6], v[7]);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (div) v[i] = __fdiv_rn(v[i], sqrt2);
-                float *dst = Xn + (f >> 2) * kGroupFloats8;
-                *reinterpret_cast<float4 *>(dst + p4 * 4) = make_float4(v[0], v[1], v[2], v[3]);
-                if (TWO) *reinterpret_cast<float4 *>(dst + (p4 + 4) * 4) = make_float4(v[4], v[5], v[6], v[7]);
-            }
-            if (li == 0) {
-                for (int i = tid; i < emb_groups16 * kGroupFloats8; i += kThreadsSdf) EMB[i] = __fdiv_rn(EMB[i], sqrt2);
-            }
+            tl.epilogue(Ly.bias, u0, ntw, Ly.activation != 0, Ly.post_div_sqrt2 != 0, Xn);
+            if (li == 0) rescale_emb(EMB, emb_groups16 * GF, tid, kThreadsSdf);
             __syncthreads();
             { float *t_ = X; X = Xn; Xn = t_; }
             HM_PROBE_S(5 + 4 * li);
@@ -889,15 +676,7 @@ __device__ __forceinline__ void sdf_m8_body(const HmLevels &lv, const SdfNet &ne
         HM_PROBE_S(100);
 
         const hm_mlp_layer &last = net.layer[net.n_layers - 1];
-        if (out_cols != 1) {
-            const int od = last.out_dim;
-            for (int i = tid; i < cnt * od; i += kThreadsSdf) {
-                const int p = i / od, f = i - p * od;
-                float v = X[(f >> 2) * kGroupFloats8 + p * 4 + (f & 3)];
-                if (f == 0) v = sdf_clamp(v, net.beta);
-                out[(base + p) * out_stride + f] = v;
-            }
-        }
+        if (out_cols != 1) store_rows(X, GF, cnt, last.out_dim, net.beta, out, base, out_stride, tid, kThreadsSdf);
     }
 }
 
@@ -915,11 +694,11 @@ __global__ __launch_bounds__(kThreadsSdf, 1) void sdf_fwd_small_kernel(HmLevels 
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));
     if (n < run_min || n > run_max) return;
     if (n <= m4_max)
-        sdf_m8_body<FRAC, 4>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, blockIdx.x, gridDim.x);
+        sdf_small_body<FRAC, Tile8<4>>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, blockIdx.x, gridDim.x);
     else if (n <= m8_max)
-        sdf_m8_body<FRAC, 8>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, blockIdx.x, gridDim.x);
+        sdf_small_body<FRAC, Tile8<8>>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, blockIdx.x, gridDim.x);
     else
-        sdf_m16_body<FRAC>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, blockIdx.x, gridDim.x);
+        sdf_small_body<FRAC, Tile16>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -977,11 +756,11 @@ __global__ __launch_bounds__(kThreadsSdf, 1) void trace_march_tail_kernel(HmLeve
         // 16-point body always - bit-identical to hm_sdf_fwd with 16-point tiles, how the tests compare this kernel
         // with the generic tracer.  (With the three bodies inlined the kernel spills ~60 VGPRs, none inside an MFMA loop.)
         if (n_loc <= 4 && !body16)
-            sdf_m8_body<FRAC, 4>(lv, net, xp, n_loc, table, Bf, vp, 1, 1, lds, 0, 1 << 30);
+            sdf_small_body<FRAC, Tile8<4>>(lv, net, xp, n_loc, table, Bf, vp, 1, 1, lds, 0, 1 << 30);
         else if (n_loc <= 8 && !body16)
-            sdf_m8_body<FRAC, 8>(lv, net, xp, n_loc, table, Bf, vp, 1, 1, lds, 0, 1 << 30);
+            sdf_small_body<FRAC, Tile8<8>>(lv, net, xp, n_loc, table, Bf, vp, 1, 1, lds, 0, 1 << 30);
         else
-            sdf_m16_body<FRAC>(lv, net, xp, n_loc, table, Bf, vp, 1, 1, lds, 0, 1 << 30);
+            sdf_small_body<FRAC, Tile16>(lv, net, xp, n_loc, table, Bf, vp, 1, 1, lds, 0, 1 << 30);
         __syncthreads();            // the values (global stores of this workgroup) are visible to its threads
         if (tid == 0) ctl[0] = 0;
         __syncthreads();
@@ -1023,11 +802,11 @@ __device__ __forceinline__ void secant_role(const HmLevels &lv, const SdfNet &ne
     const int64_t n_tiles = (n + pts - 1) / pts;
     for (int it = 0; it < n_iters; ++it) {
         if (pts == 4)
-            sdf_m8_body<FRAC, 4>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
+            sdf_small_body<FRAC, Tile8<4>>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
         else if (pts == 8)
-            sdf_m8_body<FRAC, 8>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
+            sdf_small_body<FRAC, Tile8<8>>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
         else
-            sdf_m16_body<FRAC>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
+            sdf_small_body<FRAC, Tile16>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
         __syncthreads();       // the tile's values (global stores of this workgroup) are visible to its threads
         for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
             const int64_t q = tile * pts + threadIdx.x;
@@ -1092,15 +871,6 @@ static int sdf_net_fp32(const char *who, const HmLevels &lv, const hm_mlp_desc *
     return sdf_net_from_desc(who, mlp, lv.E, emb_stride, img, 1, (lv.E + 7) / 8 * 2, false, net, all_m16);
 }
 
-// dynamic LDS of the 16-point tile bodies: two activation images + the embedding (the 8-point layout needs half of it)
-static size_t sdf_lds16(const SdfNet &net, int E) {
-    return sizeof(float) * ((size_t)(2 * net.x_groups + (E + 15) / 16 * 4) * kGroupFloats16 + kPts16 * 4 +
-                            kWaves * kPts16);
-}
-// dynamic LDS of the 64-point tile
-static size_t sdf_lds64(const SdfNet &net) {
-    return sizeof(float) * ((size_t)(net.x_groups + net.emb_groups) * kGroupFloats + kPts * 4 + kWaves * kPts);
-}
 // LDS limits of the small-tile (16 / 8 / 4-point) and 64-point launches; the tracer's persistent kernels keep 64 bytes of
 // their own on top of the tile
 constexpr size_t kLds16Max = 96 * 1024, kLds64Max = 160 * 1024, kLdsTrace = 64;
@@ -1114,8 +884,8 @@ static int sdf_fp32_fits(const hm_mlp_desc *mlp, int E) {
     bool have16 = true;
     const int rc = sdf_net_fp32("hm_sdf_net_fits", lv, mlp, 0, kImgM16Optional, net, &have16);
     if (rc != HM_OK) return rc;
-    HM_CHECK_ARG(sdf_lds64(net) + kLdsTrace <= kLds64Max, "hm_sdf_net_fits: network does not fit the 160 KB LDS tile");
-    HM_CHECK_ARG(!have16 || sdf_lds16(net, E) + kLdsTrace <= kLds16Max,
+    HM_CHECK_ARG(sdf_lds64(net).bytes() + kLdsTrace <= kLds64Max, "hm_sdf_net_fits: network does not fit the 160 KB LDS tile");
+    HM_CHECK_ARG(!have16 || sdf_lds_small(net, E, kPts16).bytes() + kLdsTrace <= kLds16Max,
                  "hm_sdf_net_fits: network does not fit the 16-point LDS tile");
     return HM_OK;
 }
@@ -1169,8 +939,8 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
                         int frac_mode, int tile_points, const int32_t *n_dev, int max_workgroups, void *stream,
                         const SdfFillArgs *fill = nullptr, int *grid64_out = nullptr);
 // hm_sdf_bf16.hip / hm_sdf_split.hip: the network and LDS checks of their launches (hm_sdf_net_fits)
-int sdf_bf16_fits(const hm_mlp_desc *mlp, int E);
-int sdf_split_fits(const hm_mlp_desc *mlp, int E);
+int sdf_bf16_fits(const hm_mlp_desc *mlp, int E, int32_t *regions);
+int sdf_split_fits(const hm_mlp_desc *mlp, int E, int32_t *regions);
 
 // hm_sdf_fwd for the ray search's sampler launches (not exported): the 64-point launch completes its last round with
 // tiles of a second point set (fill_quota; x_fill / out_fill / n_fill_dev: the closest-approach scan's points, values and
@@ -1200,9 +970,9 @@ int hm_sdf_fwd_emb(const hm_mlp_desc *mlp, const float *emb, int64_t emb_stride,
                    int64_t out_stride, int out_cols, int tile_points, const int32_t *n_dev, int max_workgroups,
                    void *stream) {
     HM_CHECK_ARG(mlp, "hm_sdf_fwd_emb: NULL descriptor");
-    HM_CHECK_ARG(emb_width >= 1 && emb_width <= 512 && emb_stride >= emb_width, "hm_sdf_fwd_emb: bad embedding width / stride");
-    HmLevels lv = {};
-    lv.L = 0; lv.F = 2; lv.E = emb_width;
+    HmLevels lv;
+    const int rc = sdf_emb_levels("hm_sdf_fwd_emb", emb_width, emb_stride, lv);
+    if (rc != HM_OK) return rc;
     return sdf_fwd_impl(lv, mlp, emb, emb_stride, n, nullptr, nullptr, out, out_stride, out_cols, HM_FRAC_REFERENCE,
                         tile_points, n_dev, max_workgroups, stream);
 }
@@ -1220,7 +990,7 @@ int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const 
     if (rc != HM_OK) return rc;
     if (a.n == 0 || first >= rounds) return HM_OK;
     HM_CHECK_ARG(a.w.cap >= ((a.n + 7) / 8) * 16, "hm_trace_march_tail: point buffer too small");
-    const int lds_floats = (int)(sdf_lds16(net, desc->lv.E) / sizeof(float));
+    const int lds_floats = (int)(sdf_lds_small(net, desc->lv.E, kPts16).bytes() / sizeof(float));
     const size_t lds = sizeof(float) * (size_t)lds_floats + kLdsTrace;
     HM_CHECK_ARG(lds <= kLds16Max, "hm_trace_march_tail: network does not fit the 16-point LDS tile");
     const unsigned grid = (unsigned)((a.n + 7) / 8);
@@ -1248,7 +1018,7 @@ int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
     const int rc = sdf_net_fp32("hm_trace_secant_persistent", desc->lv, mlp, 0, kImgM16, net);
     if (rc != HM_OK) return rc;
     if (a.n == 0 || n_iters <= 0) return HM_OK;
-    const size_t lds = sdf_lds16(net, desc->lv.E);
+    const size_t lds = sdf_lds_small(net, desc->lv.E, kPts16).bytes();
     HM_CHECK_ARG(lds <= kLds16Max, "hm_trace_secant_persistent: network does not fit the 16-point LDS tile");
     const SmallTiles t = sdf_small_tiles(tile_points);
     // workgroups for the longest list the call can see (every ray a secant ray), one tile each up to one per CU
@@ -1280,7 +1050,7 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
     rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1, frac_mode,
                     -1, a.w.cnt + C_NSEL_PTS, 0, stream);
     if (rc != HM_OK) return rc;
-    const size_t lds16 = sdf_lds16(net, desc->lv.E), lds64 = sdf_lds64(net);
+    const size_t lds16 = sdf_lds_small(net, desc->lv.E, kPts16).bytes(), lds64 = sdf_lds64(net).bytes();
     HM_CHECK_ARG(lds16 <= kLds16Max && lds64 <= kLds64Max - kLdsTrace, "hm_trace_scan_secant: network does not fit the LDS tiles");
     const size_t lds = lds16 > lds64 ? lds16 : lds64;
     // 16-point secant tiles once the scan keeps the chip busy for longer than their chain takes (8 x 131 us ~ 2.3 rounds
@@ -1323,7 +1093,7 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
                  "hm_sdf_fwd: tile_points 4 / 8 / 16 need w_packed_m16 in every layer");
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(x && out && (emb_stride > 0 || (table && B_fourier)), "hm_sdf_fwd: NULL pointer");
-    // small batches: 16-point tiles spread the call over the whole chip (see sdf_m16_body / sdf_m8_body), 8- and 4-point
+    // small batches: 16-point tiles spread the call over the whole chip (see sdf_small_body), 8- and 4-point
     // tiles below kSdfTiny / kSdfMini live points (one tile per CU), 64-point tiles above kSdfSmall.
     // With a device-side count the host cannot know the batch size: both kernels are enqueued and
     // each returns at once unless the live count falls in its range.
@@ -1341,7 +1111,7 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
     else { run16 = run64 = true; hi16 = kSdfSmall; lo64 = kSdfSmall + 1; }
     const int64_t cap = max_workgroups > 0 ? max_workgroups : 256;  // one resident workgroup per CU
     if (run16) {
-        const size_t lds = sdf_lds16(net, lv.E);
+        const size_t lds = sdf_lds_small(net, lv.E, kPts16).bytes();
         HM_CHECK_ARG(lds <= kLds16Max, "hm_sdf_fwd: network does not fit the 16-point LDS tile");
         const SmallTiles t = sdf_small_tiles(tile_points);
         const unsigned grid = sdf_small_grid(n < hi16 ? n : hi16, t, cap);
@@ -1358,7 +1128,7 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
     }
     // big batches: one 64-point workgroup per CU
     if (run64) {
-        const size_t lds = sdf_lds64(net);
+        const size_t lds = sdf_lds64(net).bytes();
         HM_CHECK_ARG(lds <= kLds64Max, "hm_sdf_fwd: network does not fit the 160 KB LDS tile");
         const int64_t tiles = (n + 31) / 32;      // (up to cap * 32 points: one 32-point half tile per workgroup)
         const int64_t grid = tiles < cap ? tiles : cap;
@@ -1384,9 +1154,24 @@ int hm_sdf_net_fits(const hm_mlp_desc *mlp, int emb_width, int family) {
     HM_CHECK_ARG(mlp && emb_width >= 1 && emb_width <= 512, "hm_sdf_net_fits: bad descriptor or embedding width");
     HM_CHECK_ARG(family == HM_SDF_FP32 || family == HM_SDF_BF16 || family == HM_SDF_SPLIT, "hm_sdf_net_fits: bad family");
     const int rc = family == HM_SDF_FP32   ? sdf_fp32_fits(mlp, emb_width)
-                   : family == HM_SDF_BF16 ? sdf_bf16_fits(mlp, emb_width)
-                                           : sdf_split_fits(mlp, emb_width);
+                   : family == HM_SDF_BF16 ? sdf_bf16_fits(mlp, emb_width, nullptr)
+                                           : sdf_split_fits(mlp, emb_width, nullptr);
     return rc == HM_OK ? 1 : 0;
+}
+
+int hm_diag_sdf_lds(const hm_mlp_desc *mlp, int emb_width, int family, int tile_points, int32_t *regions) {
+    HM_CHECK_ARG(mlp && regions && emb_width >= 1 && emb_width <= 512, "hm_diag_sdf_lds: bad descriptor, embedding width or NULL");
+    if (family == HM_SDF_BF16) return sdf_bf16_fits(mlp, emb_width, regions);
+    if (family == HM_SDF_SPLIT) return sdf_split_fits(mlp, emb_width, regions);
+    HM_CHECK_ARG(family == HM_SDF_FP32 && (tile_points == 64 || tile_points == 16 || tile_points == 8),
+                 "hm_diag_sdf_lds: bad family or tile_points");
+    HmLevels lv = {};
+    lv.E = emb_width;
+    SdfNet net;
+    const int rc = sdf_net_fp32("hm_diag_sdf_lds", lv, mlp, 0, tile_points == 64 ? kImgM16Optional : kImgM16, net);
+    if (rc != HM_OK) return rc;
+    sdf_lds_report(tile_points == 64 ? sdf_lds64(net) : sdf_lds_small(net, emb_width, tile_points), regions);
+    return HM_OK;
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 // mantissas), all accumulators, bias / Softplus, the last layer's dot product and the clamp.  Hidden activations and
 // hidden-layer weights are bf16 (round-to-nearest-even).  The C/D register layout of the two MFMA shapes is the same
 // (row = 8(reg/4) + 4(lane/32) + reg%4, col = lane%32), so both accumulate into the same tiles.
+// Point load, encode, weight stream (WeightRing<4, 2>), quad epilogue, embedding rescale, last-layer finish and the LDS
+// layout (sdf_lds_bf16) are the stages of hm_sdf_common.h.
 #include "hm_common.h"
 
 #include <math.h>
@@ -34,10 +36,10 @@ constexpr int kPT = kPB / 32;      // point tiles per wave (3)
 constexpr int kEmbGF = kPB * 4;    // floats per k-group row of the fp32 embedding image
 constexpr int kXOct = kPB * 8;     // bf16 elements per k-octet row of X
 
-union Frag16 {   // 16 bytes = 8 bf16 = one MFMA operand fragment
-    float4 f;
-    bf16x8 h;
-};
+// dynamic LDS: X as bf16 [x_groups / 2][kPB][8], the fp32 embedding, 5 partial sums per point
+__host__ __device__ inline SdfLds sdf_lds_bf16(const SdfNet &net) {
+    return sdf_lds(kPB, 1, net.x_groups / 2 * kXOct / 2, 1, net.emb_groups * kEmbGF, 5);
+}
 
 template <int FRAC>
 __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, SdfNet net, const float *__restrict__ x,
@@ -49,11 +51,11 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
     extern __shared__ __align__(16) float lds[];
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));
     if (n < run_min || n > run_max) return;
-    __bf16 *X = reinterpret_cast<__bf16 *>(lds);                                   // [x_oct][kPB][8] bf16
-    const int x_oct = net.x_groups / 2;                                           // k-octets of the widest layer
-    float *EMB = lds + (size_t)x_oct * kXOct / 2;                                 // [emb_groups][kPB][4] fp32
-    float *SX = EMB + (size_t)net.emb_groups * kEmbGF;                            // [kPB][3] raw points (+ pad)
-    float *RED = SX + kPB * 4;                                                    // [5][kPB] last-layer partial sums
+    const SdfLds at = sdf_lds_bf16(net);
+    __bf16 *X = reinterpret_cast<__bf16 *>(lds);    // [x_groups / 2][kPB][8] bf16 (k-octets of the widest layer)
+    float *EMB = lds + at.emb;                      // [emb_groups][kPB][4] fp32
+    float *SX = lds + at.sx;                        // [kPB][3] raw points (+ pad)
+    float *RED = lds + at.red;                      // [5][kPB] last-layer partial sums
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: descriptors / scalar offsets of the weight stream)
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
         const int64_t base = tile * kPB;
         const int cnt = (int)min((int64_t)kPB, n - base);
         __syncthreads();
-        if (net.emb_stride == 0 && tid < kPB * 3) SX[tid] = (tid < cnt * 3) ? x[base * 3 + tid] : 0.0f;
+        load_points(net.emb_stride == 0, SX, x, base, cnt, kPB, tid);
         __syncthreads();
 
         // ---------------- embedding -> EMB[(e/4)][p][e%4] (fp32) ------------------------------------------------
@@ -108,12 +110,7 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
                     }
                     RED[sl * kPB + p] = part;
                 }
-                __syncthreads();
-                if (tid < cnt) {
-                    float sacc = Ly.bias[0];
-                    for (int s5 = 0; s5 < 5; ++s5) sacc += RED[s5 * kPB + tid];
-                    out[(base + tid) * out_stride] = sdf_clamp(sacc, net.beta);
-                }
+                sdf_last_finish(RED, 5, kPB, cnt, Ly.bias, net.beta, out, base, out_stride, tid);
                 break;
             }
             const int nt = Ly.n_tiles;
@@ -158,40 +155,20 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
                         //  tile offsets scalar - no address VALU between the MFMAs, hm_sdf_common.h: ld_w16)
                         const __amdgpu_buffer_rsrc_t rA =
                             w_rsrc(reinterpret_cast<const float *>(Ly.w_packed_bf16) + ((size_t)t0 * nb + blk0) * 256);
-                        const int a1 = ntw > 1 ? nb * 1024 : 0, lane16 = lane * 16;
-                        Frag16 r0[4], r1[4];
-#pragma unroll
-                        for (int st = 0; st < 3; ++st) {
-                            const int off = min(st, nbs - 1) * 1024;
-                            r0[st].f = ld_w16(rA, lane16, off);
-                            r1[st].f = ld_w16(rA, lane16, a1 + off);
-                        }
-                        auto block = [&](int t, const Frag16 &a0, const Frag16 &a1) {
+                        const int so[2] = {0, ntw > 1 ? nb * 1024 : 0};   // the wave's two feature tiles
+                        WeightRing<4, 2> ring;
+                        ring.voff = lane * 16;
+                        ring.fill(rA, so, nbs);
+                        ring.run(rA, so, nbs, no_pre, [&](int t, int, const float4 (&w)[2]) {
+                            const bf16x8 a0 = __builtin_bit_cast(bf16x8, w[0]), a1 = __builtin_bit_cast(bf16x8, w[1]);
                             const __bf16 *src = X + (size_t)(2 * t + h) * kXOct;
 #pragma unroll
                             for (int q = 0; q < kPT; ++q) {
                                 const bf16x8 b = *reinterpret_cast<const bf16x8 *>(src + (32 * q + j) * 8);
-                                acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0.h, b, acc[0][q], 0, 0, 0);
-                                acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.h, b, acc[1][q], 0, 0, 0);
+                                acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b, acc[0][q], 0, 0, 0);
+                                acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b, acc[1][q], 0, 0, 0);
                             }
-                        };
-                        const int n_full = nbs & ~3;
-                        for (int tt = 0; tt < n_full; tt += 4) {
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                const int t = tt + u;
-                                {
-                                    const int off = min(t + 3, nbs - 1) * 1024;
-                                    r0[(u + 3) & 3].f = ld_w16(rA, lane16, off);
-                                    r1[(u + 3) & 3].f = ld_w16(rA, lane16, a1 + off);
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
-                                block(t, r0[u], r1[u]);
-                            }
-                        }
-                        if (n_full + 0 < nbs) block(n_full + 0, r0[0], r1[0]);
-                        if (n_full + 1 < nbs) block(n_full + 1, r0[1], r1[1]);
-                        if (n_full + 2 < nbs) block(n_full + 2, r0[2], r1[2]);
+                        });
                     }
                     oct0 += Ly.seg_octets[seg];
                     blk0 += Ly.seg_blocks16[seg];
@@ -202,7 +179,6 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
             // epilogue: registers 4q..4q+3 of a tile = features 8q + 4h + {0..3} -> 4 bf16 of one k-octet of the next layer
             const bool act = Ly.activation != 0;
             const bool div = Ly.post_div_sqrt2 != 0;
-            const float sqrt2 = 1.41421356237309515f;
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 if (a >= ntw) continue;
@@ -213,35 +189,28 @@ __global__ __launch_bounds__(kTB16, 2) void sdf_fwd_bf16_kernel(HmLevels lv, Sdf
                     for (int q = 0; q < 4; ++q) {
                         const int f = fbase + 8 * q + 4 * h;
                         const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
-                        float v0 = acc[a][pt][4 * q + 0] + bb.x, v1 = acc[a][pt][4 * q + 1] + bb.y,
-                              v2 = acc[a][pt][4 * q + 2] + bb.z, v3 = acc[a][pt][4 * q + 3] + bb.w;
-                        if (act) {
-                            softplus100_4(v0, v1, v2, v3);
-                        }
-                        if (div) {
-                            v0 = __fdiv_rn(v0, sqrt2); v1 = __fdiv_rn(v1, sqrt2); v2 = __fdiv_rn(v2, sqrt2);
-                            v3 = __fdiv_rn(v3, sqrt2);
-                        }
+                        float v[4] = {acc[a][pt][4 * q + 0] + bb.x, acc[a][pt][4 * q + 1] + bb.y,
+                                      acc[a][pt][4 * q + 2] + bb.z, acc[a][pt][4 * q + 3] + bb.w};
+                        act_quads(v, act, div);
                         bf16x4 o;
-                        o[0] = (__bf16)v0; o[1] = (__bf16)v1; o[2] = (__bf16)v2; o[3] = (__bf16)v3;
+                        o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
                         *reinterpret_cast<bf16x4 *>(X + (size_t)(f >> 3) * kXOct + (32 * pt + j) * 8 + 4 * h) = o;
                     }
                 }
             }
-            if (li == 0 && net.emb_groups > 0) {
-                // the skip layer consumes cat[x, emb]/sqrt(2): rescale the kept embedding once, in place
-                for (int i = tid; i < net.emb_groups * kEmbGF; i += kTB16) EMB[i] = __fdiv_rn(EMB[i], sqrt2);
-            }
+            if (li == 0 && net.emb_groups > 0) rescale_emb(EMB, net.emb_groups * kEmbGF, tid, kTB16);
             __syncthreads();
         }
     }
 }
 
 // the network and LDS checks of every launch of this kernel (hm_sdf_net_fits asks the same): *lds = its dynamic LDS
-static int sdf_bf16_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, size_t *lds) {
+static int sdf_bf16_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, size_t *lds,
+                        int32_t *regions = nullptr) {
     const int rc = sdf_net_from_desc(who, mlp, E, emb_stride, kImgBf16, 2, (E + 7) / 8 * 2, true, net);
     if (rc != HM_OK) return rc;
-    *lds = (size_t)(net.x_groups / 2) * kXOct * 2 + sizeof(float) * ((size_t)net.emb_groups * kEmbGF + kPB * 4 + 5 * kPB);
+    *lds = sdf_lds_bf16(net).bytes();
+    if (regions) sdf_lds_report(sdf_lds_bf16(net), regions);
     if (*lds > 160 * 1024) return hm_fail(HM_ERR_INVALID, std::string(who) + ": network does not fit the 160 KB LDS tile");
     return HM_OK;
 }
@@ -275,11 +244,11 @@ static int sdf_bf16_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float
 
 extern "C" {
 
-// (internal: hm_sdf_net_fits, HM_SDF_BF16)
-int sdf_bf16_fits(const hm_mlp_desc *mlp, int E) {
+// (internal: hm_sdf_net_fits / hm_diag_sdf_lds, HM_SDF_BF16; regions may be NULL)
+int sdf_bf16_fits(const hm_mlp_desc *mlp, int E, int32_t *regions) {
     SdfNet net;
     size_t lds = 0;
-    return sdf_bf16_net("hm_sdf_net_fits", E, mlp, 0, net, &lds);
+    return sdf_bf16_net("hm_sdf_net_fits", E, mlp, 0, net, &lds, regions);
 }
 
 int hm_sdf_fwd_bf16(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n, const float *table,
@@ -291,9 +260,9 @@ int hm_sdf_fwd_bf16(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const floa
 
 int hm_sdf_fwd_emb_bf16(const hm_mlp_desc *mlp, const float *emb, int64_t emb_stride, int emb_width, int64_t n,
                         float *out, int64_t out_stride, const int32_t *n_dev, int64_t run_min, void *stream) {
-    HM_CHECK_ARG(emb_width >= 1 && emb_width <= 512 && emb_stride >= emb_width, "hm_sdf_fwd_emb_bf16: bad embedding width / stride");
-    HmLevels lv = {};
-    lv.L = 0; lv.F = 2; lv.E = emb_width;
+    HmLevels lv;
+    const int rc = sdf_emb_levels("hm_sdf_fwd_emb_bf16", emb_width, emb_stride, lv);
+    if (rc != HM_OK) return rc;
     return sdf_bf16_impl(lv, mlp, emb, emb_stride, n, nullptr, nullptr, out, out_stride, HM_FRAC_REFERENCE, n_dev,
                          run_min, stream);
 }

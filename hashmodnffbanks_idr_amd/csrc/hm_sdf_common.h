@@ -25,6 +25,82 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t w_rsrc(const float *base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7fffffff, 0x00020000);
 }
 
+// Weight stream of a layer: a register ring of D slots over the blocks (BLK bytes apart) of a packed image, S 16-byte
+// loads per block at the scalar offsets so[0..S) (the wave's feature tiles, or the hi / lo parts of the split image).
+// D - 1 blocks are in flight.  fill() requests blocks 0 .. D-2 (for layer l + 1 before layer l's epilogue: weights do not
+// depend on the activations, so the stream does not restart from an empty pipe behind the barriers of every layer);
+// run() requests block t + D - 1 into the slot block t - 1 left, calls pre(t, u) - the hook where a body requests the LDS
+// operands of block t + 1 - and runs body(t, u, slot of block t) for every block; u = t mod D is a constant after unrolling.
+//   * Every load is unconditional with a clamped block index, so that hipcc emits counted vmcnt waits instead of
+//     draining the ring per block.
+//   * Whole groups of D blocks run without an exit test: with a `break` inside the unrolled group hipcc cannot count the
+//     loads in flight across the back edge and drains them (vmcnt(0)) at every loop head.  The 1 .. D-1 left-over blocks
+//     are already in slots 0 .. D-2.
+//   * The loads stay above the scheduling barrier: left to itself hipcc sinks them below the block's MFMAs (their
+//     destination registers double as MFMA temporaries), which halves the bytes in flight.
+template <int D, int S, int BLK = 1024>
+struct WeightRing {
+    float4 slot[D][S];
+    int voff;   // lane * 16: the one loop-invariant VGPR offset (ld_w16)
+    __device__ __forceinline__ void load(int st, const __amdgpu_buffer_rsrc_t &rs, const int (&so)[S], int t, int n) {
+        const int off = min(t, n - 1) * BLK;
+#pragma unroll
+        for (int s = 0; s < S; ++s) slot[st][s] = ld_w16(rs, voff, so[s] + off);
+    }
+    __device__ __forceinline__ void fill(const __amdgpu_buffer_rsrc_t &rs, const int (&so)[S], int n) {
+#pragma unroll
+        for (int st = 0; st < D - 1; ++st) load(st, rs, so, st, n);
+    }
+    template <class Pre, class Body>
+    __device__ __forceinline__ void run(const __amdgpu_buffer_rsrc_t &rs, const int (&so)[S], int n, Pre &&pre,
+                                        Body &&body) {
+        const int n_full = (int)((unsigned)n / D * D);   // (n >= 1)
+        for (int tt = 0; tt < n_full; tt += D) {
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                load((u + D - 1) % D, rs, so, tt + u + D - 1, n);
+                pre(tt + u, u);
+                __builtin_amdgcn_sched_barrier(0);
+                body(tt + u, u, slot[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < D - 1; ++u)
+            if (n_full + u < n) {
+                pre(n_full + u, u);
+                body(n_full + u, u, slot[u]);
+            }
+    }
+};
+__device__ __forceinline__ void no_pre(int, int) {}
+
+// LDS layout of a tile body, offsets in floats: x_regions activation regions of x_floats each (two images used
+// alternately, or the hi / lo planes of split operands), emb_regions embedding regions of emb_floats each, then
+// SX = [pts][3] raw points (+ pad) and RED = [parts][pts] partial sums of the sdf-only last layer.  Each body has one
+// function that builds it; the kernel takes its pointers from it and the host its byte count.
+struct SdfLds {
+    int x1;          // second activation region
+    int emb, emb1;   // embedding; its second region
+    int sx, red, total;
+    __host__ __device__ size_t bytes() const { return sizeof(float) * (size_t)total; }
+};
+__host__ __device__ inline SdfLds sdf_lds(int pts, int x_regions, int x_floats, int emb_regions, int emb_floats, int parts) {
+    SdfLds l;
+    l.x1 = (x_regions - 1) * x_floats;
+    l.emb = x_regions * x_floats;
+    l.emb1 = l.emb + (emb_regions - 1) * emb_floats;
+    l.sx = l.emb + emb_regions * emb_floats;
+    l.red = l.sx + pts * 4;
+    l.total = l.red + parts * pts;
+    return l;
+}
+
+// the tile's raw points -> SX[p][3], zero beyond cnt
+__device__ __forceinline__ void load_points(bool on, float *SX, const float *__restrict__ x, int64_t base, int cnt, int pts,
+                                            int tid) {
+    if (on && tid < pts * 3) SX[tid] = (tid < cnt * 3) ? x[base * 3 + tid] : 0.0f;
+}
+
 // tile of precomputed embedding rows -> EMB[(e/4)][p][e%4] (group stride gf floats), zero padded to 4*egroups columns
 __device__ __forceinline__ void load_emb_tile(float *EMB, const float *__restrict__ emb, int64_t stride, int64_t base,
                                               int cnt, int E, int egroups, int pts, int gf, int tid, int nthreads) {
@@ -69,12 +145,54 @@ __device__ __forceinline__ void softplus100_4(float &v0, float &v1, float &v2, f
     v0 = a.x; v1 = a.y; v2 = b.x; v3 = b.y;
 }
 
+// hidden-layer epilogue on register quads that already carry their bias: Softplus(100), then the /sqrt(2) in front of
+// the skip layer
+constexpr float kSqrt2 = 1.41421356237309515f;
+template <int N>
+__device__ __forceinline__ void act_quads(float (&v)[N], bool act, bool div) {
+    if (act) {
+#pragma unroll
+        for (int i = 0; i < N; i += 4) softplus100_4(v[i], v[i + 1], v[i + 2], v[i + 3]);
+    }
+    if (div) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = __fdiv_rn(v[i], kSqrt2);
+    }
+}
+// after layer 0: the skip layer consumes cat[x, emb]/sqrt(2) - rescale the kept embedding (n floats) once, in place
+__device__ __forceinline__ void rescale_emb(float *EMB, int n, int tid, int nthreads) {
+    for (int i = tid; i < n; i += nthreads) EMB[i] = __fdiv_rn(EMB[i], kSqrt2);
+}
+
 // density_net.py:20-30 + implicit_differentiable_renderer.py:112
 __device__ __forceinline__ float sdf_clamp(float s, float beta) {
     const float alpha = 1.0f / beta;
     const float sg = (s > 0.0f) ? 1.0f : ((s < 0.0f) ? -1.0f : 0.0f);
     const float rho = alpha * (0.5f + 0.5f * sg * expm1f(-fabsf(s) / beta));
     return tanhf(s / (2.0f + rho));
+}
+
+// Sdf-only last layer, second half: every lane that holds a partial dot product has written it to RED[part][pts];
+// point tid of the tile = bias[0] + its `parts` partial sums, clamped, -> out[(base + tid) * stride]
+__device__ __forceinline__ void sdf_last_finish(const float *RED, int parts, int pts, int cnt,
+                                                const float *__restrict__ bias, float beta, float *__restrict__ out,
+                                                int64_t base, int64_t stride, int tid) {
+    __syncthreads();
+    if (tid < cnt) {
+        float sacc = bias[0];
+        for (int w = 0; w < parts; ++w) sacc += RED[w * pts + tid];
+        out[(base + tid) * stride] = sdf_clamp(sacc, beta);
+    }
+}
+// Full-width output stage: X[(f/4)][p][f%4] (gf floats per k-group) -> out[base + p][f], column 0 clamped
+__device__ __forceinline__ void store_rows(const float *X, int gf, int cnt, int od, float beta, float *__restrict__ out,
+                                           int64_t base, int64_t stride, int tid, int nthreads) {
+    for (int i = tid; i < cnt * od; i += nthreads) {
+        const int p = i / od, f = i - p * od;
+        float v = X[(f >> 2) * gf + p * 4 + (f & 3)];
+        if (f == 0) v = sdf_clamp(v, beta);
+        out[(base + p) * stride + f] = v;
+    }
 }
 
 // Encode stage of the fused SDF kernels: the embedding row [x | sin a_c | cos a_c | level features | 0 ... e_pad) of
@@ -131,6 +249,21 @@ __device__ __forceinline__ void embed_slot(const HmLevels &lv, const float *__re
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+// hm_diag_sdf_lds: the byte offsets of a layout's regions, in order, and its size
+static void sdf_lds_report(const SdfLds &l, int32_t *regions) {
+    const int f[6] = {l.x1, l.emb, l.emb1, l.sx, l.red, l.total};
+    for (int i = 0; i < 6; ++i) regions[i] = 4 * f[i];
+}
+
+// the level descriptor of the precomputed-embedding entry points (no grid: only E is read) behind their common check
+static int sdf_emb_levels(const char *who, int emb_width, int64_t emb_stride, HmLevels &lv) {
+    if (!(emb_width >= 1 && emb_width <= 512 && emb_stride >= emb_width))
+        return hm_fail(HM_ERR_INVALID, std::string(who) + ": bad embedding width / stride");
+    lv = {};
+    lv.L = 0; lv.F = 2; lv.E = emb_width;
+    return HM_OK;
+}
+
 // the weight image a fused SDF kernel reads from every layer besides the fp32 one (w_packed): the fp32 16-point image
 // (w_packed_m16; optional for hm_sdf_fwd, which runs the small tiles only when every layer carries it), the bf16 image or
 // the split-operand image

@@ -24,6 +24,8 @@
 // matrix rate: stream and pipe are about balanced, as in the bf16 kernel.  fp32: accumulators, bias, Softplus, the
 // sqrt(2) of the layer before the skip, the last layer's dot product and the clamp.  The 1/sqrt(2) of the skip
 // layer's EMBEDDING segment is folded into that segment's weights at pack time (hm_pack_mlp_layer_split).
+// Point load, encode, weight stream (WeightRing<4, 4, 2048>: hi and lo part of two feature tiles per 2-KB block), quad
+// epilogue, last-layer finish and the LDS layout (sdf_lds_split) are the stages of hm_sdf_common.h.
 #include "hm_common.h"
 
 #include <math.h>
@@ -74,11 +76,11 @@ constexpr int kTS = 512;           // threads
 constexpr int kWS = 8;             // waves
 constexpr int kOctE = kPS * 8;     // 2-byte elements per k-octet row of a plane
 
-template <int KIND>
-union FragS {   // 16 bytes = 8 two-byte elements = one MFMA operand fragment
-    float4 f;
-    typename Split<KIND>::V8 h;
-};
+// dynamic LDS: hi and lo plane [x_groups / 2][kPS][8] of 2-byte elements for the activations, the same for the
+// embedding, 8 partial sums per point
+__host__ __device__ inline SdfLds sdf_lds_split(const SdfNet &net) {
+    return sdf_lds(kPS, 2, net.x_groups / 2 * kOctE / 2, 2, net.emb_groups / 2 * kOctE / 2, kWS);
+}
 
 template <int KIND, int FRAC>
 __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfNet net, const float *__restrict__ x,
@@ -94,13 +96,14 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
     extern __shared__ __align__(16) float lds[];
     if (n_dev) n = min(n, (int64_t)max(*n_dev, 0));
     if (n < run_min || n > run_max) return;
-    const int x_oct = net.x_groups / 2, e_oct = net.emb_groups / 2;
-    T *XH = reinterpret_cast<T *>(lds);                       // [x_oct][kPS][8]
-    T *XL = XH + (size_t)x_oct * kOctE;
-    T *EH = XL + (size_t)x_oct * kOctE;                       // [e_oct][kPS][8]
-    T *EL = EH + (size_t)e_oct * kOctE;
-    float *SX = reinterpret_cast<float *>(EL + (size_t)e_oct * kOctE);   // [kPS][3] raw points (+ pad)
-    float *RED = SX + kPS * 4;                                            // [8][kPS] last-layer partial sums
+    const SdfLds at = sdf_lds_split(net);
+    const int e_oct = net.emb_groups / 2;
+    T *XH = reinterpret_cast<T *>(lds);                       // [x_groups / 2][kPS][8]
+    T *XL = reinterpret_cast<T *>(lds + at.x1);
+    T *EH = reinterpret_cast<T *>(lds + at.emb);              // [e_oct][kPS][8]
+    T *EL = reinterpret_cast<T *>(lds + at.emb1);
+    float *SX = lds + at.sx;                                  // [kPS][3] raw points (+ pad)
+    float *RED = lds + at.red;                                // [8][kPS] last-layer partial sums
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: descriptors / scalar offsets of the weight stream)
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
         const int64_t base = tile * kPS;
         const int cnt = (int)min((int64_t)kPS, n - base);
         __syncthreads();
-        if (net.emb_stride == 0 && tid < kPS * 3) SX[tid] = (tid < cnt * 3) ? x[base * 3 + tid] : 0.0f;
+        load_points(net.emb_stride == 0, SX, x, base, cnt, kPS, tid);
         __syncthreads();
 
         // ---------------- embedding (fp32 arithmetic) -> split planes EH / EL ---------------------------------
@@ -143,24 +146,11 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
         __syncthreads();
 
         // ---------------- layers ------------------------------------------------------------------------------
-        // weight ring: D slots per image part, D-1 blocks in flight (fp16 kind: two accumulator sets leave room for
-        // three slots only - a fourth spills).  It lives across the layers: the first D-1 blocks of layer l+1 are
-        // requested before layer l's epilogue (weights do not depend on the activations), so the stream does not
-        // restart from an empty pipe behind the two barriers of every layer.
-        constexpr int D = 4;
-        FragS<KIND> r0h[D], r0l[D], r1h[D], r1l[D];
+        // weight ring (WeightRing, hm_sdf_common.h): 4 slots, 3 blocks of 2 KB in flight per feature tile; it lives across
+        // the layers.  Streams per block: [hi | lo] of the wave's first feature tile, then of its second, a1 bytes on.
+        WeightRing<4, 4, 2048> ring;
+        ring.voff = lane * 16;
         bool ring_ready = false;
-        // (weight stream as buffer loads: descriptor on the wave's first feature tile, lane * 16 the one VGPR offset, block /
-        //  tile offsets scalar - no address arithmetic on the VALU between the MFMAs, hm_sdf_common.h: ld_w16)
-        const int lane16 = lane * 16;
-        auto ring_fill = [&](const __amdgpu_buffer_rsrc_t &rs, int a1, int nbs) {
-#pragma unroll
-            for (int st = 0; st < D - 1; ++st) {
-                const int off = min(st, nbs - 1) * 2048;
-                r0h[st].f = ld_w16(rs, lane16, off); r0l[st].f = ld_w16(rs, lane16, off + 1024);
-                r1h[st].f = ld_w16(rs, lane16, a1 + off); r1l[st].f = ld_w16(rs, lane16, a1 + off + 1024);
-            }
-        };
         auto prefetch_layer = [&](int l) {      // segment 0 of layer l, this wave's feature tiles
             const hm_mlp_layer &Lp = net.layer[l];
             const int ntp = max(0, min(2, Lp.n_tiles - 2 * wave));
@@ -168,7 +158,9 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
             const int nbp = Lp.seg_blocks16[0] + Lp.seg_blocks16[1];
             const __amdgpu_buffer_rsrc_t rp =
                 w_rsrc(reinterpret_cast<const float *>(Lp.w_packed_split) + ((size_t)(2 * wave) * nbp) * 512);
-            ring_fill(rp, ntp > 1 ? nbp * 2048 : 0, Lp.seg_blocks16[0]);
+            const int a1 = ntp > 1 ? nbp * 2048 : 0;
+            const int so[4] = {0, 1024, a1, a1 + 1024};
+            ring.fill(rp, so, Lp.seg_blocks16[0]);
             return true;
         };
         for (int li = 0; li < net.n_layers; ++li) {
@@ -190,12 +182,7 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
                         part = __fmaf_rn(((float)xl[e] + (float)xh[e]) * (1.0f / S::xs), wv[e], part);
                 }
                 RED[sl * kPS + p] = part;
-                __syncthreads();
-                if (tid < cnt) {
-                    float sacc = Ly.bias[0];
-                    for (int s8 = 0; s8 < kWS; ++s8) sacc += RED[s8 * kPS + tid];
-                    out[(base + tid) * out_stride] = sdf_clamp(sacc, net.beta);
-                }
+                sdf_last_finish(RED, kWS, kPS, cnt, Ly.bias, net.beta, out, base, out_stride, tid);
                 break;
             }
             const int nt = Ly.n_tiles;
@@ -218,48 +205,31 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
                     const __amdgpu_buffer_rsrc_t rA =
                         w_rsrc(reinterpret_cast<const float *>(Ly.w_packed_split) + ((size_t)t0 * nb + blk0) * 512);
                     const int a1 = ntw > 1 ? nb * 2048 : 0;
-                    if (!(seg == 0 && ring_ready)) ring_fill(rA, a1, nbs);
+                    const int so[4] = {0, 1024, a1, a1 + 1024};
+                    if (!(seg == 0 && ring_ready)) ring.fill(rA, so, nbs);
                     ring_ready = false;
-                    auto block = [&](int t, const FragS<KIND> &a0h, const FragS<KIND> &a0l, const FragS<KIND> &a1h,
-                                     const FragS<KIND> &a1l) {
+                    ring.run(rA, so, nbs, no_pre, [&](int t, int, const float4 (&w)[4]) {
+                        const V8 a0h = __builtin_bit_cast(V8, w[0]), a0l = __builtin_bit_cast(V8, w[1]),
+                                 a1h = __builtin_bit_cast(V8, w[2]), a1l = __builtin_bit_cast(V8, w[3]);
                         const size_t o = (size_t)(2 * t + h) * kOctE + j * 8;
                         const V8 bh0 = *reinterpret_cast<const V8 *>(srcH + o);
                         const V8 bh1 = *reinterpret_cast<const V8 *>(srcH + o + 32 * 8);
                         const V8 bl0 = *reinterpret_cast<const V8 *>(srcL + o);
                         const V8 bl1 = *reinterpret_cast<const V8 *>(srcL + o + 32 * 8);
                         // hi x hi, then hi x lo, then lo x hi: accumulators that are used twice are four MFMAs apart
-                        acc[0][0] = S::mfma(a0h.h, bh0, acc[0][0]);
-                        acc[0][1] = S::mfma(a0h.h, bh1, acc[0][1]);
-                        acc[1][0] = S::mfma(a1h.h, bh0, acc[1][0]);
-                        acc[1][1] = S::mfma(a1h.h, bh1, acc[1][1]);
-                        acc[0][0] = S::mfma(a0h.h, bl0, acc[0][0]);
-                        acc[0][1] = S::mfma(a0h.h, bl1, acc[0][1]);
-                        acc[1][0] = S::mfma(a1h.h, bl0, acc[1][0]);
-                        acc[1][1] = S::mfma(a1h.h, bl1, acc[1][1]);
-                        acc[0][0] = S::mfma(a0l.h, bh0, acc[0][0]);
-                        acc[0][1] = S::mfma(a0l.h, bh1, acc[0][1]);
-                        acc[1][0] = S::mfma(a1l.h, bh0, acc[1][0]);
-                        acc[1][1] = S::mfma(a1l.h, bh1, acc[1][1]);
-                    };
-                    const int n_full = nbs - nbs % D;
-                    for (int tt = 0; tt < n_full; tt += D) {
-#pragma unroll
-                        for (int u = 0; u < D; ++u) {
-                            const int t = tt + u;
-                            {
-                                const int off = min(t + D - 1, nbs - 1) * 2048;
-                                r0h[(u + D - 1) % D].f = ld_w16(rA, lane16, off);
-                                r0l[(u + D - 1) % D].f = ld_w16(rA, lane16, off + 1024);
-                                r1h[(u + D - 1) % D].f = ld_w16(rA, lane16, a1 + off);
-                                r1l[(u + D - 1) % D].f = ld_w16(rA, lane16, a1 + off + 1024);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            block(t, r0h[u], r0l[u], r1h[u], r1l[u]);
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < D - 1; ++u)      // the left-over blocks are already in ring slots 0 .. D-2
-                        if (n_full + u < nbs) block(n_full + u, r0h[u], r0l[u], r1h[u], r1l[u]);
+                        acc[0][0] = S::mfma(a0h, bh0, acc[0][0]);
+                        acc[0][1] = S::mfma(a0h, bh1, acc[0][1]);
+                        acc[1][0] = S::mfma(a1h, bh0, acc[1][0]);
+                        acc[1][1] = S::mfma(a1h, bh1, acc[1][1]);
+                        acc[0][0] = S::mfma(a0h, bl0, acc[0][0]);
+                        acc[0][1] = S::mfma(a0h, bl1, acc[0][1]);
+                        acc[1][0] = S::mfma(a1h, bl0, acc[1][0]);
+                        acc[1][1] = S::mfma(a1h, bl1, acc[1][1]);
+                        acc[0][0] = S::mfma(a0l, bh0, acc[0][0]);
+                        acc[0][1] = S::mfma(a0l, bh1, acc[0][1]);
+                        acc[1][0] = S::mfma(a1l, bh0, acc[1][0]);
+                        acc[1][1] = S::mfma(a1l, bh1, acc[1][1]);
+                    });
                     blk0 += nbs;
                 }
             }
@@ -269,7 +239,6 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
             // epilogue: registers 4q..4q+3 of a tile = features 8q + 4h + {0..3} -> 4 elements of one k-octet of the next layer
             const bool act = Ly.activation != 0;
             const bool div = Ly.post_div_sqrt2 != 0;
-            const float sqrt2 = 1.41421356237309515f;
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 if (a >= ntw) continue;
@@ -286,13 +255,11 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
                         v[0] = __fmaf_rn(v[0], S::inv, bb.x); v[1] = __fmaf_rn(v[1], S::inv, bb.y);
                         v[2] = __fmaf_rn(v[2], S::inv, bb.z); v[3] = __fmaf_rn(v[3], S::inv, bb.w);
                         V4 oh, ol;
-                        if (act) softplus100_4(v[0], v[1], v[2], v[3]);
+                        act_quads(v, act, div);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float u = v[e];
-                            if (div) u = __fdiv_rn(u, sqrt2);
                             T hi, lo;
-                            split_val<KIND>(u * S::xs, hi, lo);
+                            split_val<KIND>(v[e] * S::xs, hi, lo);
                             oh[e] = hi;
                             ol[e] = lo;
                         }
@@ -343,11 +310,13 @@ __global__ __launch_bounds__(256) void pack_layer_split_kernel(PackSplitArgs a, 
 }
 
 // the network and LDS checks of every launch of this kernel (hm_sdf_net_fits asks the same): *lds = its dynamic LDS
-static int sdf_split_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, size_t *lds) {
+static int sdf_split_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t emb_stride, SdfNet &net, size_t *lds,
+                         int32_t *regions = nullptr) {
     // (EMB region: k-groups of 4 = 2 octets per 16-block)
     const int rc = sdf_net_from_desc(who, mlp, E, emb_stride, kImgSplit, 2, (E + 15) / 16 * 4, true, net);
     if (rc != HM_OK) return rc;
-    *lds = (size_t)(net.x_groups / 2 + net.emb_groups / 2) * kOctE * 2 * 2 + sizeof(float) * (kPS * 4 + kWS * kPS);
+    *lds = sdf_lds_split(net).bytes();
+    if (regions) sdf_lds_report(sdf_lds_split(net), regions);
     if (*lds > 160 * 1024) return hm_fail(HM_ERR_INVALID, std::string(who) + ": network does not fit the 160 KB LDS tile");
     return HM_OK;
 }
@@ -385,11 +354,11 @@ static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const floa
 
 extern "C" {
 
-// (internal: hm_sdf_net_fits, HM_SDF_SPLIT)
-int sdf_split_fits(const hm_mlp_desc *mlp, int E) {
+// (internal: hm_sdf_net_fits / hm_diag_sdf_lds, HM_SDF_SPLIT; regions may be NULL)
+int sdf_split_fits(const hm_mlp_desc *mlp, int E, int32_t *regions) {
     SdfNet net;
     size_t lds = 0;
-    return sdf_split_net("hm_sdf_net_fits", E, mlp, 0, net, &lds);
+    return sdf_split_net("hm_sdf_net_fits", E, mlp, 0, net, &lds, regions);
 }
 
 int hm_pack_mlp_layer_split(const float *W, int64_t ldw, int out_dim, int seg_width0, int seg_width1, float seg_scale0,
@@ -426,9 +395,9 @@ int hm_sdf_fwd_split(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const flo
 
 int hm_sdf_fwd_emb_split(const hm_mlp_desc *mlp, const float *emb, int64_t emb_stride, int emb_width, int64_t n,
                          float *out, int64_t out_stride, const int32_t *n_dev, int64_t run_min, void *stream) {
-    HM_CHECK_ARG(emb_width >= 1 && emb_width <= 512 && emb_stride >= emb_width, "hm_sdf_fwd_emb_split: bad embedding width / stride");
-    HmLevels lv = {};
-    lv.L = 0; lv.F = 2; lv.E = emb_width;
+    HmLevels lv;
+    const int rc = sdf_emb_levels("hm_sdf_fwd_emb_split", emb_width, emb_stride, lv);
+    if (rc != HM_OK) return rc;
     return sdf_split_impl(lv, mlp, emb, emb_stride, n, nullptr, nullptr, out, out_stride, HM_FRAC_REFERENCE, n_dev,
                           run_min, stream);
 }

@@ -317,6 +317,13 @@ HM_API int hm_sdf_fwd_emb(const hm_mlp_desc *mlp, const float *emb, int64_t emb_
 #define HM_SDF_SPLIT 2
 HM_API int hm_sdf_net_fits(const hm_mlp_desc *mlp, int emb_width, int family);
 
+/* Diagnostic: the dynamic LDS layout of one fused SDF tile body for the network mlp; host only.  tile_points 64, 16 or
+ * 8 selects the HM_SDF_FP32 body (the 4-point tile uses the 8-point layout); the other families have one body and
+ * ignore it.  regions[0..4] = byte offsets of the second activation region (image / lo plane; 0 where the
+ * body has one), the embedding, its second region (== regions[1] where it has one), the raw points [points][4] and the
+ * last layer's partial sums [parts][points]; regions[5] = the launch's dynamic LDS bytes.                          */
+HM_API int hm_diag_sdf_lds(const hm_mlp_desc *mlp, int emb_width, int family, int tile_points, int32_t *regions);
+
 /* ---- Fourier-filter-bank embedders ('FFB', 'StyleModNFFB') forward, no grad ------------------------------------
  * Replaces FourierFilterBanks.forward (model/embeddings/nffb3d.py:122-194, registry settings PositionalEncodingNET /
  * SIREN / has_out=False) with PositionalEncoding (frequency_enc.py:6-51), Sine (Sine.py:5-25) and StyleAttention

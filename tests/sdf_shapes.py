@@ -84,8 +84,8 @@ def wave_shares64(n_tiles):
 
 
 def wave_shares16(n_tiles):
-    """16-row feature tiles each of the 8 waves of the 16- / 8- / 4-point bodies owns (sdf_m16_body, sdf_m8_body:
-    u0 = 4 wave over 2 n_tiles tiles)"""
+    """16-row feature tiles each of the 8 waves of the 16- / 8- / 4-point bodies owns (sdf_small_body: u0 = 4 wave over
+    2 n_tiles tiles)"""
     return [max(0, min(4, 2 * n_tiles - 4 * w)) for w in range(8)]
 
 

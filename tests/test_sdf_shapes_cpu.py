@@ -104,6 +104,57 @@ def test_kernel_families_accept_what_the_table_says(lib, case):
         _lib.check(lib.hm_sdf_net_fits(ctypes.byref(S.descriptor(case)), E, 3))
 
 
+def _lds_regions(case, body):
+    """[(name, bytes)] of the dynamic LDS regions of one tile body, in order: the formulas the launches used before the
+    layout had one definition (sdf_lds64, sdf_lds16 and its 8-point half, sdf_bf16_net, sdf_split_net), written out here
+    and NOT read back from the library"""
+    E = S.emb_width(case)
+    x_groups = 8 * max(ly["n_tiles"] for ly in S.layers(case))      # k-groups of 4 of the widest layer
+    if body == "fp32_64":        # X [x_groups][64][4], EMB [2 ceil(E/8)][64][4], SX [64][4], RED [8][64], fp32
+        return [("x", x_groups * 256 * 4), ("emb", (E + 7) // 8 * 2 * 256 * 4), ("sx", 64 * 4 * 4), ("red", 8 * 64 * 4)]
+    if body in ("fp32_16", "fp32_8"):   # two images [x_groups][pts][4], EMB [4 ceil(E/16)][pts][4], SX [pts][4], RED [8][pts]
+        pts = 16 if body == "fp32_16" else 8
+        img = x_groups * pts * 4 * 4
+        return [("x0", img), ("x1", img), ("emb", (E + 15) // 16 * 4 * pts * 4 * 4), ("sx", pts * 4 * 4), ("red", 8 * pts * 4)]
+    if body == "bf16":           # X bf16 [x_groups/2][96][8], EMB fp32 [2 ceil(E/8)][96][4], SX [96][4], RED [5][96]
+        return [("x", x_groups // 2 * 96 * 8 * 2), ("emb", (E + 7) // 8 * 2 * 96 * 4 * 4), ("sx", 96 * 4 * 4), ("red", 5 * 96 * 4)]
+    assert body == "split"       # hi, lo planes [x_groups/2][64][8] and [2 ceil(E/16)][64][8] of 2 bytes, SX, RED [8][64]
+    xp, ep = x_groups // 2 * 64 * 8 * 2, (E + 15) // 16 * 2 * 64 * 8 * 2
+    return [("xh", xp), ("xl", xp), ("eh", ep), ("el", ep), ("sx", 64 * 4 * 4), ("red", 8 * 64 * 4)]
+
+
+_LDS_BODIES = {"fp32_64": (0, 64), "fp32_16": (0, 16), "fp32_8": (0, 8), "bf16": (1, 0), "split": (2, 0)}
+
+
+@pytest.mark.parametrize("body", sorted(_LDS_BODIES))
+@pytest.mark.parametrize("name", ["c2", "odd_tiles", "ragged", "L2"])
+def test_lds_layout_is_the_launch_size_and_ends_at_it(lib, name, body):
+    """hm_diag_sdf_lds: every region of a body's layout starts where the one before it ends, the last one ends exactly at
+    the byte count the launch asks for, and that count is the one the earlier host formulas gave"""
+    import ctypes
+    from hashmodnffbanks_idr_amd import _lib
+    case = S.BY_NAME[name]
+    family, tile_points = _LDS_BODIES[body]
+    regions = (ctypes.c_int32 * 6)()
+    _lib.check(lib.hm_diag_sdf_lds(ctypes.byref(S.descriptor(case)), S.emb_width(case), family, tile_points, regions))
+    x1, emb, emb1, sx, red, total = list(regions)
+    want = _lds_regions(case, body)
+    # the library's offsets, one per expected region (bodies with one activation / embedding region report no second one)
+    got = {"x": 0, "x0": 0, "xh": 0, "x1": x1, "xl": x1, "emb": emb, "eh": emb, "el": emb1, "sx": sx, "red": red}
+    if body in ("fp32_64", "bf16"):
+        assert x1 == 0
+    if body != "split":
+        assert emb1 == emb
+    off = 0
+    for region, nbytes in want:
+        assert got[region] == off, (name, body, region, got[region], off)
+        assert off % 16 == 0, (name, body, region)          # b128 LDS accesses need 16-byte aligned regions
+        off += nbytes
+    assert total == off, (name, body, total, off)
+    if name == "c2":    # the benchmarked network, in plain numbers
+        assert total == {"fp32_64": 152576, "fp32_16": 71424, "fp32_8": 35712, "bf16": 129408, "split": 154624}[body]
+
+
 def test_fp32_lds_boundary_at_512_wide_layers(lib):
     """E = 111 (L = 27) is the widest hash-grid embedding the 64-point tile holds next to 512-wide layers"""
     import ctypes
