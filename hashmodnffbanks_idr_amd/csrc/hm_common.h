@@ -61,6 +61,14 @@ auto hm_frac_dispatch(int frac_mode, F &&f) {
     return f(std::integral_constant<int, HM_FRAC_TRILINEAR>{});
 }
 
+// f(std::true_type{}) or f(std::false_type{}) for the run-time b: a launch whose kernel takes b as a template value is
+// written once
+template <class F>
+auto hm_bool_dispatch(bool b, F &&f) {
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
+}
+
 // Small-batch rule of the fused SDF forward (hm_sdf.hip): up to kSdfSmall live points run on the small-tile launch -
 // 8-point tiles up to kSdfTiny, 4-point tiles up to kSdfMini - more on 64-point tiles.  hm_trace.hip picks its launch
 // forms by the same bound: a launch that takes only counts above it passes run_min = kSdfSmall + 1.

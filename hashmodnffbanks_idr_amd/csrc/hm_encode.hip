@@ -932,15 +932,47 @@ __global__ __launch_bounds__(256) void gather_calib_kernel(const float2 *__restr
     out[i] = v.x + v.y;
 }
 
+// The z-order workspaces.  Each layout is written once, as byte offsets from the workspace's start (the slab counters
+// are at 0) and the total: the *_workspace_bytes query and the launch that carves the buffer both read it.
+struct FwdZLayout {
+    int64_t order, slab, bytes;
+};
+static FwdZLayout fwd_z_layout(int64_t n) {
+    // [slab counters 2*kSlabs u32 | order n u32 | slab ids n u16]
+    const int64_t order = 4 * 2 * kSlabs, slab = order + 4 * n;
+    return {order, slab, slab + 2 * ((n + 1) & ~(int64_t)1)};
+}
+struct BwdZLayout {
+    int64_t order, xs, dfs, slab, bytes;
+};
+static BwdZLayout bwd_z_layout(const HmLevels &lv, int64_t n) {
+    // [slab counters 2*kSlabs u32 | order n u32 | xs 3n f32 | dfs L*F*n f32 | slab ids n u16], each part 256-byte aligned
+    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t order = up(4 * 2 * kSlabs), xs = order + up(4 * n), dfs = xs + up(12 * n);
+    const int64_t slab = dfs + up(4 * n * lv.L * lv.F);
+    return {order, xs, dfs, slab, slab + up(2 * n)};
+}
+
+// The bucketing pass of both z-ordered launches: order[0..n) = the points' indices by z slab.  hist: 2 * kSlabs counters
+// ([0, kSlabs): counts -> start offsets -> cursors; [kSlabs, 2 kSlabs): the start offsets, which survive the scatter);
+// slab: n uint16 slab ids handed from the histogram pass to the scatter pass, or NULL (the scatter pass then recomputes
+// the slabs from x).
+static void zsort_points(const float *x, int64_t n, uint32_t *hist, uint32_t *order, uint16_t *slab, hipStream_t st) {
+    hm_zero_u32_async(hist, kSlabs, st);
+    const unsigned g_sort = (unsigned)((n + kSortChunk - 1) / kSortChunk);
+    hipLaunchKernelGGL(zsort_hist_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, slab);
+    hipLaunchKernelGGL(zsort_scan_kernel, dim3(1), dim3(kSlabs), 0, st, hist);
+    hipLaunchKernelGGL(zsort_scatter_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, order,
+                       static_cast<const uint16_t *>(slab));
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t hm_encode_bwd_workspace_bytes(const hm_grid_desc *desc, int64_t n) {
     if (!desc || n < 0) return hm_fail(HM_ERR_INVALID, "hm_encode_bwd_workspace_bytes: bad argument");
-    // [slab counters 2*kSlabs u32 | order n u32 | xs 3n f32 | dfs L*F*n f32 | slab ids n u16], each part 256-byte aligned
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    return up(4 * 2 * kSlabs) + up(4 * n) + up(12 * n) + up(4 * n * desc->lv.L * desc->lv.F) + up(2 * n);
+    return bwd_z_layout(desc->lv, n).bytes;
 }
 
 int hm_encode_bwd_table_ws(const hm_grid_desc *desc, const float *x, int64_t n, const float *d_feat,
@@ -949,27 +981,19 @@ int hm_encode_bwd_table_ws(const hm_grid_desc *desc, const float *x, int64_t n, 
     HM_CHECK_ARG(desc != nullptr, "hm_encode_bwd_table_ws: desc is NULL");
     const HmLevels &lv = desc->lv;
     const bool table_big = desc->total_rows * (uint64_t)lv.F * 4u > (8u << 20);
-    if (!workspace || lv.F != 2 || n < (int64_t)131072 || n >= ((int64_t)1 << 31) || !table_big ||
-        workspace_bytes < hm_encode_bwd_workspace_bytes(desc, n))
+    const BwdZLayout w = bwd_z_layout(lv, n);
+    if (!workspace || lv.F != 2 || n < (int64_t)131072 || n >= ((int64_t)1 << 31) || !table_big || workspace_bytes < w.bytes)
         return hm_encode_bwd_table(desc, x, n, d_feat, d_feat_stride, d_table, frac_mode, stream);
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_encode_bwd_table_ws: bad frac_mode");
     HM_CHECK_ARG(d_feat_stride >= lv.L * lv.F, "hm_encode_bwd_table_ws: d_feat_stride < L*F");
     HM_CHECK_ARG(x && d_feat && d_table, "hm_encode_bwd_table_ws: NULL pointer");
     hipStream_t st = as_stream(stream);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     char *wsb = static_cast<char *>(workspace);
     uint32_t *hist = reinterpret_cast<uint32_t *>(wsb);
-    uint32_t *order = reinterpret_cast<uint32_t *>(wsb + up(4 * 2 * kSlabs));
-    float *xs = reinterpret_cast<float *>(wsb + up(4 * 2 * kSlabs) + up(4 * (size_t)n));
-    float *dfs = reinterpret_cast<float *>(wsb + up(4 * 2 * kSlabs) + up(4 * (size_t)n) + up(12 * (size_t)n));
-    uint16_t *slab = reinterpret_cast<uint16_t *>(wsb + up(4 * 2 * kSlabs) + up(4 * (size_t)n) + up(12 * (size_t)n) +
-                                                  up(4 * (size_t)n * lv.L * lv.F));
-    hm_zero_u32_async(hist, kSlabs, st);
-    const unsigned g_sort = (unsigned)((n + kSortChunk - 1) / kSortChunk);
-    hipLaunchKernelGGL(zsort_hist_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, slab);
-    hipLaunchKernelGGL(zsort_scan_kernel, dim3(1), dim3(kSlabs), 0, st, hist);
-    hipLaunchKernelGGL(zsort_scatter_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, order,
-                       static_cast<const uint16_t *>(slab));
+    uint32_t *order = reinterpret_cast<uint32_t *>(wsb + w.order);
+    float *xs = reinterpret_cast<float *>(wsb + w.xs);
+    float *dfs = reinterpret_cast<float *>(wsb + w.dfs);
+    zsort_points(x, n, hist, order, reinterpret_cast<uint16_t *>(wsb + w.slab), st);
     hipLaunchKernelGGL(zsort_pack_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, x, d_feat, d_feat_stride,
                        order, n, lv.L * lv.F, xs, dfs);
     const size_t lds = sizeof(float) * kBwdSlots * kBwdBlockRows * 2 + sizeof(uint32_t) * kBwdSlots;
@@ -998,14 +1022,11 @@ int hm_encode_bwd_table_tracked(const hm_grid_desc *desc, const float *x, int64_
     const int64_t threads = n * desc->lv.L * (frac_mode == HM_FRAC_REFERENCE ? 1 : 8);
     const int64_t grid = (threads + kThreads - 1) / kThreads;
     HM_CHECK_ARG(grid <= 0x7fffffffLL, "hm_encode_bwd_table_tracked: n too large for one launch");
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(encode_bwd_table_tracked_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kThreads), 0,
+    hm_frac_dispatch(frac_mode, [&](auto frac) {
+        hipLaunchKernelGGL(encode_bwd_table_tracked_kernel<decltype(frac)::value>, dim3((unsigned)grid), dim3(kThreads), 0,
                            as_stream(stream), desc->lv, x, n, d_feat, d_feat_stride, d_table, touched_bits,
                            touched_count, touched_rows, cap);
-    else
-        hipLaunchKernelGGL(encode_bwd_table_tracked_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kThreads), 0,
-                           as_stream(stream), desc->lv, x, n, d_feat, d_feat_stride, d_table, touched_bits,
-                           touched_count, touched_rows, cap);
+    });
     HM_CHECK_LAUNCH("hm_encode_bwd_table_tracked");
     return HM_OK;
 }
@@ -1022,12 +1043,10 @@ int hm_encode_rows(const hm_grid_desc *desc, const float *x, int64_t n, int frac
     const int64_t total = n * desc->lv.L * C;
     const int64_t grid = (total + kThreads - 1) / kThreads;
     HM_CHECK_ARG(grid <= 0x7fffffffLL, "hm_encode_rows: n too large for one launch");
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(encode_rows_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kThreads), 0,
+    hm_frac_dispatch(frac_mode, [&](auto frac) {
+        hipLaunchKernelGGL(encode_rows_kernel<decltype(frac)::value>, dim3((unsigned)grid), dim3(kThreads), 0,
                            as_stream(stream), desc->lv, x, n, keys_out, weights_out);
-    else
-        hipLaunchKernelGGL(encode_rows_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kThreads), 0,
-                           as_stream(stream), desc->lv, x, n, keys_out, weights_out);
+    });
     HM_CHECK_LAUNCH("hm_encode_rows");
     return HM_OK;
 }
@@ -1101,29 +1120,13 @@ int hm_corner_ids(const hm_grid_desc *desc, int level, const float *x, int64_t n
 
 int64_t hm_encode_workspace_bytes(const hm_grid_desc *desc, int64_t n) {
     if (!desc || n < 0) return hm_fail(HM_ERR_INVALID, "hm_encode_workspace_bytes: bad argument");
-    // [slab counters 2*kSlabs u32 | order n u32 | slab ids n u16]
-    return (int64_t)sizeof(uint32_t) * (n + 2 * kSlabs) + (int64_t)sizeof(uint16_t) * ((n + 1) & ~(int64_t)1);
+    return fwd_z_layout(n).bytes;
 }
 
-static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, const float *table,
-                           const float *B_fourier, float *out, int64_t out_stride, int frac_mode, void *workspace,
-                           int64_t workspace_bytes, void *stream);
-
-int hm_encode_fwd(const hm_grid_desc *desc, const float *x, int64_t n, const float *table, const float *B_fourier,
-                  float *out, int64_t out_stride, int frac_mode, void *stream) {
-    return encode_fwd_impl(desc, x, n, table, B_fourier, out, out_stride, frac_mode, nullptr, 0, stream);
-}
-
+// (hm_encode_fwd is this call without a workspace: the messages name the forward either way)
 int hm_encode_fwd_ws(const hm_grid_desc *desc, const float *x, int64_t n, const float *table, const float *B_fourier,
                      float *out, int64_t out_stride, int frac_mode, void *workspace, int64_t workspace_bytes,
                      void *stream) {
-    return encode_fwd_impl(desc, x, n, table, B_fourier, out, out_stride, frac_mode, workspace, workspace_bytes,
-                           stream);
-}
-
-static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, const float *table,
-                           const float *B_fourier, float *out, int64_t out_stride, int frac_mode, void *workspace,
-                           int64_t workspace_bytes, void *stream) {
     HM_CHECK_ARG(desc != nullptr, "hm_encode_fwd: desc is NULL");
     HM_CHECK_ARG(n >= 0, "hm_encode_fwd: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_encode_fwd: bad frac_mode");
@@ -1137,21 +1140,17 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
     const size_t lds_sweep = sizeof(float) * (size_t)(kTileS * width + kTileS * 3);
     const bool table_exceeds_l2 = desc->total_rows * (uint64_t)lv.F * 4u > (8u << 20);   // (C1's 0.9 MiB: tile kernel)
     const size_t lds_z = sizeof(float) * (size_t)(kTileS * ((width + 3) & ~3) + kTileS * 3 + kTileS);
+    const FwdZLayout w = fwd_z_layout(n);
     if (lv.F == 2 && workspace && table_exceeds_l2 && n >= (int64_t)131072 && n < ((int64_t)1 << 32) &&
-        lds_z <= 160 * 1024 && workspace_bytes >= (int64_t)sizeof(uint32_t) * (n + 2 * kSlabs)) {
+        lds_z <= 160 * 1024 && workspace_bytes >= w.slab) {
         hipStream_t st = as_stream(stream);
-        uint32_t *hist = static_cast<uint32_t *>(workspace);        // [kSlabs] counts -> start offsets -> cursors
-        uint32_t *order = hist + 2 * kSlabs;                          // [n]
-        // [n] uint16 slab ids behind the order array when the caller's workspace has room for them (older, smaller
-        // workspaces still work: the scatter pass then recomputes the slabs from x)
-        uint16_t *slab = workspace_bytes >= hm_encode_workspace_bytes(desc, n) ? reinterpret_cast<uint16_t *>(order + n)
-                                                                             : nullptr;
-        hm_zero_u32_async(hist, kSlabs, st);
-        const unsigned g_sort = (unsigned)((n + kSortChunk - 1) / kSortChunk);
-        hipLaunchKernelGGL(zsort_hist_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, slab);
-        hipLaunchKernelGGL(zsort_scan_kernel, dim3(1), dim3(kSlabs), 0, st, hist);
-        hipLaunchKernelGGL(zsort_scatter_kernel, dim3(g_sort), dim3(1024), 0, st, x, n, hist, order,
-                           static_cast<const uint16_t *>(slab));
+        char *wsb = static_cast<char *>(workspace);
+        uint32_t *hist = reinterpret_cast<uint32_t *>(wsb);
+        uint32_t *order = reinterpret_cast<uint32_t *>(wsb + w.order);
+        // the launch needs the workspace up to the slab ids (w.slab bytes) and uses the ids when the caller's workspace
+        // has room for them (older, smaller workspaces still work: the scatter pass then recomputes the slabs from x)
+        uint16_t *slab = workspace_bytes >= w.bytes ? reinterpret_cast<uint16_t *>(wsb + w.slab) : nullptr;
+        zsort_points(x, n, hist, order, slab, st);
         const int64_t tiles = (n + kTileS - 1) / kTileS;
         const unsigned grid = (unsigned)(tiles < kZGrid ? ((tiles + 7) / 8) * 8 : kZGrid);
         const int rc = hm_frac_dispatch(frac_mode, [&](auto frac) {
@@ -1180,27 +1179,27 @@ static int encode_fwd_impl(const hm_grid_desc *desc, const float *x, int64_t n, 
         const int64_t tiles = (n + kTile - 1) / kTile;
         HM_CHECK_ARG(tiles <= 0x7fffffffLL, "hm_encode_fwd: n too large for one launch");
         const size_t lds = sizeof(float) * (size_t)(kTile * width + kTile * 3);
-        if (frac_mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(encode_fwd_f2_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)tiles), dim3(kThreads), lds,
+        hm_frac_dispatch(frac_mode, [&](auto frac) {
+            hipLaunchKernelGGL(encode_fwd_f2_kernel<decltype(frac)::value>, dim3((unsigned)tiles), dim3(kThreads), lds,
                                as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
                                out_stride);
-        else
-            hipLaunchKernelGGL(encode_fwd_f2_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)tiles), dim3(kThreads), lds,
-                               as_stream(stream), lv, x, n, reinterpret_cast<const float2 *>(table), B_fourier, out,
-                               out_stride);
+        });
     } else {
         const int64_t threads = n * (lv.L + 1);
         const int64_t grid = (threads + kThreads - 1) / kThreads;
         HM_CHECK_ARG(grid <= 0x7fffffffLL, "hm_encode_fwd: n too large for one launch");
-        if (frac_mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(encode_fwd_generic_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kThreads), 0,
+        hm_frac_dispatch(frac_mode, [&](auto frac) {
+            hipLaunchKernelGGL(encode_fwd_generic_kernel<decltype(frac)::value>, dim3((unsigned)grid), dim3(kThreads), 0,
                                as_stream(stream), lv, x, n, table, B_fourier, out, out_stride);
-        else
-            hipLaunchKernelGGL(encode_fwd_generic_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kThreads), 0,
-                               as_stream(stream), lv, x, n, table, B_fourier, out, out_stride);
+        });
     }
     HM_CHECK_LAUNCH("hm_encode_fwd");
     return HM_OK;
+}
+
+int hm_encode_fwd(const hm_grid_desc *desc, const float *x, int64_t n, const float *table, const float *B_fourier,
+                  float *out, int64_t out_stride, int frac_mode, void *stream) {
+    return hm_encode_fwd_ws(desc, x, n, table, B_fourier, out, out_stride, frac_mode, nullptr, 0, stream);
 }
 
 int hm_encode_bwd_table(const hm_grid_desc *desc, const float *x, int64_t n, const float *d_feat,
@@ -1220,21 +1219,16 @@ int hm_encode_bwd_table(const hm_grid_desc *desc, const float *x, int64_t n, con
         // small table, many contributions: LDS-privatised sums, at most 64 workgroups
         const unsigned g_small = (unsigned)(grid < 64 ? grid : 64);
         const size_t lds = sizeof(float) * (size_t)desc->total_rows * lv.F;
-        if (frac_mode == HM_FRAC_REFERENCE)
-            hipLaunchKernelGGL(encode_bwd_table_small_kernel<HM_FRAC_REFERENCE>, dim3(g_small), dim3(kThreads), lds,
+        hm_frac_dispatch(frac_mode, [&](auto frac) {
+            hipLaunchKernelGGL(encode_bwd_table_small_kernel<decltype(frac)::value>, dim3(g_small), dim3(kThreads), lds,
                                as_stream(stream), lv, x, n, d_feat, d_feat_stride, d_table, (int)desc->total_rows);
-        else
-            hipLaunchKernelGGL(encode_bwd_table_small_kernel<HM_FRAC_TRILINEAR>, dim3(g_small), dim3(kThreads), lds,
-                               as_stream(stream), lv, x, n, d_feat, d_feat_stride, d_table, (int)desc->total_rows);
-        HM_CHECK_LAUNCH("hm_encode_bwd_table");
-        return HM_OK;
+        });
+    } else {
+        hm_frac_dispatch(frac_mode, [&](auto frac) {
+            hipLaunchKernelGGL(encode_bwd_table_kernel<decltype(frac)::value>, dim3((unsigned)grid), dim3(kThreads), 0,
+                               as_stream(stream), lv, x, n, d_feat, d_feat_stride, d_table);
+        });
     }
-    if (frac_mode == HM_FRAC_REFERENCE)
-        hipLaunchKernelGGL(encode_bwd_table_kernel<HM_FRAC_REFERENCE>, dim3((unsigned)grid), dim3(kThreads), 0,
-                           as_stream(stream), lv, x, n, d_feat, d_feat_stride, d_table);
-    else
-        hipLaunchKernelGGL(encode_bwd_table_kernel<HM_FRAC_TRILINEAR>, dim3((unsigned)grid), dim3(kThreads), 0,
-                           as_stream(stream), lv, x, n, d_feat, d_feat_stride, d_table);
     HM_CHECK_LAUNCH("hm_encode_bwd_table");
     return HM_OK;
 }

@@ -268,6 +268,10 @@ __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f3
 // Deterministic split-K form of gemm_f32_kernel (no epilogue): the same main loop, k part blockIdx.z's partial tile goes
 // to its workspace slab (gemm_store_tile<false, true>).  A separate kernel rather than a template parameter of the one
 // above: hipcc schedules that kernel differently once its body is shared, and the default path keeps its instructions.
+// (Tried: the body as a __device__ __forceinline__ template with a PART parameter and both kernels as three-line
+// wrappers changed the instruction stream of all 16 gemm_f32_kernel instances and of the 4 part instances - the plain
+// big-tile NN instance went from 2862 to 3112 instructions, the big-tile epilogue ones from 11.9 - 12.7 k to
+// 14.2 - 15.4 k.  scripts/kernel_isa_diff.py shows such a change without a GPU.)
 template <int TM, int TN, int BK, int KS, bool VA, bool VB, int WM = 2>
 __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f32_part_kernel(GemmArgs g) {
     constexpr int BM = 32 * WM * TM, BN = 64 * TN, NT = 128 * WM * KS, WG = 2 * WM;  // WG = waves per k part
@@ -670,6 +674,7 @@ struct GemmPlan {
     bool k_tail;        // pipelined kernel on a K that is no multiple of the stage group (KT instantiation)
     bool vecA, vecB;    // generic / big kernel: 16-byte operand loads
     int64_t bm, bn, split, k_chunk;
+    int64_t bytesA, bytesB;   // extent of each operand from its base (the pipelined kernels' buffer descriptors)
 };
 static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t K, const void *A, int64_t lda,
                           const void *B, int64_t ldb, bool has_ep) {
@@ -694,9 +699,9 @@ static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t 
     // dimension qualify, and a K TAIL is admitted when one operand has k as its slow dimension: the K range runs to the
     // next multiple of the stage group, that operand's descriptor returns zeros beyond its end and the KT instantiation
     // zeroes the other's k >= K elements (K = 445 and 257 of the backward sweeps: 27 - 43 us on the generic kernel).
-    const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
-                  bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
-    const bool buf_ok = bytesA < (1ll << 31) && bytesB < (1ll << 31);
+    P.bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K));
+    P.bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
+    const bool buf_ok = P.bytesA < (1ll << 31) && P.bytesB < (1ll << 31);
     const bool k_whole = K % (kPipeBK * kPipeD) == 0;
     // (K >= 192: below that the rounded-up range costs more than the generic kernel's guards - K = 72 of the filter banks)
     // (and only where the generic kernel would not split K over workgroups: a tail runs as ONE chunk, so the small
@@ -778,16 +783,13 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     g.M = (int)M; g.N = (int)N; g.K = (int)K;
     g.transA = transA; g.transB = transB;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    const bool a_kc = !transA, b_kc = transB != 0;
     const GemmPlan P = gemm_plan(transA, transB, M, N, K, A, lda, B, ldb, g.ep.mode != HM_EPI_NONE);
     g.vecA = P.vecA ? 1 : 0;
     g.vecB = P.vecB ? 1 : 0;
     const bool big = P.big, m96 = P.m96, pipe_ok = P.pipe_ok;
     const int64_t bm = P.bm, bn = P.bn, split = P.split;
-    const int64_t bytesA = 4 * ((transA ? K - 1 : M - 1) * lda + (transA ? M : K)),
-                  bytesB = 4 * ((transB ? N - 1 : K - 1) * ldb + (transB ? K : N));
-    g.nrecA = (int32_t)(bytesA < 0x7fffffff ? bytesA : 0x7fffffff);
-    g.nrecB = (int32_t)(bytesB < 0x7fffffff ? bytesB : 0x7fffffff);
+    g.nrecA = (int32_t)(P.bytesA < 0x7fffffff ? P.bytesA : 0x7fffffff);
+    g.nrecB = (int32_t)(P.bytesB < 0x7fffffff ? P.bytesB : 0x7fffffff);
     g.k_chunk = (int)P.k_chunk;
     const bool part = det && split > 1;
     if (part) {
@@ -803,93 +805,57 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
     }
     dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)((N + bn - 1) / bn), (unsigned)split);
     HM_CHECK_ARG(grid.y <= 65535u && grid.z <= 65535u, "hm_gemm_f32: N or split too large for one launch");
-#define HM_GEMM_LAUNCH(TM_, TN_, BK_, KS_, WM_)                                                                     \
-    do {                                                                                                        \
-        if (g.ep.mode != HM_EPI_NONE) {                                                                         \
-            if (g.vecA && g.vecB)                                                                               \
-                hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, true, true, true, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-            else if (g.vecA)                                                                                    \
-                hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, true, false, true, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-            else if (g.vecB)                                                                                    \
-                hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, false, true, true, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-            else                                                                                                \
-                hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, false, false, true, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-        } else if (g.vecA && g.vecB)                                                                            \
-            hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, true, true, false, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-        else if (g.vecA)                                                                                        \
-            hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, true, false, false, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-        else if (g.vecB)                                                                                        \
-            hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, false, true, false, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-        else                                                                                                    \
-            hipLaunchKernelGGL((gemm_f32_kernel<TM_, TN_, BK_, KS_, false, false, false, WM_>), grid, dim3(128 * WM_ * KS_), 0, st, g); \
-    } while (0)
     hipStream_t st = as_stream(stream);
+    const bool ep_on = g.ep.mode != HM_EPI_NONE;
+    // every kernel instance is named once below: the run-time choices become template values, one launch form
+    auto launch = [&](auto kernel, unsigned threads) { hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, st, g); };
+    if (big || !pipe_ok) {   // tile kernels: 16-byte operand loads are template values
+        hm_bool_dispatch(P.vecA, [&](auto va) {
+            hm_bool_dispatch(P.vecB, [&](auto vb) {
+                constexpr bool VA = decltype(va)::value, VB = decltype(vb)::value;
+                // (big tiles are never split: they are taken only when the tile grid alone fills the chip)
+                if (part) return launch(gemm_f32_part_kernel<1, 1, 128, 2, VA, VB>, 512);
+                hm_bool_dispatch(ep_on, [&](auto ep_c) {
+                    constexpr bool EP = decltype(ep_c)::value;
+                    if (big) launch(gemm_f32_kernel<2, 2, 32, 1, VA, VB, EP, 2>, 256);
+                    else launch(gemm_f32_kernel<1, 1, 128, 2, VA, VB, EP, 2>, 512);
+                });
+            });
+        });
+    } else {   // pipelined kernels: which operands are k-contiguous
+        hm_bool_dispatch(!transA, [&](auto akc) {
+            hm_bool_dispatch(transB != 0, [&](auto bkc) {
+                constexpr bool AKC = decltype(akc)::value, BKC = decltype(bkc)::value;
+                if (part) {
+                    if (m96) launch(gemm_f32_pipe2_m96_part_kernel<AKC, BKC>, 768);
+                    else launch(gemm_f32_pipe2_part_kernel<AKC, BKC>, 512);
+                    return;
+                }
+                hm_bool_dispatch(ep_on, [&](auto ep_c) {
+                    constexpr bool EP = decltype(ep_c)::value;
+                    // (a K tail has at most one k-contiguous operand; with none, the descriptors alone zero the
+                    // k >= K products, so the K-tail instances exist for exactly one k-contiguous operand)
+                    if constexpr (AKC != BKC) {
+                        if (P.k_tail) {
+                            if (m96) launch(gemm_f32_pipe2_m96_ktail_kernel<AKC, BKC, EP>, 768);
+                            else launch(gemm_f32_pipe2_ktail_kernel<AKC, BKC, EP>, 512);
+                            return;
+                        }
+                    }
+                    if (m96) launch(gemm_f32_pipe2_m96_kernel<AKC, BKC, EP>, 768);
+                    else launch(gemm_f32_pipe2_kernel<AKC, BKC, EP>, 512);
+                });
+            });
+        });
+    }
     if (part) {
-        // (big tiles are never split: they are taken only when the tile grid alone fills the chip)
-        if (pipe_ok) {
-#define HM_PART_PIPE(AKC_, BKC_)                                                                                   \
-    do {                                                                                                          \
-        if (m96) hipLaunchKernelGGL((gemm_f32_pipe2_m96_part_kernel<AKC_, BKC_>), grid, dim3(768), 0, st, g);     \
-        else hipLaunchKernelGGL((gemm_f32_pipe2_part_kernel<AKC_, BKC_>), grid, dim3(512), 0, st, g);             \
-    } while (0)
-            if (a_kc && b_kc) HM_PART_PIPE(true, true);
-            else if (a_kc) HM_PART_PIPE(true, false);
-            else if (b_kc) HM_PART_PIPE(false, true);
-            else HM_PART_PIPE(false, false);
-#undef HM_PART_PIPE
-        } else if (g.vecA && g.vecB)
-            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, true, true>), grid, dim3(512), 0, st, g);
-        else if (g.vecA)
-            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, true, false>), grid, dim3(512), 0, st, g);
-        else if (g.vecB)
-            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, false, true>), grid, dim3(512), 0, st, g);
-        else
-            hipLaunchKernelGGL((gemm_f32_part_kernel<1, 1, 128, 2, false, false>), grid, dim3(512), 0, st, g);
         GemmReduceTable t;
         t.n = 1;
         t.end = M * N;
         t.e[0] = GemmReduceEntry{ws, C, ldc, 0, (int32_t)M, (int32_t)N, (int32_t)split, accumulate ? 1 : 0};
         const int rc = launch_part_reduce(t, st);
         if (rc != HM_OK) return rc;
-    } else if (big)
-        HM_GEMM_LAUNCH(2, 2, 32, 1, 2);
-    else if (pipe_ok) {
-#define HM_PIPE_LAUNCH(AKC_, BKC_)                                                                                \
-    do {                                                                                                          \
-        if (m96) {                                                                                                \
-            if (g.ep.mode != HM_EPI_NONE)                                                                         \
-                hipLaunchKernelGGL((gemm_f32_pipe2_m96_kernel<AKC_, BKC_, true>), grid, dim3(768), 0, st, g);     \
-            else                                                                                                  \
-                hipLaunchKernelGGL((gemm_f32_pipe2_m96_kernel<AKC_, BKC_, false>), grid, dim3(768), 0, st, g);    \
-        } else if (g.ep.mode != HM_EPI_NONE)                                                                      \
-            hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, true>), grid, dim3(512), 0, st, g);             \
-        else                                                                                                      \
-            hipLaunchKernelGGL((gemm_f32_pipe2_kernel<AKC_, BKC_, false>), grid, dim3(512), 0, st, g);            \
-    } while (0)
-#define HM_PIPE_KTAIL_LAUNCH(AKC_, BKC_)                                                                          \
-    do {                                                                                                          \
-        if (m96) {                                                                                                \
-            if (g.ep.mode != HM_EPI_NONE)                                                                         \
-                hipLaunchKernelGGL((gemm_f32_pipe2_m96_ktail_kernel<AKC_, BKC_, true>), grid, dim3(768), 0, st, g); \
-            else                                                                                                  \
-                hipLaunchKernelGGL((gemm_f32_pipe2_m96_ktail_kernel<AKC_, BKC_, false>), grid, dim3(768), 0, st, g); \
-        } else if (g.ep.mode != HM_EPI_NONE)                                                                      \
-            hipLaunchKernelGGL((gemm_f32_pipe2_ktail_kernel<AKC_, BKC_, true>), grid, dim3(512), 0, st, g);       \
-        else                                                                                                      \
-            hipLaunchKernelGGL((gemm_f32_pipe2_ktail_kernel<AKC_, BKC_, false>), grid, dim3(512), 0, st, g);      \
-    } while (0)
-        // (a K tail has at most one k-contiguous operand; with none, the descriptors alone zero the k >= K products)
-        if (a_kc && b_kc) HM_PIPE_LAUNCH(true, true);
-        else if (a_kc && P.k_tail) HM_PIPE_KTAIL_LAUNCH(true, false);
-        else if (a_kc) HM_PIPE_LAUNCH(true, false);
-        else if (b_kc && P.k_tail) HM_PIPE_KTAIL_LAUNCH(false, true);
-        else if (b_kc) HM_PIPE_LAUNCH(false, true);
-        else HM_PIPE_LAUNCH(false, false);
-#undef HM_PIPE_KTAIL_LAUNCH
-#undef HM_PIPE_LAUNCH
-    } else
-        HM_GEMM_LAUNCH(1, 1, 128, 2, 2);
-#undef HM_GEMM_LAUNCH
+    }
     HM_CHECK_LAUNCH("hm_gemm_f32");
     return HM_OK;
 }
@@ -900,56 +866,6 @@ int hm_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, const f
                 const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc, int accumulate,
                 void *stream) {
     return gemm_impl(transA, transB, M, N, K, A, lda, B, ldb, bias, C, ldc, accumulate, nullptr, stream);
-}
-
-int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, void *stream) {
-    HM_CHECK_ARG(n_items >= 0 && (n_items == 0 || items), "hm_gemm_f32_group_tn: bad argument");
-    GemmGroupTable t;
-    t.n = 0;
-    t.start[0] = 0;
-    auto flush = [&]() -> int {
-        if (t.n > 0) {
-            hipLaunchKernelGGL(gemm_f32_pipe2_group_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, as_stream(stream), t);
-            HM_CHECK_LAUNCH("hm_gemm_f32_group_tn");
-        }
-        t.n = 0;
-        t.start[0] = 0;
-        return HM_OK;
-    };
-    for (int i = 0; i < n_items; ++i) {
-        const hm_gemm_group_item &it = items[i];
-        HM_CHECK_ARG(it.M >= 0 && it.N >= 0 && it.K >= 0 && it.M < (1ll << 31) && it.N < (1ll << 31) && it.K < (1ll << 31),
-                     "hm_gemm_f32_group_tn: bad dimension");
-        if (it.M == 0 || it.N == 0 || it.K == 0) continue;
-        HM_CHECK_ARG(it.A && it.B && it.C && it.lda >= it.M && it.ldb >= it.N && it.ldc >= it.N,
-                     "hm_gemm_f32_group_tn: NULL operand or leading dimension");
-        if (it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31)) {
-            // no K tail in the pipelined kernel, 32-bit operand offsets: such a problem goes alone
-            const int rc = gemm_impl(1, 0, it.M, it.N, it.K, it.A, it.lda, it.B, it.ldb, nullptr, it.C, it.ldc, 1, nullptr, stream);
-            if (rc != HM_OK) return rc;
-            continue;
-        }
-        if (t.n == HM_GEMM_GROUP_MAX) {
-            const int rc = flush();
-            if (rc != HM_OK) return rc;
-        }
-        GemmGroupEntry &E = t.e[t.n];
-        E.A = it.A; E.B = it.B; E.C = it.C;
-        E.lda = it.lda; E.ldb = it.ldb; E.ldc = it.ldc;
-        E.M = (int32_t)it.M; E.N = (int32_t)it.N;
-        E.tiles_m = (int32_t)((it.M + 63) / 64);
-        E.tiles_n = (int32_t)((it.N + 63) / 64);
-        // k parts of >= 1024 (eight 128-deep groups) that divide K
-        int64_t split = it.K / 1024;
-        if (split < 1) split = 1;
-        if (split > 4) split = 4;
-        while (split > 1 && (it.K % split != 0 || (it.K / split) % (kPipeBK * kPipeD) != 0)) --split;
-        E.split = (int32_t)split;
-        E.k_chunk = (int32_t)(it.K / split);
-        t.start[t.n + 1] = t.start[t.n] + E.tiles_m * E.tiles_n * E.split;
-        ++t.n;
-    }
-    return flush();
 }
 
 int64_t hm_gemm_f32_det_workspace_bytes(int transA, int transB, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
@@ -982,13 +898,16 @@ int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t K, con
                      static_cast<float *>(workspace), workspace_bytes);
 }
 
-// Deterministic grouped call: the same problem table and k parts as hm_gemm_f32_group_tn, partials to workspace slabs
-// (one launch), then one gemm_part_reduce_kernel launch for all problems of the table.  With run = false only the
-// workspace need is computed (hm_gemm_f32_group_tn_det_workspace_bytes): the largest table's slabs, or the largest need
-// of a problem that goes alone - the launches of a call follow each other on one stream, so they share the buffer.
-static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws, int64_t ws_bytes, void *stream, bool run,
-                        int64_t *need) {
-    HM_CHECK_ARG(n_items >= 0 && (n_items == 0 || items), "hm_gemm_f32_group_tn_det: bad argument");
+// The grouped calls: ONE routine builds the problem table, so that the deterministic mode sums the partials of the very
+// k parts the default mode adds with atomics.  Default (det = false): every table of up to HM_GEMM_GROUP_MAX problems
+// is one gemm_f32_pipe2_group_kernel launch that adds into the callers' C (overlapping C windows are fine: atomics).
+// Deterministic: partials go to workspace slabs (one launch), then one gemm_part_reduce_kernel launch serves all
+// problems of the table.  With run = false only the workspace need is computed
+// (hm_gemm_f32_group_tn_det_workspace_bytes): the largest table's slabs, or the largest need of a problem that goes
+// alone - the launches of a call follow each other on one stream, so they share the buffer.  who: the entry point.
+static int group_tn(const char *who, const hm_gemm_group_item *items, int n_items, bool det, float *ws, int64_t ws_bytes,
+                    void *stream, bool run, int64_t *need) {
+    HM_CHECK_ARG(n_items >= 0 && (n_items == 0 || items), std::string(who) + ": bad argument");
     *need = 0;
     // byte window of a problem's C: the reduce kernel gives every C element ONE thread, so two problems of one table
     // must not overlap - a problem that overlaps one already in the table starts the next table (the two sums are then
@@ -1000,7 +919,7 @@ static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws,
     int in_table[HM_GEMM_GROUP_MAX];   // item index of every table entry
     GemmGroupTable t;
     GemmReduceTable r;
-    int64_t off = 0;   // floats of workspace the current table uses
+    int64_t off = 0;   // floats of workspace the current table uses (deterministic)
     t.n = r.n = 0;
     t.start[0] = 0;
     r.end = 0;
@@ -1008,13 +927,16 @@ static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws,
     auto flush = [&]() -> int {
         if (4 * off > *need) *need = 4 * off;
         if (t.n > 0 && run) {
-            HM_CHECK_ARG(ws != nullptr && ws_bytes >= 4 * off, "hm_gemm_f32_group_tn_det: workspace too small");
-            for (int p = 0; p < t.n; ++p) t.e[p].C = ws + reinterpret_cast<uintptr_t>(t.e[p].C);   // slab offsets -> pointers
-            for (int p = 0; p < r.n; ++p) r.e[p].P = ws + reinterpret_cast<uintptr_t>(r.e[p].P);
-            hipLaunchKernelGGL(gemm_f32_pipe2_group_part_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
-            const int rc = launch_part_reduce(r, st);
-            if (rc != HM_OK) return rc;
-            HM_CHECK_LAUNCH("hm_gemm_f32_group_tn_det");
+            if (det) {
+                HM_CHECK_ARG(ws != nullptr && ws_bytes >= 4 * off, std::string(who) + ": workspace too small");
+                for (int p = 0; p < t.n; ++p) t.e[p].C = ws + reinterpret_cast<uintptr_t>(t.e[p].C);   // slab offsets -> pointers
+                for (int p = 0; p < r.n; ++p) r.e[p].P = ws + reinterpret_cast<uintptr_t>(r.e[p].P);
+                hipLaunchKernelGGL(gemm_f32_pipe2_group_part_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
+                const int rc = launch_part_reduce(r, st);
+                if (rc != HM_OK) return rc;
+            } else
+                hipLaunchKernelGGL(gemm_f32_pipe2_group_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
+            HM_CHECK_LAUNCH(who);
         }
         t.n = r.n = 0;
         t.start[0] = 0;
@@ -1025,23 +947,25 @@ static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws,
     for (int i = 0; i < n_items; ++i) {
         const hm_gemm_group_item &it = items[i];
         HM_CHECK_ARG(it.M >= 0 && it.N >= 0 && it.K >= 0 && it.M < (1ll << 31) && it.N < (1ll << 31) && it.K < (1ll << 31),
-                     "hm_gemm_f32_group_tn_det: bad dimension");
+                     std::string(who) + ": bad dimension");
         if (it.M == 0 || it.N == 0 || it.K == 0) continue;
         HM_CHECK_ARG(!run || (it.A && it.B && it.C && it.lda >= it.M && it.ldb >= it.N && it.ldc >= it.N),
-                     "hm_gemm_f32_group_tn_det: NULL operand or leading dimension");
+                     std::string(who) + ": NULL operand or leading dimension");
         if (it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31)) {
-            // the same problems as in hm_gemm_f32_group_tn go alone
-            const int64_t b = gemm_det_bytes(gemm_plan(1, 0, it.M, it.N, it.K, nullptr, it.lda, nullptr, it.ldb, false), it.M, it.N);
-            if (b > *need) *need = b;
+            // no K tail in the pipelined kernel, 32-bit operand offsets: such a problem goes alone
+            if (det) {
+                const int64_t b = gemm_det_bytes(gemm_plan(1, 0, it.M, it.N, it.K, nullptr, it.lda, nullptr, it.ldb, false), it.M, it.N);
+                if (b > *need) *need = b;
+            }
             if (run) {
                 const int rc = gemm_impl(1, 0, it.M, it.N, it.K, it.A, it.lda, it.B, it.ldb, nullptr, it.C, it.ldc, 1,
-                                         nullptr, stream, true, ws, ws_bytes);
+                                         nullptr, stream, det, ws, ws_bytes);
                 if (rc != HM_OK) return rc;
             }
             continue;
         }
         bool overlap = false;
-        for (int p = 0; p < t.n && !overlap; ++p) {
+        for (int p = 0; det && p < t.n && !overlap; ++p) {
             uintptr_t a0, a1, b0, b1;
             window(it, a0, a1);
             window(items[in_table[p]], b0, b1);
@@ -1052,40 +976,49 @@ static int group_tn_det(const hm_gemm_group_item *items, int n_items, float *ws,
             if (rc != HM_OK) return rc;
         }
         in_table[t.n] = i;
-        int64_t split = it.K / 1024;     // k parts as in hm_gemm_f32_group_tn
+        // k parts of >= 1024 (eight 128-deep groups) that divide K
+        int64_t split = it.K / 1024;
         if (split < 1) split = 1;
         if (split > 4) split = 4;
         while (split > 1 && (it.K % split != 0 || (it.K / split) % (kPipeBK * kPipeD) != 0)) --split;
         GemmGroupEntry &E = t.e[t.n];
         E.A = it.A; E.B = it.B;
-        E.C = reinterpret_cast<float *>(static_cast<uintptr_t>(off));   // slab offset until flush
-        E.lda = it.lda; E.ldb = it.ldb; E.ldc = it.N;
+        E.C = det ? reinterpret_cast<float *>(static_cast<uintptr_t>(off)) : it.C;   // (slab offset until flush)
+        E.lda = it.lda; E.ldb = it.ldb; E.ldc = det ? it.N : it.ldc;
         E.M = (int32_t)it.M; E.N = (int32_t)it.N;
         E.tiles_m = (int32_t)((it.M + 63) / 64);
         E.tiles_n = (int32_t)((it.N + 63) / 64);
         E.split = (int32_t)split;
         E.k_chunk = (int32_t)(it.K / split);
         t.start[t.n + 1] = t.start[t.n] + E.tiles_m * E.tiles_n * E.split;
-        r.e[r.n] = GemmReduceEntry{reinterpret_cast<const float *>(static_cast<uintptr_t>(off)), it.C, it.ldc, r.end,
-                                   (int32_t)it.M, (int32_t)it.N, (int32_t)split, 1};
-        r.end += it.M * it.N;
-        off += split * it.M * it.N;
         ++t.n;
-        ++r.n;
+        if (det) {
+            r.e[r.n] = GemmReduceEntry{reinterpret_cast<const float *>(static_cast<uintptr_t>(off)), it.C, it.ldc, r.end,
+                                       (int32_t)it.M, (int32_t)it.N, (int32_t)split, 1};
+            r.end += it.M * it.N;
+            off += split * it.M * it.N;
+            ++r.n;
+        }
     }
     return flush();
 }
 
+int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, void *stream) {
+    int64_t need = 0;
+    return group_tn("hm_gemm_f32_group_tn", items, n_items, false, nullptr, 0, stream, true, &need);
+}
+
 int64_t hm_gemm_f32_group_tn_det_workspace_bytes(const hm_gemm_group_item *items, int n_items) {
     int64_t need = 0;
-    if (group_tn_det(items, n_items, nullptr, 0, nullptr, false, &need) != HM_OK) return -1;
+    if (group_tn("hm_gemm_f32_group_tn_det", items, n_items, true, nullptr, 0, nullptr, false, &need) != HM_OK) return -1;
     return need;
 }
 
 int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void *workspace, int64_t workspace_bytes,
                              void *stream) {
     int64_t need = 0;
-    return group_tn_det(items, n_items, static_cast<float *>(workspace), workspace_bytes, stream, true, &need);
+    return group_tn("hm_gemm_f32_group_tn_det", items, n_items, true, static_cast<float *>(workspace), workspace_bytes,
+                    stream, true, &need);
 }
 
 int hm_gemm_f32_ep(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,

@@ -524,12 +524,11 @@ int hm_nffb_fwd(const hm_grid_desc *desc, const hm_nffb_desc *nf, const float *x
     a.bound = nf->bound; a.w0 = nf->w0; a.style_eps = nf->style_eps;
     const bool style = nf->style_w != nullptr;
     hipStream_t st = as_stream(stream);
-    int rc;
-#define HM_NFFB(FR)                                                                                                    \
-    rc = (lv.L == 6) ? launch_nffb<FR, 6>(style, st, lv, a, x, n, table, B_fourier, out, out_stride, n_dev)            \
-                     : launch_nffb<FR, 8>(style, st, lv, a, x, n, table, B_fourier, out, out_stride, n_dev)
-    if (frac_mode == HM_FRAC_REFERENCE) { HM_NFFB(HM_FRAC_REFERENCE); } else { HM_NFFB(HM_FRAC_TRILINEAR); }
-#undef HM_NFFB
+    const int rc = hm_frac_dispatch(frac_mode, [&](auto frac) {
+        constexpr int FR = decltype(frac)::value;
+        return lv.L == 6 ? launch_nffb<FR, 6>(style, st, lv, a, x, n, table, B_fourier, out, out_stride, n_dev)
+                         : launch_nffb<FR, 8>(style, st, lv, a, x, n, table, B_fourier, out, out_stride, n_dev);
+    });
     if (rc != HM_OK) return rc;
     HM_CHECK_LAUNCH("hm_nffb_fwd");
     return HM_OK;

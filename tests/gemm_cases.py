@@ -49,7 +49,7 @@ def vec_expected(case, which):
 
 
 def instantiation(case, info):
-    """the kernel template instance a planned call launches (hm_gemm.hip's launch macros)"""
+    """the kernel template instance a planned call launches (the kernel choice at the end of hm_gemm.hip's gemm_impl)"""
     akc, bkc, ep = int(not case.ta), int(case.tb), int(case.ep is not None)
     fam = FAMILY[info.kernel]
     if info.part:
