@@ -101,6 +101,12 @@ SIGNATURES = {
     "hm_mc_count": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _i64, _p, _p]),
     "hm_mc_emit": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_float, _p, _p, _i64, _i64, _i64, _p, _p, _p,
                           _p]),
+    "hm_mcs_points_bricks": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "hm_mcs_points_index": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "hm_mcs_status": (_int, [_p, _i64, _p, C.c_float, _p, _p]),
+    "hm_mcs_workspace_bytes": (_i64, [_i64]),
+    "hm_mcs_count": (_int, [_p, _i64, _p, C.c_float, _p, _i64, _p, _p]),
+    "hm_mcs_emit": (_int, [_p, _i64, _p, _p, C.c_float, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p]),
 }
 
 
@@ -167,6 +173,11 @@ class NffbDesc(C.Structure):
 
 class MlpDesc(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("beta", C.c_float), ("layer", MlpLayer * 16), ("split_kind", C.c_int32)]
+
+
+class McsLattice(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("n_slots", C.c_int64),
+                ("map", C.c_void_p), ("pool", C.c_void_p)]
 
 
 class HashmodError(RuntimeError):

@@ -13,15 +13,11 @@
 // Order of the outputs: vertices by owning point (linear index (i*ny + j)*nz + k), then axis x < y < z; faces by cell
 // linear index, then table order - independent of the volume's strides.  No atomics: two calls give the same bits.
 // Workspace: 2 B (code) + 4 B (vbase) per lattice point + 32 B per block.
-#include "hm_common.h"
+// The scans, the gradient and the vertex arithmetic are in hm_mesh_dev.h, shared with hm_mesh_sparse.hip.
 #include "hm_mc_table.h"
+#include "hm_mesh_dev.h"
 
 namespace {
-
-constexpr int kMT = 256;                  // threads per workgroup
-constexpr int kMRounds = 16;              // rounds of kMT consecutive points per workgroup
-constexpr int kMBlock = kMT * kMRounds;   // 4096 lattice points per workgroup
-constexpr int kScanT = 1024;
 
 struct McVol {
     const float *v;
@@ -32,29 +28,6 @@ struct McVol {
     }
 };
 
-struct McWs {
-    uint16_t *code;      // [n] bits 0-7 cell case (0 on the upper faces), bits 8-10 crossing axes
-    int32_t *vbase;      // [n]
-    int32_t *bsum;       // [3][nb] vertex sum, triangle sum, NaN bit per block
-    int64_t *boff;       // [2][nb] exclusive block offsets of vertices and triangles
-};
-
-inline int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
-
-McWs carve(void *ws, int64_t n) {
-    const int64_t nb = (n + kMBlock - 1) / kMBlock;
-    char *p = static_cast<char *>(ws);
-    McWs w;
-    w.code = reinterpret_cast<uint16_t *>(p);
-    p += up256(2 * n);
-    w.vbase = reinterpret_cast<int32_t *>(p);
-    p += up256(4 * n);
-    w.bsum = reinterpret_cast<int32_t *>(p);
-    p += up256(12 * nb);
-    w.boff = reinterpret_cast<int64_t *>(p);
-    return w;
-}
-
 __device__ __forceinline__ void mc_point(int64_t q, const McVol &V, int &i, int &j, int &k) {
     const uint32_t u = (uint32_t)q;
     k = (int)(u % (uint32_t)V.nz);
@@ -63,32 +36,8 @@ __device__ __forceinline__ void mc_point(int64_t q, const McVol &V, int &i, int 
     i = (int)(r / (uint32_t)V.ny);
 }
 
-// exclusive prefix of x over the workgroup's threads (in thread order) and the workgroup total
-__device__ __forceinline__ int block_excl_scan(int x, int *lds_waves, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int s = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(s, o, 64);
-        if (lane >= o) s += y;
-    }
-    if (lane == 63) lds_waves[wave] = s;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kMT / 64; ++w) {
-        const int t = lds_waves[w];
-        before += w < wave ? t : 0;
-        total += t;
-    }
-    __syncthreads();
-    return before + s - x;
-}
-
 __global__ __launch_bounds__(kMT) void mc_classify_kernel(McVol V, float level, int64_t n, uint16_t *__restrict__ code,
                                                           int32_t *__restrict__ bsum, int64_t nb) {
-    __shared__ int red[3][kMT / 64];
     const int64_t beg = (int64_t)blockIdx.x * kMBlock;
     int nv = 0, nt = 0, nan = 0;
     for (int r = 0; r < kMRounds; ++r) {
@@ -117,80 +66,7 @@ __global__ __launch_bounds__(kMT) void mc_classify_kernel(McVol V, float level, 
         nv += __popc(mask);
         nt += hm_mc_tris[cs][0];
     }
-    // workgroup sums (fixed order: wave reduction, then the waves in order)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_xor(nv, o, 64);
-        nt += __shfl_xor(nt, o, 64);
-        nan |= __shfl_xor(nan, o, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = nv;
-        red[1][wave] = nt;
-        red[2][wave] = nan;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        int s = 0;
-        for (int w = 0; w < kMT / 64; ++w) s = threadIdx.x == 2 ? (s | red[2][w]) : s + red[threadIdx.x][w];
-        bsum[threadIdx.x * nb + blockIdx.x] = s;
-    }
-}
-
-// exclusive prefix of the block sums (int64), totals[0..2] = vertices, triangles, NaN flag
-__global__ __launch_bounds__(kScanT) void mc_scan_kernel(const int32_t *__restrict__ bsum, int64_t nb,
-                                                         int64_t *__restrict__ boff, int64_t *__restrict__ totals) {
-    __shared__ int64_t pv[kScanT], pt[kScanT];
-    __shared__ int pn[kScanT];
-    const int64_t per = (nb + kScanT - 1) / kScanT;
-    const int64_t beg = min((int64_t)threadIdx.x * per, nb), end = min(beg + per, nb);
-    int64_t sv = 0, st = 0;
-    int nan = 0;
-    for (int64_t b = beg; b < end; ++b) {
-        sv += bsum[b];
-        st += bsum[nb + b];
-        nan |= bsum[2 * nb + b];
-    }
-    pv[threadIdx.x] = sv;
-    pt[threadIdx.x] = st;
-    pn[threadIdx.x] = nan;
-    __syncthreads();
-    for (int o = 1; o < kScanT; o <<= 1) {
-        const int64_t av = (int)threadIdx.x >= o ? pv[threadIdx.x - o] : 0;
-        const int64_t at = (int)threadIdx.x >= o ? pt[threadIdx.x - o] : 0;
-        const int an = (int)threadIdx.x >= o ? pn[threadIdx.x - o] : 0;
-        __syncthreads();
-        pv[threadIdx.x] += av;
-        pt[threadIdx.x] += at;
-        pn[threadIdx.x] |= an;
-        __syncthreads();
-    }
-    int64_t rv = pv[threadIdx.x] - sv, rt = pt[threadIdx.x] - st;
-    for (int64_t b = beg; b < end; ++b) {
-        boff[b] = rv;
-        boff[nb + b] = rt;
-        rv += bsum[b];
-        rt += bsum[nb + b];
-    }
-    if (threadIdx.x == kScanT - 1) {
-        totals[0] = pv[kScanT - 1];
-        totals[1] = pt[kScanT - 1];
-        totals[2] = pn[kScanT - 1];
-    }
-}
-
-// central difference along each axis (one-sided at the border) over the spacing: numpy.gradient's rule
-__device__ __forceinline__ void mc_grad(const McVol &V, int i, int j, int k, const float (&sp)[3], float (&g)[3]) {
-    const int n[3] = {V.nx, V.ny, V.nz};
-    const int p[3] = {i, j, k};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const int lo = p[a] > 0 ? p[a] - 1 : p[a], hi = p[a] + 1 < n[a] ? p[a] + 1 : p[a];
-        const float vlo = V.at(a == 0 ? lo : i, a == 1 ? lo : j, a == 2 ? lo : k);
-        const float vhi = V.at(a == 0 ? hi : i, a == 1 ? hi : j, a == 2 ? hi : k);
-        g[a] = (vhi - vlo) / ((float)(hi - lo) * sp[a]);
-    }
+    mc_block_sums(nv, nt, nan, bsum, nb);
 }
 
 __global__ __launch_bounds__(kMT) void mc_verts_kernel(McVol V, float level, float spx, float spy, float spz, int64_t n,
@@ -218,21 +94,13 @@ __global__ __launch_bounds__(kMT) void mc_verts_kernel(McVol V, float level, flo
                 mc_grad(V, i, j, k, sp, g0);
                 for (int ax = 0; ax < 3; ++ax) {
                     if (!((mask >> ax) & 1)) continue;
-                    const int i1 = i + (ax == 0), j1 = j + (ax == 1), k1 = k + (ax == 2);
-                    const float b = V.at(i1, j1, k1);
-                    const float t = (level - a) / (b - a);
-                    float g1[3], nn[3];
-                    mc_grad(V, i1, j1, k1, sp, g1);
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) nn[m] = g0[m] + t * (g1[m] - g0[m]);
-                    const float d = nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2];
-                    const float s = sqrtf(d);
+                    float pos[3], nrm[3];
+                    mc_vertex(V, level, sp, i, j, k, ax, a, g0, pos, nrm);
                     if (vi < cap_v) {
-                        const int id[3] = {i, j, k};
 #pragma unroll
                         for (int m = 0; m < 3; ++m) {
-                            verts[vi * 3 + m] = (m == ax ? (float)id[m] + t : (float)id[m]) * sp[m];
-                            normals[vi * 3 + m] = d > 0.0f ? nn[m] / s : 0.0f;
+                            verts[vi * 3 + m] = pos[m];
+                            normals[vi * 3 + m] = nrm[m];
                         }
                     }
                     ++vi;
@@ -291,8 +159,7 @@ extern "C" {
 int64_t hm_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz) {
     if (nx < 2 || ny < 2 || nz < 2 || nx * ny * nz >= ((int64_t)1 << 31))
         return hm_fail(HM_ERR_INVALID, "hm_mc_workspace_bytes: dimensions must be >= 2 and nx*ny*nz < 2^31");
-    const int64_t n = nx * ny * nz, nb = (n + kMBlock - 1) / kMBlock;
-    return up256(2 * n) + up256(4 * n) + up256(12 * nb) + up256(16 * nb);
+    return mc_ws_bytes(nx * ny * nz);
 }
 
 int hm_mc_count(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx, int64_t sy, int64_t sz, float level,
@@ -303,7 +170,7 @@ int hm_mc_count(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx
     HM_CHECK_ARG(level == level, "hm_mc_count: level is NaN");
     const int64_t n = nx * ny * nz, nb = (n + kMBlock - 1) / kMBlock;
     const McVol V{vol, (int32_t)nx, (int32_t)ny, (int32_t)nz, sx, sy, sz};
-    const McWs w = carve(workspace, n);
+    const McWs w = mc_carve(workspace, n);
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, V, level, n, w.code, w.bsum, nb);
     hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kScanT), 0, st, static_cast<const int32_t *>(w.bsum), nb, w.boff,
@@ -326,7 +193,7 @@ int hm_mc_emit(const float *vol, int64_t nx, int64_t ny, int64_t nz, int64_t sx,
     HM_CHECK_ARG(n_faces == 0 || faces, "hm_mc_emit: NULL faces");
     const int64_t n = nx * ny * nz, nb = (n + kMBlock - 1) / kMBlock;
     const McVol V{vol, (int32_t)nx, (int32_t)ny, (int32_t)nz, sx, sy, sz};
-    const McWs w = carve(workspace, n);
+    const McWs w = mc_carve(workspace, n);
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(mc_verts_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, V, level, spacing[0], spacing[1],
                        spacing[2], n, static_cast<const uint16_t *>(w.code), w.vbase,

@@ -1346,3 +1346,203 @@ def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0)):
         check(L.hm_mc_emit(*args, sp, dptr(ws), ws.numel(), n_verts, n_faces, dptr(verts), dptr(normals), dptr(faces),
                            st))
     return verts, faces, normals
+
+
+# =========================================================================================
+# brick-sparse mesh extraction (csrc/hm_mesh_sparse.hip)
+# =========================================================================================
+_BRICK = 8
+_BRICK_POINTS = _BRICK ** 3
+_MCS_MAX_LIST = 1 << 22
+
+
+def _lattice_args(axes, rot, shift):
+    """(device fp32 axis tensors, their lengths, the [host] transform of hm_mcs_points_* or None)"""
+    dev = next((a.device for a in axes if torch.is_tensor(a) and a.is_cuda), torch.device("cuda"))
+    ax = [torch.as_tensor(a, dtype=torch.float32, device=dev).reshape(-1).contiguous() for a in axes]
+    if len(ax) != 3:
+        raise ValueError("hashmod lattice: three coordinate arrays expected")
+    xform = None
+    if rot is not None or shift is not None:
+        r = torch.eye(3) if rot is None else torch.as_tensor(rot).detach().reshape(3, 3)
+        s = torch.zeros(3) if shift is None else torch.as_tensor(shift).detach().reshape(3)
+        xform = (C.c_float * 12)(*torch.cat([r.reshape(9).float().cpu(), s.float().cpu()]).tolist())
+    return ax, tuple(int(a.numel()) for a in ax), xform
+
+
+def lattice_points(axes, q, rot=None, shift=None):
+    """Coordinates [n, 3] fp32 of the lattice points with linear indices q (int64, (i*ny + j)*nz + k) of the lattice
+    axes[0] x axes[1] x axes[2], taken to p @ rot + shift when either is given.  The generator of
+    marching_cubes_sparse: one fixed fp32 expression per point, so a point's coordinates depend on its index alone."""
+    ax, (nx, ny, nz), xform = _lattice_args(axes, rot, shift)
+    q = torch.as_tensor(q, dtype=torch.int64, device=ax[0].device).reshape(-1).contiguous()
+    out = torch.empty((q.numel(), 3), dtype=torch.float32, device=q.device)
+    check(lib().hm_mcs_points_index(dptr(q), q.numel(), dptr(ax[0]), dptr(ax[1]), dptr(ax[2]), nx, ny, nz, xform,
+                                    dptr(out), stream_ptr(out)))
+    return out
+
+
+def _grow(grid, below, above):
+    """the bool brick grid OR-ed with itself moved one brick down (below) / up (above) along every axis in turn"""
+    for a in range(3):
+        n = grid.shape[a]
+        out = grid.clone()
+        if below and n > 1:
+            out.narrow(a, 0, n - 1).logical_or_(grid.narrow(a, 1, n - 1))
+        if above and n > 1:
+            out.narrow(a, 1, n - 1).logical_or_(grid.narrow(a, 0, n - 1))
+        grid = out
+    return grid
+
+
+def _listed(grid, count):
+    """the int32 ids of the `count` set bricks of a bool brick grid, ascending (count was read by the caller)"""
+    return torch.nonzero_static(grid.reshape(-1), size=count).reshape(-1).to(torch.int32)
+
+
+@torch.no_grad()
+def marching_cubes_sparse(sdf, axes, spacing, seeds, level=0.0, rot=None, shift=None, chunk=1 << 22,
+                          return_stats=False):
+    """ops.marching_cubes of the volume sdf(lattice_points(axes, every index, rot, shift)) without evaluating that
+    volume: (verts, faces, normals[, stats]), bit for bit the dense call's outputs if every component of the level set
+    meets a brick that holds a seed, or one of its 26 neighbours.  A component that is not reached is absent as a whole.
+
+    The lattice is split into 8^3-point bricks (csrc/hm_mesh_sparse.hip).  From the seed bricks, a brick whose cell
+    block has values on both sides of `level` is a surface brick, and every block face of it with both signs makes the
+    brick across it a candidate of the next round; a round evaluates what its candidates' cell blocks need and costs
+    one host read.  Then the 27-neighbourhoods of the surface bricks are evaluated (cell corners and the +-1 points of
+    the normals) and the marching-cubes kernels run over the surface bricks.  No bound on the SDF's slope is assumed.
+
+    sdf: callable [n, 3] -> [n] fp32 whose value at a point does not depend on the batch it arrives in (for
+    ImplicitNetwork.sdf: a fixed tile_points); axes: three ascending coordinate arrays; seeds: [S, 3] in the frame of
+    the axes (before rot / shift), those outside the lattice are ignored; new bricks go to sdf in batches of at most
+    `chunk` points.  NaN in an evaluated value raises HashmodError.  stats: bricks_evaluated, surface_bricks, points
+    (handed to sdf), rounds, sdf_calls, lattice_points."""
+    L = lib()
+    ax, (nx, ny, nz), xform = _lattice_args(axes, rot, shift)
+    dev = ax[0].device
+    bdim = tuple(-(-n // _BRICK) for n in (nx, ny, nz))
+    n_bricks = bdim[0] * bdim[1] * bdim[2]
+    if min(nx, ny, nz) < 2:
+        raise ValueError("hashmod marching_cubes_sparse: every lattice dimension must be >= 2")
+    if n_bricks >= 1 << 31:
+        raise ValueError("hashmod marching_cubes_sparse: the brick map must have fewer than 2^31 entries")
+    st = stream_ptr(ax[0])
+    level = float(level)
+    map_g = torch.full(bdim, -1, dtype=torch.int32, device=dev)
+    decided = torch.zeros(n_bricks, dtype=torch.bool, device=dev)
+    surface = torch.zeros(n_bricks, dtype=torch.bool, device=dev)
+    bad = torch.zeros(2, dtype=torch.bool, device=dev)          # a NaN / an undecidable status seen so far
+    state = {"pool": torch.empty((256, _BRICK_POINTS), dtype=torch.float32, device=dev), "slots": 0, "points": 0,
+             "calls": 0}
+
+    def lattice():
+        return C.byref(_lib.McsLattice(nx, ny, nz, state["slots"], map_g.data_ptr(), state["pool"].data_ptr()))
+
+    def evaluate(ids):
+        n, pool, first = ids.numel(), state["pool"], state["slots"]
+        if first + n > pool.shape[0]:
+            pool = torch.empty((max(2 * pool.shape[0], first + n), _BRICK_POINTS), dtype=torch.float32, device=dev)
+            pool[:first] = state["pool"][:first]
+            state["pool"] = pool
+        per = min(max(1, int(chunk) // _BRICK_POINTS), _MCS_MAX_LIST)
+        for s in range(0, n, per):
+            part = ids[s:s + per]
+            pts = torch.empty((part.numel() * _BRICK_POINTS, 3), dtype=torch.float32, device=dev)
+            check(L.hm_mcs_points_bricks(dptr(part), part.numel(), dptr(ax[0]), dptr(ax[1]), dptr(ax[2]), nx, ny, nz,
+                                         xform, dptr(pts), st))
+            pool[first + s:first + s + part.numel()].view(-1).copy_(sdf(pts).reshape(-1))
+            state["points"] += pts.shape[0]
+            state["calls"] += 1
+        map_g.view(-1)[ids.long()] = torch.arange(first, first + n, dtype=torch.int32, device=dev)
+        state["slots"] = first + n
+
+    def status_of(ids):
+        out = torch.empty(ids.numel(), dtype=torch.int32, device=dev)
+        for s in range(0, ids.numel(), _MCS_MAX_LIST):
+            part = ids[s:s + _MCS_MAX_LIST]
+            check(L.hm_mcs_status(dptr(part), part.numel(), lattice(), level, dptr(out[s:]), st))
+        return out
+
+    def check_bad(nan, undecided):
+        if nan:
+            raise _lib.HashmodError("hashmod marching_cubes_sparse: the SDF returned NaN")
+        if undecided:
+            raise _lib.HashmodError("hashmod marching_cubes_sparse: a candidate brick's cell block was not evaluated")
+
+    # seed bricks and their 26 neighbours
+    pts = torch.as_tensor(seeds, dtype=torch.float32, device=dev).reshape(-1, 3)
+    inside = torch.ones(pts.shape[0], dtype=torch.bool, device=dev)
+    brick = torch.zeros(pts.shape[0], dtype=torch.int64, device=dev)
+    for a, n in enumerate((nx, ny, nz)):
+        c = pts[:, a].contiguous()
+        inside &= (c >= ax[a][0]) & (c <= ax[a][-1])
+        brick = brick * bdim[a] + (torch.searchsorted(ax[a], c, right=True) - 1).clamp_(0, n - 1) // _BRICK
+    seeded = torch.zeros(n_bricks + 1, dtype=torch.bool, device=dev)
+    seeded[torch.where(inside, brick, n_bricks)] = True
+    cand = _grow(seeded[:n_bricks].view(bdim), 1, 1)
+
+    rounds = n_decided = 0
+    strides = (bdim[1] * bdim[2], bdim[2], 1)
+    while True:
+        want = _grow(cand, 0, 1) & (map_g < 0)               # the candidates' cell blocks: they and their upper neighbours
+        n_c, n_w, nan, und = torch.stack([cand.sum(), want.sum(), *bad.long()]).tolist()    # the round's host read
+        check_bad(nan, und)
+        if n_c == 0:
+            break
+        rounds += 1
+        n_decided += n_c
+        ids = _listed(cand, n_c)
+        if n_w:
+            evaluate(_listed(want, n_w))
+        status = status_of(ids)
+        idl = ids.long()
+        decided[idl] = True
+        surface[idl] = (status & 1) != 0
+        bad |= torch.stack([(status & 128).any(), (status & 256).any()])
+        nxt = torch.zeros(n_bricks, dtype=torch.bool, device=dev)
+        for f in range(6):
+            step = strides[f // 2] * (1 if f & 1 else -1)
+            nxt[idl + step * ((status & (2 << f)) != 0)] = True     # no such face: the brick itself, which is decided
+        cand = (nxt & ~decided).view(bdim)
+
+    # halo: the 27-neighbourhood of every surface brick
+    halo = _grow(surface.view(bdim), 1, 1) & (map_g < 0)
+    n_h, n_s = torch.stack([halo.sum(), surface.sum()]).tolist()
+    if n_h:
+        evaluate(_listed(halo, n_h))
+    n_rest = state["slots"] - n_decided                          # evaluated, never a candidate: only their NaN bit
+    if n_rest:
+        bad[0] |= (status_of(_listed((map_g.view(-1) >= 0) & ~decided, n_rest)) & 128).any()
+    stats = {"bricks_evaluated": state["slots"], "surface_bricks": n_s, "points": state["points"], "rounds": rounds,
+             "sdf_calls": state["calls"], "lattice_points": nx * ny * nz}
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    if n_s:
+        ids = _listed(surface, n_s)
+        list_pos = torch.full((n_bricks,), -1, dtype=torch.int32, device=dev)
+        list_pos[ids.long()] = torch.arange(n_s, dtype=torch.int32, device=dev)
+        ws = torch.empty(check(L.hm_mcs_workspace_bytes(n_s)), dtype=torch.uint8, device=dev)
+        check(L.hm_mcs_count(dptr(ids), n_s, lattice(), level, dptr(ws), ws.numel(), dptr(counts), st))
+    n_verts, n_faces, has_nan, rest_nan, n_mapped = torch.cat([counts, bad[:1].long(),
+                                                               (map_g >= 0).sum().reshape(1)]).tolist()
+    check_bad(has_nan or rest_nan, False)
+    if n_mapped != state["slots"]:
+        raise _lib.HashmodError("hashmod marching_cubes_sparse: a brick was evaluated twice")
+    verts = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    if n_verts > 0:
+        vkeys = torch.empty(n_verts, dtype=torch.int64, device=dev)
+        fkeys = torch.empty(n_faces, dtype=torch.int64, device=dev)
+        sp = (C.c_float * 3)(*(float(s) for s in spacing))
+        check(L.hm_mcs_emit(dptr(ids), n_s, lattice(), dptr(list_pos), level, sp, dptr(ws), ws.numel(), n_verts,
+                            n_faces, dptr(verts), dptr(normals), dptr(faces), dptr(vkeys), dptr(fkeys), st))
+        if n_faces and int(faces.min()) < 0:
+            raise _lib.HashmodError("hashmod marching_cubes_sparse: a face refers to a brick that was not reached")
+        # the dense kernel's order: vertices by (owning point, axis), faces by (cell, table order)
+        order = torch.sort(vkeys)[1]
+        verts, normals = verts[order], normals[order]
+        new_id = torch.empty(n_verts, dtype=torch.int32, device=dev)
+        new_id[order] = torch.arange(n_verts, dtype=torch.int32, device=dev)
+        faces = new_id[faces.long()][torch.sort(fkeys)[1]]
+    return (verts, faces, normals, stats) if return_stats else (verts, faces, normals)

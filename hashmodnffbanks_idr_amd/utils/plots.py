@@ -234,6 +234,14 @@ def _mesh_on_lattice(sdf, axes, device, rot=None, shift=None):
     return ops.marching_cubes(volume, 0.0, (d, d, d))
 
 
+def lattice_points(axes, q, rot=None, shift=None):
+    """The points [n, 3] fp32 (device) with linear indices q (int64, volume order (i*ny + j)*nz + k) of the lattice
+    of the axes (x, y, z), taken to p @ rot + shift when given - from the generator of ops.marching_cubes_sparse, so
+    sdf(lattice_points(axes, arange(nx*ny*nz))).view(nx, ny, nz) is the volume whose ops.marching_cubes the sparse
+    call reproduces."""
+    return ops.lattice_points([np.asarray(a) if not torch.is_tensor(a) else a for a in axes], q, rot, shift)
+
+
 def _surface_moments(mesh):
     """(mean [3], covariance [3,3]) of the uniform distribution on the mesh surface, exact from its triangles"""
     v = mesh.vertices[mesh.faces]
@@ -245,12 +253,17 @@ def _surface_moments(mesh):
     return mean, cov
 
 
-def get_surface_high_res_mesh(sdf, resolution=100, device="cuda"):
+def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False):
     """plots.py:146-224: the zero level set of `sdf` on a lattice aligned with the principal axes of a coarse mesh's
     largest component, `resolution` samples along its shortest axis; a TriMesh in world space, or None without a
     sign change.  Two deliberate deviations (mesh extraction): the principal axes come from the exact
     area-weighted surface moments of the coarse component (the reference: 10 000 random trimesh.sample points), and
-    the lattices are generated on the device chunk by chunk (no host lattice)."""
+    the lattices are generated on the device chunk by chunk (no host lattice).
+
+    sparse=True evaluates the aligned lattice only near the surface (ops.marching_cubes_sparse, seeded with the coarse
+    mesh's vertices of all components): the mesh of the full lattice except for components that the coarse 100^3
+    lattice does not see, which are absent as a whole.  Its vertices differ from sparse=False in the last bits (the
+    lattice points are generated by another fp32 expression).  The lattice may exceed 2^31 points."""
     lin = np.linspace(-1.0, 1.0, 100)      # the coarse 100^3 grid of get_grid_uniform(100)
     coarse = _mesh_on_lattice(sdf, (lin, lin, lin), device)
     if coarse is None:
@@ -271,9 +284,17 @@ def get_surface_high_res_mesh(sdf, resolution=100, device="cuda"):
 
     rot = vecs.to(device=device, dtype=torch.float32)
     shift = torch.from_numpy(s_mean).to(device=device, dtype=torch.float32)
-    fine = _mesh_on_lattice(sdf, (x, y, z), device, rot, shift)
-    if fine is None:
-        return None
+    if sparse:
+        seeds = (torch.from_numpy(verts + lin[0]) - torch.from_numpy(s_mean)) @ vecs.transpose(0, 1)
+        d = float(x[2] - x[1])
+        fine = ops.marching_cubes_sparse(sdf, [torch.as_tensor(a, dtype=torch.float32, device=device)
+                                               for a in (x, y, z)], (d, d, d), seeds, 0.0, rot, shift)
+        if fine[0].shape[0] == 0:
+            return None
+    else:
+        fine = _mesh_on_lattice(sdf, (x, y, z), device, rot, shift)
+        if fine is None:
+            return None
     verts, faces, normals = fine
     origin = torch.tensor([[x[0], y[0], z[0]]], dtype=torch.float32, device=device) @ rot + shift  # grid_points[0]
     verts = verts @ rot + origin

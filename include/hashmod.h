@@ -702,6 +702,65 @@ HM_API int hm_mc_emit(const float *vol, int64_t nx, int64_t ny, int64_t nz, int6
                       float level, const float *spacing, void *workspace, int64_t workspace_bytes, int64_t n_verts,
                       int64_t n_faces, float *verts, float *normals, int32_t *faces, void *stream);
 
+/* ---- mesh extraction: brick-sparse marching cubes --------------------------------------------------
+ * The same mesh from a lattice that is evaluated only near the surface (driver: ops.marching_cubes_sparse; scheme:
+ * DESIGN.md, Mesh extraction).  The lattice [nx, ny, nz] (every dimension in [2, 65536]; nx*ny*nz may exceed 2^31) is
+ * split into bricks of HM_MCS_BRICK^3 points: point (i, j, k) is value ((i%8)*8 + j%8)*8 + k%8 of brick
+ * (i/8, j/8, k/8).  map is the dense int32 brick map [ceil(nx/8), ceil(ny/8), ceil(nz/8)]: the brick's slot in the
+ * value pool [n_slots, 8, 8, 8] fp32, or -1 (any value outside [0, n_slots) reads as -1) while it is not evaluated.
+ * Brick lists are int32 linear ids into the map, at most HM_MCS_MAX_LIST long; an id outside the map is skipped.
+ * The cell block of a brick is its 8^3 cells; their corners are the points [8b, 8b + 8] clipped to the lattice.
+ *   hm_mcs_points_bricks: points [n_bricks*512, 3] = the coordinates of the listed bricks' points, brick by brick in
+ *                pool order; padding points of a border brick take the clamped index.  ax, ay, az are the device axis
+ *                arrays [nx], [ny], [nz]; xform is [host] [12] (r [3][3] row-major, then s [3]) or NULL:
+ *                p[c] = ((x*r[0][c] + y*r[1][c]) + z*r[2][c]) + s[c] in fp32, NULL: p = (x, y, z) - a point's
+ *                coordinates depend on its lattice index alone.
+ *   hm_mcs_points_index: the same for the n lattice points of linear index ((i*ny + j)*nz + k) index[.] (int64,
+ *                device); NaN coordinates for an index outside the lattice.
+ *   hm_mcs_status: status [n_bricks] int32 of the listed bricks: HM_MCS_BOTH - the cell block holds values on both
+ *                sides of level (v < level, the rule of hm_mc_count); HM_MCS_FACE(f), f = 0..5 for -x +x -y +y -z +z -
+ *                so does that face of the block and a brick lies across it; HM_MCS_NAN - a value of the block is NaN;
+ *                HM_MCS_UNDECIDED - the brick or an upper neighbour the block reaches into is not evaluated (the other
+ *                bits then cover the evaluated part).
+ *   hm_mcs_count / hm_mcs_emit: hm_mc_count / hm_mc_emit over the points of the listed bricks - every listed point
+ *                owns its +x, +y, +z lattice edges and the cell it is the lowest corner of, values are read through
+ *                the map, and an edge or a cell with a corner that is not evaluated emits nothing; same arithmetic,
+ *                same counts convention, same workspace rule (hm_mcs_workspace_bytes), same int32 limit.  list_pos is
+ *                the int32 map-shaped inverse of the list (position of a brick in it, or -1).  Emit needs every brick
+ *                that owns a crossing edge of a listed cell to be listed (a face gets vertex id -1 otherwise) and the
+ *                +-1 points of every vertex' edge ends to be evaluated (NaN normals otherwise).  Outputs are in list
+ *                order, with vert_keys [n_verts] = ((i*ny + j)*nz + k)*3 + axis and face_keys [n_faces] = (linear
+ *                index of the cell's lowest corner)*8 + (triangle in table order), int64: sorted by key (faces
+ *                renumbered) they are hm_mc_emit's outputs on the fully evaluated lattice, bit for bit.
+ * No entry point synchronises; no atomics.                                                                         */
+#define HM_MCS_BRICK 8
+#define HM_MCS_MAX_DIM 65536
+#define HM_MCS_MAX_LIST (1 << 22)
+#define HM_MCS_BOTH 1
+#define HM_MCS_FACE(f) (2 << (f))
+#define HM_MCS_NAN 128
+#define HM_MCS_UNDECIDED 256
+typedef struct hm_mcs_lattice {
+    int64_t nx, ny, nz;
+    int64_t n_slots;
+    const int32_t *map;
+    const float *pool;
+} hm_mcs_lattice;
+HM_API int hm_mcs_points_bricks(const int32_t *bricks, int64_t n_bricks, const float *ax, const float *ay,
+                                const float *az, int64_t nx, int64_t ny, int64_t nz, const float *xform, float *points,
+                                void *stream);
+HM_API int hm_mcs_points_index(const int64_t *index, int64_t n, const float *ax, const float *ay, const float *az,
+                               int64_t nx, int64_t ny, int64_t nz, const float *xform, float *points, void *stream);
+HM_API int hm_mcs_status(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice *lat, float level,
+                         int32_t *status, void *stream);
+HM_API int64_t hm_mcs_workspace_bytes(int64_t n_bricks);
+HM_API int hm_mcs_count(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice *lat, float level,
+                        void *workspace, int64_t workspace_bytes, int64_t *counts, void *stream);
+HM_API int hm_mcs_emit(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice *lat, const int32_t *list_pos,
+                       float level, const float *spacing, void *workspace, int64_t workspace_bytes, int64_t n_verts,
+                       int64_t n_faces, float *verts, float *normals, int32_t *faces, int64_t *vert_keys,
+                       int64_t *face_keys, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

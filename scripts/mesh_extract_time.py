@@ -1,6 +1,7 @@
 """Time of mesh extraction on the GPU (csrc/hm_mesh.hip, utils/plots.get_surface_high_res_mesh).
 
-    python scripts/mesh_extract_time.py [--sizes 256 512] [--iters 10] [--warmup 3] [--res 512] [--out FILE]
+    python scripts/mesh_extract_time.py [--sizes 256 512] [--iters 10] [--warmup 3] [--res 512] [--reps 2]
+                                        [--sparse-res 1024] [--out FILE]
 
 1. ops.marching_cubes on a sphere SDF volume (radius 0.6 in [-1,1]^3) at each size: ms per call from device events
    after warm-up (the call includes its one host read of the counts), and the kernels' bytes moved over that time
@@ -10,6 +11,12 @@
 2. get_surface_high_res_mesh(resolution=--res) on the C2 network of bench.py (geometric init, seed 0), split into
    SDF evaluation and marching cubes (device events around every call) and the rest (host work: components, moments,
    eigh, copies; wall clock minus the two).
+3. the same call with sparse=True (ops.marching_cubes_sparse, csrc/hm_mesh_sparse.hip) beside it: after a warm-up of
+   both, --reps dense and sparse calls alternate in this process, every one split as in 2.; for a sparse call
+   "marching cubes" is everything of ops.marching_cubes_sparse except its SDF calls (brick bookkeeping, status, count,
+   emit, sort, and the device idling over the per-round host reads).  Also the share of the aligned lattice handed
+   to the SDF, the rounds and the SDF calls; the SDF time to expect is that share of the dense SDF time.  Then one
+   sparse call at --sparse-res (0: skip), a lattice the dense path cannot hold.
 No GPU: exits with an error instead of printing a number.  Prints a table, then one JSON line.
 """
 import argparse
@@ -76,30 +83,83 @@ class _Timed:
         return sum(s.elapsed_time(e) for s, e in self.pairs)
 
 
-def time_high_res(res):
+class _TimedSparse(_Timed):
+    """ops.marching_cubes_sparse, timed, keeping the stats of the last call"""
+
+    def __call__(self, *a, **k):
+        out = super().__call__(*a, return_stats=True, **k)
+        self.stats = out[3]
+        return out[:3]
+
+
+def time_high_res(net, res, sparse):
+    """one get_surface_high_res_mesh(res) call split into SDF, marching cubes and host time"""
     import torch
-    import bench
     from hashmodnffbanks_idr_amd import ops
     from hashmodnffbanks_idr_amd.utils import plots
-    net = bench._build("C2", "cuda", 0.0).implicit_network
-    plots.get_surface_high_res_mesh(net.sdf, 64)       # warm-up: code objects, packed weights, allocator
-    torch.cuda.synchronize()
     sdf = _Timed(net.sdf)
     mc = _Timed(ops.marching_cubes)
-    orig = ops.marching_cubes
-    ops.marching_cubes = mc
+    mcs = _TimedSparse(ops.marching_cubes_sparse)
+    orig = ops.marching_cubes, ops.marching_cubes_sparse
+    ops.marching_cubes, ops.marching_cubes_sparse = mc, mcs
     try:
         t0 = time.perf_counter()
-        mesh = plots.get_surface_high_res_mesh(sdf, res)
+        mesh = plots.get_surface_high_res_mesh(sdf, res, sparse=sparse)
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t0) * 1e3
     finally:
-        ops.marching_cubes = orig
+        ops.marching_cubes, ops.marching_cubes_sparse = orig
     if mesh is None:
         raise SystemExit("get_surface_high_res_mesh found no surface")
-    return {"res": res, "wall_ms": round(wall, 1), "sdf_ms": round(sdf.ms(), 1), "mc_ms": round(mc.ms(), 2),
-            "host_ms": round(wall - sdf.ms() - mc.ms(), 1), "sdf_calls": len(sdf.pairs),
-            "verts": len(mesh.vertices), "faces": len(mesh.faces)}
+    # a sparse call's SDF calls lie inside ops.marching_cubes_sparse: what is left of it counts as marching cubes
+    inner = sum(s.elapsed_time(e) for s, e in sdf.pairs[-mcs.stats["sdf_calls"]:]) if sparse else 0.0
+    mc_ms = mc.ms() + (mcs.ms() - inner if sparse else 0.0)
+    out = {"res": res, "sparse": sparse, "wall_ms": round(wall, 1), "sdf_ms": round(sdf.ms(), 1),
+           "mc_ms": round(mc_ms, 2), "host_ms": round(wall - sdf.ms() - mc_ms, 1), "sdf_calls": len(sdf.pairs),
+           "verts": len(mesh.vertices), "faces": len(mesh.faces)}
+    if sparse:
+        st = mcs.stats
+        out.update(share=round(st["points"] / st["lattice_points"], 4), rounds=st["rounds"],
+                   lattice_points=st["lattice_points"], bricks=st["bricks_evaluated"],
+                   surface_bricks=st["surface_bricks"], fine_sdf_ms=round(inner, 1))
+    return out
+
+
+def _show(h):
+    tail = (f"; {100 * h['share']:.1f}% of {h['lattice_points']} lattice points evaluated in {h['rounds']} rounds"
+            if h["sparse"] else "")
+    print(f"get_surface_high_res_mesh({h['res']}{', sparse' if h['sparse'] else ''}) C2: {h['wall_ms']:.0f} ms = SDF "
+          f"{h['sdf_ms']:.0f} ms ({h['sdf_calls']} calls) + marching cubes {h['mc_ms']:.2f} ms + host "
+          f"{h['host_ms']:.0f} ms; {h['verts']} verts, {h['faces']} faces{tail}", flush=True)
+
+
+def time_high_res_legs(res, reps, sparse_res):
+    import torch
+    import bench
+    from hashmodnffbanks_idr_amd.utils import plots
+    net = bench._build("C2", "cuda", 0.0).implicit_network
+    for sparse in (False, True):                      # warm-up: code objects, packed weights, allocator
+        plots.get_surface_high_res_mesh(net.sdf, 64, sparse=sparse)
+    torch.cuda.synchronize()
+    runs = []
+    for _ in range(reps):
+        for sparse in (False, True):
+            runs.append(time_high_res(net, res, sparse))
+            _show(runs[-1])
+    out = {"runs": runs}
+    dense, sp = ([r for r in runs if r["sparse"] == s] for s in (False, True))
+    best = lambda rs, key: min(r[key] for r in rs)
+    out["summary"] = {"res": res, "dense_wall_ms": best(dense, "wall_ms"), "sparse_wall_ms": best(sp, "wall_ms"),
+                      "dense_sdf_ms": best(dense, "sdf_ms"), "sparse_sdf_ms": best(sp, "sdf_ms"),
+                      "share": sp[0]["share"], "sdf_ratio": round(best(sp, "sdf_ms") / best(dense, "sdf_ms"), 4),
+                      "wall_ratio": round(best(sp, "wall_ms") / best(dense, "wall_ms"), 4)}
+    m = out["summary"]
+    print(f"sparse / dense at {res}: wall {m['wall_ratio']:.3f}, SDF {m['sdf_ratio']:.3f} (evaluated share "
+          f"{m['share']:.3f})", flush=True)
+    if sparse_res:
+        out["sparse_large"] = time_high_res(net, sparse_res, True)
+        _show(out["sparse_large"])
+    return out
 
 
 def main():
@@ -108,6 +168,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--res", type=int, default=512, help="get_surface_high_res_mesh resolution (0: skip)")
+    ap.add_argument("--reps", type=int, default=2, help="dense / sparse pairs at --res")
+    ap.add_argument("--sparse-res", type=int, default=1024, help="one more sparse call at this resolution (0: skip)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -119,10 +181,7 @@ def main():
               f"{r['gbytes']:.2f} GB -> {r['tb_s']:.2f} TB/s ({100 * r['hbm_share']:.0f}% of {HBM_TBS} TB/s)",
               flush=True)
     if args.res:
-        h = result["high_res"] = time_high_res(args.res)
-        print(f"get_surface_high_res_mesh({h['res']}) C2: {h['wall_ms']:.0f} ms = SDF {h['sdf_ms']:.0f} ms "
-              f"({h['sdf_calls']} calls) + marching cubes {h['mc_ms']:.2f} ms + host {h['host_ms']:.0f} ms; "
-              f"{h['verts']} verts, {h['faces']} faces", flush=True)
+        result["high_res"] = time_high_res_legs(args.res, args.reps, args.sparse_res)
     line = json.dumps(result)
     print(line)
     if args.out:
