@@ -24,6 +24,8 @@ struct GemmArgs {
     float *C;
     int32_t M, N, K;
     int32_t transA, transB;  // op(A) = A^T if transA (A stored [K,M]); op(B) = B^T if transB (B stored [N,K])
+    int32_t vec_out;  // pipelined kernel: outputs and epilogue operands go as aligned 16-B accesses (gemm_store_quads);
+                      // (sits in what was padding before the 64-bit fields: the other members keep their offsets)
     int64_t lda, ldb, ldc;
     int32_t k_chunk;  // K range handled by one blockIdx.z
     int32_t atomic;   // accumulate with atomics (split-K, or beta = 1)
@@ -163,6 +165,142 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 
             if (g.ep.out3) g.ep.out3[(int64_t)m * g.ep.ld3 + n] = gv[q] * d.s1;
         }
     }
+    }
+}
+
+// (The generic and big-tile kernels keep gemm_store_tile exactly as it was: built from gemm_store_oct below it computes the
+// same values, but hipcc then schedules those kernels' instruction streams differently.)
+// The fused epilogue of ONE element (include/hashmod.h): v = (acc + bias) * scale is what goes to C; z / gv are the element's
+// epilogue operands (unused by the modes that have none).  o1 / o2 / o3 go to ep.out1 / out2 / out3.
+struct GemmEpiOut {
+    float o1, o2, o3;
+};
+__device__ __forceinline__ GemmEpiOut gemm_epi_elem(const hm_gemm_epilogue &ep, int mode, float v, float z, float gv) {
+    GemmEpiOut o;
+    o.o1 = o.o2 = o.o3 = 0.0f;
+    if (mode == HM_EPI_SOFTPLUS) {
+        o.o1 = hm_softplus_fwd(v, ep.beta, ep.threshold);
+    } else if (mode == HM_EPI_RELU) {
+        o.o1 = fmaxf(v, 0.0f);
+    } else if (mode == HM_EPI_RELUMASK) {
+        o.o1 = (z > 0.0f ? v : 0.0f) + gv;
+    } else if (mode == HM_EPI_S1MUL) {
+        o.o1 = v * hm_sp_deriv(z, ep.beta, ep.threshold).s1 + gv;
+    } else if (mode == HM_EPI_ADJOINT) {
+        const SpDeriv d = hm_sp_deriv(z, ep.beta, ep.threshold);
+        o.o1 = v * d.s1;
+        o.o2 = v * gv * d.s2;
+        o.o3 = gv * d.s1;
+    }
+    return o;
+}
+
+// The pipelined kernels' form of gemm_store_tile, for the HALF tile a wave finishes: eight rows of one column, lane holds
+// column n, a[q] is row mrow0 + (q&3) + 8(q>>2).  EP and PART as above.
+template <bool EP, bool PART = false>
+__device__ __forceinline__ void gemm_store_oct(const GemmArgs &g, const float (&a)[8], int n, int mrow0, bool add_bias,
+                                               int kz = 0) {
+    const float bv = add_bias ? g.bias[n] : 0.0f;
+    const int mode = EP ? g.ep.mode : (int)HM_EPI_NONE;
+    // epilogue operands first, all 8 (+8) loads in flight together on clamped addresses: a load under
+    // a per-row guard would be waited for one at a time
+    float zv[8] = {}, gv[8] = {};
+    if (mode == HM_EPI_S1MUL || mode == HM_EPI_ADJOINT || mode == HM_EPI_RELUMASK) {
+        const int nc = mode != HM_EPI_ADJOINT ? min(n, g.ep.nz - 1) : n;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int mc = min(mrow0 + (q & 3) + 8 * (q >> 2), g.M - 1);
+            zv[q] = g.ep.z[(int64_t)mc * g.ep.ldz + nc];
+        }
+        if (g.ep.g) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int mc = min(mrow0 + (q & 3) + 8 * (q >> 2), g.M - 1);
+                gv[q] = g.ep.g[(int64_t)mc * g.ep.ldg + nc];
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) gv[q] = 0.0f;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int m = mrow0 + (q & 3) + 8 * (q >> 2);
+        if (m >= g.M) continue;
+        float v = a[q] + bv;
+        if (mode != HM_EPI_NONE) v *= g.ep.scale;
+        if (PART) {
+            g.C[((int64_t)kz * g.M + m) * g.ldc + n] = v;
+        } else if (g.C) {
+            float *dst = g.C + (int64_t)m * g.ldc + n;
+            if (g.atomic)
+                atomicAdd(dst, v);
+            else
+                *dst = v;
+        }
+        if (mode == HM_EPI_NONE) continue;
+        const GemmEpiOut o = gemm_epi_elem(g.ep, mode, v, zv[q], gv[q]);
+        const bool masked = mode == HM_EPI_S1MUL || mode == HM_EPI_RELUMASK;   // out1 has nz columns
+        if (!masked || n < g.ep.nz) g.ep.out1[(int64_t)m * g.ep.ld1 + n] = o.o1;
+        if (mode == HM_EPI_ADJOINT) {
+            g.ep.out2[(int64_t)m * g.ep.ld2 + n] = o.o2;
+            if (g.ep.out3) g.ep.out3[(int64_t)m * g.ep.ld3 + n] = o.o3;
+        }
+    }
+}
+
+// The 16-byte form of gemm_store_oct: the lane holds columns n .. n+3 (n % 4 == 0) of rows m and m + 8.  The host takes it
+// (GemmArgs::vec_out) when N, every leading dimension and every base the epilogue touches are multiples of 16 bytes and
+// nothing is accumulated, so a quad is whole - inside N and inside nz, or outside - and every access is one dwordx4.
+template <bool EP, bool PART = false>
+__device__ __forceinline__ void gemm_store_quads(const GemmArgs &g, const float4 (&a)[2], int n, int m0, bool add_bias,
+                                                 int kz = 0) {
+    const int mode = EP ? g.ep.mode : (int)HM_EPI_NONE;
+    float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (add_bias) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) bv[c] = g.bias[n + c];
+    }
+    // epilogue operands first, on clamped addresses (see gemm_store_oct)
+    float4 zq[2] = {}, gq[2] = {};
+    if (mode == HM_EPI_S1MUL || mode == HM_EPI_ADJOINT || mode == HM_EPI_RELUMASK) {
+        const int nc = mode != HM_EPI_ADJOINT ? min(n, g.ep.nz - 4) : n;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int mc = min(m0 + 8 * i, g.M - 1);
+            zq[i] = *reinterpret_cast<const float4 *>(g.ep.z + (int64_t)mc * g.ep.ldz + nc);
+            gq[i] = g.ep.g ? *reinterpret_cast<const float4 *>(g.ep.g + (int64_t)mc * g.ep.ldg + nc)
+                           : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int m = m0 + 8 * i;
+        if (m >= g.M) continue;
+        const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
+        const float zv[4] = {zq[i].x, zq[i].y, zq[i].z, zq[i].w}, gv[4] = {gq[i].x, gq[i].y, gq[i].z, gq[i].w};
+        float v[4], o1[4], o2[4], o3[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            v[c] = av[c] + bv[c];
+            if (mode != HM_EPI_NONE) v[c] *= g.ep.scale;
+            const GemmEpiOut o = gemm_epi_elem(g.ep, mode, v[c], zv[c], gv[c]);
+            o1[c] = o.o1; o2[c] = o.o2; o3[c] = o.o3;
+        }
+        auto put = [](float *dst, const float (&x)[4]) {
+            *reinterpret_cast<float4 *>(dst) = make_float4(x[0], x[1], x[2], x[3]);
+        };
+        if (PART)
+            put(g.C + ((int64_t)kz * g.M + m) * g.ldc + n, v);
+        else if (g.C)
+            put(g.C + (int64_t)m * g.ldc + n, v);
+        if (mode == HM_EPI_NONE) continue;
+        const bool masked = mode == HM_EPI_S1MUL || mode == HM_EPI_RELUMASK;   // out1 has nz columns
+        if (!masked || n < g.ep.nz) put(g.ep.out1 + (int64_t)m * g.ep.ld1 + n, o1);
+        if (mode == HM_EPI_ADJOINT) {
+            put(g.ep.out2 + (int64_t)m * g.ep.ld2 + n, o2);
+            if (g.ep.out3) put(g.ep.out3 + (int64_t)m * g.ep.ld3 + n, o3);
+        }
     }
 }
 
@@ -377,6 +515,28 @@ __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f3
 // AKC / BKC: operand is k-contiguous (one dwordx4 per k-group), else row-contiguous (four dwords).
 constexpr int kPipeBK = 32, kPipeD = 4;
 
+// Phase stamps of ONE tile (probe builds only, scripts/gemm_phase_probe.py): workgroup (0, 0, 0) / thread 0 writes the
+// 100 MHz wall clock at [0] entry, [1] first operands in LDS, [2] end of the K loop, [3] after the wave groups' exchange,
+// [4] after its last epilogue store has completed; [5] is the time it spent in the K loop's barriers.
+#ifdef HM_GEMM_PHASE_PROBE
+__device__ unsigned long long hm_gemm_probe_ts[8];
+#define HM_GEMM_PROBE_ON (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
+#define HM_GEMM_STAMP(i_)                                                                            \
+    do {                                                                                             \
+        if ((i_) == 4) __builtin_amdgcn_s_waitcnt(0);   /* vmcnt(0): the stores have left */          \
+        if (HM_GEMM_PROBE_ON) hm_gemm_probe_ts[(i_)] = wall_clock64();                               \
+    } while (0)
+#define HM_GEMM_LOOP_BARRIER()                                                                       \
+    do {                                                                                             \
+        const unsigned long long t_ = wall_clock64();                                                \
+        __syncthreads();                                                                             \
+        probe_wait += wall_clock64() - t_;                                                           \
+    } while (0)
+#else
+#define HM_GEMM_STAMP(i_) do { } while (0)
+#define HM_GEMM_LOOP_BARRIER() __syncthreads()
+#endif
+
 // one stage's operand k-groups through a buffer descriptor: voff = the thread's byte offset (loop invariant), soff = the
 // stage's byte offset (scalar)
 template <bool KC, int PER>
@@ -452,6 +612,10 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
     const int m0 = bx * BM, n0 = by * BN;
     const int kbeg = bz * g.k_chunk;
     const int stages = g.k_chunk / BK;   // multiple of kPipeD (host)
+#ifdef HM_GEMM_PHASE_PROBE
+    unsigned long long probe_wait = 0;
+#endif
+    HM_GEMM_STAMP(0);
 
     // operand fetches are BUFFER loads: descriptor on the matrix (SGPRs), the thread's own byte offset in ONE loop-invariant
     // VGPR, the stage's offset scalar - no 64-bit address arithmetic on the VALU inside the loop (VALU instructions are
@@ -511,6 +675,7 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
     store_tile<BM, BK, NT>(As[0], AKC, tid, ra0);
     if (stage_b) store_tile<BN, BK, NTB>(Bs[0], BKC, tid, rb0);
     __syncthreads();
+    HM_GEMM_STAMP(1);
     pipe_read_ops<OCT, BM>(As[0], Bs[0], wm * 32 + j, wn * 32 + j, h + 4 * kpart, opa0, opb0);
 // one stage: multiply from operand set C, meanwhile fetch stage s+D-1 into ring slot F and move ring slot N (stage
 // s+1) through LDS buffer NB into operand set X
@@ -521,7 +686,7 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
         HM_PIPE_MASK((S_) + 1, ra##N_, rb##N_);                                                     \
         store_tile<BM, BK, NT>(As[NB_], AKC, tid, ra##N_);                                          \
         if (stage_b) store_tile<BN, BK, NTB>(Bs[NB_], BKC, tid, rb##N_);                            \
-        __syncthreads();                                                                            \
+        HM_GEMM_LOOP_BARRIER();                                                                     \
         pipe_read_ops<OCT, BM>(As[NB_], Bs[NB_], wm * 32 + j, wn * 32 + j, h + 4 * kpart, opa##X_, opb##X_);        \
         pipe_mfma_oct(opa##C_[1], opb##C_[1], acc2);                                                \
     } while (0)
@@ -535,23 +700,59 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
 #undef HM_PIPE_STAGE
 #undef HM_PIPE_MASK
 #undef HM_PIPE_FETCH
+    HM_GEMM_STAMP(2);
+#ifdef HM_GEMM_PHASE_PROBE
+    if (HM_GEMM_PROBE_ON) hm_gemm_probe_ts[5] = probe_wait;
+#endif
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
-    {   // add the second wave group's partial tile (through the staging buffers, free now)
-        __syncthreads();
-        float *red = &As[0][0];   // 2 WM waves * 16 registers * 64 lanes floats == 2 * BK * BM
-        static_assert(2 * BK * BM >= 2 * WM * 16 * 64, "reduction buffer");
-        if (kpart == 1) {
+    // The two wave groups hold partial sums of the same tile.  Each FINISHES half of it: group 0 the rows of registers
+    // 0..7 (rows 0..15 of the wave's 32), group 1 those of registers 8..15; the other eight registers go to the partner
+    // wave through the staging buffers (free now).  Every element is group 0's sum + group 1's, in either group (fp32
+    // addition commutes), and all waves share the epilogue's loads, transcendentals and stores.
+    float fin[8];
+    float *red = &As[0][0];   // 4 WM waves * 8 registers * 64 lanes floats == 2 * BK * BM
+    static_assert(2 * BK * BM == 4 * WM * 8 * 64, "exchange buffer");
+    float *const mine = red + (kpart * 2 * WM + wsub) * 512, *const theirs = red + ((1 - kpart) * 2 * WM + wsub) * 512;
+    {
+        float give[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) red[(wsub * 16 + r) * 64 + lane] = acc[r];
+        for (int q = 0; q < 8; ++q) {
+            fin[q] = kpart ? acc[8 + q] : acc[q];
+            give[q] = kpart ? acc[q] : acc[8 + q];
         }
         __syncthreads();
-        if (kpart == 1) return;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] += red[(wsub * 16 + r) * 64 + lane];
+        for (int q = 0; q < 8; ++q) mine[q * 64 + lane] = give[q];
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 8; ++q) fin[q] += theirs[q * 64 + lane];
     }
-    const int n = n0 + wn * 32 + j;
-    if (n < g.N) gemm_store_tile<EP, PART>(g, acc, n, m0 + wm * 32 + 4 * h, (g.bias != nullptr) && (bz == 0), bz);
+    HM_GEMM_STAMP(3);
+    const int mrow = m0 + wm * 32 + 16 * kpart;   // first of the wave's 16 rows
+    const bool add_bias = (g.bias != nullptr) && (bz == 0);
+    if (g.vec_out) {
+        // 16-byte form: the accumulator layout has the lane on ONE column, so the wave turns its 16 x 32 block through
+        // LDS - `theirs`, which only this wave reads and has read - into row-major quads: 8 lanes span a row's 32 columns
+        // (128 B), the wave 8 rows per access.  Row pairs share a 64-float line; the halves swap with bit 2 of the row so
+        // that the two lane halves (rows r and r + 4) write different banks.
+        auto slot = [](int row, int col) { return (row >> 1) * 64 + (((row ^ (row >> 2)) & 1) * 32) + col; };
+#pragma unroll
+        for (int q = 0; q < 8; ++q) theirs[slot((q & 3) + 8 * (q >> 2) + 4 * h, j)] = fin[q];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int row = lane >> 3, col = (lane & 7) * 4;
+        float4 quad[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) quad[i] = *reinterpret_cast<const float4 *>(theirs + slot(row + 8 * i, col));
+        const int n = n0 + wn * 32 + col;
+        if (n < g.N) gemm_store_quads<EP, PART>(g, quad, n, mrow + row, add_bias, bz);
+    } else {
+        const int n = n0 + wn * 32 + j;
+        if (n < g.N) gemm_store_oct<EP, PART>(g, fin, n, mrow + 4 * h, add_bias, bz);
+    }
+    HM_GEMM_STAMP(4);
 }
 
 template <bool AKC, bool BKC, bool EP>
@@ -614,6 +815,7 @@ __device__ __forceinline__ void gemm_group_body(const GemmGroupTable &t) {
     g.k_chunk = E.k_chunk;
     g.atomic = 1;
     g.vecA = g.vecB = 0;
+    g.vec_out = 0;   // (atomics, or the slabs of the deterministic form: dword stores)
     g.nrecA = g.nrecB = 0x7fffffff;
     g.ep.mode = HM_EPI_NONE;
     gemm_pipe2_body<false, false, false, 2, PART>(g, bx, by, bz);
@@ -737,6 +939,22 @@ static GemmPlan gemm_plan(int transA, int transB, int64_t M, int64_t N, int64_t 
     return P;
 }
 
+// May the pipelined kernel's tail use 16-byte accesses (gemm_store_quads)?  Nothing accumulated with atomics, N (and nz) a
+// multiple of 4 so that no quad straddles an edge, and every pointer and row stride the tail touches 16-byte aligned - true of
+// the 512-wide chain tensors and of the row slices of the stacked buffers, not of the 445- / 257- / 67-column ones.
+static bool gemm_vec_out(const GemmArgs &g, bool part) {
+    auto ok = [](const void *p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && ld % 4 == 0; };
+    if ((g.atomic && !part) || g.N % 4 != 0 || !ok(g.C, g.ldc)) return false;   // (a NULL C is never touched)
+    const hm_gemm_epilogue &e = g.ep;
+    if (e.mode == HM_EPI_NONE) return true;
+    const bool masked = e.mode == HM_EPI_S1MUL || e.mode == HM_EPI_RELUMASK;
+    const bool has_z = masked || e.mode == HM_EPI_ADJOINT;
+    if (!ok(e.out1, e.ld1) || (masked && e.nz % 4 != 0)) return false;
+    if (has_z && (!ok(e.z, e.ldz) || (e.g && !ok(e.g, e.ldg)))) return false;
+    if (e.mode == HM_EPI_ADJOINT && (!ok(e.out2, e.ld2) || (e.out3 && !ok(e.out3, e.ld3)))) return false;
+    return true;
+}
+
 // deterministic split-K: bytes of k-part slabs a call needs (0 when K is not split)
 static int64_t gemm_det_bytes(const GemmPlan &P, int64_t M, int64_t N) {
     return P.split > 1 ? 4 * P.split * M * N : 0;
@@ -798,6 +1016,7 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
         g.ldc = N;
     }
     g.atomic = (accumulate || split > 1) ? 1 : 0;
+    g.vec_out = gemm_vec_out(g, part) ? 1 : 0;
     if (split > 1 && !accumulate && !part) {
         // split-K accumulates with atomics into a zeroed C
         hipLaunchKernelGGL(zero_window_kernel, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, as_stream(stream),
@@ -1020,6 +1239,12 @@ int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void 
     return group_tn("hm_gemm_f32_group_tn_det", items, n_items, true, static_cast<float *>(workspace), workspace_bytes,
                     stream, true, &need);
 }
+
+#ifdef HM_GEMM_PHASE_PROBE
+HM_API int hm_gemm_probe_read(unsigned long long *out, int n) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(hm_gemm_probe_ts), sizeof(unsigned long long) * (size_t)(n < 8 ? n : 8)) == hipSuccess ? 0 : -1;
+}
+#endif
 
 int hm_gemm_f32_ep(int transA, int transB, int64_t M, int64_t N, int64_t K, const float *A, int64_t lda,
                    const float *B, int64_t ldb, const float *bias, float *C, int64_t ldc,
