@@ -215,6 +215,41 @@ class PinnedRing:
         return (*bufs, ev)
 
 
+class Workspace:
+    """Grow-on-demand scratch memory of one purpose (`what`, for the error message), one uint8 buffer per device.
+    A captured graph holds the buffer's address by value, so an outgrown buffer stays allocated for as long as the
+    process lives (growth is geometric: the held memory is bounded by the final size) and nothing grows during a
+    stream capture.  A copied or pickled Workspace starts empty."""
+
+    def __init__(self, what):
+        self.what = what
+        self._live = {}     # device -> the buffer get() hands out
+        self._held = []     # outgrown buffers
+
+    def get(self, device, need):
+        """a uint8 tensor of at least `need` bytes on `device` (None for need <= 0)"""
+        if need <= 0:
+            return None
+        ws = self._live.get(device)
+        if ws is None or ws.numel() < need:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"hashmod {self.what}: a {need}-byte workspace is needed during graph capture; "
+                                   "run the captured work once eagerly first (warm-up) so that it is sized beforehand")
+            if ws is not None:
+                self._held.append(ws)
+                need = max(need, 2 * ws.numel())
+            ws = self._live[device] = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def buffers(self, device):
+        """the live buffer of `device` (if any) followed by its held ones, oldest first"""
+        live = self._live.get(device)
+        return ([] if live is None else [live]) + [t for t in self._held if t.device == device]
+
+    def __reduce__(self):
+        return (Workspace, (self.what,))
+
+
 def lib():
     """Load libhashmod.so; raises (never falls back) when it is absent."""
     global _lib

@@ -102,6 +102,9 @@ __device__ __forceinline__ void store_tile(float *__restrict__ S, bool kcontig, 
 // (mrow0 already includes the lane half's +4).  EP selects the fused Softplus epilogues (include/hashmod.h).
 // PART: deterministic split-K - the tile is k part kz's partial and goes with plain stores to the workspace slab
 // g.C + kz * M * ldc (ldc = N); gemm_part_reduce_kernel sums the slabs in k-part order.
+// The epilogue is written out here and again in gemm_store_oct and gemm_store_quads (through gemm_epi_elem) on purpose:
+// built from gemm_store_oct, or from gemm_epi_elem alone, this function computes the same values, but hipcc then grows the
+// epilogue instances of the generic and big-tile kernels by 11 - 15 % in instructions (for example 12618 -> 14368 lines).
 template <bool EP, bool PART = false>
 __device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 &acc, int n, int mrow0, bool add_bias,
                                                 int kz = 0) {
@@ -168,8 +171,6 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs &g, const f32x16 
     }
 }
 
-// (The generic and big-tile kernels keep gemm_store_tile exactly as it was: built from gemm_store_oct below it computes the
-// same values, but hipcc then schedules those kernels' instruction streams differently.)
 // The fused epilogue of ONE element (include/hashmod.h): v = (acc + bias) * scale is what goes to C; z / gv are the element's
 // epilogue operands (unused by the modes that have none).  o1 / o2 / o3 go to ep.out1 / out2 / out3.
 struct GemmEpiOut {
@@ -311,7 +312,13 @@ __device__ __forceinline__ void gemm_store_quads(const GemmArgs &g, const float4
 // 64x64 configuration from two resident workgroups per CU to one).  The 8-wave configuration is held to 128 VGPRs
 // (4 waves per SIMD = two workgroups per CU).
 // WM: wave rows of the tile (2 -> 64*TM rows); the wave columns are always 2.
-template <int TM, int TN, int BK, int KS, bool VA, bool VB, bool EP, int WM = 2>
+// PART: the deterministic split-K form (no epilogue): k part blockIdx.z's partial tile goes to its workspace slab
+// (gemm_store_tile<false, true>).  As a parameter of this kernel it is free for the PART = false instances: their
+// instruction streams and descriptors stay line for line what they were while the PART form was a copy of this kernel
+// (scripts/kernel_isa_diff.py shows that without a GPU).  Sharing the body the other way - a __device__ __forceinline__
+// template with both kernels as three-line wrappers - was not: it moved every instance, the plain big-tile NN one from
+// 2862 to 3112 instructions, the big-tile epilogue ones from 11.9 - 12.7 k to 14.2 - 15.4 k.
+template <int TM, int TN, int BK, int KS, bool VA, bool VB, bool EP, int WM = 2, bool PART = false>
 __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f32_kernel(GemmArgs g) {
     constexpr int BM = 32 * WM * TM, BN = 64 * TN, NT = 128 * WM * KS, WG = 2 * WM;  // WG = waves per k part
     __shared__ __align__(16) float smem[BK * (BM + BN)];
@@ -399,104 +406,11 @@ __global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f3
         for (int tn = 0; tn < TN; ++tn) {
             const int n = n0 + wn * 32 * TN + tn * 32 + j;
             if (n >= g.N) continue;
-            gemm_store_tile<EP>(g, acc[tm][tn], n, m0 + wm * 32 * TM + tm * 32 + 4 * h, add_bias);
-        }
-}
-
-// Deterministic split-K form of gemm_f32_kernel (no epilogue): the same main loop, k part blockIdx.z's partial tile goes
-// to its workspace slab (gemm_store_tile<false, true>).  A separate kernel rather than a template parameter of the one
-// above: hipcc schedules that kernel differently once its body is shared, and the default path keeps its instructions.
-// (Tried: the body as a __device__ __forceinline__ template with a PART parameter and both kernels as three-line
-// wrappers changed the instruction stream of all 16 gemm_f32_kernel instances and of the 4 part instances - the plain
-// big-tile NN instance went from 2862 to 3112 instructions, the big-tile epilogue ones from 11.9 - 12.7 k to
-// 14.2 - 15.4 k.  scripts/kernel_isa_diff.py shows such a change without a GPU.)
-template <int TM, int TN, int BK, int KS, bool VA, bool VB, int WM = 2>
-__global__ __launch_bounds__(128 * WM * KS, (WM * KS == 4 ? 4 : 1)) void gemm_f32_part_kernel(GemmArgs g) {
-    constexpr int BM = 32 * WM * TM, BN = 64 * TN, NT = 128 * WM * KS, WG = 2 * WM;  // WG = waves per k part
-    __shared__ __align__(16) float smem[BK * (BM + BN)];
-    float *As = smem, *Bs = smem + BK * BM;
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int kpart = wave / WG, wsub = wave % WG;
-    const int wm = wsub >> 1, wn = wsub & 1;
-    const int j = lane & 31, h = lane >> 5;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int kbeg = blockIdx.z * g.k_chunk;
-    const int kend = min(g.K, kbeg + g.k_chunk);
-    const bool a_kc = (g.transA == 0);  // A[m*lda + k]
-    const bool b_kc = (g.transB != 0);  // B stored [N,K]: B[n*ldb + k]
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-
-    float4 ra[BM * BK / 4 / NT], rb[BN * BK / 4 / NT];
-    load_tile<BM, BK, NT, VA>(g.A, g.lda, a_kc, m0, g.M, kbeg, kend, tid, ra);
-    load_tile<BN, BK, NT, VB>(g.B, g.ldb, b_kc, n0, g.N, kbeg, kend, tid, rb);
-    for (int k0 = kbeg; k0 < kend; k0 += BK) {
-        __syncthreads();  // previous stage fully consumed
-        store_tile<BM, BK, NT>(As, a_kc, tid, ra);
-        store_tile<BN, BK, NT>(Bs, b_kc, tid, rb);
-        __syncthreads();
-        if (k0 + BK < kend) {  // prefetch the next stage into registers while this one is multiplied
-            load_tile<BM, BK, NT, VA>(g.A, g.lda, a_kc, m0, g.M, k0 + BK, kend, tid, ra);
-            load_tile<BN, BK, NT, VB>(g.B, g.ldb, b_kc, n0, g.N, k0 + BK, kend, tid, rb);
-        }
-        constexpr int OCT = BK / 8 / KS;
-#pragma unroll
-        for (int oo = 0; oo < OCT; ++oo) {
-            float4 a[TM], b[TN];
-            const int kg = 2 * (kpart * OCT + oo) + h;
-#pragma unroll
-            for (int t = 0; t < TM; ++t)
-                a[t] = *reinterpret_cast<const float4 *>(As + lds_slot<BM>(kg, wm * 32 * TM + t * 32 + j));
-#pragma unroll
-            for (int t = 0; t < TN; ++t)
-                b[t] = *reinterpret_cast<const float4 *>(Bs + lds_slot<BN>(kg, wn * 32 * TN + t * 32 + j));
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn) {
-                        const float av = s == 0 ? a[tm].x : s == 1 ? a[tm].y : s == 2 ? a[tm].z : a[tm].w;
-                        const float bv = s == 0 ? b[tn].x : s == 1 ? b[tn].y : s == 2 ? b[tn].z : b[tn].w;
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[tm][tn], 0, 0, 0);
-                    }
-        }
-    }
-
-    if (KS > 1) {
-        // sum the wave groups' partial tiles through LDS (the staging buffers are free now)
-        static_assert(KS == 1 || (TM == 1 && TN == 1), "intra-workgroup K split is built for the 64x64 tile");
-        __syncthreads();
-        float *red = smem;  // (KS-1) * WG waves * 16 regs * 64 lanes floats
-        static_assert((KS - 1) * WG * 16 * 64 <= BK * (BM + BN), "K-split reduction does not fit the staging buffers");
-        if (kpart > 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[(((kpart - 1) * WG + wsub) * 16 + r) * 64 + lane] = acc[0][0][r];
-        }
-        __syncthreads();
-        if (kpart > 0) return;
-#pragma unroll
-        for (int p = 0; p < KS - 1; ++p)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][0][r] += red[((p * WG + wsub) * 16 + r) * 64 + lane];
-    }
-
-    // epilogue: lane holds column n, registers hold rows (r&3) + 8(r>>2) + 4h
-    const bool add_bias = (g.bias != nullptr) && (blockIdx.z == 0);
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            const int n = n0 + wn * 32 * TN + tn * 32 + j;
-            if (n >= g.N) continue;
-            gemm_store_tile<false, true>(g, acc[tm][tn], n, m0 + wm * 32 * TM + tm * 32 + 4 * h, add_bias, blockIdx.z);
+            const int mrow0 = m0 + wm * 32 * TM + tm * 32 + 4 * h;
+            if constexpr (PART)
+                gemm_store_tile<false, true>(g, acc[tm][tn], n, mrow0, add_bias, blockIdx.z);
+            else
+                gemm_store_tile<EP>(g, acc[tm][tn], n, mrow0, add_bias);
         }
 }
 
@@ -1033,7 +947,7 @@ static int gemm_impl(int transA, int transB, int64_t M, int64_t N, int64_t K, co
             hm_bool_dispatch(P.vecB, [&](auto vb) {
                 constexpr bool VA = decltype(va)::value, VB = decltype(vb)::value;
                 // (big tiles are never split: they are taken only when the tile grid alone fills the chip)
-                if (part) return launch(gemm_f32_part_kernel<1, 1, 128, 2, VA, VB>, 512);
+                if (part) return launch(gemm_f32_kernel<1, 1, 128, 2, VA, VB, false, 2, true>, 512);
                 hm_bool_dispatch(ep_on, [&](auto ep_c) {
                     constexpr bool EP = decltype(ep_c)::value;
                     if (big) launch(gemm_f32_kernel<2, 2, 32, 1, VA, VB, EP, 2>, 256);

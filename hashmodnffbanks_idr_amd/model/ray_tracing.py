@@ -44,7 +44,7 @@ class RayTracing(nn.Module):
         self.sampler_head = 16
         self._stats = {}
         self._stats_dev = None
-        self._ws = None
+        self._ws = _lib.Workspace("ray tracer")     # per module: it carries counters across the tracer's own launches
 
     @property
     def last_stats(self):
@@ -82,9 +82,7 @@ class RayTracing(nn.Module):
                                 net.coarse_mode() if hasattr(net, "coarse_mode") else 0,
                                 int(self.sampler_head))
             nf = net._nffb_embedder() if net._hash_embedder() is None else None
-            need = ops.trace_workspace_bytes(N, cfg, nf.n_levels if nf is not None else 0)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._ws.get(dev, ops.trace_workspace_bytes(N, cfg, nf.n_levels if nf is not None else 0))
             steps_u = None
             if self.training:
                 if self.steps_override is not None:
@@ -100,7 +98,7 @@ class RayTracing(nn.Module):
                 ops.FRAC_MODES[emb.frac_mode], net.sdf_tile_points, cfg, cam_loc.detach().contiguous().float(),
                 ray_directions.detach().reshape(N, 3).contiguous().float(),
                 object_mask.reshape(N).to(torch.uint8).contiguous(), t_sphere.reshape(N, 2).contiguous(),
-                hit.reshape(N).to(torch.uint8).contiguous(), P, self._linspace(dev), steps_u, self._ws, stats,
+                hit.reshape(N).to(torch.uint8).contiguous(), P, self._linspace(dev), steps_u, ws, stats,
                 nffb=nffb)
         self._stats = {"rays": N}
         self._stats_dev = stats

@@ -45,24 +45,17 @@ def is_deterministic():
     return _DETERMINISTIC[-1] if _DETERMINISTIC else torch.are_deterministic_algorithms_enabled()
 
 
-_DET_WS = {}        # device -> uint8 workspace of the deterministic reductions (shared: one stream orders their use)
-_DET_WS_OLD = []    # outgrown workspaces stay allocated: a captured graph may still name them
+# library scratch memory, one owner per purpose (DESIGN.md "Scratch memory under graph capture")
+_DET_WS = _lib.Workspace("deterministic mode")      # shared by the deterministic reductions: one stream orders their use
+_ENC_WS = _lib.Workspace("encode_fwd")              # the z-ordered encode's point permutation
+_ENC_BWD_WS = _lib.Workspace("encode_bwd_table")    # the z-ordered table backward
+_SORT_WS = _lib.Workspace("sort_pairs")
 
 
 def _det_workspace(device, need):
-    """(pointer, bytes) of the per-device workspace, grown to `need` bytes outside a graph capture"""
-    if need <= 0:
-        return None, 0
-    ws = _DET_WS.get(device)
-    if ws is None or ws.numel() < need:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"hashmod deterministic mode: a {need}-byte workspace is needed during graph capture; "
-                               "run the captured work once eagerly first (warm-up) so that it is sized beforehand")
-        if ws is not None:
-            _DET_WS_OLD.append(ws)
-            need = max(need, 2 * ws.numel())
-        ws = _DET_WS[device] = torch.empty(need, dtype=torch.uint8, device=device)
-    return dptr(ws), ws.numel()
+    """(pointer, bytes) of the deterministic reductions' workspace"""
+    ws = _DET_WS.get(device, need)
+    return dptr(ws), 0 if ws is None else ws.numel()
 
 
 def level_table(n_levels, log2_hashmap_size, base_resolution, desired_resolution, in_dim=3):
@@ -127,10 +120,6 @@ def corner_ids(desc, level, x):
     return xi, ids.long() & 0xFFFFFFFF
 
 
-_ENC_BWD_WS = {}   # device -> scratch of the z-ordered table backward
-_ENC_WS = {}   # device -> scratch of the z-ordered encode (grown on demand, reused by every launch on that stream)
-
-
 def encode_fwd(desc, x, table, B, frac_mode=0, hash_only=False):
     """[N,E] embedding (or [N,L*F] hash features when hash_only) - no autograd."""
     x = _prep_x(x)
@@ -145,10 +134,7 @@ def encode_fwd(desc, x, table, B, frac_mode=0, hash_only=False):
         stride = (width + 3) & ~3
         buf = torch.empty((n, stride), dtype=torch.float32, device=x.device)
         out = buf[:, :width] if stride != width else buf
-        need = check(lib().hm_encode_workspace_bytes(desc.handle, n))
-        ws = _ENC_WS.get(x.device)
-        if ws is None or ws.numel() < need:
-            ws = _ENC_WS[x.device] = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = _ENC_WS.get(x.device, check(lib().hm_encode_workspace_bytes(desc.handle, n)))
         check(lib().hm_encode_fwd_ws(desc.handle, dptr(x), n, dptr(table), dptr(Bp), dptr(buf), stride, int(frac_mode),
                                      dptr(ws), ws.numel(), stream_ptr(x)))
     else:
@@ -179,10 +165,7 @@ def encode_bwd_table(desc, x, d_feat, frac_mode=0, out=None, deterministic=None)
                                                d_feat.stride(0), dptr(wts), dptr(out), stream_ptr(x)))
         return out
     if n >= 131072 and desc.F == 2:     # big launches: z-ordered, LDS-privatised scatter (needs scratch)
-        need = check(lib().hm_encode_bwd_workspace_bytes(desc.handle, n))
-        ws = _ENC_BWD_WS.get(x.device)
-        if ws is None or ws.numel() < need:
-            ws = _ENC_BWD_WS[x.device] = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = _ENC_BWD_WS.get(x.device, check(lib().hm_encode_bwd_workspace_bytes(desc.handle, n)))
         check(lib().hm_encode_bwd_table_ws(desc.handle, dptr(x), n, dptr(d_feat), d_feat.stride(0), dptr(out),
                                            int(frac_mode), dptr(ws), ws.numel(), stream_ptr(x)))
         return out
@@ -203,9 +186,6 @@ def sorted_rows(desc, x, frac_mode=0):
     return corners, skeys, perm, wts
 
 
-_SORT_WS = {}
-
-
 def sort_pairs(keys, key_bits=31):
     """(sorted keys, permutation as int64) of non-negative int32 keys < 2^key_bits: the library's stable LSD radix sort
     (hm_sort_pairs_i32), the sort behind encode_bwd_table(deterministic=True)."""
@@ -217,10 +197,7 @@ def sort_pairs(keys, key_bits=31):
     perm = torch.empty(n, dtype=torch.int64, device=keys.device)
     if n == 0:
         return out, perm
-    need = check(lib().hm_sort_workspace_bytes(n))
-    ws = _SORT_WS.get(keys.device)
-    if ws is None or ws.numel() < need:
-        ws = _SORT_WS[keys.device] = torch.empty(need, dtype=torch.uint8, device=keys.device)
+    ws = _SORT_WS.get(keys.device, check(lib().hm_sort_workspace_bytes(n)))
     check(lib().hm_sort_pairs_i32(dptr(keys), n, int(key_bits), dptr(out), dptr(perm), dptr(ws), ws.numel(),
                                   stream_ptr(keys)))
     return out, perm
@@ -1071,6 +1048,40 @@ def colsum_into_multi(pairs):
     check(lib().hm_colsum_acc_multi(C.cast(items, C.c_void_p), len(pairs), stream_ptr(pairs[0][0])))
 
 
+def _twice_differentiable(name, call, prep, doc):
+    """The autograd node of y = f(x; *params), differentiable twice, over ONE kernel entry call(order, x, gy, gg, *params)
+    -> (out0, out1): order 0 gives y, order 1 gx = J(x)^T gy, order 2 (d_gy, d_x) of gx for its cotangent gg.  prep puts
+    x and gy into the layout the kernel reads.  Returns the forward node; its backward is the node `name`Bwd."""
+
+    def bwd_forward(ctx, x, gy, *params):
+        gy = prep(gy)
+        ctx.params = params
+        ctx.save_for_backward(x, gy)
+        return call(1, x, gy, None, *params)[0]
+
+    @torch.autograd.function.once_differentiable
+    def bwd_backward(ctx, gg):
+        x, gy = ctx.saved_tensors
+        d_gy, d_x = call(2, x, gy, gg.contiguous(), *ctx.params)
+        return (d_x, d_gy) + (None,) * len(ctx.params)
+
+    bwd = type(name + "Bwd", (torch.autograd.Function,),
+               {"forward": staticmethod(bwd_forward), "backward": staticmethod(bwd_backward)})
+
+    def forward(ctx, x, *params):
+        x = prep(x)
+        ctx.params = params
+        ctx.save_for_backward(x)
+        return call(0, x, None, None, *params)[0]
+
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        return (bwd.apply(x, gy, *ctx.params),) + (None,) * len(ctx.params)
+
+    return type(name, (torch.autograd.Function,),
+                {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
+
+
 def _softplus_call(order, z, gy, gg, beta, thr):
     n = z.numel()
     out0 = torch.empty_like(z)
@@ -1080,36 +1091,9 @@ def _softplus_call(order, z, gy, gg, beta, thr):
     return out0, out1
 
 
-class _Softplus(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, beta, thr):
-        z = z.contiguous()
-        ctx.beta, ctx.thr = beta, thr
-        ctx.save_for_backward(z)
-        return _softplus_call(0, z, None, None, beta, thr)[0]
-
-    @staticmethod
-    def backward(ctx, gy):
-        (z,) = ctx.saved_tensors
-        return _SoftplusBwd.apply(z, gy, ctx.beta, ctx.thr), None, None
-
-
-class _SoftplusBwd(torch.autograd.Function):
-    """gz = gy * s1(z); differentiable once more (d/dgy and d/dz in one fused pass)."""
-
-    @staticmethod
-    def forward(ctx, z, gy, beta, thr):
-        gy = gy.contiguous()
-        ctx.beta, ctx.thr = beta, thr
-        ctx.save_for_backward(z, gy)
-        return _softplus_call(1, z, gy, None, beta, thr)[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gg):
-        z, gy = ctx.saved_tensors
-        d_gy, d_z = _softplus_call(2, z, gy, gg.contiguous(), ctx.beta, ctx.thr)
-        return d_z, d_gy, None, None
+_Softplus = _twice_differentiable(
+    "_Softplus", _softplus_call, torch.Tensor.contiguous,
+    "nn.Softplus(beta, threshold); gz = gy * s1(z) is differentiable once more (d/dgy and d/dz in one fused pass).")
 
 
 def _sine_call(order, x, gy, gg, w0):
@@ -1119,36 +1103,9 @@ def _sine_call(order, x, gy, gg, w0):
     return out0, out1
 
 
-class _Sine(torch.autograd.Function):
-    """sin(w0 x) (SIREN activation) with one-kernel backward and double backward (csrc/hm_elem.hip)."""
-
-    @staticmethod
-    def forward(ctx, x, w0):
-        x = x.contiguous()
-        ctx.w0 = w0
-        ctx.save_for_backward(x)
-        return _sine_call(0, x, None, None, w0)[0]
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        return _SineBwd.apply(x, gy, ctx.w0), None
-
-
-class _SineBwd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gy, w0):
-        gy = gy.contiguous()
-        ctx.w0 = w0
-        ctx.save_for_backward(x, gy)
-        return _sine_call(1, x, gy, None, w0)[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gg):
-        x, gy = ctx.saved_tensors
-        d_gy, d_x = _sine_call(2, x, gy, gg.contiguous(), ctx.w0)
-        return d_x, d_gy, None
+_Sine = _twice_differentiable(
+    "_Sine", _sine_call, torch.Tensor.contiguous,
+    "sin(w0 x) (SIREN activation) with one-kernel backward and double backward (csrc/hm_elem.hip).")
 
 
 def sine(x, w0):
@@ -1215,36 +1172,9 @@ def _rownorm_call(order, y, g, gg, eps):
     return out0, out1
 
 
-class _RowNorm(torch.autograd.Function):
-    """(y - mean) / sqrt(var + eps) per row with one-kernel backward and double backward (csrc/hm_elem.hip)."""
-
-    @staticmethod
-    def forward(ctx, y, eps):
-        y = y.contiguous()
-        ctx.eps = eps
-        ctx.save_for_backward(y)
-        return _rownorm_call(0, y, None, None, eps)[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (y,) = ctx.saved_tensors
-        return _RowNormBwd.apply(y, g, ctx.eps), None
-
-
-class _RowNormBwd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, y, g, eps):
-        g = g.contiguous()
-        ctx.eps = eps
-        ctx.save_for_backward(y, g)
-        return _rownorm_call(1, y, g, None, eps)[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gg):
-        y, g = ctx.saved_tensors
-        d_g, d_y = _rownorm_call(2, y, g, gg.contiguous(), ctx.eps)
-        return d_y, d_g, None
+_RowNorm = _twice_differentiable(
+    "_RowNorm", _rownorm_call, torch.Tensor.contiguous,
+    "(y - mean) / sqrt(var + eps) per row with one-kernel backward and double backward (csrc/hm_elem.hip).")
 
 
 def rownorm(y, eps=1e-5):
@@ -1255,7 +1185,7 @@ def rownorm(y, eps=1e-5):
     return _RowNorm.apply(y, float(eps))
 
 
-def _posenc_call(order, freqs, c, g, gg):
+def _posenc_call(order, c, g, gg, freqs):
     n, D = c.shape
     W = 2 * D + 2 * len(freqs) * D
     fa = (C.c_float * len(freqs))(*freqs)
@@ -1267,37 +1197,10 @@ def _posenc_call(order, freqs, c, g, gg):
     return out0, out1
 
 
-class _PosEnc(torch.autograd.Function):
-    """[c | c | sin(f0 c) | cos(f0 c) | ...] (NeRF positional encoding as the reference builds it with include_input)
-    with one-kernel backward and double backward (csrc/hm_elem.hip)."""
-
-    @staticmethod
-    def forward(ctx, c, freqs):
-        c = _rowmajor(c)
-        ctx.freqs = freqs
-        ctx.save_for_backward(c)
-        return _posenc_call(0, freqs, c, None, None)[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (c,) = ctx.saved_tensors
-        return _PosEncBwd.apply(c, g, ctx.freqs), None
-
-
-class _PosEncBwd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, c, g, freqs):
-        g = _rowmajor(g)
-        ctx.freqs = freqs
-        ctx.save_for_backward(c, g)
-        return _posenc_call(1, freqs, c, g, None)[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gg):
-        c, g = ctx.saved_tensors
-        d_g, d_c = _posenc_call(2, ctx.freqs, c, g, gg.contiguous())
-        return d_c, d_g, None
+_PosEnc = _twice_differentiable(
+    "_PosEnc", _posenc_call, _rowmajor,
+    "[c | c | sin(f0 c) | cos(f0 c) | ...] (NeRF positional encoding as the reference builds it with include_input) "
+    "with one-kernel backward and double backward (csrc/hm_elem.hip).")
 
 
 def posenc(c, freqs):

@@ -7,6 +7,11 @@ Both trees are compiled with the library's own flags plus `--cuda-device-only -S
 reports the kernels present on one side only, the kernels whose instruction stream differs and the kernels whose
 `.amdhsa_kernel` descriptor (VGPR / AGPR / SGPR counts, LDS, scratch) differs, then one summary line.  Exit status 1
 if any source has any of them: a refactor of host code passes with 0.
+
+    --alias REGEX=REPLACEMENT    (repeatable) rewrite REV's symbol names with re.sub before matching, for a change that
+                                 renames kernels or gives them template parameters: REV's kernel is then compared with
+                                 the working tree's kernel of the new name.  Symbols are the mangled names of the
+                                 assembly; the rewrite covers REV's labels and every compared line.
 """
 import argparse
 import os
@@ -38,13 +43,16 @@ def compile_asm(tree, src, out):
     return out
 
 
-def kernels(path):
-    """{symbol: (instruction stream, descriptor)} of one assembly file; both are lists of comment-free lines."""
+def kernels(path, aliases=()):
+    """{symbol: (instruction stream, descriptor)} of one assembly file; both are lists of comment-free lines.
+    aliases: (compiled regex, replacement) pairs applied to every line first, symbol names included."""
     out = {}
     if path is None:
         return out
     name, cur, desc, in_desc = None, None, None, False
     for ln in open(path):
+        for rx, to in aliases:
+            ln = rx.sub(to, ln)
         m = re.match(r"\s*\.type\s+(\S+),@function", ln)
         if m:
             name = m.group(1)
@@ -73,8 +81,8 @@ def kernels(path):
     return out
 
 
-def compare(src, a, b, rev):
-    ka, kb = kernels(a), kernels(b)
+def compare(src, a, b, rev, aliases=()):
+    ka, kb = kernels(a, aliases), kernels(b)
     only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
     both = sorted(set(ka) & set(kb))
     isa = [k for k in both if ka[k][0] != kb[k][0]]
@@ -100,7 +108,15 @@ def main():
     ap.add_argument("rev", nargs="?", default="HEAD", help="git revision to compare the working tree with")
     ap.add_argument("sources", nargs="*", default=build.SOURCES, help="sources under csrc/ (default: all)")
     ap.add_argument("--jobs", type=int, default=min(MAX_JOBS, os.cpu_count() or 1), help=f"compiler jobs (at most {MAX_JOBS})")
+    ap.add_argument("--alias", action="append", default=[], metavar="REGEX=REPLACEMENT",
+                    help="rewrite the revision's (mangled) symbol names with re.sub before matching; repeatable")
     args = ap.parse_args()
+    aliases = []
+    for a in args.alias:
+        rx, sep, to = a.partition("=")
+        if not sep or not rx:
+            ap.error(f"--alias {a!r}: REGEX=REPLACEMENT expected")
+        aliases.append((re.compile(rx), to))
     rev = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", args.rev], text=True).strip()
     sources = [os.path.basename(s) for s in args.sources]
     with tempfile.TemporaryDirectory(prefix="kernel_isa_diff_") as tmp:
@@ -113,7 +129,7 @@ def main():
         with ThreadPoolExecutor(max_workers=max(1, min(MAX_JOBS, args.jobs))) as pool:
             jobs = [(src, pool.submit(compile_asm, old, src, os.path.join(tmp, "a_" + src + ".s")),
                      pool.submit(compile_asm, ROOT, src, os.path.join(tmp, "b_" + src + ".s"))) for src in sources]
-            moved = [compare(src, fa.result(), fb.result(), rev) for src, fa, fb in jobs]
+            moved = [compare(src, fa.result(), fb.result(), rev, aliases) for src, fa, fb in jobs]
     n = sum(moved)
     print(f"device code {'MOVED in ' + str(n) + ' of' if n else 'identical in all'} {len(sources)} sources (against {rev})")
     return 1 if n else 0

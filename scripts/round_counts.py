@@ -33,5 +33,5 @@ for step in range(int(sys.argv[1]) if len(sys.argv) > 1 else 1):
     if step in (0, 20, 100, 200, 299):
         torch.cuda.synchronize()
         st = model.ray_tracer.last_stats
-        c = counters(model.ray_tracer._ws, 2048)
+        c = counters(model.ray_tracer._ws.buffers(dev)[0], 2048)
         print("step", step, st, "rounds:", [int(v) for v in c[:42]], flush=True)

@@ -341,3 +341,101 @@ def test_scene_dataset_on_the_reference_dummy_scan():
         ds.change_sampling_idx(256)
         _, s2, g2 = ds[0]
         assert s2["uv"].shape == (256, 2) and g2["rgb"].shape == (256, 3)
+
+
+@pytest.fixture
+def capturing(monkeypatch):
+    """torch.cuda.is_current_stream_capturing replaced by a switch (state["on"]) that counts how often it is asked"""
+    state = {"on": False, "asked": 0}
+
+    def fake():
+        state["asked"] += 1
+        return state["on"]
+
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", fake)
+    return state
+
+
+def test_workspace_grows_and_holds_what_it_outgrew(capturing):
+    """_lib.Workspace: at least `need` bytes, an outgrown buffer stays listed (a captured graph may name it), growth is
+    geometric, a smaller request gets the live buffer again, need <= 0 gets None, a copy starts empty."""
+    import copy
+    import pickle
+    from hashmodnffbanks_idr_amd._lib import Workspace
+    cpu = torch.device("cpu")
+    ws = Workspace("unit test")
+    assert ws.get(cpu, 0) is None and ws.get(cpu, -5) is None and ws.buffers(cpu) == []
+    a = ws.get(cpu, 100)
+    assert a.dtype == torch.uint8 and a.device == cpu and a.numel() == 100      # the first allocation is exact
+    assert ws.get(cpu, 100) is a and ws.get(cpu, 1) is a
+    b = ws.get(cpu, 101)
+    assert b is not a and b.data_ptr() != a.data_ptr() and b.numel() == 200     # max(need, 2 * old)
+    assert [t.data_ptr() for t in ws.buffers(cpu)] == [b.data_ptr(), a.data_ptr()]
+    assert ws.get(cpu, 64) is b and ws.get(cpu, 200) is b
+    c = ws.get(cpu, 1000)
+    assert c.numel() == 1000 and [t.numel() for t in ws.buffers(cpu)] == [1000, 100, 200]
+    assert ws.buffers(torch.device("meta")) == []
+    assert capturing["asked"] == 0      # only CUDA devices are asked: the call raises on a machine without a GPU
+    for twin in (copy.deepcopy(ws), pickle.loads(pickle.dumps(ws))):
+        assert twin.what == "unit test" and twin.buffers(cpu) == []
+    assert len(ws.buffers(cpu)) == 3
+
+
+def test_workspace_refuses_to_grow_during_a_capture(capturing):
+    """growth on a CUDA device while its stream is capturing raises before anything is allocated (so this needs no GPU);
+    the message names the workspace, the size and the remedy"""
+    from hashmodnffbanks_idr_amd._lib import Workspace
+    ws = Workspace("unit-test scratch")
+    gpu = torch.device("cuda", 0)
+    capturing["on"] = True
+    with pytest.raises(RuntimeError, match=r"unit-test scratch.* 4096-byte .*graph capture.*eagerly first"):
+        ws.get(gpu, 4096)
+    assert capturing["asked"] == 1 and ws.buffers(gpu) == []
+    assert ws.get(gpu, 0) is None                               # nothing to grow: not refused
+    assert ws.get(torch.device("cpu"), 16).numel() == 16        # host memory is not part of any capture
+
+
+def test_ray_tracer_copies_start_with_an_empty_workspace():
+    import copy
+    from hashmodnffbanks_idr_amd.model.ray_tracing import RayTracing
+    cpu = torch.device("cpu")
+    rt = RayTracing()
+    rt._ws.get(cpu, 32)
+    twin = copy.deepcopy(rt)
+    assert twin._ws is not rt._ws and twin._ws.buffers(cpu) == [] and len(rt._ws.buffers(cpu)) == 1
+
+
+def test_twice_differentiable_factory_against_autograd():
+    """ops._twice_differentiable with a torch stand-in for the kernel entry (y = p * x^3): value, gradient and the
+    gradient of the gradient w.r.t. x and gy agree with autograd through the plain expression"""
+    from hashmodnffbanks_idr_amd import ops
+    orders = []
+
+    def call(order, x, gy, gg, p):
+        orders.append(order)
+        if order == 0:
+            return p * x ** 3, None
+        if order == 1:
+            return gy * 3 * p * x ** 2, None
+        return gg * 3 * p * x ** 2, gg * gy * 6 * p * x      # (d_gy, d_x)
+
+    prepared = []
+
+    def prep(t):
+        prepared.append(t)
+        return t.contiguous()
+
+    node = ops._twice_differentiable("_Cube", call, prep, "p * x^3")
+    assert node.__name__ == "_Cube" and node.__doc__ == "p * x^3"
+    torch.manual_seed(0)
+    x = torch.randn(3, 5, dtype=torch.float64, requires_grad=True)
+    gy = torch.randn(3, 5, dtype=torch.float64, requires_grad=True)
+    gg = torch.randn(3, 5, dtype=torch.float64)
+    got, want = [], []
+    for f, out in ((lambda t: node.apply(t, 2.0), got), (lambda t: 2.0 * t ** 3, want)):
+        y = f(x)
+        (gx,) = torch.autograd.grad(y, x, gy, create_graph=True)
+        out += [y, gx, *torch.autograd.grad(gx, (x, gy), gg)]
+    assert orders == [0, 1, 2] and len(prepared) == 2      # x in the forward, gy in the backward
+    for a, b in zip(got, want):
+        torch.testing.assert_close(a, b, rtol=1e-12, atol=1e-12)
