@@ -11,10 +11,13 @@ namespace {
 
 constexpr int kET = 256;
 
+// Four elements per thread: one float4 access when every pointer is 16-byte aligned (vec4), else the same four elements one
+// by one (a contiguous view that starts inside its storage); the last, partial group of four is always scalar.  The
+// arithmetic per element is the same on every path.
 __global__ __launch_bounds__(kET) void softplus_fwd_kernel(const float *__restrict__ z, float *__restrict__ y,
-                                                           int64_t n, float beta, float thr) {
+                                                           int64_t n, float beta, float thr, int vec4) {
     const int64_t i = ((int64_t)blockIdx.x * kET + threadIdx.x) * 4;
-    if (i + 3 < n) {
+    if (vec4 && i + 3 < n) {
         const float4 v = *reinterpret_cast<const float4 *>(z + i);
         float4 o;
         o.x = hm_softplus_fwd(v.x, beta, thr);
@@ -23,15 +26,16 @@ __global__ __launch_bounds__(kET) void softplus_fwd_kernel(const float *__restri
         o.w = hm_softplus_fwd(v.w, beta, thr);
         *reinterpret_cast<float4 *>(y + i) = o;
     } else {
-        for (int64_t k = i; k < n; ++k) y[k] = hm_softplus_fwd(z[k], beta, thr);
+        for (int64_t k = i; k < min(n, i + 4); ++k) y[k] = hm_softplus_fwd(z[k], beta, thr);
     }
 }
 
 // gz = gy * s1(z)
 __global__ __launch_bounds__(kET) void softplus_bwd_kernel(const float *__restrict__ z, const float *__restrict__ gy,
-                                                           float *__restrict__ gz, int64_t n, float beta, float thr) {
+                                                           float *__restrict__ gz, int64_t n, float beta, float thr,
+                                                           int vec4) {
     const int64_t i = ((int64_t)blockIdx.x * kET + threadIdx.x) * 4;
-    if (i + 3 < n) {
+    if (vec4 && i + 3 < n) {
         const float4 v = *reinterpret_cast<const float4 *>(z + i);
         const float4 g = *reinterpret_cast<const float4 *>(gy + i);
         float4 o;
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(kET) void softplus_bwd_kernel(const float *__restri
         o.w = g.w * hm_sp_deriv(v.w, beta, thr).s1;
         *reinterpret_cast<float4 *>(gz + i) = o;
     } else {
-        for (int64_t k = i; k < n; ++k) gz[k] = gy[k] * hm_sp_deriv(z[k], beta, thr).s1;
+        for (int64_t k = i; k < min(n, i + 4); ++k) gz[k] = gy[k] * hm_sp_deriv(z[k], beta, thr).s1;
     }
 }
 
@@ -50,9 +54,9 @@ __global__ __launch_bounds__(kET) void softplus_bwd_bwd_kernel(const float *__re
                                                                const float *__restrict__ gy,
                                                                const float *__restrict__ gg,
                                                                float *__restrict__ d_gy, float *__restrict__ d_z,
-                                                               int64_t n, float beta, float thr) {
+                                                               int64_t n, float beta, float thr, int vec4) {
     const int64_t i = ((int64_t)blockIdx.x * kET + threadIdx.x) * 4;
-    if (i + 3 < n) {
+    if (vec4 && i + 3 < n) {
         const float4 v = *reinterpret_cast<const float4 *>(z + i);
         const float4 g = *reinterpret_cast<const float4 *>(gy + i);
         const float4 q = *reinterpret_cast<const float4 *>(gg + i);
@@ -62,7 +66,7 @@ __global__ __launch_bounds__(kET) void softplus_bwd_bwd_kernel(const float *__re
         *reinterpret_cast<float4 *>(d_z + i) =
             make_float4(q.x * g.x * a.s2, q.y * g.y * b.s2, q.z * g.z * c.s2, q.w * g.w * d.s2);
     } else {
-        for (int64_t k = i; k < n; ++k) {
+        for (int64_t k = i; k < min(n, i + 4); ++k) {
             const SpDeriv a = hm_sp_deriv(z[k], beta, thr);
             d_gy[k] = gg[k] * a.s1;
             d_z[k] = gg[k] * gy[k] * a.s2;
@@ -302,27 +306,36 @@ __global__ __launch_bounds__(kET) void rownorm_kernel(int order, const float *__
         yv[i] = i < cnt ? y[r * W + sub + kRowLanes * i] : 0.0f;
         s += yv[i];
     }
-    const float mean = row_sum8(s) * inv_n;
+    // centred values y - mean in two steps: the fp32 mean of a row that lies far from 0 is off by up to an ulp of the
+    // MEAN (5e-7 at 8, against a spread of 1); y - mean0 is exact or rounds at the size of the difference, and the mean of
+    // those differences is the rounding of mean0, taken off again.  yv holds the centred row from here on.
+    const float mean0 = row_sum8(s) * inv_n;
+    float ds = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kRowMaxPerLane; ++i) {
+        yv[i] = i < cnt ? yv[i] - mean0 : 0.0f;
+        ds += yv[i];
+    }
+    const float dmean = row_sum8(ds) * inv_n;
     float var = 0.0f;
 #pragma unroll
     for (int i = 0; i < kRowMaxPerLane; ++i) {
-        const float d = i < cnt ? yv[i] - mean : 0.0f;
-        var += d * d;
+        yv[i] = i < cnt ? yv[i] - dmean : 0.0f;
+        var += yv[i] * yv[i];
     }
     var = row_sum8(var) * inv_n;
-    const float sigma = sqrtf(var + eps);
-    const float rs = 1.0f / sigma;
+    const float sigma = sqrtf(var + eps);     // every scaling below DIVIDES by sigma: one rounding, where * (1 / sigma) has two
     if (order == 0) {
 #pragma unroll
         for (int i = 0; i < kRowMaxPerLane; ++i)
-            if (live && i < cnt) out0[r * W + sub + kRowLanes * i] = (yv[i] - mean) / sigma;
+            if (live && i < cnt) out0[r * W + sub + kRowLanes * i] = yv[i] / sigma;
         return;
     }
     float sg = 0.0f, c = 0.0f;
 #pragma unroll
     for (int i = 0; i < kRowMaxPerLane; ++i) {
         gv[i] = i < cnt ? g[r * W + sub + kRowLanes * i] : 0.0f;
-        yv[i] = i < cnt ? (yv[i] - mean) * rs : 0.0f;          // yh from here on
+        yv[i] = yv[i] / sigma;                                  // yh from here on (0 in the empty slots)
         sg += gv[i];
         c += gv[i] * yv[i];
     }
@@ -331,7 +344,7 @@ __global__ __launch_bounds__(kET) void rownorm_kernel(int order, const float *__
     if (order == 1) {
 #pragma unroll
         for (int i = 0; i < kRowMaxPerLane; ++i)
-            if (live && i < cnt) out0[r * W + sub + kRowLanes * i] = (gv[i] - sg * inv_n - yv[i] * c * inv_n) * rs;
+            if (live && i < cnt) out0[r * W + sub + kRowLanes * i] = (gv[i] - sg * inv_n - yv[i] * c * inv_n) / sigma;
         return;
     }
     float sq = 0.0f, b = 0.0f, a = 0.0f;
@@ -346,12 +359,12 @@ __global__ __launch_bounds__(kET) void rownorm_kernel(int order, const float *__
     b = row_sum8(b);
     a = row_sum8(a) - sq * sg * inv_n;
     const float tt = a - b * c * inv_n;
-    const float k2 = rs * rs * inv_n;
+    const float k2 = 1.0f / (sigma * sigma * (float)W);
 #pragma unroll
     for (int i = 0; i < kRowMaxPerLane; ++i) {
         if (!(live && i < cnt)) continue;
         const float fq = qv[i] - sq * inv_n - yv[i] * b * inv_n, fg = gv[i] - sg * inv_n - yv[i] * c * inv_n;
-        out0[r * W + sub + kRowLanes * i] = fq * rs;
+        out0[r * W + sub + kRowLanes * i] = fq / sigma;
         out1[r * W + sub + kRowLanes * i] = -k2 * (yv[i] * tt + c * fq + b * fg);
     }
 }
@@ -479,20 +492,19 @@ int hm_softplus(int order, const float *z, const float *gy, const float *gg, flo
     HM_CHECK_ARG(n >= 0, "hm_softplus: n < 0");
     if (n == 0) return HM_OK;
     HM_CHECK_ARG(z && out0, "hm_softplus: NULL pointer");
-    HM_CHECK_ARG(((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(out0) | reinterpret_cast<uintptr_t>(gy) |
-                   reinterpret_cast<uintptr_t>(gg) | reinterpret_cast<uintptr_t>(out1)) & 15u) == 0,
-                 "hm_softplus: pointers must be 16-byte aligned");
+    const int vec4 = ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(out0) | reinterpret_cast<uintptr_t>(gy) |
+                       reinterpret_cast<uintptr_t>(gg) | reinterpret_cast<uintptr_t>(out1)) & 15u) == 0;
     const unsigned grid = (unsigned)((n + kET * 4 - 1) / (kET * 4));
     hipStream_t st = as_stream(stream);
     if (order == 0) {
-        hipLaunchKernelGGL(softplus_fwd_kernel, dim3(grid), dim3(kET), 0, st, z, out0, n, beta, threshold);
+        hipLaunchKernelGGL(softplus_fwd_kernel, dim3(grid), dim3(kET), 0, st, z, out0, n, beta, threshold, vec4);
     } else if (order == 1) {
         HM_CHECK_ARG(gy != nullptr, "hm_softplus: gy is NULL");
-        hipLaunchKernelGGL(softplus_bwd_kernel, dim3(grid), dim3(kET), 0, st, z, gy, out0, n, beta, threshold);
+        hipLaunchKernelGGL(softplus_bwd_kernel, dim3(grid), dim3(kET), 0, st, z, gy, out0, n, beta, threshold, vec4);
     } else {
         HM_CHECK_ARG(gy && gg && out1, "hm_softplus: NULL pointer");
         hipLaunchKernelGGL(softplus_bwd_bwd_kernel, dim3(grid), dim3(kET), 0, st, z, gy, gg, out0, out1, n, beta,
-                           threshold);
+                           threshold, vec4);
     }
     HM_CHECK_LAUNCH("hm_softplus");
     return HM_OK;

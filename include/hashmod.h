@@ -467,7 +467,8 @@ HM_API int hm_diag_gemm_plan(int transA, int transB, int64_t M, int64_t N, int64
  *   order 1: out0 = gy * s1(z)                         (its backward; s1 = d softplus / dz)
  *   order 2: out0 = gg * s1(z),  out1 = gg * gy * s2(z)  (backward of order 1 w.r.t. gy and z; the
  *            double backward autograd needs for ImplicitNetwork.gradient(create_graph=True), :116-128)
- * All pointers 16-byte aligned.                                                                   */
+ * With every pointer 16-byte aligned the pass moves float4s; any other alignment (a contiguous view that
+ * starts inside its storage) takes a scalar pass with the same arithmetic, so the results are bit-identical. */
 HM_API int hm_softplus(int order, const float *z, const float *gy, const float *gg, float *out0, float *out1,
                        int64_t n, float beta, float threshold, void *stream);
 

@@ -62,7 +62,7 @@ def test_clip_adam_matches_torch(max_norm, gscale):
 
 
 def test_clip_adam_many_tensors():
-    """more tensors than one launch's by-value table holds (HM_ADAM_MAX_TENSORS = 80)"""
+    """more tensors than one launch's by-value table holds (HM_ADAM_MAX_TENSORS = 64)"""
     from hashmodnffbanks_idr_amd.training.optim import ClipAdam
     dev = torch.device("cuda")
     g = torch.Generator(device="cpu").manual_seed(5)
