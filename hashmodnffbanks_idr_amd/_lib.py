@@ -107,6 +107,16 @@ SIGNATURES = {
     "hm_mcs_workspace_bytes": (_i64, [_i64]),
     "hm_mcs_count": (_int, [_p, _i64, _p, C.c_float, _p, _i64, _p, _p]),
     "hm_mcs_emit": (_int, [_p, _i64, _p, _p, C.c_float, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    # eval.py's cleanup of the fine mesh: split -> hm_mesh_cc_labels, the parts' areas -> hm_mesh_cc_face_stats and
+    # hm_mesh_cc_sums, components[areas.argmax()] -> hm_mesh_select_*; hm_mesh_moments is plots._surface_moments
+    "hm_mesh_cc_labels": (_int, [_p, _i64, _i64, _p, _p, _p]),
+    "hm_mesh_cc_face_stats": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p]),
+    "hm_mesh_cc_sums_workspace_bytes": (_i64, [_i64]),
+    "hm_mesh_cc_sums": (_int, [_p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p]),
+    "hm_mesh_moments_workspace_bytes": (_i64, [_i64]),
+    "hm_mesh_moments": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _p]),
+    "hm_mesh_select_mark": (_int, [_p, _i64, _i64, _p, C.c_int32, _p, _p, _p, _p]),
+    "hm_mesh_select_emit": (_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
 }
 
 

@@ -1449,3 +1449,147 @@ def marching_cubes_sparse(sdf, axes, spacing, seeds, level=0.0, rot=None, shift=
         new_id[order] = torch.arange(n_verts, dtype=torch.int32, device=dev)
         faces = new_id[faces.long()][torch.sort(fkeys)[1]]
     return (verts, faces, normals, stats) if return_stats else (verts, faces, normals)
+
+
+# =========================================================================================
+# mesh cleanup: components, areas, moments, largest component (csrc/hm_mesh_cc.hip)
+# =========================================================================================
+def _check_mesh(what, faces, n_verts=None, verts=None, normals=None, label=None):
+    """the checks the mesh cleanup ops share; returns (F, V)"""
+    require_gpu(faces, verts, normals, label)
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise ValueError(f"hashmod {what}: contiguous int32 faces [F, 3] expected")
+    if verts is not None:
+        if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3 or not verts.is_contiguous():
+            raise ValueError(f"hashmod {what}: contiguous fp32 verts [V, 3] expected")
+        n_verts = verts.shape[0]
+    n_verts, n_faces = int(n_verts), int(faces.shape[0])
+    if n_verts < 0 or n_verts >= 1 << 31 or n_faces >= 1 << 31:
+        raise ValueError(f"hashmod {what}: the numbers of vertices and faces must be below 2^31")
+    if normals is not None and (normals.dtype != torch.float32 or normals.shape != verts.shape
+                                or not normals.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous fp32 normals [V, 3] expected")
+    if label is not None and (label.dtype != torch.int32 or label.shape != (n_verts,) or not label.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous int32 label [V] expected")
+    for t in (verts, normals, label):
+        if t is not None and t.device != faces.device:
+            raise ValueError(f"hashmod {what}: the tensors are on different devices")
+    return n_faces, n_verts
+
+
+def _check_mesh_status(what, status):
+    if int(status.item()):
+        raise _lib.HashmodError(f"hashmod {what}: a face index lies outside [0, n_verts) (or the label does not belong "
+                                "to this mesh)")
+
+
+def mesh_components(faces, n_verts):
+    """label [V] int32 of the mesh with faces [F,3] int32 (as marching_cubes returns them) over `n_verts` vertices:
+    label[v] is the smallest vertex id of v's connected component - eval.py's mesh.split(only_watertight=False) as a
+    labelling, in TriMesh.split's order (components by their lowest vertex).  Vertices are connected when a face holds
+    both; a vertex of no face labels itself.  Lock-free union-find in one pass over the faces plus a flatten launch.
+    A face index outside [0, n_verts) raises HashmodError (it is reported by the kernel, never dereferenced).
+    V and F < 2^31; one host read of the status word, so not graph-capturable."""
+    n_faces, n_verts = _check_mesh("mesh_components", faces, n_verts)
+    dev = faces.device
+    label = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().hm_mesh_cc_labels(dptr(faces), n_faces, n_verts, dptr(label), dptr(status), stream_ptr(faces)))
+    _check_mesh_status("mesh_components", status)
+    return label
+
+
+def mesh_component_areas(verts, faces, label):
+    """(ids [C] int32 ascending, area [C] float64, n_faces [C] int64) of the components of mesh_components' `label`
+    that own at least one face - eval.py's areas = [c.area for c in components], in the same order.  Face areas are
+    0.5 |(v1 - v0) x (v2 - v0)| of the fp32 vertices cast to fp64 (TriMesh.area_faces); each component's faces are
+    brought together by the library's stable sort and summed in a fixed order without atomics, so two calls give the
+    same bits.  V and F < 2^31; host reads of C and the status word, so not graph-capturable."""
+    n_faces, n_verts = _check_mesh("mesh_component_areas", faces, verts=verts, label=label)
+    dev = faces.device
+    L = lib()
+    st = stream_ptr(faces)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    used = torch.zeros(n_verts, dtype=torch.int32, device=dev)
+    face_area = torch.empty(n_faces, dtype=torch.float64, device=dev)
+    check(L.hm_mesh_cc_face_stats(dptr(verts), dptr(faces), n_faces, n_verts, dptr(face_area), dptr(used), dptr(status),
+                                  st))
+    # bookkeeping between the launches: the roots that own faces, ranked in ascending order
+    root = (label == torch.arange(n_verts, dtype=torch.int32, device=dev)) & (used != 0)
+    incl = torch.cumsum(root, 0, dtype=torch.int32)
+    rank = incl - root.to(torch.int32)
+    ids = torch.nonzero(root).reshape(-1).to(torch.int32)
+    n_comp = int(ids.shape[0])
+    area = torch.empty(n_comp, dtype=torch.float64, device=dev)
+    count = torch.empty(n_comp, dtype=torch.int64, device=dev)
+    if n_comp:
+        ws = torch.empty(check(L.hm_mesh_cc_sums_workspace_bytes(n_faces)), dtype=torch.uint8, device=dev)
+        check(L.hm_mesh_cc_sums(dptr(faces), n_faces, n_verts, dptr(label), dptr(rank), dptr(face_area), n_comp,
+                                dptr(area), dptr(count), dptr(ws), ws.numel(), dptr(status), st))
+    _check_mesh_status("mesh_component_areas", status)
+    return ids, area, count
+
+
+def mesh_select(verts, faces, normals, label, component_id):
+    """(verts, faces, normals or None) of the component `component_id` (a value of mesh_components' `label`): its used
+    vertices in ascending original order, its faces in original order and renumbered, the normals gathered like the
+    vertices - the element of TriMesh.split() with that lowest vertex, bit for bit (np.unique(faces,
+    return_inverse=True)).  A component without faces gives empty outputs.  V and F < 2^31; one host read of the two
+    counts between marking and emitting, so not graph-capturable."""
+    n_faces, n_verts = _check_mesh("mesh_select", faces, verts=verts, normals=normals, label=label)
+    dev = faces.device
+    L = lib()
+    st = stream_ptr(faces)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    vflag = torch.zeros(n_verts, dtype=torch.int32, device=dev)
+    fflag = torch.empty(n_faces, dtype=torch.int32, device=dev)
+    component_id = int(component_id)
+    if not -(1 << 31) <= component_id < 1 << 31:
+        raise ValueError("hashmod mesh_select: component_id does not fit int32")
+    check(L.hm_mesh_select_mark(dptr(faces), n_faces, n_verts, dptr(label), component_id, dptr(vflag), dptr(fflag),
+                                dptr(status), st))
+    vincl = torch.cumsum(vflag, 0, dtype=torch.int32)
+    fincl = torch.cumsum(fflag, 0, dtype=torch.int32)
+    zero = torch.zeros(1, dtype=torch.int32, device=dev)
+    nv, nf, bad = torch.cat([vincl[-1:] if n_verts else zero, fincl[-1:] if n_faces else zero, status]).tolist()
+    if bad:
+        _check_mesh_status("mesh_select", status)
+    vpre, fpre = vincl - vflag, fincl - fflag
+    verts_out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    faces_out = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    normals_out = None if normals is None else torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    if nv:
+        check(L.hm_mesh_select_emit(dptr(verts), dptr(normals), dptr(faces), n_faces, n_verts, dptr(vflag), dptr(vpre),
+                                    dptr(fflag), dptr(fpre), nv, nf, dptr(verts_out), dptr(normals_out),
+                                    dptr(faces_out), st))
+    return verts_out, faces_out, normals_out
+
+
+def mesh_largest_component(verts, faces, normals=None):
+    """(verts, faces, normals) of the component with the largest area - eval.py's components[areas.argmax()] after
+    mesh.split(only_watertight=False), on the device: mesh_components, mesh_component_areas, the first maximum (equal
+    areas go to the lower id, as numpy's argmax over split()'s order), mesh_select.  A mesh without faces comes back
+    unchanged.  Host reads in every step; not graph-capturable."""
+    n_faces, n_verts = _check_mesh("mesh_largest_component", faces, verts=verts, normals=normals)
+    if n_faces == 0:
+        return verts, faces, normals
+    label = mesh_components(faces, n_verts)
+    ids, area, _ = mesh_component_areas(verts, faces, label)
+    return mesh_select(verts, faces, normals, label, int(ids[torch.argmax(area)].item()))
+
+
+def mesh_surface_moments(verts, faces):
+    """(area [] , mean [3], cov [3,3]) float64 of the uniform distribution on the mesh surface, exact from its
+    triangles: the formula of utils/plots._surface_moments in fp64 on the fp32 vertices, as a fixed-order two-level
+    reduction (two calls give the same bits).  NaN mean and covariance for a mesh without area.  V and F < 2^31; one
+    host read of the status word, so not graph-capturable."""
+    n_faces, n_verts = _check_mesh("mesh_surface_moments", faces, verts=verts)
+    dev = faces.device
+    L = lib()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(13, dtype=torch.float64, device=dev)
+    ws = torch.empty(check(L.hm_mesh_moments_workspace_bytes(n_faces)), dtype=torch.uint8, device=dev)
+    check(L.hm_mesh_moments(dptr(verts), dptr(faces), n_faces, n_verts, dptr(out), dptr(ws), ws.numel(), dptr(status),
+                            stream_ptr(faces)))
+    _check_mesh_status("mesh_surface_moments", status)
+    return out[0], out[1:4], out[4:13].view(3, 3)

@@ -253,7 +253,7 @@ def _surface_moments(mesh):
     return mean, cov
 
 
-def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False):
+def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False, largest_component=False):
     """plots.py:146-224: the zero level set of `sdf` on a lattice aligned with the principal axes of a coarse mesh's
     largest component, `resolution` samples along its shortest axis; a TriMesh in world space, or None without a
     sign change.  Two deliberate deviations (mesh extraction): the principal axes come from the exact
@@ -263,7 +263,14 @@ def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False):
     sparse=True evaluates the aligned lattice only near the surface (ops.marching_cubes_sparse, seeded with the coarse
     mesh's vertices of all components): the mesh of the full lattice except for components that the coarse 100^3
     lattice does not see, which are absent as a whole.  Its vertices differ from sparse=False in the last bits (the
-    lattice points are generated by another fp32 expression).  The lattice may exceed 2^31 points."""
+    lattice points are generated by another fp32 expression).  The lattice may exceed 2^31 points.
+
+    largest_component=True keeps only the fine mesh's component of the largest area (ops.mesh_largest_component) - the
+    cleanup evaluation/eval.py applies to every fine mesh, mesh.split(only_watertight=False) and the part at the
+    areas' argmax - on the device, so that only that component is downloaded: the TriMesh
+    max(get_surface_high_res_mesh(...).split(only_watertight=False), key=area), bit for bit.  The component is taken
+    from the world-space fp32 vertices, the ones the host split would see: the transform of all vertices is a [V,3] x
+    [3,3] product, and selecting rows afterwards cannot change their bits."""
     lin = np.linspace(-1.0, 1.0, 100)      # the coarse 100^3 grid of get_grid_uniform(100)
     coarse = _mesh_on_lattice(sdf, (lin, lin, lin), device)
     if coarse is None:
@@ -299,4 +306,7 @@ def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False):
     origin = torch.tensor([[x[0], y[0], z[0]]], dtype=torch.float32, device=device) @ rot + shift  # grid_points[0]
     verts = verts @ rot + origin
     normals = normals @ rot
+    if largest_component:
+        verts, faces, normals = ops.mesh_largest_component(verts.contiguous(), faces.contiguous(),
+                                                           normals.contiguous())
     return TriMesh(verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy())

@@ -762,6 +762,54 @@ HM_API int hm_mcs_emit(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lat
                        int64_t n_faces, float *verts, float *normals, int32_t *faces, int64_t *vert_keys,
                        int64_t *face_keys, void *stream);
 
+/* ---- mesh cleanup: connected components, their areas, surface moments, one component's submesh ---------
+ * Replaces what evaluation/eval.py does to every fine mesh on the host - components = mesh.split(only_watertight=
+ * False); areas = [c.area for c in components]; mesh = components[areas.argmax()] - and the exact surface moments
+ * (plots._surface_moments) that stand in for the reference's trimesh.sample.  Driver: ops.mesh_components,
+ * ops.mesh_component_areas, ops.mesh_select, ops.mesh_largest_component, ops.mesh_surface_moments.
+ * A mesh is verts [n_verts, 3] fp32 and faces [n_faces, 3] int32, contiguous (what hm_mc_emit writes); n_verts and
+ * n_faces < 2^31.  status is one device int32 the CALLER has zeroed: bit 0 is set when a face index lies outside
+ * [0, n_verts) (or a label / rank does not fit the mesh) - such an index is never dereferenced and its face is left
+ * out; the caller reads the word with its counts and raises.  No entry point synchronises; the floating-point sums
+ * use no atomics and a fixed order, so repeated calls give the same bits.
+ *   hm_mesh_cc_labels (split): label [n_verts] int32 = the smallest vertex id of the vertex' component; two vertices
+ *                are connected when a face holds both, a vertex of no face labels itself.  Lock-free union-find over
+ *                the face edges (f0, f1), (f1, f2) in one pass, then a flatten launch (csrc/hm_mesh_cc.hip).
+ *   hm_mesh_cc_face_stats (c.area, per face): face_area [n_faces] fp64 = 0.5 |(v1 - v0) x (v2 - v0)| of the vertices
+ *                cast to fp64 (TriMesh.area_faces); used [n_verts] int32, zeroed by the caller, gets 1 at every vertex
+ *                of a face.
+ *   hm_mesh_cc_sums (c.area, per component): rank [n_verts] int32 is, at a root with used != 0, its position among
+ *                those roots in ascending order (an exclusive prefix sum; other entries are not read); area
+ *                [n_components] fp64 and count [n_components] int64 receive each such component's area and number of
+ *                faces: the faces are sorted by their component's rank with hm_sort_pairs_i32 (stable) and every run
+ *                is summed in a fixed order.  workspace: hm_mesh_cc_sums_workspace_bytes(n_faces).
+ *   hm_mesh_moments: out [13] fp64 = total area, mean [3] and covariance [3][3] of the uniform distribution on the
+ *                surface, the formula of plots._surface_moments in fp64: block partials, then one workgroup.  NaN mean
+ *                and covariance when the area is 0.  workspace: hm_mesh_moments_workspace_bytes(n_faces).
+ *   hm_mesh_select_mark (components[argmax]): fflag [n_faces] int32 = 1 for the faces whose first vertex has label
+ *                == component, else 0; vflag [n_verts] int32, zeroed by the caller, gets 1 at their vertices.
+ *   hm_mesh_select_emit: vpre / fpre are the exclusive prefix sums of vflag / fflag (int32) and n_verts_out /
+ *                n_faces_out their totals, read by the caller: verts_out / normals_out [n_verts_out, 3] are the flagged
+ *                rows in ascending order (normals may be NULL), faces_out [n_faces_out, 3] the flagged faces in order
+ *                with index v replaced by vpre[v] - np.unique(faces, return_inverse=True) as TriMesh.split uses it. */
+HM_API int hm_mesh_cc_labels(const int32_t *faces, int64_t n_faces, int64_t n_verts, int32_t *label, int32_t *status,
+                             void *stream);
+HM_API int hm_mesh_cc_face_stats(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                                 double *face_area, int32_t *used, int32_t *status, void *stream);
+HM_API int64_t hm_mesh_cc_sums_workspace_bytes(int64_t n_faces);
+HM_API int hm_mesh_cc_sums(const int32_t *faces, int64_t n_faces, int64_t n_verts, const int32_t *label,
+                           const int32_t *rank, const double *face_area, int64_t n_components, double *area,
+                           int64_t *count, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+HM_API int64_t hm_mesh_moments_workspace_bytes(int64_t n_faces);
+HM_API int hm_mesh_moments(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, double *out,
+                           void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+HM_API int hm_mesh_select_mark(const int32_t *faces, int64_t n_faces, int64_t n_verts, const int32_t *label,
+                               int32_t component, int32_t *vflag, int32_t *fflag, int32_t *status, void *stream);
+HM_API int hm_mesh_select_emit(const float *verts, const float *normals, const int32_t *faces, int64_t n_faces,
+                               int64_t n_verts, const int32_t *vflag, const int32_t *vpre, const int32_t *fflag,
+                               const int32_t *fpre, int64_t n_verts_out, int64_t n_faces_out, float *verts_out,
+                               float *normals_out, int32_t *faces_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
