@@ -117,6 +117,12 @@ SIGNATURES = {
     "hm_mesh_moments": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _p]),
     "hm_mesh_select_mark": (_int, [_p, _i64, _i64, _p, C.c_int32, _p, _p, _p, _p]),
     "hm_mesh_select_emit": (_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    # the DTU Chamfer evaluation: exact nearest neighbours on a uniform grid, triangle upsampling to a point density
+    "hm_nn_workspace_bytes": (_i64, [_i64]),
+    "hm_nn_build": (_int, [_p, _i64, _p, C.c_float, _p, _p, _p, _p, _i64, _p, _p]),
+    "hm_nn_query": (_int, [_p, _i64, _p, _i64, _p, _p, C.c_float, _p, C.c_float, _p, _p, _p, _i64, _p, _p, _p]),
+    "hm_mesh_sample_count": (_int, [_p, _p, _i64, _i64, C.c_double, _p, _p, _p, _p]),
+    "hm_mesh_sample_emit": (_int, [_p, _p, _i64, _i64, C.c_double, _p, _i64, _i64, _p, _p, _p]),
 }
 
 

@@ -1454,9 +1454,11 @@ def marching_cubes_sparse(sdf, axes, spacing, seeds, level=0.0, rot=None, shift=
 # =========================================================================================
 # mesh cleanup: components, areas, moments, largest component (csrc/hm_mesh_cc.hip)
 # =========================================================================================
-def _check_mesh(what, faces, n_verts=None, verts=None, normals=None, label=None):
-    """the checks the mesh cleanup ops share; returns (F, V)"""
-    require_gpu(faces, verts, normals, label)
+def _check_mesh(what, faces, n_verts=None, verts=None, normals=None, label=None, gpu_first=True):
+    """the checks the mesh ops share; returns (F, V).  A CPU tensor raises HashmodError before its dtype and shape are
+    looked at, or after them with gpu_first=False"""
+    if gpu_first:
+        require_gpu(faces, verts, normals, label)
     if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
         raise ValueError(f"hashmod {what}: contiguous int32 faces [F, 3] expected")
     if verts is not None:
@@ -1474,6 +1476,7 @@ def _check_mesh(what, faces, n_verts=None, verts=None, normals=None, label=None)
     for t in (verts, normals, label):
         if t is not None and t.device != faces.device:
             raise ValueError(f"hashmod {what}: the tensors are on different devices")
+    require_gpu(faces, verts, normals, label)
     return n_faces, n_verts
 
 
@@ -1593,3 +1596,239 @@ def mesh_surface_moments(verts, faces):
                             stream_ptr(faces)))
     _check_mesh_status("mesh_surface_moments", status)
     return out[0], out[1:4], out[4:13].view(3, 3)
+
+
+# =========================================================================================
+# Chamfer evaluation: nearest neighbours, triangle upsampling, the metric (csrc/hm_nn.hip, csrc/hm_mesh_sample.hip)
+# =========================================================================================
+NN_MAX_CELLS = 1 << 26      # cap of the dense cell_start table (256 MiB of int32)
+_NN_PER_CELL = 4.0          # points per occupied cell the default cell edge aims at
+_NN_WS = _lib.Workspace("nearest_neighbors")
+
+
+def _check_cloud(what, name, t, like=None):
+    """contiguous fp32 [., 3]; on `like`'s device; a GPU tensor"""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3
+            or not t.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous fp32 {name} [., 3] expected")
+    if t.shape[0] >= 1 << 31:
+        raise ValueError(f"hashmod {what}: {name} must have fewer than 2^31 rows")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"hashmod {what}: the tensors are on different devices")
+
+
+def _nn_grid(lo, hi, n, cell):
+    """(h as fp32, g[3]) of the grid over the box [lo, hi] (float lists): the cell edge a surface-like cloud of n points
+    needs for _NN_PER_CELL points per occupied cell - its area taken as half the box's - unless `cell` gives it, grown
+    until the grid has at most NN_MAX_CELLS cells; a zero extent gives one cell on that axis"""
+    ext = [max(float(b) - float(a), 0.0) for a, b in zip(lo, hi)]
+    if cell is None:
+        area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2]
+        if area > 0.0:
+            h = math.sqrt(_NN_PER_CELL * area / n)
+        elif max(ext) > 0.0:
+            h = _NN_PER_CELL * max(ext) / n
+        else:
+            h = 1.0
+        h = max(h, max(ext) * 2.0 ** -20)
+    else:
+        h = float(cell)
+    while True:
+        h = float(np.float32(h))
+        if not (h > 0.0 and math.isfinite(h)):
+            raise ValueError("hashmod nn_index: the cell edge must be positive and finite in fp32")
+        g = [int(math.floor(e / h)) + 1 for e in ext]
+        if max(g) <= 1 << 30 and g[0] * g[1] * g[2] <= NN_MAX_CELLS:
+            return h, g
+        if cell is not None:
+            raise ValueError(f"hashmod nn_index: cell={cell} gives a grid of {g[0]}x{g[1]}x{g[2]} cells, more than "
+                             f"NN_MAX_CELLS = {NN_MAX_CELLS}")
+        h *= 1.125
+
+
+class NNIndex:
+    """The uniform grid over a point cloud that ops.nn_index builds: the points ordered by cell as 16-byte records and
+    the dense cell_start table.  query() answers nearest-neighbour queries against it."""
+
+    def __init__(self, points, cell=None):
+        _check_cloud("nn_index", "points", points)
+        if cell is not None and not (isinstance(cell, (int, float)) and math.isfinite(cell) and cell > 0):
+            raise ValueError("hashmod nn_index: cell must be a positive finite number")
+        n = int(points.shape[0])
+        if n < 1:
+            raise ValueError("hashmod nn_index: at least one point is needed")
+        require_gpu(points)
+        dev = points.device
+        lo, hi = torch.aminmax(points, dim=0)
+        box = torch.stack([lo, hi]).tolist()
+        if not all(math.isfinite(v) for v in box[0] + box[1]):
+            raise _lib.HashmodError("hashmod nn_index: a point has a non-finite coordinate")
+        self.h, self.g = _nn_grid(box[0], box[1], n, cell)
+        self.lo = box[0]
+        self.n = n
+        self.device = dev
+        cells = self.g[0] * self.g[1] * self.g[2]
+        self.cell_start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+        self.records = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        L = lib()
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _NN_WS.get(dev, check(L.hm_nn_workspace_bytes(n)))
+        check(L.hm_nn_build(dptr(points), n, self._lo(), self.h, self._g(), dptr(self.cell_start), dptr(self.records),
+                            dptr(ws), ws.numel(), dptr(status), stream_ptr(points)))
+        if int(status.item()):
+            raise _lib.HashmodError("hashmod nn_index: a point has a non-finite coordinate")
+
+    def _lo(self):
+        return (C.c_float * 3)(*self.lo)
+
+    def _g(self):
+        return (C.c_int32 * 3)(*self.g)
+
+    def _query(self, query, max_dist2, stats=None):
+        """stats: a dict that receives "candidate_tests", the launch's number of distance evaluations (one more host
+        read; for scripts/chamfer_time.py)"""
+        _check_cloud("nearest_neighbors", "query", query, self.records)
+        m = int(query.shape[0])
+        dev = self.device
+        d2 = torch.empty(m, dtype=torch.float32, device=dev)
+        index = torch.empty(m, dtype=torch.int32, device=dev)
+        if m == 0:
+            return d2, index
+        L = lib()
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _NN_WS.get(dev, check(L.hm_nn_workspace_bytes(m)))
+        tests = None if stats is None else torch.zeros(1, dtype=torch.int64, device=dev)
+        check(L.hm_nn_query(dptr(query), m, dptr(self.records), self.n, dptr(self.cell_start), self._lo(), self.h,
+                            self._g(), max_dist2, dptr(d2), dptr(index), dptr(ws), ws.numel(), dptr(status),
+                            dptr(tests), stream_ptr(query)))
+        if stats is not None:
+            stats["candidate_tests"] = int(tests.item())
+        if int(status.item()):
+            raise _lib.HashmodError("hashmod nearest_neighbors: a query has a non-finite coordinate")
+        return d2, index
+
+    def query(self, query, max_dist=None):
+        """(d2 [m] fp32, index [m] int32) of the nearest point of every row of query [m,3]: see nearest_neighbors"""
+        return self._query(query, _max_dist2("nearest_neighbors", max_dist))
+
+
+def _max_dist2(what, max_dist):
+    """max_dist as the kernel's fp32 bound on d2: fp32(max_dist) squared in fp32; inf for None"""
+    if max_dist is None:
+        return math.inf
+    if not (isinstance(max_dist, (int, float)) and max_dist >= 0):      # NaN fails
+        raise ValueError(f"hashmod {what}: max_dist must be a number >= 0 (or None)")
+    md = np.float32(max_dist)
+    with np.errstate(over="ignore"):
+        return float(md * md)
+
+
+def nn_index(points, cell=None):
+    """The search structure of nearest_neighbors over points [n,3] fp32 (n >= 1), to be queried many times: a uniform
+    grid of cell edge `cell` over the points' bounding box (read by the host through aminmax).  Without `cell` the
+    edge is chosen from n and the box so that an occupied cell of a surface-like cloud holds a handful of points; the
+    dense cell table is capped at NN_MAX_CELLS = 2^26 cells (the edge grows to fit; an explicit `cell` that does not
+    fit raises ValueError).  A zero extent on an axis gives one cell on that axis.  The points are ordered by cell with
+    the library's stable radix sort.  A non-finite coordinate raises HashmodError.  The grid changes the speed of a
+    query, never its result.  Host reads of the box and the status word, so not graph-capturable."""
+    return NNIndex(points, cell)
+
+
+def nearest_neighbors(query, points, max_dist=None, cell=None):
+    """(d2 [m] fp32, index [m] int32): for every row of query [m,3] the row of points [n,3] that minimises the fp32
+    value d2 = (dx*dx + dy*dy) + dz*dz, dx = q.x - p.x and so on, each operation rounded once; among equal d2 the
+    lowest index.  That is a brute-force fp32 argmin over all points, bit for bit: exact, and independent of the grid,
+    of m and of the thread order.  With max_dist, a query whose d2 exceeds fp32(max_dist)^2 (squared in fp32) gets
+    index -1 and d2 = inf; d2 equal to the bound is reported.  m = 0 gives empty outputs; n >= 1, contiguous fp32
+    tensors on one GPU (else ValueError); a non-finite coordinate raises HashmodError.  nn_index(points, cell).query(
+    query, max_dist) is the same in two steps.  Host reads of the box and the status words, so not
+    graph-capturable."""
+    _check_cloud("nearest_neighbors", "query", query)
+    _check_cloud("nearest_neighbors", "points", points, query)
+    md2 = _max_dist2("nearest_neighbors", max_dist)
+    return NNIndex(points, cell)._query(query, md2)
+
+
+def mesh_sample_surface(verts, faces, density, return_face=False):
+    """samples [S,3] fp32 (and face_of [S] int32 with return_face): every triangle upsampled to one point per
+    density^2 of area by the rule of the DTU evaluation, in fp64 on the fp32 vertices - include/hashmod.h states it;
+    tests/nn_cases.sample_ref is its numpy restatement and gives the same points bit for bit.  Faces ascending, then
+    the rule's own order; faces without area or smaller than the density give nothing, a mesh without faces [0,3].
+    density > 0 and finite (else ValueError); a face index outside [0, V) raises HashmodError (reported by the kernel,
+    never dereferenced); S < 2^31.  Host reads of the total and the status word, so not graph-capturable."""
+    if not (isinstance(density, (int, float)) and math.isfinite(density) and density > 0):
+        raise ValueError("hashmod mesh_sample_surface: density must be a positive finite number")
+    n_faces, n_verts = _check_mesh("mesh_sample_surface", faces, verts=verts, gpu_first=False)
+    dev = faces.device
+    samples = torch.empty((0, 3), dtype=torch.float32, device=dev)
+    face_of = torch.empty(0, dtype=torch.int32, device=dev)
+    if n_faces:
+        L = lib()
+        st = stream_ptr(faces)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        count = torch.empty(n_faces, dtype=torch.int64, device=dev)
+        rows = torch.empty(n_faces, dtype=torch.int32, device=dev)
+        check(L.hm_mesh_sample_count(dptr(verts), dptr(faces), n_faces, n_verts, float(density), dptr(count),
+                                     dptr(rows), dptr(status), st))
+        # bookkeeping between the launches: positions from the counts, the totals to the host
+        incl = torch.cumsum(count, 0)
+        total, max_rows, bad = torch.stack([incl[-1], rows.max().to(torch.int64), status[0].to(torch.int64)]).tolist()
+        if bad:
+            _check_mesh_status("mesh_sample_surface", status)
+        if total >= 1 << 31:
+            raise ValueError(f"hashmod mesh_sample_surface: density={density} gives 2^31 samples or more")
+        if total:
+            samples = torch.empty((total, 3), dtype=torch.float32, device=dev)
+            face_of = torch.empty(total, dtype=torch.int32, device=dev)
+            prefix = incl - count
+            check(L.hm_mesh_sample_emit(dptr(verts), dptr(faces), n_faces, n_verts, float(density), dptr(prefix),
+                                        total, max_rows, dptr(samples), dptr(face_of), st))
+    return (samples, face_of) if return_face else samples
+
+
+class ChamferResult(tuple):
+    """mean_a2b, mean_b2a, overall = (mean_a2b + mean_b2a)/2 and the numbers of distances n_a2b, n_b2a that entered
+    the two means, as host scalars; mesh_chamfer adds n_cloud"""
+    _fields = ("mean_a2b", "mean_b2a", "overall", "n_a2b", "n_b2a", "n_cloud")
+
+    def __new__(cls, mean_a2b, mean_b2a, n_a2b, n_b2a, n_cloud=None):
+        return super().__new__(cls, (mean_a2b, mean_b2a, 0.5 * (mean_a2b + mean_b2a), n_a2b, n_b2a, n_cloud))
+
+    def __getattr__(self, name):
+        try:
+            return self[self._fields.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+    def __repr__(self):
+        return "ChamferResult(" + ", ".join(f"{k}={v!r}" for k, v in zip(self._fields, self)) + ")"
+
+
+def _one_sided(src, index, max_dist, md2):
+    """(sum, count) as one fp64 [2] device tensor of the distances src -> the index's cloud below max_dist"""
+    d2, _ = index._query(src, md2)
+    d = torch.sqrt(d2.to(torch.float64))
+    keep = d < max_dist if max_dist is not None else torch.ones_like(d, dtype=torch.bool)
+    zero = torch.zeros((), dtype=torch.float64, device=d.device)
+    return torch.stack([torch.where(keep, d, zero).sum(), keep.sum().to(torch.float64)])
+
+
+def chamfer_distance(a, b, max_dist=None):
+    """ChamferResult of the clouds a [na,3] and b [nb,3] (fp32, both non-empty): the DTU evaluation's accuracy and
+    completeness.  mean_a2b is the mean over the points of a of the distance to their nearest point of b, taken over
+    the distances < max_dist (strict, the DTU rule; all of them for None), mean_b2a the same the other way, overall
+    their mean; n_a2b, n_b2a count the distances that entered.  A mean over no distance is nan with count 0.  The
+    distances are the fp64 square roots of nearest_neighbors' exact fp32 d2; the sums are fixed-order fp64 device
+    reductions, so two calls give the same bits.  Only the four scalars come to the host.  Not graph-capturable."""
+    _check_cloud("chamfer_distance", "a", a)
+    _check_cloud("chamfer_distance", "b", b, a)
+    if max_dist is not None and not (isinstance(max_dist, (int, float)) and max_dist > 0):
+        raise ValueError("hashmod chamfer_distance: max_dist must be a positive number (or None)")
+    if a.shape[0] < 1 or b.shape[0] < 1:
+        raise ValueError("hashmod chamfer_distance: both clouds need at least one point")
+    # the kernel may stop searching beyond a bound safely above max_dist; the strict fp64 rule is applied afterwards
+    md2 = math.inf if max_dist is None else float(np.nextafter(np.float32(min(float(max_dist) ** 2 * (1.0 + 1e-6),
+                                                                             3.0e38)), np.float32(np.inf)))
+    sa, ca, sb, cb = torch.cat([_one_sided(a, NNIndex(b), max_dist, md2),
+                                _one_sided(b, NNIndex(a), max_dist, md2)]).tolist()
+    return ChamferResult(sa / ca if ca else math.nan, sb / cb if cb else math.nan, int(ca), int(cb))

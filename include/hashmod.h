@@ -810,6 +810,52 @@ HM_API int hm_mesh_select_emit(const float *verts, const float *normals, const i
                                const int32_t *fpre, int64_t n_verts_out, int64_t n_faces_out, float *verts_out,
                                float *normals_out, int32_t *faces_out, void *stream);
 
+/* ---- Chamfer evaluation: exact nearest neighbours on a uniform grid, deterministic triangle upsampling ---------
+ * The device side of the reference's DTU Chamfer evaluation (code/evaluation/dtu_eval): upsample every triangle to a
+ * point density, nearest-neighbour distances between two clouds.  Driver: ops.nn_index, ops.nearest_neighbors,
+ * ops.mesh_sample_surface, ops.chamfer_distance, evaluation.chamfer.mesh_chamfer.  status is one device int32 the
+ * CALLER has zeroed; no entry point synchronises, none uses floating-point atomics, no atomic decides a position.
+ *
+ * The grid: origin lo[3], cell edge h > 0 and dimensions g[3] >= 1 are HOST values, g[0]*g[1]*g[2] < 2^31.  The cell
+ * of a coordinate is clamp(floor((p - lo) / h), 0, g - 1) per axis in fp32, its key (cx*g[1] + cy)*g[2] + cz.
+ *   hm_nn_workspace_bytes(n): the scratch of hm_nn_build over n points, and of hm_nn_query over n queries.
+ *   hm_nn_build: points [n,3] fp32, 1 <= n < 2^31.  Writes cell_start [cells + 1] int32 (the points of cell c are
+ *                records [cell_start[c], cell_start[c+1])) and records [n,4] fp32: the points ordered by cell with the
+ *                library's stable sort (ascending original index inside a cell) as x, y, z and the original index as
+ *                the int32 bits of the fourth word.  cell_start comes from a binary search of the sorted keys per
+ *                cell: plain stores.  A non-finite coordinate sets status bit 0 and goes to cell 0.
+ *   hm_nn_query: query [m,3] fp32, m >= 0.  For every query, index [m] int32 is the point that minimises the fp32
+ *                value d2 = (dx*dx + dy*dy) + dz*dz (dx = q.x - p.x, ..., every operation rounded once), the smallest
+ *                original index among equal d2, and d2 [m] that value: what a brute-force fp32 argmin over all points
+ *                returns, bit for bit, whatever the grid, m and the thread order.  max_dist2 (fp32, +inf = none): a
+ *                query whose minimum is > max_dist2 gets index -1 and d2 +inf; == max_dist2 is reported.  A non-finite
+ *                query coordinate sets status bit 1.  The queries are sorted by cell, a wave takes 64 of them and
+ *                searches a growing box of cells (csrc/hm_nn.hip states the stopping rule).  n_tests (may be NULL;
+ *                a measurement aid): a device counter the caller has zeroed, receives the number of (query lane,
+ *                candidate) distance evaluations of the launch.
+ * Triangle upsampling (the DTU rule; fp64, every operation rounded once; a, b, c the face's fp32 vertices as fp64):
+ *   v1 = b - a, v2 = c - a, l1 = sqrt((v1x^2 + v1y^2) + v1z^2), l2 likewise, A2 = |v1 x v2| (same sum order); no
+ *   samples unless A2 > 0; thr = density*sqrt(l1*l2/A2), n1 = floor(l1/thr), n2 = floor(l2/thr); no samples unless
+ *   n1 >= 1 and n2 >= 1; for i in 0..n1, j in 0..n2 (inclusive, i outer): u = (i + 0.5)/n1, v = (j + 0.5)/n2, keep
+ *   when u + v < 1 the point fp32((v1*u + v2*v) + a).
+ *   hm_mesh_sample_count: count [n_faces] int64 samples per face and rows [n_faces] int32 (n1 + 1, or 0 without
+ *                samples).  A face index outside [0, n_verts) sets status bit 0 and is never dereferenced; a face whose
+ *                n1*n2 exceeds 2^33 counts as 2^40 samples (the caller rejects totals >= 2^31 anyway).
+ *   hm_mesh_sample_emit: prefix [n_faces] int64 = the exclusive prefix sum of count, n_samples its total (< 2^31),
+ *                max_rows the maximum of rows.  Writes samples [n_samples,3] fp32 and face_of [n_samples] int32: faces
+ *                ascending, then i, then j.  One wave per face and per 1024 rows of it, lanes over the samples. */
+HM_API int64_t hm_nn_workspace_bytes(int64_t n);
+HM_API int hm_nn_build(const float *points, int64_t n, const float *lo, float h, const int32_t *g, int32_t *cell_start,
+                       float *records, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+HM_API int hm_nn_query(const float *query, int64_t m, const float *records, int64_t n, const int32_t *cell_start,
+                       const float *lo, float h, const int32_t *g, float max_dist2, float *d2, int32_t *index,
+                       void *workspace, int64_t workspace_bytes, int32_t *status, uint64_t *n_tests, void *stream);
+HM_API int hm_mesh_sample_count(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                                double density, int64_t *count, int32_t *rows, int32_t *status, void *stream);
+HM_API int hm_mesh_sample_emit(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                               double density, const int64_t *prefix, int64_t n_samples, int64_t max_rows,
+                               float *samples, int32_t *face_of, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
