@@ -123,6 +123,13 @@ SIGNATURES = {
     "hm_nn_query": (_int, [_p, _i64, _p, _i64, _p, _p, C.c_float, _p, C.c_float, _p, _p, _p, _i64, _p, _p, _p]),
     "hm_mesh_sample_count": (_int, [_p, _p, _i64, _i64, C.c_double, _p, _p, _p, _p]),
     "hm_mesh_sample_emit": (_int, [_p, _p, _i64, _i64, C.c_double, _p, _i64, _i64, _p, _p, _p]),
+    # the rest of the DTU evaluation: greedy radius down-sampling on hm_nn_build's grid, the per-point filters
+    "hm_nn_radius_workspace_bytes": (_i64, [_i64]),
+    "hm_nn_radius_begin": (_int, [_i64, _p, _i64, _p, _p]),
+    "hm_nn_radius_rounds": (_int, [_p, _i64, _p, _p, C.c_float, _p, C.c_float, C.c_float, _i64, _i64, C.c_int32, _p,
+                                   _i64, _p, _p]),
+    "hm_nn_radius_finish": (_int, [_p, _i64, _p, _i64, _p, _p]),
+    "hm_dtu_point_flags": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
 }
 
 

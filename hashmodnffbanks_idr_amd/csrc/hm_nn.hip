@@ -16,36 +16,18 @@
 // under the total order (d2, original index): it does not depend on which wave or box the query fell into.
 // Lanes that are not finished (stopping rule at nn_face_low) make the wave grow the box on all sides by a doubling
 // ring; only the new shell is scanned.  A box that covers the grid has no faces left and ends the search.
+// The grid record, the cell function and the host-side grid check are in hm_nn_dev.h, shared with hm_nn_radius.hip.
 #include <math.h>
 
 #include "hm_common.h"
+#include "hm_nn_dev.h"
 
 namespace {
 
-constexpr int kNT = 256;      // threads of the elementwise kernels
 constexpr int kChunk = 256;   // records staged in LDS per pass (4 KiB)
 constexpr int32_t kNoIndex = 0x7fffffff;
 
-struct NnGrid {
-    float lo[3];
-    float h;
-    int32_t g[3];
-    int32_t pad_;
-};
-
 inline int64_t nn_up256(int64_t b) { return (b + 255) / 256 * 256; }
-inline unsigned nn_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-// clamp(floor((p - lo) / h), 0, g - 1) with every operation rounded once; monotone non-decreasing in p.  g <= 2^30.
-__device__ __forceinline__ int32_t nn_cell(float p, float lo, float h, int32_t g) {
-    const float t = floorf(__fdiv_rn(__fsub_rn(p, lo), h));
-    const int32_t c = (int32_t)fminf(fmaxf(t, 0.0f), 1073741824.0f);   // NaN -> 0
-    return c < g - 1 ? c : g - 1;
-}
-
-__device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
-    return isfinite(x) && isfinite(y) && isfinite(z);
-}
 
 __global__ __launch_bounds__(kNT) void nn_key_kernel(const float *__restrict__ p, int64_t n, NnGrid G,
                                                      int32_t *__restrict__ key, int32_t *status, int32_t bit) {
@@ -275,24 +257,6 @@ __global__ __launch_bounds__(64) void nn_query_kernel(const float *__restrict__ 
         d2_out[src] = hit ? best : INFINITY;
         idx_out[src] = hit ? best_i : -1;
     }
-}
-
-int nn_grid(const float *lo, float h, const int32_t *g, const char *what, NnGrid &G, int64_t &cells) {
-    const std::string w(what);
-    HM_CHECK_ARG(lo && g, w + ": NULL grid");
-    HM_CHECK_ARG(std::isfinite(lo[0]) && std::isfinite(lo[1]) && std::isfinite(lo[2]) && std::isfinite(h) && h > 0.0f,
-                 w + ": the grid origin must be finite and the cell edge finite and positive");
-    cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        HM_CHECK_ARG(g[a] >= 1 && g[a] <= (1 << 30), w + ": grid dimensions must be in [1, 2^30]");
-        cells *= g[a];
-        HM_CHECK_ARG(cells < ((int64_t)1 << 31), w + ": the grid must have fewer than 2^31 cells");
-        G.lo[a] = lo[a];
-        G.g[a] = g[a];
-    }
-    G.h = h;
-    G.pad_ = 0;
-    return HM_OK;
 }
 
 struct NnWs {

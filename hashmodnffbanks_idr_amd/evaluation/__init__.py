@@ -1,2 +1,2 @@
 """Evaluation of a reconstructed mesh on the device (reference: code/evaluation)."""
-from .chamfer import mesh_chamfer  # noqa: F401
+from .chamfer import dtu_chamfer, load_dtu_scan, mesh_chamfer  # noqa: F401

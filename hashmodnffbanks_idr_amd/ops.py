@@ -1826,9 +1826,129 @@ def chamfer_distance(a, b, max_dist=None):
         raise ValueError("hashmod chamfer_distance: max_dist must be a positive number (or None)")
     if a.shape[0] < 1 or b.shape[0] < 1:
         raise ValueError("hashmod chamfer_distance: both clouds need at least one point")
-    # the kernel may stop searching beyond a bound safely above max_dist; the strict fp64 rule is applied afterwards
-    md2 = math.inf if max_dist is None else float(np.nextafter(np.float32(min(float(max_dist) ** 2 * (1.0 + 1e-6),
-                                                                             3.0e38)), np.float32(np.inf)))
+    md2 = _search_bound2(max_dist)
     sa, ca, sb, cb = torch.cat([_one_sided(a, NNIndex(b), max_dist, md2),
                                 _one_sided(b, NNIndex(a), max_dist, md2)]).tolist()
     return ChamferResult(sa / ca if ca else math.nan, sb / cb if cb else math.nan, int(ca), int(cb))
+
+
+def _search_bound2(max_dist):
+    """the kernel may stop searching beyond a bound safely above max_dist; the strict fp64 rule is applied afterwards"""
+    return math.inf if max_dist is None else float(np.nextafter(np.float32(min(float(max_dist) ** 2 * (1.0 + 1e-6),
+                                                                              3.0e38)), np.float32(np.inf)))
+
+
+def one_sided_distance(src, dst, max_dist=None, cell=None):
+    """(mean, count): one direction of chamfer_distance for two different sets - the mean over the rows of src [m,3]
+    of the distance to their nearest row of dst [n,3], over the distances < max_dist (strict; all for None), and how
+    many entered.  The same distances, rule and fixed-order fp64 reduction as chamfer_distance's mean_a2b, which it
+    equals bit for bit for (a, b).  An empty src or dst, or no distance below max_dist, gives (nan, 0).  `cell` is
+    nn_index's.  Host scalars; not graph-capturable."""
+    _check_cloud("one_sided_distance", "src", src)
+    _check_cloud("one_sided_distance", "dst", dst, src)
+    if max_dist is not None and not (isinstance(max_dist, (int, float)) and max_dist > 0):
+        raise ValueError("hashmod one_sided_distance: max_dist must be a positive number (or None)")
+    if src.shape[0] < 1 or dst.shape[0] < 1:
+        return math.nan, 0
+    s, c = _one_sided(src, NNIndex(dst, cell), max_dist, _search_bound2(max_dist)).tolist()
+    return (s / c if c else math.nan), int(c)
+
+
+# =========================================================================================
+# The rest of the DTU evaluation: greedy radius down-sampling, mask and plane filters (csrc/hm_nn_radius.hip,
+# csrc/hm_dtu_filter.hip)
+# =========================================================================================
+_NR_WS = _lib.Workspace("radius_downsample")
+_NR_BATCH = 4               # rounds launched between two host reads of the remaining count
+_NR_TAIL = 1024             # hm_nn_radius_rounds finishes a list this short in one workgroup
+
+
+def radius_downsample(points, radius, cell=None, stats=None):
+    """keep [n] bool: DTU's greedy down-sampling of points [n,3] fp32 -
+        mask = ones; for i in range(n): if mask[i]: mask[neighbours of i within radius] = 0; mask[i] = 1
+    - on the device.  Index order is the greedy order (shuffle beforehand, as DTU does).  j is a neighbour of i when the
+    fp32 value d2 = (dx*dx + dy*dy) + dz*dz of nearest_neighbors is <= fp32(radius)^2 (squared in fp32); equality
+    counts, as in sklearn's radius_neighbors.  A point is kept exactly when none of its lower-index neighbours is kept,
+    which csrc/hm_nn_radius.hip finds in rounds on nn_index's grid; the result is the sequential loop's, bit for bit,
+    whatever the grid (`cell`, nn_index's argument, changes the speed only) and the thread order.  Shuffled clouds take
+    a handful of rounds, an ordered one up to n.  The loop below ends when the device reports no undecided point and
+    has no other exit.  stats: a dict that receives "rounds".  radius > 0 and finite, also as fp32 (else ValueError);
+    n = 0 gives an empty mask; a non-finite coordinate raises HashmodError.  Host reads of the count between batches of
+    rounds, so not graph-capturable."""
+    _check_cloud("radius_downsample", "points", points)
+    if not (isinstance(radius, (int, float)) and math.isfinite(radius) and radius > 0):
+        raise ValueError("hashmod radius_downsample: radius must be a positive finite number")
+    r32 = np.float32(radius)
+    if not (r32 > 0 and np.isfinite(r32)):
+        raise ValueError("hashmod radius_downsample: radius must be positive and finite in fp32")
+    radius2 = _max_dist2("radius_downsample", float(radius))
+    # an outward estimate of the largest per-axis offset inside the radius; the kernel checks and widens it per point
+    bound = float(min(np.nextafter(np.float32(max(math.sqrt(min(radius2, 3.0e38)), float(r32)) * (1.0 + 2.0 ** -20)),
+                                   np.float32(np.inf)), np.float32(3.0e38)))
+    n = int(points.shape[0])
+    if stats is not None:
+        stats["rounds"] = 0
+    if n == 0:
+        return torch.zeros(0, dtype=torch.bool, device=points.device)
+    index = NNIndex(points, cell)
+    dev = index.device
+    L = lib()
+    st = stream_ptr(points)
+    ws = _NR_WS.get(dev, check(L.hm_nn_radius_workspace_bytes(n)))
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    check(L.hm_nn_radius_begin(n, dptr(ws), ws.numel(), dptr(info), st))
+    remaining, rounds = n, 0
+    while remaining > 0:
+        # a list of at most _NR_TAIL points is finished by one workgroup, which leaves the count in the same word
+        check(L.hm_nn_radius_rounds(dptr(index.records), n, dptr(index.cell_start), index._lo(), index.h, index._g(),
+                                    radius2, bound, remaining, rounds, _NR_BATCH, dptr(ws), ws.numel(), dptr(info), st))
+        if remaining > _NR_TAIL:
+            rounds += _NR_BATCH
+        remaining = info.tolist()[rounds & 1]
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    check(L.hm_nn_radius_finish(dptr(index.records), n, dptr(ws), ws.numel(), dptr(keep), st))
+    if stats is not None:
+        stats["rounds"] = int(info[2].item())
+    return keep.view(torch.bool)
+
+
+DTU_INBOUND, DTU_IN_MASK, DTU_ABOVE_PLANE = 1, 2, 4
+
+
+def _dtu_params(what, obs_mask, bb, res, patch, plane):
+    """(shape (c_int64 * 3), params (c_double * 14)) of hm_dtu_point_flags from the scan's data, checked"""
+    if (not isinstance(obs_mask, torch.Tensor) or obs_mask.dtype != torch.uint8 or obs_mask.dim() != 3
+            or not obs_mask.is_contiguous() or obs_mask.numel() == 0):
+        raise ValueError(f"hashmod {what}: obs_mask must be a non-empty contiguous uint8 [X, Y, Z] tensor")
+    try:
+        bb = np.asarray(bb, np.float64)
+        plane = np.asarray(plane, np.float64).reshape(-1)
+        res, patch = float(res), float(patch)
+    except (TypeError, ValueError):
+        raise ValueError(f"hashmod {what}: bb [2,3], res, patch and plane [4] must be numbers") from None
+    if bb.shape != (2, 3) or plane.shape != (4,):
+        raise ValueError(f"hashmod {what}: bb must be [2,3] and plane [4]")
+    if not (np.isfinite(bb).all() and np.isfinite(plane).all() and math.isfinite(res) and res > 0
+            and math.isfinite(patch)):
+        raise ValueError(f"hashmod {what}: bb, plane and patch must be finite, res finite and positive")
+    params = np.concatenate([bb[0] - patch, bb[1] + patch * 2, bb[0], [res], plane])
+    return (C.c_int64 * 3)(*obs_mask.shape), (C.c_double * 14)(*params.tolist())
+
+
+def dtu_point_flags(points, obs_mask, bb, res, patch, plane):
+    """flags [n] uint8 of points [n,3] fp32 against a DTU scan's data (evaluation.chamfer.load_dtu_scan): bit 0
+    (DTU_INBOUND) bb[0] - patch <= p < bb[1] + 2*patch on all axes; bit 1 (DTU_IN_MASK) the voxel
+    k = rint((p - bb[0])/res) (half to even, np.around) lies inside obs_mask [X,Y,Z] uint8 and is set there; bit 2
+    (DTU_ABOVE_PLANE) ((P0*x + P1*y) + P2*z) + P3 > 0.  fp64 on the fp32 coordinates, every operation rounded once:
+    tests/dtu_cases.flags_ref gives the same bits.  A non-finite coordinate gives 0; no voxel outside the volume is
+    read.  bb [2,3], res, patch and plane [4] are host values.  n = 0 gives an empty tensor.  No host read."""
+    _check_cloud("dtu_point_flags", "points", points)
+    shape, params = _dtu_params("dtu_point_flags", obs_mask, bb, res, patch, plane)
+    if obs_mask.device != points.device:
+        raise ValueError("hashmod dtu_point_flags: the tensors are on different devices")
+    require_gpu(points)
+    n = int(points.shape[0])
+    flags = torch.empty(n, dtype=torch.uint8, device=points.device)
+    if n:
+        check(lib().hm_dtu_point_flags(dptr(points), n, dptr(obs_mask), shape, params, dptr(flags), stream_ptr(points)))
+    return flags

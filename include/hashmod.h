@@ -856,6 +856,54 @@ HM_API int hm_mesh_sample_emit(const float *verts, const int32_t *faces, int64_t
                                double density, const int64_t *prefix, int64_t n_samples, int64_t max_rows,
                                float *samples, int32_t *face_of, void *stream);
 
+/* ---- DTU evaluation: greedy radius down-sampling, observation-mask and ground-plane filters ---------------------
+ * What the reference's evaluation/dtu_eval does between the sampled cloud and the mean distances.  Driver:
+ * ops.radius_downsample, ops.dtu_point_flags, ops.one_sided_distance, evaluation.chamfer.dtu_chamfer.  As in the
+ * Chamfer section: no entry point synchronises, no atomic decides a position (the thinning uses no atomic
+ * read-modify-write at all), and no thread waits for another workgroup.
+ *
+ * Radius thinning (csrc/hm_nn_radius.hip) reproduces
+ *     mask = ones; for i in index order: if mask[i]: mask[neighbours(i)] = 0; mask[i] = 1
+ * where j is a neighbour of i when the fp32 value d2 = (dx*dx + dy*dy) + dz*dz of hm_nn_query is <= radius2 (equality
+ * counts).  A point is kept exactly when none of its lower-index neighbours is kept - a unique set - and it is found in
+ * rounds over a state per point: an undecided point with a kept lower-index neighbour is removed, one whose
+ * lower-index neighbours are all removed is kept, any other waits.  The file's header comment gives the arguments:
+ *   (a) the scan of a point reaches every j with d2 <= radius2 for ANY cell edge: per axis the cells from
+ *       nn_cell(L) to nn_cell(H), L and H checked by the kernel to lie outside the radius by that axis alone, the cell
+ *       function being monotone (points on cell faces and cells smaller than the radius included);
+ *   (b) states only move from undecided to a final value that depends on final values of lower indices alone, so the
+ *       result is the sequential loop's for any thread order, and concurrent reads of a state being written are benign;
+ *   (c) the lowest-index undecided point is decided by the next round, so n rounds suffice; the driver loops until
+ *       the remaining count is 0 and has no other exit.
+ * records, cell_start, lo, h, g: what hm_nn_build made and was given.  info: 4 device int32; info[0], info[1] hold the
+ * number of undecided points before even / odd rounds, info[2] the number of rounds that had something to decide.
+ *   hm_nn_radius_workspace_bytes(n): the scratch all three calls share (states, two lists, block counts).
+ *   hm_nn_radius_begin:  every point undecided, the list is all sorted positions, info = {n, 0, 0, 0}.
+ *   hm_nn_radius_rounds: radius2 >= 0 the fp32 bound on d2; bound > 0 an estimate of the radius rounded outward (the
+ *                kernel checks and widens it per point, see (a)); capacity in [1, n]: an upper bound of the current
+ *                count, normally the count last read; round0: the rounds run so far (selects the list and info word).
+ *                capacity > 1024: runs n_rounds (1..64) rounds - decide, exclusive scan of the blocks' waiting counts,
+ *                ordered scatter of the waiting points into the other list; rounds past completion do nothing.  The
+ *                caller then reads info[(round0 + n_rounds) & 1].  capacity <= 1024: one workgroup runs rounds until
+ *                the list is empty, at most as many as it has points, and writes the count left (0) to info[round0 & 1].
+ *   hm_nn_radius_finish: keep [n] uint8 by ORIGINAL index, 1 = kept; call when the count is 0.
+ * Point flags (csrc/hm_dtu_filter.hip), flags [n] uint8; fp64 on the fp32 coordinates, every operation rounded once:
+ *   bit 0  lo <= p < hi on all three axes (lo = BB0 - patch, hi = BB1 + 2*patch, formed by the caller in fp64)
+ *   bit 1  k = rint((p - bb0)/res) per axis (half to even), 0 <= k < shape on all axes and mask[kx, ky, kz] != 0;
+ *          mask is a contiguous uint8 [shape0, shape1, shape2] volume; an index outside it - from a huge coordinate
+ *          included - is never dereferenced
+ *   bit 2  ((P0*x + P1*y) + P2*z) + P3 > 0
+ *   a non-finite coordinate gives 0.  shape: 3 host int64; params: 14 host doubles lo[3], hi[3], bb0[3], res, P[4]. */
+HM_API int64_t hm_nn_radius_workspace_bytes(int64_t n);
+HM_API int hm_nn_radius_begin(int64_t n, void *workspace, int64_t workspace_bytes, int32_t *info, void *stream);
+HM_API int hm_nn_radius_rounds(const float *records, int64_t n, const int32_t *cell_start, const float *lo, float h,
+                               const int32_t *g, float radius2, float bound, int64_t capacity, int64_t round0,
+                               int32_t n_rounds, void *workspace, int64_t workspace_bytes, int32_t *info, void *stream);
+HM_API int hm_nn_radius_finish(const float *records, int64_t n, void *workspace, int64_t workspace_bytes, uint8_t *keep,
+                               void *stream);
+HM_API int hm_dtu_point_flags(const float *points, int64_t n, const uint8_t *mask, const int64_t *shape,
+                              const double *params, uint8_t *flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
