@@ -41,6 +41,42 @@ int hm_fail(int code, const std::string &msg);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Carves a workspace into its parts: take<T>(count) is the next 256-byte-aligned block of count elements of T, `bytes`
+// what has been taken so far.  With a null base it only counts, so ONE layout function written over it yields both
+// hm_*_workspace_bytes and the launcher's pointers, and a part cannot be in one and not in the other.
+struct HmCarve {
+    char *base;
+    int64_t bytes = 0;
+    explicit HmCarve(void *ws) : base(static_cast<char *>(ws)) {}
+    template <class T>
+    T *take(int64_t count) {
+        T *p = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
+        bytes += ((int64_t)sizeof(T) * count + 255) / 256 * 256;
+        return p;
+    }
+};
+
+// Workspace of "sort n int32 keys, keep the permutation" (hm_mesh_cc_sums, hm_nn_build, hm_nn_query):
+// [key n i32 | keys_sorted n i32 | perm n i64 | hm_sort_pairs_i32's own workspace]
+struct HmKeySortWs {
+    int32_t *key, *keys_sorted;
+    int64_t *perm;
+    void *sort_ws;
+    int64_t sort_bytes, bytes;
+};
+
+inline HmKeySortWs hm_keysort_layout(void *ws, int64_t n) {
+    HmCarve c(ws);
+    HmKeySortWs w;
+    w.key = c.take<int32_t>(n);
+    w.keys_sorted = c.take<int32_t>(n);
+    w.perm = c.take<int64_t>(n);
+    w.sort_bytes = hm_sort_workspace_bytes(n);
+    w.sort_ws = c.take<char>(w.sort_bytes);
+    w.bytes = c.bytes;
+    return w;
+}
+
 // Opts Kernel in to `bytes` of dynamic LDS (above the 64 KB default), once per host thread (not a stream operation).
 template <auto Kernel>
 int hm_allow_dynamic_lds(int bytes) {

@@ -27,8 +27,9 @@
 // what the kernel boundary made visible.
 //
 // A face index outside [0, n_verts) is never dereferenced: the face is skipped and bit 0 of the status word is set.
-// Floating-point sums use no atomics and a fixed order: two calls give the same bits.
-#include "hm_common.h"
+// Floating-point sums use no atomics and a fixed order: two calls give the same bits.  The face-index loader, the tree
+// sum and the grid size are hm_block_dev.h's.
+#include "hm_block_dev.h"
 
 namespace {
 
@@ -38,22 +39,8 @@ constexpr int kCBlock = kCT * kCRounds;  // 4096 faces per moments block
 constexpr int kSegT = 512;               // threads of a segment-sum workgroup
 constexpr int kMom = 10;                 // area, 3 first moments, 6 second moments (xx xy xz yy yz zz)
 
-inline int64_t cc_up256(int64_t b) { return (b + 255) / 256 * 256; }
-inline unsigned cc_grid(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 __device__ __forceinline__ int32_t cc_load(const int32_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the three indices of face f; false (and the status bit) when one is outside [0, n_verts)
-__device__ __forceinline__ bool cc_face(const int32_t *__restrict__ faces, int64_t f, int64_t n_verts, int32_t (&v)[3],
-                                        int32_t *status) {
-#pragma unroll
-    for (int m = 0; m < 3; ++m) v[m] = faces[f * 3 + m];
-    const bool ok = (uint64_t)(int64_t)v[0] < (uint64_t)n_verts && (uint64_t)(int64_t)v[1] < (uint64_t)n_verts &&
-                    (uint64_t)(int64_t)v[2] < (uint64_t)n_verts;
-    if (!ok) atomicOr(status, 1);
-    return ok;
 }
 
 // root of x as far as this thread can see, halving the path on the way (parent[x] only ever decreases)
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(kCT) void cc_union_kernel(const int32_t *__restrict
     const int64_t f = (int64_t)blockIdx.x * kCT + threadIdx.x;
     if (f >= n_faces) return;
     int32_t v[3];
-    if (!cc_face(faces, f, n_verts, v, status)) return;
+    if (!hm_face_ids(faces, f, n_verts, v, status)) return;
     cc_union(parent, v[0], v[1]);
     cc_union(parent, v[1], v[2]);
 }
@@ -140,7 +127,7 @@ __global__ __launch_bounds__(kCT) void cc_face_stats_kernel(const float *__restr
     const int64_t f = (int64_t)blockIdx.x * kCT + threadIdx.x;
     if (f >= n_faces) return;
     int32_t v[3];
-    if (!cc_face(faces, f, n_verts, v, status)) {
+    if (!hm_face_ids(faces, f, n_verts, v, status)) {
         face_area[f] = 0.0;
         return;
     }
@@ -158,7 +145,7 @@ __global__ __launch_bounds__(kCT) void cc_key_kernel(const int32_t *__restrict__
     if (f >= n_faces) return;
     int32_t v[3];
     int32_t k = 0;
-    if (cc_face(faces, f, n_verts, v, status)) {
+    if (hm_face_ids(faces, f, n_verts, v, status)) {
         const int32_t l = label[v[0]];
         if ((uint64_t)(int64_t)l < (uint64_t)n_verts) k = rank[l];
         if ((uint64_t)(int64_t)l >= (uint64_t)n_verts || (uint64_t)(int64_t)k >= (uint64_t)n_comp) {
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(kSegT) void cc_segment_kernel(const int32_t *__rest
                                                            const int64_t *__restrict__ perm, int64_t n_faces,
                                                            const double *__restrict__ face_area,
                                                            double *__restrict__ area, int64_t *__restrict__ count) {
-    __shared__ double red[kSegT];
+    __shared__ double red[1][kSegT];
     __shared__ int64_t range[2];
     const int32_t c = (int32_t)blockIdx.x;
     if (threadIdx.x < 2) range[threadIdx.x] = cc_lower_bound(keys_sorted, n_faces, c + (int32_t)threadIdx.x);
@@ -199,14 +186,10 @@ __global__ __launch_bounds__(kSegT) void cc_segment_kernel(const int32_t *__rest
         for (int u = 0; u < 4; ++u) s[u] += face_area[perm[i + u * (int64_t)kSegT]];
     }
     for (int u = 0; i < end; i += kSegT, ++u) s[u] += face_area[perm[i]];
-    red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-    __syncthreads();
-    for (int o = kSegT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    red[0][threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+    hm_block_tree_sum(red);
     if (threadIdx.x == 0) {
-        area[c] = red[0];
+        area[c] = red[0][0];
         count[c] = end - beg;
     }
 }
@@ -225,7 +208,7 @@ __global__ __launch_bounds__(kCT) void mom_partial_kernel(const float *__restric
         const int64_t f = beg + (int64_t)r * kCT + threadIdx.x;
         if (f >= n_faces) break;
         int32_t v[3];
-        if (!cc_face(faces, f, n_verts, v, status)) continue;
+        if (!hm_face_ids(faces, f, n_verts, v, status)) continue;
         const Tri t = cc_tri(verts, v);
         const double a = cc_area(t);
         double s[3];
@@ -245,14 +228,7 @@ __global__ __launch_bounds__(kCT) void mom_partial_kernel(const float *__restric
     }
 #pragma unroll
     for (int k = 0; k < kMom; ++k) red[k][threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int o = kCT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-#pragma unroll
-            for (int k = 0; k < kMom; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    hm_block_tree_sum(red);
     if (threadIdx.x < kMom) partial[(int64_t)blockIdx.x * kMom + threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -268,14 +244,7 @@ __global__ __launch_bounds__(kCT) void mom_final_kernel(const double *__restrict
         for (int k = 0; k < kMom; ++k) acc[k] += partial[b * kMom + k];
 #pragma unroll
     for (int k = 0; k < kMom; ++k) red[k][threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int o = kCT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-#pragma unroll
-            for (int k = 0; k < kMom; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    hm_block_tree_sum(red);
     if (threadIdx.x == 0) {
         const double A = red[0][0];
         double mean[3];
@@ -298,7 +267,7 @@ __global__ __launch_bounds__(kCT) void sel_mark_kernel(const int32_t *__restrict
     const int64_t f = (int64_t)blockIdx.x * kCT + threadIdx.x;
     if (f >= n_faces) return;
     int32_t v[3];
-    const bool in = cc_face(faces, f, n_verts, v, status) && label[v[0]] == component;
+    const bool in = hm_face_ids(faces, f, n_verts, v, status) && label[v[0]] == component;
     fflag[f] = in ? 1 : 0;
     if (in) {
 #pragma unroll
@@ -347,24 +316,20 @@ int cc_check_mesh(int64_t n_faces, int64_t n_verts, const void *faces, const cha
     return HM_OK;
 }
 
-struct CcWs {
-    int32_t *key, *keys_sorted;
-    int64_t *perm;
-    void *sort_ws;
-    int64_t sort_bytes;
+int64_t mom_blocks(int64_t n_faces) { return (n_faces + kCBlock - 1) / kCBlock; }
+
+// the block partials of hm_mesh_moments (one block's worth for an empty mesh)
+struct MomWs {
+    double *partial;
+    int64_t bytes;
 };
 
-inline CcWs cc_carve(void *ws, int64_t n_faces) {
-    char *p = static_cast<char *>(ws);
-    CcWs w;
-    w.key = reinterpret_cast<int32_t *>(p);
-    p += cc_up256(4 * n_faces);
-    w.keys_sorted = reinterpret_cast<int32_t *>(p);
-    p += cc_up256(4 * n_faces);
-    w.perm = reinterpret_cast<int64_t *>(p);
-    p += cc_up256(8 * n_faces);
-    w.sort_ws = p;
-    w.sort_bytes = hm_sort_workspace_bytes(n_faces);
+MomWs mom_layout(void *ws, int64_t n_faces) {
+    const int64_t nb = mom_blocks(n_faces);
+    HmCarve c(ws);
+    MomWs w;
+    w.partial = c.take<double>(kMom * (nb > 0 ? nb : 1));
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -379,12 +344,12 @@ int hm_mesh_cc_labels(const int32_t *faces, int64_t n_faces, int64_t n_verts, in
     HM_CHECK_ARG(status && (n_verts == 0 || label), "hm_mesh_cc_labels: NULL label or status");
     hipStream_t st = as_stream(stream);
     if (n_verts > 0)
-        hipLaunchKernelGGL(cc_init_kernel, dim3(cc_grid(n_verts, kCT)), dim3(kCT), 0, st, label, n_verts);
+        hipLaunchKernelGGL(cc_init_kernel, dim3(hm_grid(n_verts, kCT)), dim3(kCT), 0, st, label, n_verts);
     if (n_faces > 0)
-        hipLaunchKernelGGL(cc_union_kernel, dim3(cc_grid(n_faces, kCT)), dim3(kCT), 0, st, faces, n_faces, n_verts,
+        hipLaunchKernelGGL(cc_union_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, st, faces, n_faces, n_verts,
                            label, status);
     if (n_verts > 0 && n_faces > 0)
-        hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_grid(n_verts, kCT)), dim3(kCT), 0, st, label, n_verts);
+        hipLaunchKernelGGL(cc_flatten_kernel, dim3(hm_grid(n_verts, kCT)), dim3(kCT), 0, st, label, n_verts);
     HM_CHECK_LAUNCH("hm_mesh_cc_labels");
     return HM_OK;
 }
@@ -394,7 +359,7 @@ int hm_mesh_cc_face_stats(const float *verts, const int32_t *faces, int64_t n_fa
     if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_face_stats")) return rc;
     if (n_faces == 0) return HM_OK;
     HM_CHECK_ARG(verts && face_area && used && status, "hm_mesh_cc_face_stats: NULL pointer");
-    hipLaunchKernelGGL(cc_face_stats_kernel, dim3(cc_grid(n_faces, kCT)), dim3(kCT), 0, as_stream(stream), verts, faces,
+    hipLaunchKernelGGL(cc_face_stats_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, as_stream(stream), verts, faces,
                        n_faces, n_verts, face_area, used, status);
     HM_CHECK_LAUNCH("hm_mesh_cc_face_stats");
     return HM_OK;
@@ -403,7 +368,7 @@ int hm_mesh_cc_face_stats(const float *verts, const int32_t *faces, int64_t n_fa
 int64_t hm_mesh_cc_sums_workspace_bytes(int64_t n_faces) {
     if (n_faces < 0 || n_faces >= ((int64_t)1 << 31))
         return hm_fail(HM_ERR_INVALID, "hm_mesh_cc_sums_workspace_bytes: n_faces must be in [0, 2^31)");
-    return 2 * cc_up256(4 * n_faces) + cc_up256(8 * n_faces) + hm_sort_workspace_bytes(n_faces);
+    return hm_keysort_layout(nullptr, n_faces).bytes;
 }
 
 int hm_mesh_cc_sums(const int32_t *faces, int64_t n_faces, int64_t n_verts, const int32_t *label, const int32_t *rank,
@@ -414,9 +379,9 @@ int hm_mesh_cc_sums(const int32_t *faces, int64_t n_faces, int64_t n_verts, cons
     if (n_faces == 0 || n_components == 0) return HM_OK;
     HM_CHECK_ARG(label && rank && face_area && area && count && workspace && status, "hm_mesh_cc_sums: NULL pointer");
     HM_CHECK_ARG(workspace_bytes >= hm_mesh_cc_sums_workspace_bytes(n_faces), "hm_mesh_cc_sums: workspace too small");
-    const CcWs w = cc_carve(workspace, n_faces);
+    const HmKeySortWs w = hm_keysort_layout(workspace, n_faces);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(cc_key_kernel, dim3(cc_grid(n_faces, kCT)), dim3(kCT), 0, st, faces, n_faces, n_verts, label,
+    hipLaunchKernelGGL(cc_key_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, st, faces, n_faces, n_verts, label,
                        rank, n_components, w.key, status);
     int key_bits = 1;
     while (key_bits < 31 && ((int64_t)1 << key_bits) < n_components) ++key_bits;
@@ -432,8 +397,7 @@ int hm_mesh_cc_sums(const int32_t *faces, int64_t n_faces, int64_t n_verts, cons
 int64_t hm_mesh_moments_workspace_bytes(int64_t n_faces) {
     if (n_faces < 0 || n_faces >= ((int64_t)1 << 31))
         return hm_fail(HM_ERR_INVALID, "hm_mesh_moments_workspace_bytes: n_faces must be in [0, 2^31)");
-    const int64_t nb = (n_faces + kCBlock - 1) / kCBlock;
-    return cc_up256(8 * kMom * (nb > 0 ? nb : 1));
+    return mom_layout(nullptr, n_faces).bytes;
 }
 
 int hm_mesh_moments(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, double *out,
@@ -441,8 +405,8 @@ int hm_mesh_moments(const float *verts, const int32_t *faces, int64_t n_faces, i
     if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_moments")) return rc;
     HM_CHECK_ARG(out && workspace && status && (n_faces == 0 || verts), "hm_mesh_moments: NULL pointer");
     HM_CHECK_ARG(workspace_bytes >= hm_mesh_moments_workspace_bytes(n_faces), "hm_mesh_moments: workspace too small");
-    const int64_t nb = (n_faces + kCBlock - 1) / kCBlock;
-    double *partial = static_cast<double *>(workspace);
+    const int64_t nb = mom_blocks(n_faces);
+    double *partial = mom_layout(workspace, n_faces).partial;
     hipStream_t st = as_stream(stream);
     if (nb > 0)
         hipLaunchKernelGGL(mom_partial_kernel, dim3((unsigned)nb), dim3(kCT), 0, st, verts, faces, n_faces, n_verts,
@@ -457,7 +421,7 @@ int hm_mesh_select_mark(const int32_t *faces, int64_t n_faces, int64_t n_verts, 
     if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_select_mark")) return rc;
     if (n_faces == 0) return HM_OK;
     HM_CHECK_ARG(label && vflag && fflag && status, "hm_mesh_select_mark: NULL pointer");
-    hipLaunchKernelGGL(sel_mark_kernel, dim3(cc_grid(n_faces, kCT)), dim3(kCT), 0, as_stream(stream), faces, n_faces,
+    hipLaunchKernelGGL(sel_mark_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, as_stream(stream), faces, n_faces,
                        n_verts, label, component, vflag, fflag, status);
     HM_CHECK_LAUNCH("hm_mesh_select_mark");
     return HM_OK;
@@ -475,10 +439,10 @@ int hm_mesh_select_emit(const float *verts, const float *normals, const int32_t 
     HM_CHECK_ARG(n_faces_out == 0 || (vpre && fflag && fpre && faces_out), "hm_mesh_select_emit: NULL face pointer");
     hipStream_t st = as_stream(stream);
     if (n_verts_out > 0)
-        hipLaunchKernelGGL(sel_verts_kernel, dim3(cc_grid(n_verts, kCT)), dim3(kCT), 0, st, verts, normals, n_verts,
+        hipLaunchKernelGGL(sel_verts_kernel, dim3(hm_grid(n_verts, kCT)), dim3(kCT), 0, st, verts, normals, n_verts,
                            vflag, vpre, n_verts_out, verts_out, normals_out);
     if (n_faces_out > 0)
-        hipLaunchKernelGGL(sel_faces_kernel, dim3(cc_grid(n_faces, kCT)), dim3(kCT), 0, st, faces, n_faces, n_verts,
+        hipLaunchKernelGGL(sel_faces_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, st, faces, n_faces, n_verts,
                            vpre, fflag, fpre, n_faces_out, faces_out);
     HM_CHECK_LAUNCH("hm_mesh_select_emit");
     return HM_OK;

@@ -13,7 +13,7 @@
 // corrected by the predicate.  A sample's position is prefix[f] + the counts of the rows before it + j: no atomics.
 #include <math.h>
 
-#include "hm_common.h"
+#include "hm_block_dev.h"
 
 namespace {
 
@@ -29,12 +29,9 @@ struct MsFace {
 __device__ __forceinline__ bool ms_face(const float *__restrict__ verts, const int32_t *__restrict__ faces, int64_t f,
                                         int64_t n_verts, double density, MsFace &F, int32_t *status) {
     int32_t id[3];
-#pragma unroll
-    for (int m = 0; m < 3; ++m) id[m] = faces[f * 3 + m];
     F.n1 = F.n2 = 0.0;
-    if (!((uint64_t)(int64_t)id[0] < (uint64_t)n_verts && (uint64_t)(int64_t)id[1] < (uint64_t)n_verts &&
-          (uint64_t)(int64_t)id[2] < (uint64_t)n_verts)) {
-        if (status) atomicOr(status, 1);
+    if (!hm_face_ids(faces, f, n_verts, id)) {
+        if (status) atomicOr(status, 1);   // only one lane of a wave reports
         return false;
     }
 #pragma unroll
@@ -78,12 +75,6 @@ __device__ __forceinline__ int64_t ms_row_count(int64_t i, double n1, double n2)
     return j + 1;
 }
 
-__device__ __forceinline__ int64_t ms_wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(64) void ms_count_kernel(const float *__restrict__ verts,
                                                       const int32_t *__restrict__ faces, int64_t n_verts,
                                                       double density, int64_t *__restrict__ count,
@@ -97,7 +88,7 @@ __global__ __launch_bounds__(64) void ms_count_kernel(const float *__restrict__ 
         const int64_t n1i = (int64_t)F.n1;
         for (int64_t i = lane; i <= n1i; i += 64) c += ms_row_count(i, F.n1, F.n2);
     }
-    c = ms_wave_sum(c);
+    c = hm_wave_reduce(c, HmSum{});
     if (lane == 0) {
         count[f] = F.n1 < 0.0 ? kTooMany : c;
         rows[f] = F.n1 >= 1.0 ? (int32_t)fmin(F.n1 + 1.0, 2147483647.0) : 0;
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(64) void ms_emit_kernel(const float *__restrict__ v
     // the samples of the face's earlier rows
     int64_t before = 0;
     for (int64_t i = lane; i < row0; i += 64) before += ms_row_count(i, F.n1, F.n2);
-    int64_t pos = prefix[f] + ms_wave_sum(before);
+    int64_t pos = prefix[f] + hm_wave_reduce(before, HmSum{});
 
     for (int64_t r = row0; r < row1; r += 64) {
         const int64_t i = r + lane;

@@ -8,12 +8,12 @@
 //   hm_mcs_points_bricks / _index   lattice points -> coordinates for the SDF (one fixed fp32 expression per point)
 //   hm_mcs_status                   per listed brick: does its cell block / do its 6 block faces hold values on both
 //                                   sides of the level, a NaN bit, and "a needed brick is not evaluated"
-//   hm_mcs_count / hm_mcs_emit      the two phases of hm_mesh.hip over the points of the listed (surface) bricks, the
-//                                   lattice read through the brick map; the arithmetic is hm_mesh_dev.h, shared with the
-//                                   dense kernels.  A cell or an edge with a corner that is not evaluated emits nothing.
+//   hm_mcs_count / hm_mcs_emit      the two phases of hm_mesh.hip over the points of the listed (surface) bricks: the
+//                                   kernels of hm_mesh_dev.h, the ones the dense volume runs, over the lattice BrickLat
+//                                   (values through the brick map, work items through the brick list and its position
+//                                   map).  A cell or an edge with a corner that is not evaluated emits nothing.
 //                                   Outputs come in list order with an int64 key each; sorted by key they are the dense
 //                                   kernels' outputs.
-#include "hm_mc_table.h"
 #include "hm_mesh_dev.h"
 
 namespace {
@@ -129,13 +129,10 @@ __global__ __launch_bounds__(256) void mcs_status_kernel(const int32_t *__restri
         if (v < level) below |= where;
         else above |= where;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        below |= __shfl_xor(below, o, 64);
-        above |= __shfl_xor(above, o, 64);
-        nan |= __shfl_xor(nan, o, 64);
-        missing |= __shfl_xor(missing, o, 64);
-    }
+    below = hm_wave_reduce(below, HmOr{});
+    above = hm_wave_reduce(above, HmOr{});
+    nan = hm_wave_reduce(nan, HmOr{});
+    missing = hm_wave_reduce(missing, HmOr{});
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         red[0][wave] = below;
@@ -157,131 +154,29 @@ __global__ __launch_bounds__(256) void mcs_status_kernel(const int32_t *__restri
     }
 }
 
-// mc_classify of hm_mesh.hip over the points of the listed bricks
-__global__ __launch_bounds__(kMT) void mcs_classify_kernel(const int32_t *__restrict__ bricks, BrickVol V, float level,
-                                                           int64_t n, uint16_t *__restrict__ code,
-                                                           int32_t *__restrict__ bsum, int64_t nb) {
-    const int64_t beg = (int64_t)blockIdx.x * kMBlock;
-    int nv = 0, nt = 0, nan = 0;
-    for (int r = 0; r < kMRounds; ++r) {
-        const int64_t q = beg + (int64_t)r * kMT + threadIdx.x;
-        if (q >= n) break;
-        int i, j, k;
-        if (!mcs_point(q, bricks, V, i, j, k) || !V.has(i, j, k)) {
-            code[q] = 0;
-            continue;
-        }
-        const float c0 = V.at(i, j, k);
-        nan |= c0 != c0;
-        const bool in0 = c0 < level;
-        const bool hx = i + 1 < V.nx && V.has(i + 1, j, k), hy = j + 1 < V.ny && V.has(i, j + 1, k),
-                   hz = k + 1 < V.nz && V.has(i, j, k + 1);
-        const float c1 = hx ? V.at(i + 1, j, k) : c0;
-        const float c2 = hy ? V.at(i, j + 1, k) : c0;
-        const float c4 = hz ? V.at(i, j, k + 1) : c0;
-        const int mask = ((hx && (c1 < level) != in0) ? 1 : 0) | ((hy && (c2 < level) != in0) ? 2 : 0) |
-                         ((hz && (c4 < level) != in0) ? 4 : 0);
-        int cs = 0;
-        if (hx && hy && hz && V.has(i + 1, j + 1, k) && V.has(i + 1, j, k + 1) && V.has(i, j + 1, k + 1) &&
-            V.has(i + 1, j + 1, k + 1)) {
-            const float c3 = V.at(i + 1, j + 1, k), c5 = V.at(i + 1, j, k + 1);
-            const float c6 = V.at(i, j + 1, k + 1), c7 = V.at(i + 1, j + 1, k + 1);
-            cs = (int)in0 | (int)(c1 < level) << 1 | (int)(c2 < level) << 2 | (int)(c3 < level) << 3 |
-                 (int)(c4 < level) << 4 | (int)(c5 < level) << 5 | (int)(c6 < level) << 6 | (int)(c7 < level) << 7;
-        }
-        code[q] = (uint16_t)(cs | mask << 8);
-        nv += __popc(mask);
-        nt += hm_mc_tris[cs][0];
+// the brick lattice: work item q is point q & 511 of listed brick q >> 9.  smap: brick -> its position in the brick list
+// (or -1), for the work items of the neighbour bricks' points; vkeys / fkeys: the dense linear order of each output
+struct BrickLat : BrickVol {
+    const int32_t *bricks, *smap;
+    int64_t n;   // work items: listed bricks * 512
+    int64_t *vkeys, *fkeys;
+    __device__ __forceinline__ bool point(int64_t q, int &i, int &j, int &k) const {
+        return mcs_point(q, bricks, *this, i, j, k);
     }
-    mc_block_sums(nv, nt, nan, bsum, nb);
-}
-
-__global__ __launch_bounds__(kMT) void mcs_verts_kernel(const int32_t *__restrict__ bricks, BrickVol V, float level,
-                                                        float spx, float spy, float spz, int64_t n,
-                                                        const uint16_t *__restrict__ code, int32_t *__restrict__ vbase,
-                                                        const int64_t *__restrict__ boff, int64_t cap_v,
-                                                        float *__restrict__ verts, float *__restrict__ normals,
-                                                        int64_t *__restrict__ vkeys) {
-    __shared__ int lds_waves[kMT / 64];
-    const float sp[3] = {spx, spy, spz};
-    const int64_t beg = (int64_t)blockIdx.x * kMBlock;
-    int64_t base = boff[blockIdx.x];
-    for (int r = 0; r < kMRounds; ++r) {
-        if (beg + (int64_t)r * kMT >= n) break;  // uniform over the workgroup
-        const int64_t q = beg + (int64_t)r * kMT + threadIdx.x;
-        const int mask = q < n ? code[q] >> 8 : 0;
-        int total;
-        const int pre = block_excl_scan(__popc(mask), lds_waves, total);
-        if (q < n) {
-            int64_t vi = base + pre;
-            vbase[q] = (int32_t)vi;
-            if (mask) {
-                int i, j, k;
-                mcs_point(q, bricks, V, i, j, k);   // true: the point has a code
-                const float a = V.at(i, j, k);
-                float g0[3];
-                mc_grad(V, i, j, k, sp, g0);
-                for (int ax = 0; ax < 3; ++ax) {
-                    if (!((mask >> ax) & 1)) continue;
-                    float pos[3], nrm[3];
-                    mc_vertex(V, level, sp, i, j, k, ax, a, g0, pos, nrm);
-                    if (vi < cap_v) {
-#pragma unroll
-                        for (int m = 0; m < 3; ++m) {
-                            verts[vi * 3 + m] = pos[m];
-                            normals[vi * 3 + m] = nrm[m];
-                        }
-                        vkeys[vi] = (((int64_t)i * V.ny + j) * V.nz + k) * 3 + ax;
-                    }
-                    ++vi;
-                }
-            }
-        }
-        base += total;
+    // false: the corner's brick is not listed, the caller's closure is broken
+    __device__ __forceinline__ bool corner(int64_t, int i, int j, int k, int c, int64_t &p) const {
+        const int ci = i + (c & 1), cj = j + ((c >> 1) & 1), ck = k + ((c >> 2) & 1);
+        const int64_t s = smap[brick_of(ci, cj, ck)];
+        p = s * kB3 + ((ci & 7) << 6 | (cj & 7) << 3 | (ck & 7));
+        return s >= 0 && s * kB3 < n;
     }
-}
-
-// smap: brick -> its position in the brick list (or -1), for the vertex ids of the neighbour bricks' points
-__global__ __launch_bounds__(kMT) void mcs_faces_kernel(const int32_t *__restrict__ bricks, BrickVol V,
-                                                        const int32_t *__restrict__ smap, int64_t n,
-                                                        const uint16_t *__restrict__ code,
-                                                        const int32_t *__restrict__ vbase,
-                                                        const int64_t *__restrict__ boff, int64_t cap_f,
-                                                        int32_t *__restrict__ faces, int64_t *__restrict__ fkeys) {
-    __shared__ int lds_waves[kMT / 64];
-    const int64_t beg = (int64_t)blockIdx.x * kMBlock;
-    int64_t base = boff[blockIdx.x];
-    for (int r = 0; r < kMRounds; ++r) {
-        if (beg + (int64_t)r * kMT >= n) break;
-        const int64_t q = beg + (int64_t)r * kMT + threadIdx.x;
-        const int cs = q < n ? code[q] & 255 : 0;
-        const int nt = hm_mc_tris[cs][0];
-        int total;
-        const int pre = block_excl_scan(nt, lds_waves, total);
-        int64_t f = base + pre;
-        int i = 0, j = 0, k = 0;
-        if (nt) mcs_point(q, bricks, V, i, j, k);
-        for (int t = 0; t < nt; ++t, ++f) {
-            if (f >= cap_f) break;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                const int e = hm_mc_tris[cs][1 + 3 * t + m];
-                const int c = hm_mc_edge_corner[e], ax = hm_mc_edge_axis[e];
-                const int ci = i + (c & 1), cj = j + ((c >> 1) & 1), ck = k + ((c >> 2) & 1);
-                const int64_t s = smap[V.brick_of(ci, cj, ck)];
-                int32_t id = -1;   // the corner's brick is not listed: the caller's closure is broken
-                if (s >= 0 && s * kB3 < n) {
-                    const int64_t p = s * kB3 + ((ci & 7) << 6 | (cj & 7) << 3 | (ck & 7));
-                    const int pmask = code[p] >> 8;
-                    id = vbase[p] + __popc(pmask & ((1 << ax) - 1));
-                }
-                faces[f * 3 + m] = id;
-            }
-            fkeys[f] = (((int64_t)i * V.ny + j) * V.nz + k) * 8 + t;
-        }
-        base += total;
+    __device__ __forceinline__ void vert_key(int64_t vi, int i, int j, int k, int ax) const {
+        vkeys[vi] = (((int64_t)i * ny + j) * nz + k) * 3 + ax;
     }
-}
+    __device__ __forceinline__ void face_key(int64_t f, int i, int j, int k, int t) const {
+        fkeys[f] = (((int64_t)i * ny + j) * nz + k) * 8 + t;
+    }
+};
 
 int mcs_check_dims(int64_t nx, int64_t ny, int64_t nz, const std::string &w) {
     HM_CHECK_ARG(nx >= 2 && ny >= 2 && nz >= 2, w + ": every lattice dimension must be >= 2");
@@ -304,6 +199,12 @@ int mcs_check_lattice(const hm_mcs_lattice *lat, const std::string &w) {
 BrickVol brick_vol(const hm_mcs_lattice *lat) {
     return BrickVol{lat->pool, lat->map, lat->n_slots, (int32_t)lat->nx, (int32_t)lat->ny, (int32_t)lat->nz,
                     (int32_t)bricks_along(lat->nx), (int32_t)bricks_along(lat->ny), (int32_t)bricks_along(lat->nz)};
+}
+
+// the lattice of hm_mcs_count / hm_mcs_emit; the count phase uses neither the position map nor the keys
+BrickLat brick_lat(const hm_mcs_lattice *lat, const int32_t *bricks, int64_t n_bricks, const int32_t *list_pos = nullptr,
+                   int64_t *vert_keys = nullptr, int64_t *face_keys = nullptr) {
+    return BrickLat{brick_vol(lat), bricks, list_pos, n_bricks * kB3, vert_keys, face_keys};
 }
 
 int mcs_check_list(const int32_t *bricks, int64_t n_bricks, const std::string &w) {
@@ -372,7 +273,7 @@ int hm_mcs_status(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice 
 int64_t hm_mcs_workspace_bytes(int64_t n_bricks) {
     if (n_bricks < 1 || n_bricks > HM_MCS_MAX_LIST)
         return hm_fail(HM_ERR_INVALID, "hm_mcs_workspace_bytes: n_bricks must be in [1, 2^22]");
-    return mc_ws_bytes(n_bricks * kB3);
+    return mc_layout(nullptr, n_bricks * kB3).bytes;
 }
 
 int hm_mcs_count(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice *lat, float level, void *workspace,
@@ -383,12 +284,12 @@ int hm_mcs_count(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice *
     HM_CHECK_ARG(workspace && counts, "hm_mcs_count: NULL workspace or counts");
     HM_CHECK_ARG(workspace_bytes >= hm_mcs_workspace_bytes(n_bricks), "hm_mcs_count: workspace too small");
     HM_CHECK_ARG(level == level, "hm_mcs_count: level is NaN");
-    const int64_t n = n_bricks * kB3, nb = (n + kMBlock - 1) / kMBlock;
-    const McWs w = mc_carve(workspace, n);
+    const BrickLat V = brick_lat(lat, bricks, n_bricks);
+    const McWs w = mc_layout(workspace, V.n);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(mcs_classify_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, bricks, brick_vol(lat), level, n,
-                       w.code, w.bsum, nb);
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kScanT), 0, st, static_cast<const int32_t *>(w.bsum), nb, w.boff,
+    hipLaunchKernelGGL(mc_classify_kernel<BrickLat>, dim3((unsigned)w.nb), dim3(kMT), 0, st, V, level, V.n, w.code,
+                       w.bsum, w.nb);
+    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kScanT), 0, st, static_cast<const int32_t *>(w.bsum), w.nb, w.boff,
                        counts);
     HM_CHECK_LAUNCH("hm_mcs_count");
     return HM_OK;
@@ -409,17 +310,16 @@ int hm_mcs_emit(const int32_t *bricks, int64_t n_bricks, const hm_mcs_lattice *l
                      " faces do not fit int32 indices");
     HM_CHECK_ARG(n_verts == 0 || (verts && normals && vert_keys), "hm_mcs_emit: NULL verts, normals or vert_keys");
     HM_CHECK_ARG(n_faces == 0 || (faces && face_keys), "hm_mcs_emit: NULL faces or face_keys");
-    const int64_t n = n_bricks * kB3, nb = (n + kMBlock - 1) / kMBlock;
-    const McWs w = mc_carve(workspace, n);
-    const BrickVol V = brick_vol(lat);
+    const BrickLat V = brick_lat(lat, bricks, n_bricks, list_pos, vert_keys, face_keys);
+    const McWs w = mc_layout(workspace, V.n);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(mcs_verts_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, bricks, V, level, spacing[0],
-                       spacing[1], spacing[2], n, static_cast<const uint16_t *>(w.code), w.vbase,
-                       static_cast<const int64_t *>(w.boff), n_verts, verts, normals, vert_keys);
+    hipLaunchKernelGGL(mc_verts_kernel<BrickLat>, dim3((unsigned)w.nb), dim3(kMT), 0, st, V, level, spacing[0],
+                       spacing[1], spacing[2], V.n, static_cast<const uint16_t *>(w.code), w.vbase,
+                       static_cast<const int64_t *>(w.boff), n_verts, verts, normals);
     if (n_faces > 0)
-        hipLaunchKernelGGL(mcs_faces_kernel, dim3((unsigned)nb), dim3(kMT), 0, st, bricks, V, list_pos, n,
+        hipLaunchKernelGGL(mc_faces_kernel<BrickLat>, dim3((unsigned)w.nb), dim3(kMT), 0, st, V, V.n,
                            static_cast<const uint16_t *>(w.code), static_cast<const int32_t *>(w.vbase),
-                           static_cast<const int64_t *>(w.boff + nb), n_faces, faces, face_keys);
+                           static_cast<const int64_t *>(w.boff + w.nb), n_faces, faces);
     HM_CHECK_LAUNCH("hm_mcs_emit");
     return HM_OK;
 }

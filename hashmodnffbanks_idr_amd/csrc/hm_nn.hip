@@ -19,15 +19,13 @@
 // The grid record, the cell function and the host-side grid check are in hm_nn_dev.h, shared with hm_nn_radius.hip.
 #include <math.h>
 
-#include "hm_common.h"
+#include "hm_block_dev.h"
 #include "hm_nn_dev.h"
 
 namespace {
 
 constexpr int kChunk = 256;   // records staged in LDS per pass (4 KiB)
 constexpr int32_t kNoIndex = 0x7fffffff;
-
-inline int64_t nn_up256(int64_t b) { return (b + 255) / 256 * 256; }
 
 __global__ __launch_bounds__(kNT) void nn_key_kernel(const float *__restrict__ p, int64_t n, NnGrid G,
                                                      int32_t *__restrict__ key, int32_t *status, int32_t bit) {
@@ -65,17 +63,6 @@ __global__ __launch_bounds__(kNT) void nn_cell_start_kernel(const int32_t *__res
         else hi = mid;
     }
     cell_start[c] = (int32_t)lo;
-}
-
-__device__ __forceinline__ int32_t nn_wave_min(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int32_t nn_wave_max(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
 }
 
 // THE STOPPING RULE.  A lane is finished when its best d2 is strictly below b2 = min over the box's faces that have
@@ -131,9 +118,9 @@ __global__ __launch_bounds__(64) void nn_query_kernel(const float *__restrict__ 
     const int32_t cx = nn_cell(qx, G.lo[0], G.h, gx), cy = nn_cell(qy, G.lo[1], G.h, gy),
                   cz = nn_cell(qz, G.lo[2], G.h, gz);
     // the box [b0, b1] per axis (wave-uniform), and the box scanned so far [o0, o1]
-    int32_t b0x = max(nn_wave_min(cx) - 1, 0), b1x = min(nn_wave_max(cx) + 1, gx - 1);
-    int32_t b0y = max(nn_wave_min(cy) - 1, 0), b1y = min(nn_wave_max(cy) + 1, gy - 1);
-    int32_t b0z = max(nn_wave_min(cz) - 1, 0), b1z = min(nn_wave_max(cz) + 1, gz - 1);
+    int32_t b0x = max(hm_wave_reduce(cx, HmMin{}) - 1, 0), b1x = min(hm_wave_reduce(cx, HmMax{}) + 1, gx - 1);
+    int32_t b0y = max(hm_wave_reduce(cy, HmMin{}) - 1, 0), b1y = min(hm_wave_reduce(cy, HmMax{}) + 1, gy - 1);
+    int32_t b0z = max(hm_wave_reduce(cz, HmMin{}) - 1, 0), b1z = min(hm_wave_reduce(cz, HmMax{}) + 1, gz - 1);
     int32_t o0x = 0, o1x = -1, o0y = 0, o1y = -1, o0z = 0, o1z = -1;
     int32_t ring = 1;
 
@@ -259,31 +246,10 @@ __global__ __launch_bounds__(64) void nn_query_kernel(const float *__restrict__ 
     }
 }
 
-struct NnWs {
-    int32_t *key, *keys_sorted;
-    int64_t *perm;
-    void *sort_ws;
-    int64_t sort_bytes;
-};
-
-inline NnWs nn_carve(void *ws, int64_t n) {
-    char *p = static_cast<char *>(ws);
-    NnWs w;
-    w.key = reinterpret_cast<int32_t *>(p);
-    p += nn_up256(4 * n);
-    w.keys_sorted = reinterpret_cast<int32_t *>(p);
-    p += nn_up256(4 * n);
-    w.perm = reinterpret_cast<int64_t *>(p);
-    p += nn_up256(8 * n);
-    w.sort_ws = p;
-    w.sort_bytes = hm_sort_workspace_bytes(n);
-    return w;
-}
-
 // keys of the n rows of p, sorted: w.keys_sorted, w.perm
-int nn_sorted_keys(const float *p, int64_t n, const NnGrid &G, int64_t cells, const NnWs &w, int32_t *status,
+int nn_sorted_keys(const float *p, int64_t n, const NnGrid &G, int64_t cells, const HmKeySortWs &w, int32_t *status,
                    int32_t bit, void *stream) {
-    hipLaunchKernelGGL(nn_key_kernel, dim3(nn_blocks(n, kNT)), dim3(kNT), 0, as_stream(stream), p, n, G, w.key, status,
+    hipLaunchKernelGGL(nn_key_kernel, dim3(hm_grid(n, kNT)), dim3(kNT), 0, as_stream(stream), p, n, G, w.key, status,
                        bit);
     int key_bits = 1;
     while (key_bits < 31 && ((int64_t)1 << key_bits) < cells) ++key_bits;
@@ -297,7 +263,7 @@ extern "C" {
 int64_t hm_nn_workspace_bytes(int64_t n) {
     if (n < 0 || n >= ((int64_t)1 << 31))
         return hm_fail(HM_ERR_INVALID, "hm_nn_workspace_bytes: n must be in [0, 2^31)");
-    return 2 * nn_up256(4 * n) + nn_up256(8 * n) + hm_sort_workspace_bytes(n);
+    return hm_keysort_layout(nullptr, n).bytes;
 }
 
 int hm_nn_build(const float *points, int64_t n, const float *lo, float h, const int32_t *g, int32_t *cell_start,
@@ -308,12 +274,12 @@ int hm_nn_build(const float *points, int64_t n, const float *lo, float h, const 
     if (int rc = nn_grid(lo, h, g, "hm_nn_build", G, cells)) return rc;
     HM_CHECK_ARG(points && cell_start && records && workspace && status, "hm_nn_build: NULL pointer");
     HM_CHECK_ARG(workspace_bytes >= hm_nn_workspace_bytes(n), "hm_nn_build: workspace too small");
-    const NnWs w = nn_carve(workspace, n);
+    const HmKeySortWs w = hm_keysort_layout(workspace, n);
     hipStream_t st = as_stream(stream);
     if (int rc = nn_sorted_keys(points, n, G, cells, w, status, 1, stream)) return rc;
-    hipLaunchKernelGGL(nn_records_kernel, dim3(nn_blocks(n, kNT)), dim3(kNT), 0, st, points, n,
+    hipLaunchKernelGGL(nn_records_kernel, dim3(hm_grid(n, kNT)), dim3(kNT), 0, st, points, n,
                        static_cast<const int64_t *>(w.perm), reinterpret_cast<float4 *>(records));
-    hipLaunchKernelGGL(nn_cell_start_kernel, dim3(nn_blocks(cells + 1, kNT)), dim3(kNT), 0, st,
+    hipLaunchKernelGGL(nn_cell_start_kernel, dim3(hm_grid(cells + 1, kNT)), dim3(kNT), 0, st,
                        static_cast<const int32_t *>(w.keys_sorted), n, cells, cell_start);
     HM_CHECK_LAUNCH("hm_nn_build");
     return HM_OK;
@@ -331,9 +297,9 @@ int hm_nn_query(const float *query, int64_t m, const float *records, int64_t n, 
     if (m == 0) return HM_OK;
     HM_CHECK_ARG(query && records && cell_start && d2 && index && workspace && status, "hm_nn_query: NULL pointer");
     HM_CHECK_ARG(workspace_bytes >= hm_nn_workspace_bytes(m), "hm_nn_query: workspace too small");
-    const NnWs w = nn_carve(workspace, m);
+    const HmKeySortWs w = hm_keysort_layout(workspace, m);
     if (int rc = nn_sorted_keys(query, m, G, cells, w, status, 2, stream)) return rc;
-    hipLaunchKernelGGL(nn_query_kernel, dim3(nn_blocks(m, 64)), dim3(64), 0, as_stream(stream), query, m,
+    hipLaunchKernelGGL(nn_query_kernel, dim3(hm_grid(m, 64)), dim3(64), 0, as_stream(stream), query, m,
                        static_cast<const int64_t *>(w.perm), reinterpret_cast<const float4 *>(records), n, cell_start,
                        G, max_dist2, d2, index, reinterpret_cast<unsigned long long *>(n_tests));
     HM_CHECK_LAUNCH("hm_nn_query");

@@ -15,8 +15,6 @@ struct NnGrid {
     int32_t pad_;
 };
 
-inline unsigned nn_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 // clamp(floor((p - lo) / h), 0, g - 1) with every operation rounded once; monotone non-decreasing in p.  g <= 2^30.
 __device__ __forceinline__ int32_t nn_cell(float p, float lo, float h, int32_t g) {
     const float t = floorf(__fdiv_rn(__fsub_rn(p, lo), h));

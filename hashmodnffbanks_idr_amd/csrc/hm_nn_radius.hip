@@ -41,7 +41,7 @@
 //     starts, so that round decides it: every round with a non-empty list shortens it.  The driver (ops.py) loops until
 //     the count it reads is 0 and has no other exit; nr_tail's loop runs at most as many rounds as it has points, which
 //     by the same argument is enough.
-#include "hm_common.h"
+#include "hm_block_dev.h"
 #include "hm_nn_dev.h"
 
 namespace {
@@ -50,26 +50,21 @@ constexpr int kTail = 1024;    // a list this short is finished by one workgroup
 constexpr int kScanT = 1024;
 constexpr uint8_t kUndecided = 0, kKept = 1, kRemoved = 2;
 
-inline int64_t nr_up256(int64_t b) { return (b + 255) / 256 * 256; }
-
 struct NrWs {
     uint8_t *state;      // [n] by sorted position
     int32_t *list[2];    // [n] each: the undecided sorted positions, ascending
     int32_t *bcnt;       // [ceil(n / kNT)] waiting points per block of the round, then their exclusive prefix sum
+    int64_t bytes;
 };
 
-inline int64_t nr_ws_bytes(int64_t n) { return nr_up256(n) + 2 * nr_up256(4 * n) + nr_up256(4 * ((n + kNT - 1) / kNT)); }
-
-inline NrWs nr_carve(void *ws, int64_t n) {
-    char *p = static_cast<char *>(ws);
+NrWs nr_layout(void *ws, int64_t n) {
+    HmCarve c(ws);
     NrWs w;
-    w.state = reinterpret_cast<uint8_t *>(p);
-    p += nr_up256(n);
-    w.list[0] = reinterpret_cast<int32_t *>(p);
-    p += nr_up256(4 * n);
-    w.list[1] = reinterpret_cast<int32_t *>(p);
-    p += nr_up256(4 * n);
-    w.bcnt = reinterpret_cast<int32_t *>(p);
+    w.state = c.take<uint8_t>(n);
+    w.list[0] = c.take<int32_t>(n);
+    w.list[1] = c.take<int32_t>(n);
+    w.bcnt = c.take<int32_t>((n + kNT - 1) / kNT);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -176,29 +171,6 @@ __global__ __launch_bounds__(kNT) void nr_round_kernel(NrQuery Q, const int32_t 
     if (threadIdx.x == 0) bcnt[blockIdx.x] = c;
 }
 
-// the inclusive prefix sum of v over the workgroup's T threads (T / 64 <= 16 waves); wsum: T / 64 words of LDS
-template <int T>
-__device__ __forceinline__ int32_t nr_block_scan(int32_t v, int32_t *wsum, int32_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t up = __shfl_up(v, o);
-        if (lane >= o) v += up;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    int32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) {
-        const int32_t s = wsum[w];
-        before += w < wave ? s : 0;
-        total += s;
-    }
-    return v + before;
-}
-
 // bcnt[0 .. nb) -> its exclusive prefix sum; *count_out = the total; one productive round more when *count_in > 0
 __global__ __launch_bounds__(kScanT) void nr_scan_kernel(int32_t *__restrict__ bcnt, int64_t nb,
                                                          const int32_t *__restrict__ count_in,
@@ -209,7 +181,7 @@ __global__ __launch_bounds__(kScanT) void nr_scan_kernel(int32_t *__restrict__ b
         const int64_t b = base + threadIdx.x;
         const int32_t v = b < nb ? bcnt[b] : 0;
         int32_t total;
-        const int32_t incl = nr_block_scan<kScanT>(v, wsum, total);
+        const int32_t incl = hm_block_scan<kScanT>(v, wsum, total);
         if (b < nb) bcnt[b] = carry + incl - v;
         carry += total;
     }
@@ -229,7 +201,7 @@ __global__ __launch_bounds__(kNT) void nr_scatter_kernel(const int32_t *__restri
     if (t < nr_count(count, n)) r = list[t];
     const bool waiting = (uint32_t)r < (uint64_t)n && nr_load(state + r) == kUndecided;
     int32_t total;
-    const int32_t incl = nr_block_scan<kNT>(waiting ? 1 : 0, wsum, total);
+    const int32_t incl = hm_block_scan<kNT>(waiting ? 1 : 0, wsum, total);
     const int64_t dst = (int64_t)boff[blockIdx.x] + incl - 1;
     if (waiting && dst >= 0 && dst < n) list_out[dst] = r;
 }
@@ -274,15 +246,15 @@ extern "C" {
 int64_t hm_nn_radius_workspace_bytes(int64_t n) {
     if (n < 0 || n >= ((int64_t)1 << 31))
         return hm_fail(HM_ERR_INVALID, "hm_nn_radius_workspace_bytes: n must be in [0, 2^31)");
-    return nr_ws_bytes(n);
+    return nr_layout(nullptr, n).bytes;
 }
 
 int hm_nn_radius_begin(int64_t n, void *workspace, int64_t workspace_bytes, int32_t *info, void *stream) {
     HM_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31), "hm_nn_radius_begin: n must be in [1, 2^31)");
     HM_CHECK_ARG(workspace && info, "hm_nn_radius_begin: NULL pointer");
-    HM_CHECK_ARG(workspace_bytes >= nr_ws_bytes(n), "hm_nn_radius_begin: workspace too small");
-    const NrWs w = nr_carve(workspace, n);
-    hipLaunchKernelGGL(nr_begin_kernel, dim3(nn_blocks(n, kNT)), dim3(kNT), 0, as_stream(stream), w.state, w.list[0], n,
+    HM_CHECK_ARG(workspace_bytes >= nr_layout(nullptr, n).bytes, "hm_nn_radius_begin: workspace too small");
+    const NrWs w = nr_layout(workspace, n);
+    hipLaunchKernelGGL(nr_begin_kernel, dim3(hm_grid(n, kNT)), dim3(kNT), 0, as_stream(stream), w.state, w.list[0], n,
                        info);
     HM_CHECK_LAUNCH("hm_nn_radius_begin");
     return HM_OK;
@@ -300,8 +272,8 @@ int hm_nn_radius_rounds(const float *records, int64_t n, const int32_t *cell_sta
     HM_CHECK_ARG(capacity >= 1 && capacity <= n, "hm_nn_radius_rounds: capacity must be in [1, n]");
     HM_CHECK_ARG(round0 >= 0 && n_rounds >= 1 && n_rounds <= 64, "hm_nn_radius_rounds: round0 >= 0, 1 <= n_rounds <= 64");
     HM_CHECK_ARG(records && cell_start && workspace && info, "hm_nn_radius_rounds: NULL pointer");
-    HM_CHECK_ARG(workspace_bytes >= nr_ws_bytes(n), "hm_nn_radius_rounds: workspace too small");
-    const NrWs w = nr_carve(workspace, n);
+    HM_CHECK_ARG(workspace_bytes >= nr_layout(nullptr, n).bytes, "hm_nn_radius_rounds: workspace too small");
+    const NrWs w = nr_layout(workspace, n);
     hipStream_t st = as_stream(stream);
     NrQuery Q;
     Q.rec = reinterpret_cast<const float4 *>(records);
@@ -318,7 +290,7 @@ int hm_nn_radius_rounds(const float *records, int64_t n, const int32_t *cell_sta
         HM_CHECK_LAUNCH("hm_nn_radius_rounds");
         return HM_OK;
     }
-    const unsigned nb = nn_blocks(capacity, kNT);
+    const unsigned nb = hm_grid(capacity, kNT);
     for (int32_t i = 0; i < n_rounds; ++i) {
         const int cur = (int)((round0 + i) & 1);
         hipLaunchKernelGGL(nr_round_kernel, dim3(nb), dim3(kNT), 0, st, Q, static_cast<const int32_t *>(w.list[cur]),
@@ -337,9 +309,9 @@ int hm_nn_radius_finish(const float *records, int64_t n, void *workspace, int64_
                         void *stream) {
     HM_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31), "hm_nn_radius_finish: n must be in [1, 2^31)");
     HM_CHECK_ARG(records && workspace && keep, "hm_nn_radius_finish: NULL pointer");
-    HM_CHECK_ARG(workspace_bytes >= nr_ws_bytes(n), "hm_nn_radius_finish: workspace too small");
-    const NrWs w = nr_carve(workspace, n);
-    hipLaunchKernelGGL(nr_finish_kernel, dim3(nn_blocks(n, kNT)), dim3(kNT), 0, as_stream(stream),
+    HM_CHECK_ARG(workspace_bytes >= nr_layout(nullptr, n).bytes, "hm_nn_radius_finish: workspace too small");
+    const NrWs w = nr_layout(workspace, n);
+    hipLaunchKernelGGL(nr_finish_kernel, dim3(hm_grid(n, kNT)), dim3(kNT), 0, as_stream(stream),
                        reinterpret_cast<const float4 *>(records), n, static_cast<const uint8_t *>(w.state), keep);
     HM_CHECK_LAUNCH("hm_nn_radius_finish");
     return HM_OK;

@@ -99,7 +99,24 @@ __global__ __launch_bounds__(kST) void radix_scatter_kernel(const int32_t *__res
     }
 }
 
-inline int64_t up256(int64_t b) { return (b + 255) / 256 * 256; }
+// [keys tmp n i32 | vals a n i32 | vals b n i32 | hist 256 * n_chunks u32]
+struct SortWs {
+    int32_t *ktmp, *va, *vb;
+    uint32_t *hist;
+    int64_t bytes;
+};
+
+SortWs sort_layout(void *ws, int64_t n) {
+    const int64_t n_chunks = (n + kChunk - 1) / kChunk;
+    HmCarve c(ws);
+    SortWs w;
+    w.ktmp = c.take<int32_t>(n);
+    w.va = c.take<int32_t>(n);
+    w.vb = c.take<int32_t>(n);
+    w.hist = c.take<uint32_t>(256 * (n_chunks > 0 ? n_chunks : 1));
+    w.bytes = c.bytes;
+    return w;
+}
 
 }  // namespace
 
@@ -107,9 +124,7 @@ extern "C" {
 
 int64_t hm_sort_workspace_bytes(int64_t n) {
     if (n < 0) return hm_fail(HM_ERR_INVALID, "hm_sort_workspace_bytes: n < 0");
-    const int64_t n_chunks = (n + kChunk - 1) / kChunk;
-    // [keys tmp n i32 | vals a n i32 | vals b n i32 | hist 256 * n_chunks u32]
-    return 3 * up256(4 * n) + up256(4 * 256 * (n_chunks > 0 ? n_chunks : 1));
+    return sort_layout(nullptr, n).bytes;
 }
 
 int hm_sort_pairs_i32(const int32_t *keys, int64_t n, int key_bits, int32_t *keys_sorted, int64_t *perm, void *workspace,
@@ -120,11 +135,7 @@ int hm_sort_pairs_i32(const int32_t *keys, int64_t n, int key_bits, int32_t *key
     HM_CHECK_ARG(keys && keys_sorted && perm && workspace, "hm_sort_pairs_i32: NULL pointer");
     HM_CHECK_ARG(workspace_bytes >= hm_sort_workspace_bytes(n), "hm_sort_pairs_i32: workspace too small");
     const int64_t n_chunks = (n + kChunk - 1) / kChunk;
-    char *ws = static_cast<char *>(workspace);
-    int32_t *ktmp = reinterpret_cast<int32_t *>(ws);
-    int32_t *va = reinterpret_cast<int32_t *>(ws + up256(4 * n));
-    int32_t *vb = reinterpret_cast<int32_t *>(ws + 2 * up256(4 * n));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(ws + 3 * up256(4 * n));
+    const SortWs w = sort_layout(workspace, n);
     const int passes = (key_bits + 7) / 8;
     hipStream_t st = as_stream(stream);
     // ping-pong so that the LAST pass writes keys_sorted: with an even number of passes the first one writes the temporary
@@ -132,12 +143,13 @@ int hm_sort_pairs_i32(const int32_t *keys, int64_t n, int key_bits, int32_t *key
     const int32_t *vin = nullptr;
     for (int p = 0; p < passes; ++p) {
         const bool last = p == passes - 1;
-        int32_t *kout = ((passes - 1 - p) % 2 == 0) ? keys_sorted : ktmp;
-        int32_t *vout = (p % 2 == 0) ? va : vb;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)n_chunks), dim3(kST), 0, st, kin, n, 8 * p, n_chunks, hist);
-        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, st, hist, 256 * n_chunks);
+        int32_t *kout = ((passes - 1 - p) % 2 == 0) ? keys_sorted : w.ktmp;
+        int32_t *vout = (p % 2 == 0) ? w.va : w.vb;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)n_chunks), dim3(kST), 0, st, kin, n, 8 * p, n_chunks,
+                           w.hist);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, st, w.hist, 256 * n_chunks);
         hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)n_chunks), dim3(kST), 0, st, kin, vin, n, 8 * p, n_chunks,
-                           static_cast<const uint32_t *>(hist), kout, vout, last ? perm : nullptr);
+                           static_cast<const uint32_t *>(w.hist), kout, vout, last ? perm : nullptr);
         kin = kout;
         vin = vout;
     }

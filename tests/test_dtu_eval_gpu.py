@@ -115,6 +115,21 @@ def test_long_chain_through_the_batched_rounds():
     _check_thin(p, 1.0, np.arange(4097) % 2 == 0)
 
 
+def test_block_counts_span_two_scan_chunks():
+    # 87 553 groups of three points = 262 659 points = 1027 blocks of 256: the scan of the blocks' counts takes two
+    # chunks of 1024, the second partial, and carries the first one's total.  Group g has its points m = 0, 1, 2 at
+    # ((g % 512)*4 + 0.5*m, (g // 512)*4, 0), index 3g + m: every coordinate and squared distance is exact in fp32,
+    # 0.5 is inside the radius 0.75, 1.0 and the 2.0 or more between groups are outside.  Point 0 has no lower
+    # neighbour, point 1 sees the kept point 0, point 2 sees only the removed point 1: the mask is m != 1.
+    groups = 87553
+    g, m = np.divmod(np.arange(3 * groups), 3)
+    p = np.stack([(g % 512) * 4 + 0.5 * m, (g // 512) * 4, np.zeros(len(g))], 1).astype(np.float32)
+    assert len(p) == 262659 and -(-len(p) // 256) == 1027
+    want = m != 1
+    assert np.array_equal(DC.downsample_ref(p[:900], 0.75), want[:900])
+    _check_thin(p, 0.75, want)
+
+
 def test_two_calls_agree_and_nan_raises():
     p = _dev(DC.sphere("shuffled"))
     a, b = ops.radius_downsample(p, 0.05), ops.radius_downsample(p, 0.05)

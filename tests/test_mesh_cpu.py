@@ -182,3 +182,26 @@ def test_abi_rejects_bad_volumes_with_a_status():
     assert rc == -1 and b"int32" in L.hm_last_error()
     with pytest.raises(ValueError, match="int32"):
         _lib.check(rc)
+
+
+_WS_N = [0, 1, 255, 256, 257, 4096, 4097, 1 << 20]
+# the sizes the library reported before its workspace layouts were written once over HmCarve (csrc/hm_common.h): a
+# buffer sized by an older build must still fit, and a part dropped from or added to a layout shows here
+_WS_BYTES = {
+    "hm_sort_workspace_bytes": [1024, 1792, 4096, 4096, 4864, 50176, 51968, 12845056],
+    "hm_nn_workspace_bytes": [1024, 2560, 8192, 8192, 9728, 115712, 118272, 29622272],
+    "hm_nn_radius_workspace_bytes": [0, 1024, 2560, 2560, 3328, 37120, 37888, 9453568],
+    "hm_mesh_cc_sums_workspace_bytes": [1024, 2560, 8192, 8192, 9728, 115712, 118272, 29622272],
+    "hm_mesh_moments_workspace_bytes": [256, 256, 256, 256, 256, 256, 256, 20480],
+}
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    from hashmodnffbanks_idr_amd import build, _lib
+    build.build(verbose=False)
+    L = _lib.lib()
+    for name, want in _WS_BYTES.items():
+        assert [getattr(L, name)(n) for n in _WS_N] == want, name
+    dims = [(2, 2, 2), (16, 16, 16), (17, 16, 16), (64, 64, 64)]
+    assert [L.hm_mc_workspace_bytes(*d) for d in dims] == [1024, 25088, 26624, 1574656]
+    assert [L.hm_mcs_workspace_bytes(n) for n in (1, 8, 9)] == [3584, 25088, 28160]
