@@ -207,6 +207,11 @@ class HashmodError(RuntimeError):
     pass
 
 
+class HashmodArgumentError(HashmodError, ValueError):
+    """An argument the library rejected (HM_ERR_INVALID): a HashmodError like every other failure of the library, and
+    still the ValueError that the reference raises for it."""
+
+
 # Parameters written through raw pointers (hm_adam_step, graph replays) do not bump torch's tensor._version, so
 # every cache derived from parameter VALUES (ImplicitNetwork.packed_weights) also keys on this counter; every
 # writer that bypasses ATen calls bump_param_epoch().
@@ -295,7 +300,7 @@ def check(rc, what=""):
         msg = lib().hm_last_error()
         msg = msg.decode() if msg else "unknown error"
         if rc == -1:
-            raise ValueError(f"hashmod: {msg}")
+            raise HashmodArgumentError(f"hashmod: {msg}")
         raise HashmodError(f"hashmod: {msg} (code {rc}) {what}")
     return rc
 
