@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import params as P
+from encode_cases import _trilinear_torch
 from oracle import c_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -264,30 +265,6 @@ def test_zordered_table_backward_vs_oracle(cfg, mode):
     print(f"z-ordered table backward vs the C oracle {cfg}/{mode}: max |d| {err:.3e} (scale {scale:.3e})")
     assert err <= 3e-5 * scale
     assert abs(got.astype(np.float64).sum() - ref.astype(np.float64).sum()) <= 1e-5 * np.abs(ref).astype(np.float64).sum()
-
-
-def _trilinear_torch(x, table, desc):
-    """differentiable torch restatement of the trilinear encoder (fp64): floor voxel, 8 hashed corners, product
-    weights - the opt-in mode has no counterpart in the reference, so autograd on this expression is the checker"""
-    feats = []
-    xd = x.double()
-    for l in range(desc.L):
-        r, rows, off = int(desc.res[l]), int(desc.rows[l]), int(desc.row_off[l])
-        xs = (x.detach() * float(r)).double()              # value: the kernel forms x * res in fp32
-        xs = xs + (xd * float(r) - (xd * float(r)).detach())   # gradient: of the exact product
-        fl = torch.floor(xs.detach())
-        t = xs - fl
-        acc = 0.0
-        for c in range(8):
-            w, h = 1.0, None
-            for d, prime in enumerate((1, 3, 2654435761)):
-                bit = (c >> d) & 1
-                w = w * (t[:, d] if bit else 1.0 - t[:, d])
-                u = ((fl[:, d].long() + bit) & 0xFFFFFFFF) * prime & 0xFFFFFFFF
-                h = u if h is None else h ^ u
-            acc = acc + w[:, None] * table[off + (h % rows)].double()
-        feats.append(acc)
-    return torch.cat(feats, 1)
 
 
 @pytest.mark.parametrize("cfg", ["C1", "C2"])
