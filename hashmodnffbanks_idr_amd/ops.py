@@ -834,9 +834,26 @@ def nffb_fwd(mod, x, n_dev=None, out=None):
     """[N, 3 + 8 + 8L] embedding of a FourierFilterBanks module in one kernel (no autograd)."""
     x = _prep_x(x)
     grid = mod.grid_enc
-    require_gpu(x, grid.table)
     n = x.shape[0]
     width = mod.embeddings_dim
+    # the kernel writes n rows of `width` fp32 values through raw pointers and reads one int32 count: whatever it cannot
+    # address as such is rejected here, before anything is enqueued
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.dim() == 2):
+            raise ValueError("hashmod nffb_fwd: out must be a 2-D float32 tensor")
+        if out.shape[0] < n or out.shape[1] < width:
+            raise ValueError(f"hashmod nffb_fwd: out {tuple(out.shape)} is smaller than [{n}, {width}]")
+        if out.stride(1) != 1 or out.stride(0) < width:
+            raise ValueError(f"hashmod nffb_fwd: out needs unit column stride and a row stride of at least {width}, "
+                             f"got strides {tuple(out.stride())}")
+        if out.device != x.device:
+            raise ValueError(f"hashmod nffb_fwd: out is on {out.device}, the points on {x.device}")
+    if n_dev is not None:
+        if not (isinstance(n_dev, torch.Tensor) and n_dev.dtype == torch.int32 and n_dev.numel() >= 1):
+            raise ValueError("hashmod nffb_fwd: n_dev must be an int32 tensor holding the live point count")
+        if n_dev.device != x.device:
+            raise ValueError(f"hashmod nffb_fwd: n_dev is on {n_dev.device}, the points on {x.device}")
+    require_gpu(x, grid.table)
     if out is None:
         out = torch.empty((n, width), dtype=torch.float32, device=x.device)
     pk = nffb_packed(mod)
