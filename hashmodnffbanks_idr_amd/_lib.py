@@ -130,6 +130,11 @@ SIGNATURES = {
                                    _i64, _p, _p]),
     "hm_nn_radius_finish": (_int, [_p, _i64, _p, _i64, _p, _p]),
     "hm_dtu_point_flags": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
+    # eval.py's per-view image scores: masked squared error (PSNR) and SSIM
+    "hm_image_sqerr_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "hm_image_sqerr": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    "hm_image_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "hm_image_ssim": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, C.c_double, C.c_double, _p, _p, _p, _p]),
 }
 
 

@@ -1969,3 +1969,116 @@ def dtu_point_flags(points, obs_mask, bb, res, patch, plane):
     if n:
         check(lib().hm_dtu_point_flags(dptr(points), n, dptr(obs_mask), shape, params, dptr(flags), stream_ptr(points)))
     return flags
+
+
+# =========================================================================================
+# Image metrics of rendered views: PSNR over a mask and SSIM (csrc/hm_image.hip)
+# =========================================================================================
+_IMG_WS = _lib.Workspace("image metrics")
+SSIM_TILE = (16, 16)        # window positions (rows, columns) one workgroup of hm_image_ssim scores
+SQERR_PIXELS = 1024         # pixels one workgroup of hm_image_sqerr sums
+SSIM_MAX_WIN = 31
+
+
+def _check_images(what, x, y):
+    """(x, y) as contiguous fp32 [B, H, W, C] on one device, 1 <= C <= 4; [H, W, C] becomes B = 1"""
+    for name, t in (("x", x), ("y", y)):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (3, 4)
+                or not t.is_contiguous()):
+            raise ValueError(f"hashmod {what}: contiguous fp32 {name} [B, H, W, C] or [H, W, C] expected")
+    if x.shape != y.shape:
+        raise ValueError(f"hashmod {what}: x {tuple(x.shape)} and y {tuple(y.shape)} differ in shape")
+    if x.device != y.device:
+        raise ValueError(f"hashmod {what}: the tensors are on different devices")
+    if x.dim() == 3:
+        x, y = x[None], y[None]
+    B, H, W, Cn = x.shape
+    if not 1 <= Cn <= 4:
+        raise ValueError(f"hashmod {what}: C must be in [1, 4], got {Cn}")
+    if min(B, H, W) < 1 or max(B, H, W) >= 1 << 31:
+        raise ValueError(f"hashmod {what}: B, H and W must be in [1, 2^31)")
+    return x, y
+
+
+def _check_data_range(what, data_range):
+    if not (isinstance(data_range, (int, float)) and not isinstance(data_range, bool) and math.isfinite(data_range)
+            and data_range > 0):
+        raise ValueError(f"hashmod {what}: data_range must be a positive finite number")
+    return float(data_range)
+
+
+def image_psnr(x, y, mask=None, data_range=1.0):
+    """psnr [B] fp64 (device) of the images x, y [B, H, W, C] fp32, contiguous, 1 <= C <= 4 ([H, W, C]: B = 1) - the
+    reference's calculate_psnr.  mask: None or [B, H, W] bool / uint8 on the same device; n_b = its set pixels of image
+    b (H*W without a mask), mse_b = sum over the set pixels and their channels of (x - y)^2 / (n_b * C),
+    psnr_b = 10 log10(data_range^2 / mse_b); mse_b == 0 gives +inf and n_b == 0 nan.  Pixels outside the mask are not
+    read.  Differences, squares and sums are fp64; the sum is a fixed-order two-stage reduction without atomics, so two
+    calls give the same bits.  A wrong dtype, shape, device, contiguity, C, data_range or mask raises ValueError before
+    the GPU is touched.  No host read; the partials' buffer is a module workspace, so capture only after a warm-up."""
+    x, y = _check_images("image_psnr", x, y)
+    L2 = _check_data_range("image_psnr", data_range) ** 2
+    B, H, W, Cn = x.shape
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8)
+                or not mask.is_contiguous()):
+            raise ValueError("hashmod image_psnr: mask must be a contiguous bool or uint8 tensor")
+        if tuple(mask.shape) not in ((B, H, W), (H, W)) or (mask.dim() == 2 and B != 1):
+            raise ValueError(f"hashmod image_psnr: mask {tuple(mask.shape)} is not [B, H, W] = {(B, H, W)}")
+        if mask.device != x.device:
+            raise ValueError("hashmod image_psnr: mask is on a different device than the images")
+    require_gpu(x)
+    lib_ = lib()
+    ws = _IMG_WS.get(x.device, check(lib_.hm_image_sqerr_workspace_bytes(B, H, W)))
+    out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    check(lib_.hm_image_sqerr(dptr(x), dptr(y), dptr(mask), B, H, W, Cn, dptr(ws), dptr(out), stream_ptr(x)))
+    return 10.0 * torch.log10(L2 / (out[:, 0] / (out[:, 1] * Cn)))
+
+
+def ssim_window(win=11, sigma=1.5):
+    """the win fp64 weights g(r) ~ exp(-(r - (win-1)/2)^2 / (2 sigma^2)) normalised to sum 1 (numpy); the SSIM window
+    is their outer product"""
+    if not (isinstance(win, int) and not isinstance(win, bool) and 3 <= win <= SSIM_MAX_WIN and win % 2 == 1):
+        raise ValueError(f"hashmod image_ssim: win must be an odd integer in [3, {SSIM_MAX_WIN}]")
+    if not (isinstance(sigma, (int, float)) and math.isfinite(sigma) and sigma > 0):
+        raise ValueError("hashmod image_ssim: sigma must be a positive finite number")
+    r = np.arange(win, dtype=np.float64) - (win - 1) / 2.0
+    g = np.exp(-(r * r) / (2.0 * float(sigma) ** 2))
+    return g / g.sum()
+
+
+def image_ssim(x, y, data_range=1.0, win=11, sigma=1.5, k1=0.01, k2=0.03, return_map=False):
+    """ssim [B] fp64 (device) of the images x, y [B, H, W, C] fp32, contiguous, 1 <= C <= 4 ([H, W, C]: B = 1): SSIM of
+    Wang et al. 2004 with the win x win Gaussian window g(i) g(j), g = ssim_window(win, sigma), C1 = (k1 data_range)^2,
+    C2 = (k2 data_range)^2 - the torchmetrics defaults, skimage with gaussian_weights=True,
+    use_sample_covariance=False.  For every window wholly inside the image, (H-win+1)(W-win+1) positions per channel
+    and no padding (both libraries pad and crop the same border away), the weighted moments mx, my, Exx, Eyy, Exy,
+    sx2 = Exx - mx^2, sy2 = Eyy - my^2, sxy = Exy - mx my and
+        s = ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sx2 + sy2 + C2));
+    ssim_b is the mean of s over positions and channels.  Moments, formula and mean are fp64 from the fp32 values, the
+    mean a fixed-order two-stage reduction without atomics: two calls give the same bits and image_ssim(x, x) is
+    exactly 1.  return_map=True returns (ssim, map) with map [B, H-win+1, W-win+1, C] fp64 = s.  win odd in [3, 31];
+    H < win or W < win, a wrong dtype, shape, device, contiguity, C, data_range, k1 or k2 raise ValueError before the
+    GPU is touched.  SSIM_TILE is the block of positions one workgroup scores.  The weights are uploaded per call (a
+    host-to-device copy) and the partials' buffer is a module workspace: not graph-capturable."""
+    x, y = _check_images("image_ssim", x, y)
+    L = _check_data_range("image_ssim", data_range)
+    weights = ssim_window(win, sigma)
+    for name, k in (("k1", k1), ("k2", k2)):
+        if not (isinstance(k, (int, float)) and math.isfinite(k) and k > 0):
+            raise ValueError(f"hashmod image_ssim: {name} must be a positive finite number")
+    B, H, W, Cn = x.shape
+    if H < win or W < win:
+        raise ValueError(f"hashmod image_ssim: the image {H} x {W} is smaller than the {win} x {win} window")
+    c1, c2 = (float(k1) * L) ** 2, (float(k2) * L) ** 2
+    if not (c1 > 0 and c2 > 0 and math.isfinite(c1) and math.isfinite(c2)):
+        raise ValueError("hashmod image_ssim: (k1 data_range)^2 and (k2 data_range)^2 must be positive and finite")
+    require_gpu(x)
+    lib_ = lib()
+    dev = x.device
+    ws = _IMG_WS.get(dev, check(lib_.hm_image_ssim_workspace_bytes(B, H, W, win)))
+    wdev = torch.from_numpy(weights).to(dev)
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    smap = torch.empty((B, H - win + 1, W - win + 1, Cn), dtype=torch.float64, device=dev) if return_map else None
+    check(lib_.hm_image_ssim(dptr(x), dptr(y), B, H, W, Cn, win, dptr(wdev), c1, c2, dptr(smap), dptr(ws), dptr(out),
+                             stream_ptr(x)))
+    return (out, smap) if return_map else out

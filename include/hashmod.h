@@ -904,6 +904,34 @@ HM_API int hm_nn_radius_finish(const float *records, int64_t n, void *workspace,
 HM_API int hm_dtu_point_flags(const float *points, int64_t n, const uint8_t *mask, const int64_t *shape,
                               const double *params, uint8_t *flags, void *stream);
 
+/* ---- image metrics: PSNR over a mask and SSIM of rendered views ---------------------------------------------------
+ * What the reference's evaluation/eval.py computes per view on the host (calculate_psnr; SSIM of Wang et al. 2004 with
+ * a Gaussian window, the torchmetrics defaults).  Driver: ops.image_psnr, ops.image_ssim, evaluation.images.
+ * csrc/hm_image.hip.  x, y: fp32 [B, H, W, C], contiguous, 1 <= C <= 4; B, H, W in [1, 2^31), B*H*W*C < 2^62.  Every
+ * difference, product, sum and quotient is fp64 on the fp32 values.  Both reductions have a fixed order - per-workgroup
+ * partials, then one workgroup per image over its partials in index order - and use no atomics: two calls give the
+ * same bits.  No entry point synchronises and there is no device-side error path.
+ *   hm_image_sqerr: out [B,2] fp64 = {sum over the set pixels and their channels of (x - y)^2, n = the number of set
+ *                pixels}; mask [B,H,W] bytes (non-zero = set) or NULL for every pixel.  Pixels that are not set are not
+ *                read.  The caller forms mse = sum / (n*C) and psnr = 10 log10(L^2 / mse).  One workgroup per 1024
+ *                pixels of an image.  partial_ws: hm_image_sqerr_workspace_bytes(B, H, W) bytes.
+ *   hm_image_ssim:  win odd in [3, 31], H >= win and W >= win; weights: win DEVICE fp64 that sum to 1, the window is
+ *                weights[i]*weights[j]; c1, c2 finite and > 0.  For every window inside the image - (H-win+1)(W-win+1)
+ *                positions per channel, no padding - the weighted moments mx, my, Exx, Eyy, Exy (horizontal pass, then
+ *                vertical), sx2 = Exx - mx^2, sy2 = Eyy - my^2, sxy = Exy - mx my and
+ *                    s = ((2 mx my + c1)(2 sxy + c2)) / ((mx^2 + my^2 + c1)(sx2 + sy2 + c2)).
+ *                out [B] fp64 = the mean of s over positions and channels; map, unless NULL, [B, H-win+1, W-win+1, C]
+ *                fp64 = s.  y == x gives exactly 1.  One workgroup per 16 x 16 positions; partial_ws:
+ *                hm_image_ssim_workspace_bytes(B, H, W, win) bytes.  A window and channel count whose tile does not
+ *                fit the CU's LDS is refused (none within the limits above: 99,456 bytes at win = 31, C = 4). */
+HM_API int64_t hm_image_sqerr_workspace_bytes(int64_t B, int64_t H, int64_t W);
+HM_API int hm_image_sqerr(const float *x, const float *y, const uint8_t *mask, int64_t B, int64_t H, int64_t W,
+                          int64_t C, double *partial_ws, double *out, void *stream);
+HM_API int64_t hm_image_ssim_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t win);
+HM_API int hm_image_ssim(const float *x, const float *y, int64_t B, int64_t H, int64_t W, int64_t C, int64_t win,
+                         const double *weights, double c1, double c2, double *map, double *partial_ws, double *out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
