@@ -820,11 +820,14 @@ template <int FRAC>
 __global__ __launch_bounds__(kThreadsSdf, 1) void trace_secant_kernel(HmLevels lv, SdfNet net,
                                                                        const float *__restrict__ table,
                                                                        const float *__restrict__ Bf, TraceArgs a,
-                                                                       int n_iters, int64_t m8_max, int64_t m4_max) {
+                                                                       int n_iters, int64_t m8_max, int64_t m4_max,
+                                                                       int64_t scan_hide) {
     extern __shared__ __align__(16) float lds[];
     const int64_t n = a.w.cnt[C_NSEC];
     if (n <= 0) return;
-    const int pts = n <= m4_max ? 4 : (n <= m8_max ? 8 : 16);
+    // scan_hide > 0: the tile rule of sdf_scan_secant_kernel, so that both forms of the search give the same values
+    const bool as_scan = scan_hide > 0 && a.w.cnt[C_NSEL_PTS] >= scan_hide;
+    const int pts = as_scan ? 16 : (n <= m4_max ? 4 : (n <= m8_max ? 8 : 16));
     secant_role<FRAC>(lv, net, table, Bf, a, n_iters, n, pts, lds);
 }
 
@@ -1007,8 +1010,11 @@ int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const 
 
 // internal entry of the ray search (hm_trace.hip, not exported): all secant iterations as ONE launch
 // (trace_secant_kernel).  tile_points 0 = the tile size follows the list's length as in hm_sdf_fwd; 4 / 8 / 16 = fixed.
+// scan_rule != 0 (tile_points 0 only): 16-point tiles when the closest-approach scan has at least kTraceScanHide points,
+// as hm_trace_scan_secant chooses them.
 int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                               int frac_mode, int tile_points, const void *trace_args, int n_iters, void *stream) {
+                               int frac_mode, int tile_points, const void *trace_args, int n_iters, int scan_rule,
+                               void *stream) {
     HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_secant_persistent: NULL argument");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_secant_persistent: bad frac_mode");
     HM_CHECK_ARG(tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16,
@@ -1028,7 +1034,7 @@ int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
         const int rc = hm_allow_dynamic_lds<kernel>(96 * 1024);
         if (rc != HM_OK) return rc;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier,
-                           a, n_iters, t.m8_max, t.m4_max);
+                           a, n_iters, t.m8_max, t.m4_max, (int64_t)((scan_rule && tile_points == 0) ? kTraceScanHide : 0));
         HM_CHECK_LAUNCH("hm_trace_secant_persistent");
         return HM_OK;
     });
@@ -1055,7 +1061,8 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
     const size_t lds = lds16 > lds64 ? lds16 : lds64;
     // 16-point secant tiles once the scan keeps the chip busy for longer than their chain takes (8 x 131 us ~ 2.3 rounds
     // of 64-point tiles: 3 rounds = 49 152 points)
-    const int64_t scan_hide = 3 * 256 * kPts;
+    static_assert(kTraceScanHide == 3 * 256 * kPts, "kTraceScanHide counts rounds of 64-point tiles");
+    const int64_t scan_hide = kTraceScanHide;
     // c_prev*: counters holding the own-point counts of the sampler launches that took filler tiles of this scan (-1: none)
     const int p1 = grid1 > 0 ? c_prev1 : -1, p2 = grid2 > 0 ? c_prev2 : -1;
     const SmallTiles t = sdf_small_tiles(0);

@@ -16,6 +16,7 @@
 #include "hm_common.h"
 
 #include <stdlib.h>
+#include <string.h>
 
 // hm_sdf.hip (not exported): rounds [first, rounds) of the sphere-tracing march as one persistent launch
 extern "C" int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
@@ -24,7 +25,7 @@ extern "C" int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *
 
 extern "C" int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
                                           const float *B_fourier, int frac_mode, int tile_points, const void *trace_args,
-                                          int n_iters, void *stream);
+                                          int n_iters, int scan_rule, void *stream);
 
 // hm_sdf.hip (not exported): the closest-approach scan and the secant refinement as ONE launch (workgroups without secant
 // rays start on the scan at once, 64-point tiles handed out by an atomic cursor)
@@ -299,6 +300,163 @@ __global__ __launch_bounds__(kTB) void closest_reduce_kernel(TraceArgs a) {
     a.out_pts[i * 3] = px; a.out_pts[i * 3 + 1] = py; a.out_pts[i * 3 + 2] = pz;
 }
 
+// ---- guarded coarse scans (hm_trace_cfg.coarse_bf16 = 3) ------------------------------------------------------------
+// A floating-point filter, as in exact geometric predicates: the coarse rows are evaluated on the f16x2 split kernel,
+// the samples whose approximate value cannot settle what the reduce kernels read are re-evaluated by the exact-fp32
+// kernel (compact refinement region, one launch), the exact values are written over the approximate ones, and the
+// reduce kernels run unchanged on the patched rows.
+//
+// Marking rule.  tau = kGuardTau, a_s = approximate value of sample s.  s is UNCERTAIN if a_s is non-finite or
+// |a_s| <= tau; c = first sample with a_s < -tau (if any).  Sampler rows:
+//   1. every uncertain sample is marked;
+//   2. c is marked, and its predecessor (index 0 wraps to the row's last sample, as lo_idx does);
+//   3. the predecessor of every uncertain u before c (of every uncertain u when there is no c) is marked: u may turn out
+//      to be `first`, and its bracket partner must then be exact;
+//   4. when the arg-min can be read (the ray is outside the object mask, or it has no c): every sample with
+//      a_s <= m + 2 tau, m = smallest finite a_s of the row.
+// Closest-approach rows: non-finite samples and rule 4.
+// The lazy sampler's first pass applies 1-3 to its own row (samples 0..head-1, then n_steps-1: the wrap of rule 2 is
+// the row's own); a ray it resolves reads nothing else.  Every other ray is in the second pass, which applies 1-4 to the
+// ray's whole row (first-pass samples already patched are exact; marking one again changes nothing).
+//
+// Why the outputs are those of the all-fp32 scan, given |a_s - exact_s| <= tau:
+//   * an unmarked sample has |a_s| > tau, so its sign is the exact one; marked samples are exact.  Hence `first` - and
+//     the first pass's "a head sample is negative" - is the fp32 scan's, and v_first, v_lo (rules 2, 3) are exact values;
+//   * arg-min over the patched row: an unmarked sample has a_s > m + 2 tau, so its exact value is > m + tau, while the
+//     sample that attains m is marked and its exact value is <= m + tau: an unmarked sample never wins.  Every exact
+//     minimiser has a_s <= m + 2 tau, so it is marked and carries its exact value; ties resolve by first index as before;
+//   * the non-finite counter is unchanged under the ASSUMPTION that a sample whose fp32 value is non-finite is non-finite
+//     in f16x2 too (fp16 overflows first): such a sample is marked and patched with its fp32 value.
+// |a - exact| <= tau is monitored, not assumed: guard_patch_kernel sees both values of every refined sample; a deviation
+// above kGuardTrip = tau / 4 sets the workspace's sticky word, and from then on (the following launches of that call
+// included) every sample is marked, i.e. the scans are all-fp32.  The tripping call itself is still exact (tau/4 < tau).
+//
+// A launch of fewer than min_live points ran on the exact kernel already (the small-tile launch of coarse()): nothing is
+// marked for it.  val(s) / slot(s): value and index in vals of the row's sample s; own(s): s was evaluated by this launch,
+// own_approx / other_approx: this launch / the row's other launch was an approximate one.
+template <class V, class S, class O>
+__device__ __forceinline__ void guard_mark_row(const TraceArgs &a, int n, bool signs, bool min_rule, bool true_obj,
+                                               bool all, bool own_approx, bool other_approx, int c_ref, V val, S slot,
+                                               O own) {
+    const float tau = kGuardTau;
+    const int kNone = 1 << 30;
+    auto unc = [&](float x) { return !isfinite(x) || fabsf(x) <= tau; };
+    int c = kNone;
+    float m = INFINITY;
+    for (int s = 0; s < n; ++s) {
+        const float x = val(s);
+        if (signs && c == kNone && x < -tau) c = s;
+        if (isfinite(x) && x < m) m = x;
+    }
+    const bool use_min = min_rule && (!signs || !true_obj || c == kNone);
+    const float lim = m + 2.0f * tau;
+    // x = a_s, xn = a_next with next = s + 1 (0 behind the last sample)
+    auto marked = [&](int s, float x, float xn) -> bool {
+        if (!(own(s) ? own_approx : other_approx)) return false;     // an exact launch's value: nothing to refine
+        if (all && own(s)) return true;
+        if (!isfinite(x)) return true;
+        if (use_min && x <= lim) return true;
+        if (!signs) return false;
+        if (fabsf(x) <= tau || s == c) return true;
+        const int nx = s + 1 == n ? 0 : s + 1;
+        return nx <= c && (nx == c || unc(xn));
+    };
+    int n_mark = 0;
+    float x = val(0);
+    for (int s = 0; s < n; ++s) {
+        const float xn = val(s + 1 == n ? 0 : s + 1);
+        n_mark += marked(s, x, xn) ? 1 : 0;
+        x = xn;
+    }
+    if (n_mark == 0) return;
+    int64_t k = atomicAdd(a.w.cnt + c_ref, n_mark);
+    x = val(0);
+    for (int s = 0; s < n; ++s) {
+        const float xn = val(s + 1 == n ? 0 : s + 1);
+        if (marked(s, x, xn)) {
+            const int64_t o = slot(s);
+            a.w.ref_slot[k] = (int32_t)o;
+            a.w.ref_pts[k * 3] = a.w.pts[o * 3]; a.w.ref_pts[k * 3 + 1] = a.w.pts[o * 3 + 1];
+            a.w.ref_pts[k * 3 + 2] = a.w.pts[o * 3 + 2];
+            ++k;
+        }
+        x = xn;
+    }
+}
+
+// pass 1: the sampler's first (or only) pass; pass 2: the lazy sampler's second pass.  c_live, c_live2: counters of the
+// launches that evaluated the row's samples (pass 2 reads first-pass samples too: rule 4 is left to it; -1: none).
+__global__ __launch_bounds__(kTB) void guard_select_sampler_kernel(TraceArgs a, int pass, int c_live, int c_live2,
+                                                                   int64_t min_live, int c_ref) {
+    const int64_t m = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    const TraceWs &w = a.w;
+    if (m >= w.cnt[C_NSAMP]) return;
+    const bool approx = w.cnt[c_live] >= min_live, approx2 = c_live2 >= 0 && w.cnt[c_live2] >= min_live;
+    if (!approx && !approx2) return;
+    const bool all = *w.guard == kGuardTripped;
+    const bool true_obj = a.obj[w.list_samp[m]] != 0;
+    const int n = a.n_steps, head = a.head;
+    if (pass == 1) {
+        const int row = head > 0 ? head + 1 : n;
+        const int64_t base = m * row;
+        guard_mark_row(a, row, true, head == 0, true_obj, all, true, false, c_ref, [&](int s) { return w.vals[base + s]; },
+                       [&](int s) { return base + s; }, [](int) { return true; });
+        return;
+    }
+    const int32_t tq = w.tail_slot[m];
+    if (tq < 0) return;     // resolved by the head samples
+    const int64_t b_head = m * (head + 1), b_tail = a.tail_off + (int64_t)tq * (n - head - 1) - head;
+    auto slot = [&](int s) -> int64_t { return s < head ? b_head + s : (s == n - 1 ? b_head + head : b_tail + s); };
+    guard_mark_row(a, n, true, true, true_obj, all, approx, approx2, c_ref, [&](int s) { return w.vals[slot(s)]; }, slot,
+                   [&](int s) { return s >= head && s != n - 1; });
+}
+
+__global__ __launch_bounds__(kTB) void guard_select_closest_kernel(TraceArgs a, int c_live, int64_t min_live, int c_ref) {
+    const int64_t m = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    const TraceWs &w = a.w;
+    if (m >= w.cnt[C_NSEL] || w.cnt[c_live] < min_live) return;
+    const int n = a.n_steps;
+    const int64_t base = (a.sel_off >= 0 ? a.sel_off : (int64_t)w.cnt[a.head > 0 ? C_HEAD_PTS : C_NSAMP_PTS]) + m * n;
+    guard_mark_row(a, n, false, true, false, *w.guard == kGuardTripped, true, false, c_ref,
+                   [&](int s) { return w.vals[base + s]; },
+                   [&](int s) { return base + s; }, [](int) { return true; });
+}
+
+// exact values over the approximate ones; the monitor (statistics slots 14, 15 and the sticky word)
+__global__ __launch_bounds__(kTB) void guard_patch_kernel(TraceArgs a, int c_ref) {
+    const int64_t k = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    const TraceWs &w = a.w;
+    const int32_t n_ref = w.cnt[c_ref];
+    if (k == 0 && n_ref > 0) atomicAdd(w.cnt + C_GUARD_REFINED, n_ref);
+    if (k >= n_ref) return;
+    const int64_t o = w.ref_slot[k];
+    const float e = w.ref_vals[k], ap = w.vals[o];
+    if (isfinite(e) && isfinite(ap)) {
+        const float d = fabsf(ap - e);
+        if (d > 0.0f) atomicMax(w.cnt + C_GUARD_MAXDEV, __float_as_int(d));   // (non-negative floats order as their bits)
+        if (d > kGuardTrip) *w.guard = kGuardTripped;
+    }
+    w.vals[o] = e;
+}
+
+// HM_TRACE_GUARD_NOISE (tests): worst-case errors of the approximate values of one launch.  nan_k > 0: every nan_k-th
+// slot becomes NaN or +Inf in turn; otherwise a pseudo-random offset in [-amp, amp], a function of the slot index.
+__global__ __launch_bounds__(kTB) void guard_noise_kernel(float *vals, int64_t off, const int32_t *n_live, int64_t min_live,
+                                                          float amp, int nan_k) {
+    const int64_t g = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    const int64_t n = *n_live;
+    if (n < min_live || g >= n) return;
+    const int64_t o = off + g;
+    if (nan_k > 0) {
+        if (o % nan_k == 0) vals[o] = ((o / nan_k) & 1) ? INFINITY : NAN;
+        return;
+    }
+    uint32_t h = (uint32_t)o * 2654435761u;
+    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+    const float u = (float)(h >> 8) * (2.0f / 16777216.0f) - 1.0f;     // [-1, 1)
+    vals[o] = __fadd_rn(vals[o], __fmul_rn(amp, u));
+}
+
 __global__ void count_evals_kernel(int32_t *cnt, int rounds, int n_secant) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int64_t tot = 0;
@@ -310,14 +468,16 @@ __global__ void count_evals_kernel(int32_t *cnt, int rounds, int n_secant) {
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct Layout {
-    size_t off_f, off_i, off_b, off_pts, off_vals, off_cnt, off_emb, total;
+    size_t off_f, off_i, off_b, off_pts, off_vals, off_cnt, off_emb, off_ref, total;
     int64_t cap;   // points of one SDF launch; pts / vals hold two such regions (the lazy sampler's second pass)
 };
 
-Layout make_layout(int64_t n, int n_steps, int emb_width = 0) {
+constexpr size_t kWsHeader = 256;   // the guard's sticky word: at the same place for every ray count
+
+Layout make_layout(int64_t n, int n_steps, int emb_width = 0, bool guard = false) {
     Layout L;
     L.cap = n * (n_steps > 2 ? n_steps : 2);
-    size_t o = 0;
+    size_t o = kWsHeader;
     L.off_f = o; o = align_up(o + sizeof(float) * 13 * (size_t)n, 256);
     L.off_i = o; o = align_up(o + sizeof(int32_t) * 6 * (size_t)n, 256);
     L.off_b = o; o = align_up(o + 6 * (size_t)n, 256);
@@ -325,6 +485,9 @@ Layout make_layout(int64_t n, int n_steps, int emb_width = 0) {
     L.off_vals = o; o = align_up(o + sizeof(float) * 3 * (size_t)L.cap, 256);
     L.off_cnt = o; o = align_up(o + sizeof(int32_t) * C_COUNT, 256);
     L.off_emb = o; o = align_up(o + sizeof(float) * (size_t)emb_width * (size_t)L.cap, 256);   // (filter-bank embedders)
+    // guarded coarse scans: refinement region for every coarse point of a launch (a tripped guard refines them all):
+    // points [cap,3], exact values [cap], slots [cap]
+    L.off_ref = o; o = align_up(o + (guard ? sizeof(float) * 5 * (size_t)L.cap : 0), 256);
     L.total = o;
     return L;
 }
@@ -335,7 +498,21 @@ extern "C" {
 
 int64_t hm_trace_workspace_bytes(int64_t n_rays, const hm_trace_cfg *cfg) {
     if (n_rays < 0 || !cfg || cfg->n_steps < 1) return hm_fail(HM_ERR_INVALID, "hm_trace_workspace_bytes: bad argument");
-    return (int64_t)make_layout(n_rays, cfg->n_steps).total;
+    return (int64_t)make_layout(n_rays, cfg->n_steps, 0, cfg->coarse_bf16 == 3).total;
+}
+
+int hm_trace_guard_clear(void *workspace, int64_t workspace_bytes, void *stream) {
+    HM_CHECK_ARG(workspace && workspace_bytes >= (int64_t)kWsHeader, "hm_trace_guard_clear: no workspace");
+    hm_zero_u32_async(reinterpret_cast<int32_t *>(workspace), kWsHeader / sizeof(int32_t), as_stream(stream));
+    HM_CHECK_LAUNCH("hm_trace_guard_clear");
+    return HM_OK;
+}
+
+int hm_trace_guard_tolerances(float *tau, float *tau_trip) {
+    HM_CHECK_ARG(tau && tau_trip, "hm_trace_guard_tolerances: NULL pointer");
+    *tau = kGuardTau;
+    *tau_trip = kGuardTrip;
+    return HM_OK;
 }
 
 int64_t hm_trace_workspace_bytes_nffb(int64_t n_rays, const hm_trace_cfg *cfg, int n_levels) {
@@ -396,8 +573,12 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
                      out_points && out_net_mask && out_dists && workspace,
                  "hm_trace_forward: NULL pointer");
     HM_CHECK_ARG(!cfg->training || steps_u, "hm_trace_forward: training mode needs steps_u");
+    HM_CHECK_ARG(cfg->coarse_bf16 >= 0 && cfg->coarse_bf16 <= 3, "hm_trace_forward: coarse_bf16 must be 0, 1, 2 or 3");
+    const bool guard = cfg->coarse_bf16 == 3;
+    HM_CHECK_ARG(!guard || !nffb, "hm_trace_forward: the guarded coarse scans do not cover filter-bank embedders");
+    HM_CHECK_ARG(!guard || 3 * n_rays * (int64_t)cfg->n_steps < (1ll << 31), "hm_trace_forward: too many rays for one call");
     const int emb_width = nffb ? 3 + 8 + 8 * nffb->n_levels : 0;
-    const Layout L = make_layout(n_rays, cfg->n_steps, emb_width);
+    const Layout L = make_layout(n_rays, cfg->n_steps, emb_width, guard);
     HM_CHECK_ARG(workspace_bytes >= (int64_t)L.total, "hm_trace_forward: workspace too small");
     hipStream_t st = as_stream(stream);
     char *base = static_cast<char *>(workspace);
@@ -417,6 +598,10 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     a.w.vals = reinterpret_cast<float *>(base + L.off_vals);
     a.w.cnt = reinterpret_cast<int32_t *>(base + L.off_cnt);
     a.w.cap = L.cap;
+    a.w.ref_pts = reinterpret_cast<float *>(base + L.off_ref);
+    a.w.ref_vals = a.w.ref_pts + 3 * (size_t)L.cap;
+    a.w.ref_slot = reinterpret_cast<int32_t *>(a.w.ref_vals + (size_t)L.cap);
+    a.w.guard = reinterpret_cast<int32_t *>(base);
     a.cam = cam_loc; a.dirs = ray_dirs; a.obj = object_mask; a.t_sphere = t_sphere; a.hit = hit_mask;
     a.fracs = sampler_fracs; a.steps_u = steps_u;
     a.out_pts = out_points; a.out_mask = out_net_mask; a.out_t = out_dists;
@@ -433,9 +618,14 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     // launch and the secant runs behind it on a few dozen workgroups (A/B).
     const char *e_ov = getenv("HM_TRACE_OVERLAP");      // (read per call: the tests compare both forms in one process)
     const bool overlap_ok = !(e_ov && atoi(e_ov) == 0);
-    const bool overlap = overlap_ok && cfg->training && !nffb && !cfg->coarse_bf16 && tile_points == 0 &&
-                         cfg->n_secant_steps > 0 && n_rays <= kSdfSmall;
-    a.sel_off = overlap ? 2 * L.cap : -1;
+    const bool overlap_shape = overlap_ok && cfg->training && !nffb && tile_points == 0 && cfg->n_secant_steps > 0 &&
+                               n_rays <= kSdfSmall;
+    const bool overlap = overlap_shape && !cfg->coarse_bf16;
+    // Guarded scans take the values of the exact scan they stand for, and which fp32 tile body that scan runs on follows
+    // the live count of ITS launch: where the exact mode scans the closest-approach rows in a launch of their own, the
+    // guarded mode evaluates them by their own count too (and the secant picks its tiles by the rule of that launch).
+    const bool sel_own = overlap || (guard && overlap_shape);
+    a.sel_off = sel_own ? 2 * L.cap : -1;
 
     hm_zero_u32_async(a.w.cnt, C_COUNT, st);
     const unsigned g_rays = (unsigned)((n_rays + kTB - 1) / kTB);
@@ -475,14 +665,40 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
                 rc = cfg->coarse_bf16 == 2
                          ? hm_sdf_fwd_emb_split(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, stream)
                          : hm_sdf_fwd_emb_bf16(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, stream);
+        } else if (guard && tile_points != 0) {   // fixed tile size: every count is approximated (and refined on that tile)
+            rc = hm_sdf_fwd_split(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, 1, stream);
         } else {
             rc = hm_sdf_fwd(desc, mlp, p, capacity, table, B_fourier, v, 1, 1, frac_mode, -1, n_dev, 0, stream);
             if (rc == HM_OK)
-                rc = cfg->coarse_bf16 == 2
+                rc = cfg->coarse_bf16 >= 2
                          ? hm_sdf_fwd_split(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, run_min, stream)
                          : hm_sdf_fwd_bf16(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, run_min, stream);
         }
         return rc;
+    };
+    // Guarded mode, behind the approximate launch(es) of a coarse evaluation: [test noise] -> select -> one exact launch
+    // over the compact refinement region -> patch.  The exact launch runs the tile body the exact mode's launch of the
+    // same live count runs: the 64-point one with the tile size left to the library (smaller launches were exact already
+    // and mark nothing: guard_min), the caller's otherwise.
+    const int64_t guard_min = tile_points == 0 ? kSdfSmall + 1 : 1;
+    float noise_amp = 0.0f;
+    int noise_nan = 0;
+    if (guard) {   // HM_TRACE_GUARD_NOISE = f (0 < f < 1) | nan:K  (tests; read per call)
+        const char *e = getenv("HM_TRACE_GUARD_NOISE");
+        if (e && strncmp(e, "nan:", 4) == 0) noise_nan = atoi(e + 4) > 0 ? atoi(e + 4) : 0;
+        else if (e) { const double f_ = atof(e); if (f_ > 0.0 && f_ < 1.0) noise_amp = (float)(f_ * kGuardTau); }
+    }
+    auto guard_noise = [&](int64_t off, int64_t capacity, int c_live) {
+        if (noise_amp > 0.0f || noise_nan > 0)
+            hipLaunchKernelGGL(guard_noise_kernel, dim3((unsigned)((capacity + kTB - 1) / kTB)), dim3(kTB), 0, st, a.w.vals,
+                               off, a.w.cnt + c_live, guard_min, noise_amp, noise_nan);
+    };
+    auto guard_refine = [&](int c_ref) -> int {
+        const int rc = hm_sdf_fwd(desc, mlp, a.w.ref_pts, L.cap, table, B_fourier, a.w.ref_vals, 1, 1, frac_mode,
+                                  tile_points == 0 ? 64 : tile_points, a.w.cnt + c_ref, 0, stream);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(guard_patch_kernel, dim3((unsigned)((L.cap + kTB - 1) / kTB)), dim3(kTB), 0, st, a, c_ref);
+        return HM_OK;
     };
 
     // ---- 1. bidirectional sphere tracing: one state-machine round per SDF launch -------------------
@@ -525,7 +741,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
                        a.w.list_samp, (int)C_NSAMP, c_first, a.w.t_s, a.w.t_e, sampler_fracs, -1, per_ray);
     if (cfg->training)
         hipLaunchKernelGGL(ray_samples_kernel, dim3(g_samp), dim3(kTB), 0, st, a, a.w.list_sel, (int)C_NSEL,
-                           (int)C_NSEL_PTS, a.w.t_min, a.w.t_max, steps_u, overlap ? -2 : c_first, cfg->n_steps);
+                           (int)C_NSEL_PTS, a.w.t_min, a.w.t_max, steps_u, sel_own ? -2 : c_first, cfg->n_steps);
     int grid_p1 = 0, grid_p2 = 0;      // overlap: grids of the sampler launches that took filler tiles of the scan
     if (overlap) {
         // the sampler's points only - the closest-approach scan runs with the secant refinement below, except for the
@@ -535,8 +751,22 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
                                  nullptr, 0, &grid_p1, stream);
         if (rc != HM_OK) return rc;
     } else {
-        int rc = coarse(0, n_rays * cfg->n_steps, a.w.cnt + C_BIG_PTS);
+        // (guarded, closest-approach rows in their own region: two launches, each by its own count)
+        const int c_samp = sel_own ? c_first : (int)C_BIG_PTS, c_sel = sel_own ? (int)C_NSEL_PTS : (int)C_BIG_PTS;
+        int rc = coarse(0, n_rays * cfg->n_steps, a.w.cnt + c_samp);
+        if (rc == HM_OK && sel_own) rc = coarse(a.sel_off, n_rays * cfg->n_steps, a.w.cnt + c_sel);
         if (rc != HM_OK) return rc;
+        if (guard) {
+            guard_noise(0, n_rays * cfg->n_steps, c_samp);
+            if (sel_own) guard_noise(a.sel_off, n_rays * cfg->n_steps, c_sel);
+            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rays), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
+                               (int)C_GUARD_N1);
+            if (cfg->training)
+                hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rays), dim3(kTB), 0, st, a, c_sel, guard_min,
+                                   (int)C_GUARD_N1);
+            rc = guard_refine((int)C_GUARD_N1);
+            if (rc != HM_OK) return rc;
+        }
     }
     if (cfg->training && !overlap) hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
     if (a.head > 0) {   // second pass: the remaining samples of the rays the head samples did not resolve
@@ -548,6 +778,13 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
                                            a.w.cnt + c_first, grid_p1, &grid_p2, stream)
                          : coarse(a.tail_off, n_rays * (cfg->n_steps - a.head - 1), a.w.cnt + C_TAIL_PTS);
         if (rc != HM_OK) return rc;
+        if (guard) {
+            guard_noise(a.tail_off, n_rays * (cfg->n_steps - a.head - 1), (int)C_TAIL_PTS);
+            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rays), dim3(kTB), 0, st, a, 2, (int)C_TAIL_PTS,
+                               sel_own ? c_first : (int)C_BIG_PTS, guard_min, (int)C_GUARD_N2);
+            rc = guard_refine((int)C_GUARD_N2);
+            if (rc != HM_OK) return rc;
+        }
     }
     hipLaunchKernelGGL(sampler_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
     if (cfg->n_secant_steps > 0) {
@@ -564,7 +801,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
         } else if (!nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
             (tile_points != 0 || n_rays <= kSdfSmall)) {
             const int rc = hm_trace_secant_persistent(desc, mlp, table, B_fourier, frac_mode, tile_points, &a,
-                                                      cfg->n_secant_steps, stream);
+                                                      cfg->n_secant_steps, sel_own ? 1 : 0, stream);
             if (rc != HM_OK) return rc;
         } else {
             for (int s = 0; s < cfg->n_secant_steps; ++s) {

@@ -23,8 +23,27 @@ enum : int32_t {  // counters (device int32 array)
     C_HEAD_PTS = 75,     // points of the sampler's first pass (= where the closest-approach values start)
     C_TAIL_PTS = 76,     // lazy sampler: points of the second pass
     C_TILE_CURSOR = 77,  // sdf_scan_secant_kernel: next 64-point tile of the closest-approach scan (zero at launch)
-    C_COUNT = 80
+    C_GUARD_REFINED = 78,  // guarded coarse scans: samples re-evaluated in exact fp32 (statistics slot 14)
+    C_GUARD_MAXDEV = 79,   // ... largest finite |approximate - exact| among them, as float bits (statistics slot 15)
+    C_GUARD_N1 = 80,     // ... points of the first refinement launch (sampler's first pass + closest approach)
+    C_GUARD_N2 = 81,     // ... points of the second one (lazy sampler's second pass)
+    C_COUNT = 96
 };
+
+// Guard width of the guarded coarse scans (hm_trace_cfg.coarse_bf16 = 3, see guard_select_sampler_kernel in hm_trace.hip).
+// D = largest |f16x2 kernel - fp32 kernel| measured on the device over 2^20 uniform points of the cube plus 2e5 - 5e5
+// points within 1e-3 of the surface along the fixtures' rays, per network, against the 64- and the 16-point fp32 tile
+// (tests/golden/guard_tolerances.json):
+//   raytrace_init 4.77e-7, raytrace_bumpy 4.47e-7, raytrace_C2 5.96e-7, bench C2 4.47e-7, bench C4 5.36e-7
+// tau = smallest power of two >= 16 D = 9.54e-6, i.e. 2^-16; the monitor trips at tau / 4 = 2^-18 = 3.8e-6, which is
+// 6.4 D, above every measured error, and 4x below what the exactness argument needs.
+constexpr float kGuardTau = 1.52587890625e-05f;    // 2^-16
+constexpr float kGuardTrip = kGuardTau * 0.25f;
+constexpr int32_t kGuardTripped = 0x47554152;      // value of the workspace's sticky word once the monitor has tripped
+
+// closest-approach scans of at least this many points hide a chain of 16-point secant tiles (sdf_scan_secant_kernel:
+// 8 x 131 us ~ 2.3 rounds of 64-point tiles: 3 rounds of 256 workgroups)
+constexpr int64_t kTraceScanHide = 3 * 256 * 64;
 
 enum : uint8_t { ST_WAIT_FIRST = 1, ST_WAIT_MARCH = 2, ST_WAIT_LS = 3, ST_DONE = 4 };
 
@@ -38,6 +57,12 @@ struct TraceWs {
     float *vals;   // [cap]
     int32_t *cnt;  // [C_COUNT]
     int64_t cap;
+    // guarded coarse scans: the compact refinement region (points, their exact values, their slots in vals) and the
+    // sticky word at the start of the workspace (kGuardTripped once the monitor has tripped; not zeroed per call)
+    float *ref_pts;     // [cap,3]
+    float *ref_vals;    // [cap]
+    int32_t *ref_slot;  // [cap]
+    int32_t *guard;
 };
 
 struct TraceArgs {

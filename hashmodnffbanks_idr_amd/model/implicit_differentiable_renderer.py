@@ -123,14 +123,31 @@ class ImplicitNetwork(nn.Module):
         # lo fp16, 22 significant bits: error below the rounding noise of an fp32 accumulation).  Takes precedence over
         # bf16_coarse_search.  Off by default, like it.
         self.coarse_split = None
+        # The exact-fp32 mode (neither switch above) evaluates the coarse scans on the f16x2 split kernel behind an fp32
+        # guard: the samples whose approximate value cannot settle what the search reads from a row are re-evaluated by
+        # the exact-fp32 kernel before the rows are reduced, so every value that reaches an output was computed in exact
+        # fp32 and the tracer's outputs are bit-identical to all-fp32 scans (csrc/hm_trace.hip:
+        # guard_select_sampler_kernel).  False: all-fp32 scans.  Hash-grid networks; filter-bank networks keep all-fp32
+        # scans.
+        self.guarded_coarse_scans = True
+
+    def _split_kind(self):
+        """kind of the split operand images the packed weights carry: the chosen one, or f16x2 for the guarded scans"""
+        if self.coarse_split is not None:
+            return self.coarse_split
+        guarded = self.guarded_coarse_scans and not self.bf16_coarse_search and self._hash_embedder() is not None
+        return "f16x2" if guarded else None
 
     def coarse_mode(self):
-        """hm_trace_cfg.coarse_bf16 value of this network: 0 exact fp32, 1 bf16, 2 split operands.  A 16-bit mode is
-        used only where its kernel accepts the network (hm_sdf_net_fits); the coarse scans stay exact fp32 otherwise."""
+        """hm_trace_cfg.coarse_bf16 value of this network: 0 exact fp32, 1 bf16, 2 split operands, 3 f16x2 behind the
+        fp32 guard (no 16-bit mode chosen, guarded_coarse_scans on).  A mode is used only where its kernel accepts the
+        network (hm_sdf_net_fits); the coarse scans stay all-fp32 otherwise."""
         if self.coarse_split is not None:
             return 2 if self.packed_weights().fits(ops.SDF_SPLIT) else 0
         if self.bf16_coarse_search:
             return 1 if self.packed_weights().fits(ops.SDF_BF16) else 0
+        if self._split_kind() is not None:
+            return 3 if self.packed_weights().fits(ops.SDF_SPLIT) else 0
         return 0
 
     def __getstate__(self):  # the packed-weight cache holds raw device pointers: never copied / pickled
@@ -178,7 +195,7 @@ class ImplicitNetwork(nn.Module):
         # _lib.param_epoch(), which is part of the key
         key = (_lib.param_epoch(),) + tuple((p.data_ptr(), p._version) for p in ps)
         if self._packed is None or key != self._packed_key or self._force_repack or \
-                self._packed.has_bf16 != bool(self.bf16_coarse_search) or self._packed.split != self.coarse_split:
+                self._packed.has_bf16 != bool(self.bf16_coarse_search) or self._packed.split != self._split_kind():
             self._force_repack = False
             with torch.no_grad():
                 fc = self._fold_cache or {}      # this forward's folds (made with grad enabled): reuse their values
@@ -189,9 +206,9 @@ class ImplicitNetwork(nn.Module):
                     Ws.append(w.detach() if w is not None else _folded_weight(lin))
                 bs = [getattr(self, "lin" + str(l)).bias for l in range(self.num_layers - 1)]
                 if self._packed is None or self._packed.bufs[0][0].device != Ws[0].device or \
-                        self._packed.has_bf16 != bool(self.bf16_coarse_search) or self._packed.split != self.coarse_split:
+                        self._packed.has_bf16 != bool(self.bf16_coarse_search) or self._packed.split != self._split_kind():
                     self._packed = ops.PackedSdf(Ws, bs, self.dims[0], self.skip_in, self._beta_value(),
-                                                 with_bf16=bool(self.bf16_coarse_search), split=self.coarse_split)
+                                                 with_bf16=bool(self.bf16_coarse_search), split=self._split_kind())
                 else:
                     self._packed.update(Ws, bs, self._beta_value())
             self._packed_key = key

@@ -44,6 +44,7 @@ class RayTracing(nn.Module):
         self.sampler_head = 16
         self._stats = {}
         self._stats_dev = None
+        self._guard_word = None     # int32 view of the workspace's sticky guard word
         self._ws = _lib.Workspace("ray tracer")     # per module: it carries counters across the tracer's own launches
 
     @property
@@ -54,8 +55,20 @@ class RayTracing(nn.Module):
             # (the device tensor is kept: inside a captured graph it is refreshed by every replay)
             self._stats = {"rays": self._stats.get("rays"), "sampler_rays": v[0], "secant_rays": v[2],
                            "mask_loss_rays": v[3], "sdf_evals": v[6], "unfinished": v[7], "nonfinite": v[8],
-                           "sampler_points": v[1], "sampler_second_pass_rays": v[10]}
+                           "sampler_points": v[1], "sampler_second_pass_rays": v[10],
+                           # guarded coarse scans (ImplicitNetwork.guarded_coarse_scans): samples re-evaluated in exact
+                           # fp32, the largest |f16x2 - fp32| among them, and whether that ever exceeded the trip
+                           # threshold - from then on every coarse sample is re-evaluated (clear_guard() re-arms)
+                           "guard_refined": v[14],
+                           "guard_max_dev": float(torch.tensor(v[15], dtype=torch.int32).view(torch.float32)),
+                           "guard_tripped": self._guard_word is not None and
+                           int(self._guard_word.item()) == ops.TRACE_GUARD_TRIPPED}
         return self._stats
+
+    def clear_guard(self):
+        """re-arm the guard of the coarse scans after its monitor has tripped (last_stats['guard_tripped'])"""
+        if self._guard_word is not None:
+            self._guard_word.zero_()
 
     def _fused_network(self, sdf, ray_directions):
         net = getattr(sdf, "__self__", None)
@@ -83,6 +96,13 @@ class RayTracing(nn.Module):
                                 int(self.sampler_head))
             nf = net._nffb_embedder() if net._hash_embedder() is None else None
             ws = self._ws.get(dev, ops.trace_workspace_bytes(N, cfg, nf.n_levels if nf is not None else 0))
+            if self._guard_word is None or self._guard_word.data_ptr() != ws.data_ptr():
+                # a fresh buffer: its header (the guard's sticky word) starts cleared, or with the outgrown buffer's word
+                ops.trace_guard_clear(ws)
+                word = ws[:4].view(torch.int32)
+                if self._guard_word is not None and self._guard_word.device == ws.device:
+                    word.copy_(self._guard_word)
+                self._guard_word = word
             steps_u = None
             if self.training:
                 if self.steps_override is not None:

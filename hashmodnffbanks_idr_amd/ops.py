@@ -872,6 +872,22 @@ def trace_workspace_bytes(n_rays, cfg, nffb_levels=0):
     return check(lib().hm_trace_workspace_bytes(int(n_rays), C.byref(cfg)))
 
 
+def trace_guard_clear(workspace):
+    """zeroes the tracer workspace's persistent header: the sticky word of the guarded coarse scans (no host sync)"""
+    require_gpu(workspace)
+    check(lib().hm_trace_guard_clear(dptr(workspace), workspace.numel(), stream_ptr(workspace)))
+
+
+def trace_guard_tolerances():
+    """(tau, tau_trip) of the guarded coarse scans (csrc/hm_trace_dev.h: kGuardTau, kGuardTrip)"""
+    tau, trip = C.c_float(), C.c_float()
+    check(lib().hm_trace_guard_tolerances(C.byref(tau), C.byref(trip)))
+    return tau.value, trip.value
+
+
+TRACE_GUARD_TRIPPED = 0x47554152    # the sticky word's value once the guard's monitor has tripped (kGuardTripped)
+
+
 def camera_rays(uv, pose, intrinsics, radius):
     """(ray_dirs [B,N,3], cam_loc [B,3], t_sphere [B,N,2], hit [B,N] bool) of fixed 4x4 cameras in one launch
     (hm_camera_rays: rend_util.get_camera_params + get_sphere_intersection; no gradient)."""

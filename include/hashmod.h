@@ -375,7 +375,17 @@ typedef struct hm_trace_cfg {
     int32_t n_secant_steps;
     int32_t training;
     int32_t coarse_bf16;           /* precision of the sampler / closest-approach scans: 0 exact fp32, 1 hm_sdf_fwd_bf16 (needs
-                                      w_packed_bf16), 2 hm_sdf_fwd_split (needs w_packed_split; kind = mlp->split_kind);
+                                      w_packed_bf16), 2 hm_sdf_fwd_split (needs w_packed_split; kind = mlp->split_kind),
+                                      3 f16x2 behind an fp32 guard (needs the f16x2 w_packed_split; hash-grid networks):
+                                      the rows are evaluated as in mode 2, the samples whose approximate value cannot
+                                      settle what the search reads from a row (sign pattern up to the first negative
+                                      sample, its bracket, the arg-min) are re-evaluated by the exact-fp32 kernel and
+                                      written back before the rows are reduced - every output and counter is that of
+                                      mode 0, bit for bit (hm_trace.hip: guard_select_sampler_kernel).  Statistics slot 14
+                                      = samples re-evaluated, 15 = float bits of the largest |approximate - exact| met;
+                                      above tau / 4 a sticky word in the workspace makes this and later calls re-evaluate
+                                      every sample (hm_trace_guard_clear resets it).  HM_TRACE_GUARD_NOISE = f | nan:K
+                                      (tests) perturbs the approximate values by up to f * tau / makes every K-th NaN, +Inf;
                                       sphere tracing and the secant refinement stay on the exact-fp32 kernels */
     int32_t sampler_head;          /* lazy sampler.  ray_sampler (ray_tracing.py:189-249) evaluates n_steps samples per
                                       unconverged ray but reads only those up to the FIRST negative one (:212-218, and
@@ -387,6 +397,10 @@ typedef struct hm_trace_cfg {
 } hm_trace_cfg;
 
 HM_API int64_t hm_trace_workspace_bytes(int64_t n_rays, const hm_trace_cfg *cfg);
+/* The first 256 bytes of a tracer workspace outlive the calls (the guard's sticky word): zero them once after allocating
+ * the workspace, and to re-arm a tripped guard.  hm_trace_guard_tolerances: the guard width tau and the trip threshold. */
+HM_API int hm_trace_guard_clear(void *workspace, int64_t workspace_bytes, void *stream);
+HM_API int hm_trace_guard_tolerances(float *tau, float *tau_trip);
 HM_API int hm_trace_forward(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
                             const float *B_fourier, int frac_mode, int tile_points, const hm_trace_cfg *cfg,
                             const float *cam_loc, const float *ray_dirs, const uint8_t *object_mask,
