@@ -334,19 +334,27 @@ __global__ __launch_bounds__(kTB) void closest_reduce_kernel(TraceArgs a) {
 // A launch of fewer than min_live points ran on the exact kernel already (the small-tile launch of coarse()): nothing is
 // marked for it.  val(s) / slot(s): value and index in vals of the row's sample s; own(s): s was evaluated by this launch,
 // own_approx / other_approx: this launch / the row's other launch was an approximate one.
+// One wave per row: lanes take samples lane, lane + 64, ... (coalesced), c and m come from wave reductions, every lane
+// applies the marking rule to its own samples, and the row's entries go behind ONE atomicAdd in ascending sample order
+// (ballot / prefix rank) - the set of marked slots of a row and their order are those of a serial walk over the row.
+constexpr int kGuardRows = kTB / 64;     // rows per workgroup
 template <class V, class S, class O>
-__device__ __forceinline__ void guard_mark_row(const TraceArgs &a, int n, bool signs, bool min_rule, bool true_obj,
-                                               bool all, bool own_approx, bool other_approx, int c_ref, V val, S slot,
-                                               O own) {
+__device__ __forceinline__ void guard_mark_row(const TraceArgs &a, int lane, int n, bool signs, bool min_rule,
+                                               bool true_obj, bool all, bool own_approx, bool other_approx, int c_ref,
+                                               V val, S slot, O own) {
     const float tau = kGuardTau;
     const int kNone = 1 << 30;
     auto unc = [&](float x) { return !isfinite(x) || fabsf(x) <= tau; };
     int c = kNone;
     float m = INFINITY;
-    for (int s = 0; s < n; ++s) {
+    for (int s = lane; s < n; s += 64) {
         const float x = val(s);
         if (signs && c == kNone && x < -tau) c = s;
         if (isfinite(x) && x < m) m = x;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        c = min(c, __shfl_xor(c, d));
+        m = fminf(m, __shfl_xor(m, d));
     }
     const bool use_min = min_rule && (!signs || !true_obj || c == kNone);
     const float lim = m + 2.0f * tau;
@@ -361,26 +369,25 @@ __device__ __forceinline__ void guard_mark_row(const TraceArgs &a, int n, bool s
         const int nx = s + 1 == n ? 0 : s + 1;
         return nx <= c && (nx == c || unc(xn));
     };
+    auto mark_of = [&](int s) -> bool { return s < n && marked(s, val(s), val(s + 1 == n ? 0 : s + 1)); };
     int n_mark = 0;
-    float x = val(0);
-    for (int s = 0; s < n; ++s) {
-        const float xn = val(s + 1 == n ? 0 : s + 1);
-        n_mark += marked(s, x, xn) ? 1 : 0;
-        x = xn;
-    }
+    for (int s0 = 0; s0 < n; s0 += 64) n_mark += __popcll(__ballot(mark_of(s0 + lane)));
     if (n_mark == 0) return;
-    int64_t k = atomicAdd(a.w.cnt + c_ref, n_mark);
-    x = val(0);
-    for (int s = 0; s < n; ++s) {
-        const float xn = val(s + 1 == n ? 0 : s + 1);
-        if (marked(s, x, xn)) {
+    int k0 = 0;
+    if (lane == 0) k0 = atomicAdd(a.w.cnt + c_ref, n_mark);
+    int64_t k = __shfl(k0, 0);
+    for (int s0 = 0; s0 < n; s0 += 64) {
+        const int s = s0 + lane;
+        const bool mk = mark_of(s);
+        const unsigned long long b = __ballot(mk);
+        if (mk) {
+            const int64_t kk = k + __popcll(b & ((1ull << lane) - 1ull));
             const int64_t o = slot(s);
-            a.w.ref_slot[k] = (int32_t)o;
-            a.w.ref_pts[k * 3] = a.w.pts[o * 3]; a.w.ref_pts[k * 3 + 1] = a.w.pts[o * 3 + 1];
-            a.w.ref_pts[k * 3 + 2] = a.w.pts[o * 3 + 2];
-            ++k;
+            a.w.ref_slot[kk] = (int32_t)o;
+            a.w.ref_pts[kk * 3] = a.w.pts[o * 3]; a.w.ref_pts[kk * 3 + 1] = a.w.pts[o * 3 + 1];
+            a.w.ref_pts[kk * 3 + 2] = a.w.pts[o * 3 + 2];
         }
-        x = xn;
+        k += __popcll(b);
     }
 }
 
@@ -388,7 +395,8 @@ __device__ __forceinline__ void guard_mark_row(const TraceArgs &a, int n, bool s
 // launches that evaluated the row's samples (pass 2 reads first-pass samples too: rule 4 is left to it; -1: none).
 __global__ __launch_bounds__(kTB) void guard_select_sampler_kernel(TraceArgs a, int pass, int c_live, int c_live2,
                                                                    int64_t min_live, int c_ref) {
-    const int64_t m = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    const int64_t m = (int64_t)blockIdx.x * kGuardRows + (threadIdx.x >> 6);     // (wave-uniform)
+    const int lane = threadIdx.x & 63;
     const TraceWs &w = a.w;
     if (m >= w.cnt[C_NSAMP]) return;
     const bool approx = w.cnt[c_live] >= min_live, approx2 = c_live2 >= 0 && w.cnt[c_live2] >= min_live;
@@ -399,25 +407,26 @@ __global__ __launch_bounds__(kTB) void guard_select_sampler_kernel(TraceArgs a, 
     if (pass == 1) {
         const int row = head > 0 ? head + 1 : n;
         const int64_t base = m * row;
-        guard_mark_row(a, row, true, head == 0, true_obj, all, true, false, c_ref, [&](int s) { return w.vals[base + s]; },
-                       [&](int s) { return base + s; }, [](int) { return true; });
+        guard_mark_row(a, lane, row, true, head == 0, true_obj, all, true, false, c_ref,
+                       [&](int s) { return w.vals[base + s]; }, [&](int s) { return base + s; }, [](int) { return true; });
         return;
     }
     const int32_t tq = w.tail_slot[m];
     if (tq < 0) return;     // resolved by the head samples
     const int64_t b_head = m * (head + 1), b_tail = a.tail_off + (int64_t)tq * (n - head - 1) - head;
     auto slot = [&](int s) -> int64_t { return s < head ? b_head + s : (s == n - 1 ? b_head + head : b_tail + s); };
-    guard_mark_row(a, n, true, true, true_obj, all, approx, approx2, c_ref, [&](int s) { return w.vals[slot(s)]; }, slot,
-                   [&](int s) { return s >= head && s != n - 1; });
+    guard_mark_row(a, lane, n, true, true, true_obj, all, approx, approx2, c_ref, [&](int s) { return w.vals[slot(s)]; },
+                   slot, [&](int s) { return s >= head && s != n - 1; });
 }
 
 __global__ __launch_bounds__(kTB) void guard_select_closest_kernel(TraceArgs a, int c_live, int64_t min_live, int c_ref) {
-    const int64_t m = (int64_t)blockIdx.x * kTB + threadIdx.x;
+    const int64_t m = (int64_t)blockIdx.x * kGuardRows + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
     const TraceWs &w = a.w;
     if (m >= w.cnt[C_NSEL] || w.cnt[c_live] < min_live) return;
     const int n = a.n_steps;
     const int64_t base = (a.sel_off >= 0 ? a.sel_off : (int64_t)w.cnt[a.head > 0 ? C_HEAD_PTS : C_NSAMP_PTS]) + m * n;
-    guard_mark_row(a, n, false, true, false, *w.guard == kGuardTripped, true, false, c_ref,
+    guard_mark_row(a, lane, n, false, true, false, *w.guard == kGuardTripped, true, false, c_ref,
                    [&](int s) { return w.vals[base + s]; },
                    [&](int s) { return base + s; }, [](int) { return true; });
 }
@@ -630,6 +639,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     hm_zero_u32_async(a.w.cnt, C_COUNT, st);
     const unsigned g_rays = (unsigned)((n_rays + kTB - 1) / kTB);
     const unsigned g_samp = (unsigned)((n_rays * cfg->n_steps + kTB - 1) / kTB);
+    const unsigned g_rows = (unsigned)((n_rays + kGuardRows - 1) / kGuardRows);   // guard select kernels: a wave per ray
 
     float *emb_ws = reinterpret_cast<float *>(base + L.off_emb);
     auto sdf = [&](int64_t capacity, const int32_t *n_dev) -> int {
@@ -759,10 +769,10 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
         if (guard) {
             guard_noise(0, n_rays * cfg->n_steps, c_samp);
             if (sel_own) guard_noise(a.sel_off, n_rays * cfg->n_steps, c_sel);
-            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rays), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
+            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
                                (int)C_GUARD_N1);
             if (cfg->training)
-                hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rays), dim3(kTB), 0, st, a, c_sel, guard_min,
+                hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, c_sel, guard_min,
                                    (int)C_GUARD_N1);
             rc = guard_refine((int)C_GUARD_N1);
             if (rc != HM_OK) return rc;
@@ -780,7 +790,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
         if (rc != HM_OK) return rc;
         if (guard) {
             guard_noise(a.tail_off, n_rays * (cfg->n_steps - a.head - 1), (int)C_TAIL_PTS);
-            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rays), dim3(kTB), 0, st, a, 2, (int)C_TAIL_PTS,
+            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 2, (int)C_TAIL_PTS,
                                sel_own ? c_first : (int)C_BIG_PTS, guard_min, (int)C_GUARD_N2);
             rc = guard_refine((int)C_GUARD_N2);
             if (rc != HM_OK) return rc;
