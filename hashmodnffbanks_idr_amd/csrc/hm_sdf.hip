@@ -21,7 +21,7 @@
 // 4-point tiles so that every call is ONE tile per CU; the tile size is chosen on the device from the live
 // point count (sdf_fwd_small_kernel -> sdf_small_body<Tile16 | Tile8<8> | Tile8<4>>).
 // The stages all tile bodies share - point load, weight stream (WeightRing), quad epilogue, embedding rescale, last-layer
-// finish, output rows, LDS layout (SdfLds) - are in hm_sdf_common.h; sdf64_run below is the 64-point body.
+// finish, output rows, LDS layout (SdfLds) - are in hm_sdf_common.h; sdf64_run (hm_sdf_tile64.h) is the 64-point body.
 #include "hm_common.h"
 
 #include <math.h>
@@ -31,11 +31,6 @@ namespace {
 
 #include "hm_sdf_common.h"
 #include "hm_trace_dev.h"   // the ray search's state machine, run by the persistent march kernel below
-
-// third value of the kernels' FRAC template parameter: `x` holds PRECOMPUTED embedding rows (hm_sdf_fwd_emb).  A template
-// value rather than a run-time branch on net.emb_stride: with both input paths in one kernel body the register
-// allocation of the hash-grid variant changed (178 -> 205 VGPRs, 33 -> 42 spilled SGPRs) and it lost 4 %.
-constexpr int kFracEmb = 2;
 
 #ifdef HM_SDF_PHASE_PROBE
 // scripts/sdf_phase_probe.py: cycle stamps of one tile's phases (workgroup 0, wave 0, second tile), never in the product build
@@ -62,292 +57,13 @@ __device__ unsigned long long hm_probe_ts[128];
 #define HM_PROBE_S(i_) do { } while (0)
 #endif
 
-constexpr int kPts = 64;        // points per workgroup tile
-constexpr int kThreadsSdf = 512;
-constexpr int kWaves = 8;
-constexpr int kGroupFloats = kPts * 4;  // floats per k-group row of X: [point][4]
+#include "hm_sdf_tile64.h"        // sdf64_run: the 64-point fp32 tile body
+#include "hm_sdf_split_tile.h"    // sdf_split_tile: the 64-point f16x2 / bf16x2 tile body (sdf_refine_scan_kernel)
 
-// dynamic LDS of the 64-point tile: X, the embedding (kept for the skip connection), 8 partial sums per point
-__host__ __device__ inline SdfLds sdf_lds64(const SdfNet &net) {
-    return sdf_lds(kPts, 1, net.x_groups * kGroupFloats, 1, net.emb_groups * kGroupFloats, kWaves);
-}
 // ... of the small tiles (pts = 16 or 8 points in the LDS image): two activation images + the embedding in whole
 // 16-blocks.  (The 8-point layout needs half of the 16-point one, which is what every launch asks for.)
 __host__ __device__ inline SdfLds sdf_lds_small(const SdfNet &net, int E, int pts) {
     return sdf_lds(pts, 2, net.x_groups * pts * 4, 1, (E + 15) / 16 * 4 * pts * 4, kWaves);
-}
-
-// Filler tiles.  A launch whose own points end in a partly filled last round can take the 64-point tiles that complete
-// the round from a SECOND point set that has to be evaluated anyway (the ray search: the closest-approach scan, whose
-// values nothing in the sampler's launches waits for).  Which of that set's tiles a launch takes follows from the
-// device-side counts alone, the same way in every launch of the chain: a launch with TA own tiles on G workgroups takes
-// pad = (G - TA mod G) mod G filler tiles if that many are still available and it runs on the 64-point kernel at all,
-// none otherwise (its remainder then follows the half-tile rule).
-struct SdfFill {               // resolved, per launch
-    const float *x;
-    float *out;
-    int64_t n;                 // points of the filler set
-    int64_t tile0;             // its first tile that is still free
-};
-struct SdfFillArgs {           // kernel argument (all zero: no filler)
-    const float *x;
-    float *out;
-    const int32_t *n_dev;      // device-side point count of the filler set
-    const int32_t *prev_dev;   // own-point count of the launch that took filler tiles before this one (or NULL)
-    int32_t prev_grid;
-    int32_t pad_;
-};
-
-__device__ __forceinline__ int64_t fill_quota(int64_t n_own, int64_t grid, int64_t avail, int64_t run_min) {
-    if (n_own < run_min || grid <= 0) return 0;
-    const int64_t ta = (n_own + 63) / 64;
-    const int64_t pad = (grid - ta % grid) % grid;
-    return (pad > 0 && avail >= pad) ? pad : 0;
-}
-
-// The 64-point tile loop of sdf_fwd_kernel / sdf_scan_secant_kernel.  DYN = false: the static schedule below
-// (tile = round * grid + workgroup); DYN = true: the SAME tiles in the same enumeration, handed out by an atomic cursor
-// (zero at launch) - workgroups that start late (they carried secant rays first) simply take fewer of them.
-template <int FRAC, bool DYN>
-__device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net, const float *__restrict__ x, int64_t n,
-                                          const float *__restrict__ table, const float *__restrict__ Bf,
-                                          float *__restrict__ out, int64_t out_stride, int out_cols, float *lds,
-                                          unsigned *cursor, const SdfFill &fb) {
-    __shared__ unsigned s_next_tile;
-    const SdfLds at = sdf_lds64(net);
-    float *X = lds;
-    float *EMB = lds + at.emb;
-    float *SX = lds + at.sx;     // [64][3] raw points
-    float *RED = lds + at.red;   // [8][64] cross-wave partial sums
-
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: the weight pointers below stay in SGPRs)
-    const int lane = tid & 63;
-    const int j = lane & 31;  // point within a 32-point tile / feature row within a 32-feature tile
-    const int h = lane >> 5;
-    const int E = lv.E;
-    // Tile schedule: `rounds` full rounds of 64-point tiles (tile = round * grid + workgroup), then ONE remainder tile
-    // per workgroup.  When the remainder fits 32 points per workgroup it is cut into 32-point HALF tiles (the MFMAs of
-    // the second point block are skipped), so the last round costs about half a round instead of a full one on part of
-    // the chip: 204 800 points on 256 CUs are 12 rounds + 256 half tiles instead of 13 rounds on 128 CUs.  A point's
-    // value does not depend on the tile it sits in (tests: permutation equivariance bit for bit).
-    const int64_t G = gridDim.x;
-    // filler tiles (static schedule only): TA own tiles, then tiles fb.tile0 .. of the second set up to the end of the round
-    const int64_t TA = (n + kPts - 1) / kPts;
-    const int64_t n_fill = DYN ? 0 : fill_quota(n, G, max((fb.n + kPts - 1) / kPts - fb.tile0, (int64_t)0), 0);
-    const int64_t rounds = n_fill > 0 ? (TA + n_fill) / G : (n / kPts) / G;
-    const int64_t rem_base = rounds * G * kPts;
-    const int64_t rem_step = (n - rem_base <= G * 32) ? 32 : kPts;
-
-    for (int64_t it = 0;; ++it) {
-        int64_t itr = it, wg = blockIdx.x;
-        if (DYN) {
-            __syncthreads();   // every thread has read the previous hand-out
-            if (tid == 0) s_next_tile = atomicAdd(cursor, 1u);
-            __syncthreads();
-            const int64_t u = s_next_tile;
-            itr = u / G;
-            wg = u - itr * G;
-        }
-        if (itr > rounds) break;
-        int64_t base;
-        int cnt;
-        const float *__restrict__ xs = x;       // this tile's point set
-        float *__restrict__ os = out;
-        if (n_fill > 0) {                        // whole rounds: own tiles (the last one may be ragged), then filler tiles
-            if (itr == rounds) break;
-            const int64_t v = itr * G + wg;
-            if (v < TA) {
-                base = v * kPts;
-                cnt = (int)min((int64_t)kPts, n - base);
-            } else {
-                base = (fb.tile0 + (v - TA)) * kPts;
-                cnt = (int)min((int64_t)kPts, fb.n - base);
-                xs = fb.x;
-                os = fb.out;
-            }
-        } else if (itr < rounds) {
-            base = (itr * G + wg) * kPts;
-            cnt = kPts;
-        } else {
-            base = rem_base + wg * rem_step;
-            if (base >= n) break;
-            cnt = (int)min(rem_step, n - base);
-        }
-        const bool half = cnt <= 32;   // (also a ragged last tile of <= 32 points)
-        HM_PROBE(0);
-        __syncthreads();  // previous tile's output stage is done with X
-        load_points(FRAC != kFracEmb, SX, xs, base, cnt, kPts, tid);
-        __syncthreads();
-
-        // ---------------- encode -> EMB[(e/4)][p][e%4] ------------------------------------
-        if constexpr (FRAC == kFracEmb) {
-            load_emb_tile(EMB, xs, net.emb_stride, base, cnt, E, net.emb_groups, kPts, kGroupFloats, tid, kThreadsSdf);
-        } else {
-            const int p = tid & (kPts - 1);
-            const int grp = tid >> 6;  // 0..7
-            const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, grp, kWaves, net.emb_groups * 4,
-                              [&](int e, float v) { EMB[(e >> 2) * kGroupFloats + p * 4 + (e & 3)] = v; });
-        }
-        __syncthreads();
-        HM_PROBE(1);
-
-        // ---------------- layers ------------------------------------------------------------
-        // weight ring (WeightRing, hm_sdf_common.h: 4 slots, 3 octets = 6 KB per wave in flight); it lives across layers
-        WeightRing<4, 2> ring;
-        ring.voff = lane * 16;
-        bool ring_ready = false;
-        auto prefetch64 = [&](int l) {
-            const hm_mlp_layer &Lp = net.layer[l];
-            const int nop = Lp.seg_octets[0] + Lp.seg_octets[1];
-            const int ntp = max(0, min(2, Lp.n_tiles - 2 * wave));
-            // descriptor on the wave's first feature tile; the second one is nop KB on
-            const __amdgpu_buffer_rsrc_t rs = w_rsrc(Lp.w_packed + ((size_t)(2 * wave) * nop) * 256);
-            const int so[2] = {0, ntp > 1 ? nop * 1024 : 0};
-            ring.fill(rs, so, nop);
-        };
-        for (int li = 0; li < net.n_layers; ++li) {
-            const hm_mlp_layer &Ly = net.layer[li];
-            const int n_oct = Ly.seg_octets[0] + Ly.seg_octets[1];
-            if (li == net.n_layers - 1 && out_cols == 1) {
-                // sdf-only: one output feature.  A 32-row MFMA tile would idle 7 of 8 waves for a full
-                // layer time; instead every wave takes a k-slice of the dot product on the VALU
-                // (row 0 of the packed image: tile 0, lanes 0 and 32).
-                const float4 *W0 = reinterpret_cast<const float4 *>(Ly.w_packed);
-                float part = 0.0f;
-                int kg0 = 0;
-                for (int seg = 0; seg < 2; ++seg) {
-                    const float *src = (Ly.seg_src[seg] == 0) ? X : EMB;
-                    const int ng = 2 * Ly.seg_octets[seg];
-                    for (int kg = wave; kg < ng; kg += kWaves) {
-                        const float4 xv = *reinterpret_cast<const float4 *>(src + kg * kGroupFloats + lane * 4);
-                        const int kk = kg0 + kg;
-                        const float4 wv = W0[(size_t)(kk >> 1) * 64 + 32 * (kk & 1)];
-                        part = __fmaf_rn(xv.x, wv.x, part);
-                        part = __fmaf_rn(xv.y, wv.y, part);
-                        part = __fmaf_rn(xv.z, wv.z, part);
-                        part = __fmaf_rn(xv.w, wv.w, part);
-                    }
-                    kg0 += ng;
-                }
-                RED[wave * kPts + lane] = part;
-                sdf_last_finish(RED, kWaves, kPts, cnt, Ly.bias, net.beta, os, base, out_stride, tid);
-                break;
-            }
-            const int nt = Ly.n_tiles;
-            const int t0 = 2 * wave;
-            const int ntw = max(0, min(2, nt - t0));
-            f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
-            if (ntw > 0) {
-                const __amdgpu_buffer_rsrc_t rsA = w_rsrc(Ly.w_packed + ((size_t)t0 * n_oct) * 256);
-                const int so[2] = {0, ntw > 1 ? n_oct * 1024 : 0};     // byte offsets of the wave's two feature tiles
-                const int no0 = Ly.seg_octets[0];
-                const float *src0 = (Ly.seg_src[0] == 0) ? X : EMB;
-                const float *src1 = (Ly.seg_src[1] == 0) ? X : EMB;
-                if (!ring_ready) prefetch64(li);
-                ring_ready = false;
-                auto loadB = [&](int gg, float4 &b0, float4 &b1) {
-                    const int gc = min(gg, n_oct - 1);
-                    const float *src = (gc < no0) ? src0 + (2 * gc + h) * kGroupFloats
-                                                  : src1 + (2 * (gc - no0) + h) * kGroupFloats;
-                    b0 = *reinterpret_cast<const float4 *>(src + j * 4);
-                    b1 = *reinterpret_cast<const float4 *>(src + (32 + j) * 4);
-                };
-                auto mfma16 = [&](const float4 &a0, const float4 &a1, const float4 &b0, const float4 &b1) {
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc00, 0, 0, 0);
-                    acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b1.x, acc01, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b0.x, acc10, 0, 0, 0);
-                    acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, acc11, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc00, 0, 0, 0);
-                    acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b1.y, acc01, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b0.y, acc10, 0, 0, 0);
-                    acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc11, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc00, 0, 0, 0);
-                    acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b1.z, acc01, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b0.z, acc10, 0, 0, 0);
-                    acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b1.z, acc11, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc00, 0, 0, 0);
-                    acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b1.w, acc01, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b0.w, acc10, 0, 0, 0);
-                    acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b1.w, acc11, 0, 0, 0);
-                };
-                // (full tiles request the B fragments of octet gg + 1 before octet gg's MFMAs - two register sets, loadB / mfma16:
-                //  with the ds_reads behind the scheduling barrier of their own octet every octet starts with an exposed
-                //  LDS round trip.  Alone this changed nothing - one wave's k-loop 62.4 -> 54.2 us per layer, but then 11 us
-                //  at the barrier, scripts/sdf_phase_probe.py; on top of the buffer-load weight stream: 132.0 -> 134.2
-                //  TFLOP/s)
-                // half tile: the same stream, point block 0 only (8 MFMAs per octet)
-                auto octet_h = [&](int gg, const float4 &a0, const float4 &a1) {
-                    const float *src = (gg < no0) ? src0 + (2 * gg + h) * kGroupFloats
-                                                  : src1 + (2 * (gg - no0) + h) * kGroupFloats;
-                    const float4 b0 = *reinterpret_cast<const float4 *>(src + j * 4);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc00, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b0.x, acc10, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc00, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b0.y, acc10, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc00, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b0.z, acc10, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc00, 0, 0, 0);
-                    acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b0.w, acc10, 0, 0, 0);
-                };
-                if (!half) {
-                    float4 bA0, bA1, bB0, bB1;      // B fragments: even octets in set A, odd octets in set B
-                    loadB(0, bA0, bA1);
-                    ring.run(rsA, so, n_oct,
-                             [&](int gg, int u) { if (u & 1) loadB(gg + 1, bA0, bA1); else loadB(gg + 1, bB0, bB1); },
-                             [&](int, int u, const float4 (&w)[2]) {
-                                 if (u & 1) mfma16(w[0], w[1], bB0, bB1); else mfma16(w[0], w[1], bA0, bA1);
-                             });
-                } else {
-                    ring.run(rsA, so, n_oct, no_pre, [&](int gg, int, const float4 (&w)[2]) { octet_h(gg, w[0], w[1]); });
-                }
-            }
-            if (li + 1 < net.n_layers && !(li + 1 == net.n_layers - 1 && out_cols == 1) &&
-                net.layer[li + 1].n_tiles - 2 * wave > 0) {
-                prefetch64(li + 1);
-                ring_ready = true;
-            }
-            HM_PROBE(2 + 4 * li);
-            HM_PROBE_WAVES(64);
-            __syncthreads();  // every wave has finished reading X / EMB for this layer
-            HM_PROBE(3 + 4 * li);
-            HM_PROBE_WAVES(72);
-
-            // epilogue: registers 4q..4q+3 of a tile = features 8q+4h+{0..3} = one k-group of the next layer
-            const bool act = Ly.activation != 0;
-            const bool div = Ly.post_div_sqrt2 != 0;
-            auto store_tile = [&](const f32x16 &acc, int ft, int pt) {
-                const int fbase = 32 * (t0 + ft);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int f = fbase + 8 * q + 4 * h;
-                    const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
-                    float v[4] = {acc[4 * q + 0] + bb.x, acc[4 * q + 1] + bb.y, acc[4 * q + 2] + bb.z, acc[4 * q + 3] + bb.w};
-                    act_quads(v, act, div);
-                    *reinterpret_cast<float4 *>(X + (f >> 2) * kGroupFloats + (32 * pt + j) * 4) =
-                        make_float4(v[0], v[1], v[2], v[3]);
-                }
-            };
-            if (ntw > 0) {
-                store_tile(acc00, 0, 0);
-                if (!half) store_tile(acc01, 0, 1);
-            }
-            if (ntw > 1) {
-                store_tile(acc10, 1, 0);
-                if (!half) store_tile(acc11, 1, 1);
-            }
-            if (li == 0 && net.emb_groups > 0) rescale_emb(EMB, net.emb_groups * kGroupFloats, tid, kThreadsSdf);
-            HM_PROBE(4 + 4 * li);
-            __syncthreads();
-            HM_PROBE(5 + 4 * li);
-        }
-        HM_PROBE(100);
-
-        // ---------------- output: X[(f/4)][p][f%4] -> out[p][f] -----------------------------
-        const hm_mlp_layer &last = net.layer[net.n_layers - 1];
-        if (out_cols != 1) store_rows(X, kGroupFloats, cnt, last.out_dim, net.beta, os, base, out_stride, tid, kThreadsSdf);
-    }
 }
 
 template <int FRAC>
@@ -841,22 +557,28 @@ __global__ __launch_bounds__(kThreadsSdf, 1) void trace_secant_kernel(HmLevels l
 // are those of sdf_fwd_kernel (same tiles); the secant uses 16-point tiles when the scan is long enough to hide their
 // latency (a 16-point tile does four times the rays of a 4-point one for 1.6x the time: least chip time), and the list
 // length rule of trace_secant_kernel otherwise.
+// The guarded mode runs the same kernel with another scan: scan_x -> scan_out, cnt[c_scan] points = the refinement list of
+// the closest-approach rows' marked samples (any length on the 64-point body: scan_min 1), whose ~60 tiles fit beside the
+// secant tiles; the secant's tile rule still reads the closest-approach scan's length.
 template <int FRAC>
 __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevels lv, SdfNet net,
                                                                           const float *__restrict__ table,
                                                                           const float *__restrict__ Bf, TraceArgs a,
                                                                           int n_iters, int64_t m8_max, int64_t m4_max,
-                                                                          int64_t scan_off, int64_t scan_min,
+                                                                          const float *__restrict__ scan_x,
+                                                                          float *__restrict__ scan_out, int c_scan,
+                                                                          int64_t scan_cap, int64_t scan_min,
                                                                           int64_t scan_hide, int c_prev1, int grid1,
                                                                           int c_prev2, int grid2) {
     extern __shared__ __align__(16) float lds[];
-    const int64_t n_scan = max(a.w.cnt[C_NSEL_PTS], 0);
+    const int64_t n_scan = min((int64_t)max(a.w.cnt[c_scan], 0), scan_cap);
     const int64_t n_sec = a.w.cnt[C_NSEC];
     if (n_sec > 0 && n_iters > 0) {
-        const int pts = n_scan >= scan_hide ? 16 : (n_sec <= m4_max ? 4 : (n_sec <= m8_max ? 8 : 16));
+        // (the secant's tiles follow the closest-approach scan's length also where the scan of this launch is another list)
+        const int pts = a.w.cnt[C_NSEL_PTS] >= scan_hide ? 16 : (n_sec <= m4_max ? 4 : (n_sec <= m8_max ? 8 : 16));
         secant_role<FRAC>(lv, net, table, Bf, a, n_iters, n_sec, pts, lds);
     }
-    if (n_scan < scan_min) return;        // (a short scan is the small-tile launch's job)
+    if (n_scan < scan_min) return;        // (a short scan is the small-tile launch's job; an empty list is nobody's)
     // the scan's first tiles completed the last rounds of the sampler's launches (filler tiles, see fill_quota)
     const int64_t tb = (n_scan + kPts - 1) / kPts;
     int64_t done = c_prev1 >= 0 ? fill_quota(max(a.w.cnt[c_prev1], 0), grid1, tb, scan_min) : 0;
@@ -864,8 +586,45 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevel
     const int64_t skip = done * kPts;
     if (skip >= n_scan) return;
     const SdfFill none = {nullptr, nullptr, 0, 0};
-    sdf64_run<FRAC, true>(lv, net, a.w.pts + (scan_off + skip) * 3, n_scan - skip, table, Bf, a.w.vals + scan_off + skip, 1, 1,
-                          lds, reinterpret_cast<unsigned *>(a.w.cnt + C_TILE_CURSOR), none);
+    sdf64_run<FRAC, true>(lv, net, scan_x + skip * 3, n_scan - skip, table, Bf, scan_out + skip, 1, 1, lds,
+                          reinterpret_cast<unsigned *>(a.w.cnt + C_TILE_CURSOR), none);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Guarded coarse scans (hm_trace.hip): the exact refinement of the sampler's marked samples and the approximate
+// closest-approach scan in ONE launch.  The refinement list is ~90 fp32 tiles, one ~0.47 ms round on a third of the chip;
+// the closest-approach scan (1200 split tiles at the bench workload) depends on neither the sampler's values nor their
+// refinement.  Every workgroup first takes fp32 64-point tiles of the list (sdf64_run with the atomic cursor: the tiles
+// and values of the stand-alone refinement launch), then split tiles of the scan from a second cursor (the tile of
+// sdf_fwd_split_kernel: a tile's values do not depend on the workgroup that runs it).  The workgroups that got no fp32
+// tile start on the scan at once; nothing is exchanged between workgroups.  Both cursors are zero at launch.
+// scan_min: shorter scans ran on the exact small-tile launch in front of this one.
+template <int KIND, int FRAC>
+__global__ __launch_bounds__(kThreadsSdf, 2) void sdf_refine_scan_kernel(HmLevels lv, SdfNet net, SdfNet net_split,
+                                                                          const float *__restrict__ table,
+                                                                          const float *__restrict__ Bf, TraceArgs a,
+                                                                          int c_ref, int64_t scan_off, int64_t scan_min) {
+    extern __shared__ __align__(16) float lds[];
+    __shared__ unsigned s_scan_tile;
+    const int64_t n_ref = min((int64_t)max(a.w.cnt[c_ref], 0), a.w.cap);
+    const int64_t n_scan = min((int64_t)max(a.w.cnt[C_NSEL_PTS], 0), a.w.cap);
+    if (n_ref > 0) {
+        const SdfFill none = {nullptr, nullptr, 0, 0};
+        sdf64_run<FRAC, true>(lv, net, a.w.ref_pts, n_ref, table, Bf, a.w.ref_vals, 1, 1, lds,
+                              reinterpret_cast<unsigned *>(a.w.cnt + C_XREF_CURSOR), none);
+    }
+    if (n_scan < scan_min) return;
+    const int64_t n_tiles = (n_scan + kPS - 1) / kPS;
+    unsigned *cursor = reinterpret_cast<unsigned *>(a.w.cnt + C_XSCAN_CURSOR);
+    for (;;) {
+        __syncthreads();   // every thread has read the previous hand-out (and is done with the fp32 tiles' LDS)
+        if (threadIdx.x == 0) s_scan_tile = atomicAdd(cursor, 1u);
+        __syncthreads();
+        const int64_t tile = s_scan_tile;
+        if (tile >= n_tiles) break;
+        sdf_split_tile<KIND, FRAC>(lv, net_split, a.w.pts + scan_off * 3, n_scan, table, Bf, a.w.vals + scan_off, 1, lds,
+                                   tile);
+    }
 }
 
 // network descriptor -> kernel argument for the exact-fp32 kernels (sdf_net_from_desc)
@@ -1040,22 +799,30 @@ int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
     });
 }
 
-// Closest-approach scan (points at pts + scan_off, count cnt[C_NSEL_PTS]) and the secant refinement in one launch
-// (sdf_scan_secant_kernel); scans of <= kSdfSmall points run on the small-tile launch in front of it.  tile_points = 0 only.
+// A 64-point-tile scan (scan_capacity points at scan_x, values to scan_out, count cnt[c_scan]) and the secant refinement in
+// one launch (sdf_scan_secant_kernel).  tile_points = 0 only.  small_front != 0 - the closest-approach scan of the exact
+// mode: scans of <= kSdfSmall points run on the small-tile launch in front of it; 0 - a refinement list of the guarded
+// mode: every count runs on the 64-point body, and no sampler launch took tiles of it (c_prev* = -1).
 int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                         int frac_mode, const void *trace_args, int n_iters, int64_t scan_off, int64_t scan_capacity,
-                         int c_prev1, int grid1, int c_prev2, int grid2, void *stream) {
+                         int frac_mode, const void *trace_args, int n_iters, const float *scan_x, float *scan_out,
+                         int64_t scan_capacity, int c_scan, int small_front, int c_prev1, int grid1, int c_prev2, int grid2,
+                         void *stream) {
     HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_scan_secant: NULL argument");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_scan_secant: bad frac_mode");
+    HM_CHECK_ARG(c_scan >= 0 && c_scan < C_COUNT && scan_capacity >= 0, "hm_trace_scan_secant: bad scan counter / capacity");
+    HM_CHECK_ARG(small_front || (grid1 <= 0 && grid2 <= 0), "hm_trace_scan_secant: a refinement list has no filler tiles");
     const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
     SdfNet net;
     int rc = sdf_net_fp32("hm_trace_scan_secant", desc->lv, mlp, 0, kImgM16, net);
     if (rc != HM_OK) return rc;
     if (a.n == 0) return HM_OK;
-    // the scan's small-count form (tile_points -1: returns at once above kSdfSmall live points)
-    rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1, frac_mode,
-                    -1, a.w.cnt + C_NSEL_PTS, 0, stream);
-    if (rc != HM_OK) return rc;
+    HM_CHECK_ARG(scan_x && scan_out, "hm_trace_scan_secant: NULL scan pointer");
+    if (small_front) {
+        // the scan's small-count form (tile_points -1: returns at once above kSdfSmall live points)
+        rc = hm_sdf_fwd(desc, mlp, scan_x, scan_capacity, table, B_fourier, scan_out, 1, 1, frac_mode, -1, a.w.cnt + c_scan, 0,
+                        stream);
+        if (rc != HM_OK) return rc;
+    }
     const size_t lds16 = sdf_lds_small(net, desc->lv.E, kPts16).bytes(), lds64 = sdf_lds64(net).bytes();
     HM_CHECK_ARG(lds16 <= kLds16Max && lds64 <= kLds64Max - kLdsTrace, "hm_trace_scan_secant: network does not fit the LDS tiles");
     const size_t lds = lds16 > lds64 ? lds16 : lds64;
@@ -1071,9 +838,54 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
         const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
         if (rc != HM_OK) return rc;
         hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier, a,
-                           n_iters, t.m8_max, t.m4_max, scan_off, kSdfSmall + 1, scan_hide, p1, grid1, p2, grid2);
+                           n_iters, t.m8_max, t.m4_max, scan_x, scan_out, c_scan, scan_capacity,
+                           (int64_t)(small_front ? kSdfSmall + 1 : 1), scan_hide, p1, grid1, p2, grid2);
         HM_CHECK_LAUNCH("hm_trace_scan_secant");
         return HM_OK;
+    });
+}
+
+// internal entry of the ray search (hm_trace.hip, not exported), guarded coarse scans: the exact refinement of the list
+// ref_pts -> ref_vals (count cnt[c_ref]) and the approximate closest-approach scan (scan_capacity points at pts + scan_off,
+// count cnt[C_NSEL_PTS]) in one launch (sdf_refine_scan_kernel); scans of <= kSdfSmall points run on the exact small-tile
+// launch in front of it, as in hm_sdf_fwd_split's callers.  tile_points = 0 only.
+int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
+                         int frac_mode, const void *trace_args, int c_ref, int64_t scan_off, int64_t scan_capacity,
+                         void *stream) {
+    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_refine_scan: NULL argument");
+    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_refine_scan: bad frac_mode");
+    HM_CHECK_ARG(c_ref >= 0 && c_ref < C_COUNT, "hm_trace_refine_scan: bad list counter");
+    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
+    static_assert(sizeof(HmLevels) + 2 * sizeof(SdfNet) + sizeof(TraceArgs) + 64 <= 4096, "kernel arguments exceed 4 KB");
+    SdfNet net, net_split;
+    size_t lds_split = 0;
+    int rc = sdf_net_fp32("hm_trace_refine_scan", desc->lv, mlp, 0, kImgM16, net);
+    if (rc == HM_OK) rc = sdf_split_net("hm_trace_refine_scan", desc->lv.E, mlp, 0, net_split, &lds_split);
+    if (rc != HM_OK) return rc;
+    if (a.n == 0) return HM_OK;
+    HM_CHECK_ARG(a.w.pts && a.w.vals && a.w.ref_pts && a.w.ref_vals && a.w.cnt, "hm_trace_refine_scan: NULL workspace pointer");
+    HM_CHECK_ARG(scan_off >= 0 && scan_capacity >= 0 && scan_capacity <= a.w.cap, "hm_trace_refine_scan: bad scan region");
+    rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1, frac_mode,
+                    -1, a.w.cnt + C_NSEL_PTS, 0, stream);
+    if (rc != HM_OK) return rc;
+    const size_t lds64 = sdf_lds64(net).bytes();
+    HM_CHECK_ARG(lds64 <= kLds64Max - kLdsTrace && lds_split <= kLds64Max - kLdsTrace,
+                 "hm_trace_refine_scan: network does not fit the LDS tiles");
+    const size_t lds = lds_split > lds64 ? lds_split : lds64;
+    const int64_t tiles = (a.w.cap + 31) / 32;     // (up to one 32-point half tile of the list per workgroup)
+    const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
+    const auto launch = [&](auto kind, auto frac) {
+        constexpr auto kernel = sdf_refine_scan_kernel<decltype(kind)::value, decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, net_split, table,
+                           B_fourier, a, c_ref, scan_off, (int64_t)kSdfSmall + 1);
+        HM_CHECK_LAUNCH("hm_trace_refine_scan");
+        return HM_OK;
+    };
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
+        return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
     });
 }
 

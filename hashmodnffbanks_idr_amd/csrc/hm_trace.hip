@@ -27,12 +27,19 @@ extern "C" int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp
                                           const float *B_fourier, int frac_mode, int tile_points, const void *trace_args,
                                           int n_iters, int scan_rule, void *stream);
 
-// hm_sdf.hip (not exported): the closest-approach scan and the secant refinement as ONE launch (workgroups without secant
-// rays start on the scan at once, 64-point tiles handed out by an atomic cursor)
+// hm_sdf.hip (not exported): a 64-point-tile scan (the closest-approach scan of the exact mode, or a refinement list of the
+// guarded mode) and the secant refinement as ONE launch (workgroups without secant rays start on the scan at once, 64-point
+// tiles handed out by an atomic cursor)
 extern "C" int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
                                     const float *B_fourier, int frac_mode, const void *trace_args, int n_iters,
-                                    int64_t scan_off, int64_t scan_capacity, int c_prev1, int grid1, int c_prev2,
-                                    int grid2, void *stream);
+                                    const float *scan_x, float *scan_out, int64_t scan_capacity, int c_scan,
+                                    int small_front, int c_prev1, int grid1, int c_prev2, int grid2, void *stream);
+
+// hm_sdf.hip (not exported), guarded mode: the exact refinement of a list and the approximate closest-approach scan as ONE
+// launch (fp32 tiles of the list first, then split tiles of the scan, each from an atomic cursor)
+extern "C" int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
+                                    const float *B_fourier, int frac_mode, const void *trace_args, int c_ref,
+                                    int64_t scan_off, int64_t scan_capacity, void *stream);
 
 // hm_sdf.hip (not exported): hm_sdf_fwd whose 64-point launch completes its last round with tiles of a second point set
 extern "C" int hm_sdf_fwd_fill(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n,
@@ -330,6 +337,10 @@ __global__ __launch_bounds__(kTB) void closest_reduce_kernel(TraceArgs a) {
 // |a - exact| <= tau is monitored, not assumed: guard_patch_kernel sees both values of every refined sample; a deviation
 // above kGuardTrip = tau / 4 sets the workspace's sticky word, and from then on (the following launches of that call
 // included) every sample is marked, i.e. the scans are all-fp32.  The tripping call itself is still exact (tau/4 < tau).
+// Where the refinements are co-scheduled (trace_forward_impl: cosched) the closest-approach rows are selected BEHIND the
+// sampler's patch, on a list and a counter of their own (C_GUARD_NC): a call in which the sampler's patch trips the monitor
+// marks every closest-approach sample in that same call already - conservative and still exact; that call's refined count
+// is then larger than with HM_TRACE_OVERLAP=1, where both selections run in front of the one patch.
 //
 // A launch of fewer than min_live points ran on the exact kernel already (the small-tile launch of coarse()): nothing is
 // marked for it.  val(s) / slot(s): value and index in vals of the row's sample s; own(s): s was evaluated by this launch,
@@ -624,7 +635,8 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     a.tail_off = L.cap;
     // Closest-approach scan and secant refinement as one launch (hm_sdf.hip: sdf_scan_secant_kernel): training, hash-grid
     // network, exact-fp32 coarse scans, tile size left to the library.  HM_TRACE_OVERLAP=0: the scan joins the sampler's
-    // launch and the secant runs behind it on a few dozen workgroups (A/B).
+    // launch and the secant runs behind it on a few dozen workgroups (A/B).  =1: the default, except that the guarded
+    // scans run every launch on its own (see cosched below).
     const char *e_ov = getenv("HM_TRACE_OVERLAP");      // (read per call: the tests compare both forms in one process)
     const bool overlap_ok = !(e_ov && atoi(e_ov) == 0);
     const bool overlap_shape = overlap_ok && cfg->training && !nffb && tile_points == 0 && cfg->n_secant_steps > 0 &&
@@ -635,6 +647,13 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     // guarded mode evaluates them by their own count too (and the secant picks its tiles by the rule of that launch).
     const bool sel_own = overlap || (guard && overlap_shape);
     a.sel_off = sel_own ? 2 * L.cap : -1;
+    // Guarded scans of that shape keep the chip busy through the guard's exact refinements, which are one round of fp32
+    // tiles on a third of the chip each: the refinement of the sampler's marks runs beside the closest-approach rows' split
+    // tiles (hm_sdf.hip: sdf_refine_scan_kernel), and the refinement of the closest-approach rows' marks beside the secant
+    // chain (sdf_scan_secant_kernel with the list as its scan).  Same tiles, same values, one stream; the rows of the two
+    // lists are disjoint and the sampler's list is patched before the closest-approach rows are selected, so both lists
+    // start at the head of the refinement region.  HM_TRACE_OVERLAP=1: every launch on its own, one list (A/B, tests).
+    const bool cosched = guard && overlap_shape && !(e_ov && atoi(e_ov) == 1);
 
     hm_zero_u32_async(a.w.cnt, C_COUNT, st);
     const unsigned g_rays = (unsigned)((n_rays + kTB - 1) / kTB);
@@ -703,11 +722,14 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             hipLaunchKernelGGL(guard_noise_kernel, dim3((unsigned)((capacity + kTB - 1) / kTB)), dim3(kTB), 0, st, a.w.vals,
                                off, a.w.cnt + c_live, guard_min, noise_amp, noise_nan);
     };
+    auto guard_patch = [&](int c_ref) {
+        hipLaunchKernelGGL(guard_patch_kernel, dim3((unsigned)((L.cap + kTB - 1) / kTB)), dim3(kTB), 0, st, a, c_ref);
+    };
     auto guard_refine = [&](int c_ref) -> int {
         const int rc = hm_sdf_fwd(desc, mlp, a.w.ref_pts, L.cap, table, B_fourier, a.w.ref_vals, 1, 1, frac_mode,
                                   tile_points == 0 ? 64 : tile_points, a.w.cnt + c_ref, 0, stream);
         if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(guard_patch_kernel, dim3((unsigned)((L.cap + kTB - 1) / kTB)), dim3(kTB), 0, st, a, c_ref);
+        guard_patch(c_ref);
         return HM_OK;
     };
 
@@ -764,9 +786,19 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
         // (guarded, closest-approach rows in their own region: two launches, each by its own count)
         const int c_samp = sel_own ? c_first : (int)C_BIG_PTS, c_sel = sel_own ? (int)C_NSEL_PTS : (int)C_BIG_PTS;
         int rc = coarse(0, n_rays * cfg->n_steps, a.w.cnt + c_samp);
-        if (rc == HM_OK && sel_own) rc = coarse(a.sel_off, n_rays * cfg->n_steps, a.w.cnt + c_sel);
+        if (rc == HM_OK && sel_own && !cosched) rc = coarse(a.sel_off, n_rays * cfg->n_steps, a.w.cnt + c_sel);
         if (rc != HM_OK) return rc;
-        if (guard) {
+        if (cosched) {
+            // the sampler's marks are refined beside the closest-approach rows' approximate scan; those rows are selected,
+            // refined and reduced with the secant chain below
+            guard_noise(0, n_rays * cfg->n_steps, c_samp);
+            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
+                               (int)C_GUARD_N1);
+            rc = hm_trace_refine_scan(desc, mlp, table, B_fourier, frac_mode, &a, (int)C_GUARD_N1, a.sel_off,
+                                      n_rays * cfg->n_steps, stream);
+            if (rc != HM_OK) return rc;
+            guard_patch((int)C_GUARD_N1);
+        } else if (guard) {
             guard_noise(0, n_rays * cfg->n_steps, c_samp);
             if (sel_own) guard_noise(a.sel_off, n_rays * cfg->n_steps, c_sel);
             hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
@@ -778,7 +810,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             if (rc != HM_OK) return rc;
         }
     }
-    if (cfg->training && !overlap) hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
+    if (cfg->training && !overlap && !cosched) hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
     if (a.head > 0) {   // second pass: the remaining samples of the rays the head samples did not resolve
         hipLaunchKernelGGL(sampler_head_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         hipLaunchKernelGGL(sampler_tail_points_kernel, dim3(g_samp), dim3(kTB), 0, st, a);
@@ -804,9 +836,21 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
         // (hm_sdf.hip: trace_secant_kernel; with the closest-approach scan in the same launch: sdf_scan_secant_kernel);
         // otherwise an (SDF launch, update launch) pair per iteration
         if (overlap) {
-            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps, a.sel_off,
-                                                n_rays * cfg->n_steps, c_first, grid_p1, (int)C_TAIL_PTS, grid_p2, stream);
+            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps,
+                                                a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, n_rays * cfg->n_steps,
+                                                (int)C_NSEL_PTS, 1, c_first, grid_p1, (int)C_TAIL_PTS, grid_p2, stream);
             if (rc != HM_OK) return rc;
+            hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
+        } else if (cosched) {
+            // the closest-approach rows' marks (selected behind the sampler's patch: see guard_mark_row) are refined by the
+            // workgroups the secant chain leaves free - the 64-point body whatever the list's length, as guard_refine asks
+            guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
+            hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
+                               (int)C_GUARD_NC);
+            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps, a.w.ref_pts,
+                                                a.w.ref_vals, L.cap, (int)C_GUARD_NC, 0, -1, 0, -1, 0, stream);
+            if (rc != HM_OK) return rc;
+            guard_patch((int)C_GUARD_NC);
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         } else if (!nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
             (tile_points != 0 || n_rays <= kSdfSmall)) {

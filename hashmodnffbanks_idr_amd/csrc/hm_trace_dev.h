@@ -25,8 +25,12 @@ enum : int32_t {  // counters (device int32 array)
     C_TILE_CURSOR = 77,  // sdf_scan_secant_kernel: next 64-point tile of the closest-approach scan (zero at launch)
     C_GUARD_REFINED = 78,  // guarded coarse scans: samples re-evaluated in exact fp32 (statistics slot 14)
     C_GUARD_MAXDEV = 79,   // ... largest finite |approximate - exact| among them, as float bits (statistics slot 15)
-    C_GUARD_N1 = 80,     // ... points of the first refinement launch (sampler's first pass + closest approach)
-    C_GUARD_N2 = 81,     // ... points of the second one (lazy sampler's second pass)
+    C_GUARD_N1 = 80,     // ... refinement list of the sampler's first (or only) pass; HM_TRACE_OVERLAP=1 and the sequences
+                         //     without a launch of their own for the closest-approach rows: of those rows too
+    C_GUARD_N2 = 81,     // ... of the lazy sampler's second pass
+    C_GUARD_NC = 82,     // ... of the closest-approach rows (refined beside the secant chain)
+    C_XREF_CURSOR = 83,  // sdf_refine_scan_kernel: next fp32 tile of the refinement list (zero at launch)
+    C_XSCAN_CURSOR = 84, // ... next split tile of the closest-approach scan (zero at launch)
     C_COUNT = 96
 };
 
