@@ -119,6 +119,16 @@ SIGNATURES = {
     "hm_mesh_moments": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _p]),
     "hm_mesh_select_mark": (_int, [_p, _i64, _i64, _p, C.c_int32, _p, _p, _p, _p]),
     "hm_mesh_select_emit": (_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    # vertex clustering (ops.mesh_simplify): keys and runs, the clusters' representatives, the face pass, the emit
+    "hm_mesh_simplify_keys_workspace_bytes": (_i64, [_i64]),
+    "hm_mesh_simplify_keys": (_int, [_p, _p, _i64, _i64, _p, C.c_float, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "hm_mesh_simplify_clusters": (_int, [_p, _p, _i64, _p, _p, _p, _i64, _p, C.c_float, _p, _int, C.c_double, _p, _p,
+                                         _p, _p]),
+    "hm_mesh_simplify_face_flags": (_int, [_p, _i64, _i64, _p, _i64, _p, _p]),
+    "hm_mesh_simplify_dedupe_workspace_bytes": (_i64, [_i64]),
+    "hm_mesh_simplify_dedupe": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _i64, _p]),
+    "hm_mesh_simplify_emit": (_int, [_p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p,
+                                     _p]),
     # the DTU Chamfer evaluation: exact nearest neighbours on a uniform grid, triangle upsampling to a point density
     "hm_nn_workspace_bytes": (_i64, [_i64]),
     "hm_nn_build": (_int, [_p, _i64, _p, C.c_float, _p, _p, _p, _p, _i64, _p, _p]),

@@ -8,6 +8,15 @@
 // workgroups of `per` items that cover n items
 inline unsigned hm_grid(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
+// the size check of the mesh entry points: both counts in [0, 2^31), and faces given unless there are none
+inline int hm_check_mesh(int64_t n_faces, int64_t n_verts, const void *faces, const char *what) {
+    const std::string w(what);
+    HM_CHECK_ARG(n_faces >= 0 && n_faces < ((int64_t)1 << 31), w + ": n_faces must be in [0, 2^31)");
+    HM_CHECK_ARG(n_verts >= 0 && n_verts < ((int64_t)1 << 31), w + ": n_verts must be in [0, 2^31)");
+    HM_CHECK_ARG(n_faces == 0 || faces, w + ": NULL faces");
+    return HM_OK;
+}
+
 #ifdef __HIPCC__
 struct HmSum {
     template <class T>

@@ -28,7 +28,7 @@
 //
 // A face index outside [0, n_verts) is never dereferenced: the face is skipped and bit 0 of the status word is set.
 // Floating-point sums use no atomics and a fixed order: two calls give the same bits.  The face-index loader, the tree
-// sum and the grid size are hm_block_dev.h's.
+// sum, the grid size and the mesh size check are hm_block_dev.h's.
 #include "hm_block_dev.h"
 
 namespace {
@@ -308,14 +308,6 @@ __global__ __launch_bounds__(kCT) void sel_faces_kernel(const int32_t *__restric
     }
 }
 
-int cc_check_mesh(int64_t n_faces, int64_t n_verts, const void *faces, const char *what) {
-    const std::string w(what);
-    HM_CHECK_ARG(n_faces >= 0 && n_faces < ((int64_t)1 << 31), w + ": n_faces must be in [0, 2^31)");
-    HM_CHECK_ARG(n_verts >= 0 && n_verts < ((int64_t)1 << 31), w + ": n_verts must be in [0, 2^31)");
-    HM_CHECK_ARG(n_faces == 0 || faces, w + ": NULL faces");
-    return HM_OK;
-}
-
 int64_t mom_blocks(int64_t n_faces) { return (n_faces + kCBlock - 1) / kCBlock; }
 
 // the block partials of hm_mesh_moments (one block's worth for an empty mesh)
@@ -339,7 +331,7 @@ extern "C" {
 
 int hm_mesh_cc_labels(const int32_t *faces, int64_t n_faces, int64_t n_verts, int32_t *label, int32_t *status,
                       void *stream) {
-    if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_labels")) return rc;
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_labels")) return rc;
     if (n_verts == 0 && n_faces == 0) return HM_OK;
     HM_CHECK_ARG(status && (n_verts == 0 || label), "hm_mesh_cc_labels: NULL label or status");
     hipStream_t st = as_stream(stream);
@@ -356,7 +348,7 @@ int hm_mesh_cc_labels(const int32_t *faces, int64_t n_faces, int64_t n_verts, in
 
 int hm_mesh_cc_face_stats(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
                           double *face_area, int32_t *used, int32_t *status, void *stream) {
-    if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_face_stats")) return rc;
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_face_stats")) return rc;
     if (n_faces == 0) return HM_OK;
     HM_CHECK_ARG(verts && face_area && used && status, "hm_mesh_cc_face_stats: NULL pointer");
     hipLaunchKernelGGL(cc_face_stats_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, as_stream(stream), verts, faces,
@@ -374,7 +366,7 @@ int64_t hm_mesh_cc_sums_workspace_bytes(int64_t n_faces) {
 int hm_mesh_cc_sums(const int32_t *faces, int64_t n_faces, int64_t n_verts, const int32_t *label, const int32_t *rank,
                     const double *face_area, int64_t n_components, double *area, int64_t *count, void *workspace,
                     int64_t workspace_bytes, int32_t *status, void *stream) {
-    if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_sums")) return rc;
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_cc_sums")) return rc;
     HM_CHECK_ARG(n_components >= 0 && n_components <= n_verts, "hm_mesh_cc_sums: n_components must be in [0, n_verts]");
     if (n_faces == 0 || n_components == 0) return HM_OK;
     HM_CHECK_ARG(label && rank && face_area && area && count && workspace && status, "hm_mesh_cc_sums: NULL pointer");
@@ -402,7 +394,7 @@ int64_t hm_mesh_moments_workspace_bytes(int64_t n_faces) {
 
 int hm_mesh_moments(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, double *out,
                     void *workspace, int64_t workspace_bytes, int32_t *status, void *stream) {
-    if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_moments")) return rc;
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_moments")) return rc;
     HM_CHECK_ARG(out && workspace && status && (n_faces == 0 || verts), "hm_mesh_moments: NULL pointer");
     HM_CHECK_ARG(workspace_bytes >= hm_mesh_moments_workspace_bytes(n_faces), "hm_mesh_moments: workspace too small");
     const int64_t nb = mom_blocks(n_faces);
@@ -418,7 +410,7 @@ int hm_mesh_moments(const float *verts, const int32_t *faces, int64_t n_faces, i
 
 int hm_mesh_select_mark(const int32_t *faces, int64_t n_faces, int64_t n_verts, const int32_t *label,
                         int32_t component, int32_t *vflag, int32_t *fflag, int32_t *status, void *stream) {
-    if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_select_mark")) return rc;
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_select_mark")) return rc;
     if (n_faces == 0) return HM_OK;
     HM_CHECK_ARG(label && vflag && fflag && status, "hm_mesh_select_mark: NULL pointer");
     hipLaunchKernelGGL(sel_mark_kernel, dim3(hm_grid(n_faces, kCT)), dim3(kCT), 0, as_stream(stream), faces, n_faces,
@@ -431,7 +423,7 @@ int hm_mesh_select_emit(const float *verts, const float *normals, const int32_t 
                         int64_t n_verts, const int32_t *vflag, const int32_t *vpre, const int32_t *fflag,
                         const int32_t *fpre, int64_t n_verts_out, int64_t n_faces_out, float *verts_out,
                         float *normals_out, int32_t *faces_out, void *stream) {
-    if (int rc = cc_check_mesh(n_faces, n_verts, faces, "hm_mesh_select_emit")) return rc;
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_select_emit")) return rc;
     HM_CHECK_ARG(n_verts_out >= 0 && n_verts_out <= n_verts && n_faces_out >= 0 && n_faces_out <= n_faces,
                  "hm_mesh_select_emit: output counts out of range");
     HM_CHECK_ARG(n_verts_out == 0 || (verts && vflag && vpre && verts_out && (!normals || normals_out)),

@@ -1632,6 +1632,121 @@ def mesh_surface_moments(verts, faces):
 
 
 # =========================================================================================
+# mesh simplification: vertex clustering (csrc/hm_mesh_simplify.hip, DESIGN.md "Mesh simplification")
+# =========================================================================================
+def _simplify_grid(lo, hi, cell):
+    """(h as fp32, g[3]) of the clustering grid over the box [lo, hi] (float lists), g as _nn_grid computes it; a grid
+    beyond nn_grid()'s limits (hm_nn_dev.h) raises ValueError"""
+    h = float(np.float32(cell))
+    if not (h > 0.0 and math.isfinite(h)):
+        raise ValueError("hashmod mesh_simplify: cell must be positive and finite in fp32")
+    g = []
+    for a, b in zip(lo, hi):
+        q = max(float(b) - float(a), 0.0) / h
+        g.append(int(math.floor(q)) + 1 if math.isfinite(q) else 1 << 62)
+    if max(g) > 1 << 30 or g[0] * g[1] * g[2] >= 1 << 31:
+        raise ValueError(f"hashmod mesh_simplify: cell={cell} gives a grid of {g[0]}x{g[1]}x{g[2]} cells; a dimension "
+                         "may be at most 2^30 and the grid must have fewer than 2^31 cells")
+    return h, g
+
+
+def mesh_simplify(verts, faces, normals=None, cell=None, placement="quadric", reg=0.05):
+    """(verts_out [C,3] fp32, faces_out [G,3] int32, normals_out [C,3] fp32 or None, vertex_map [V] int32): the mesh
+    decimated by vertex clustering on a uniform grid of edge `cell` (DESIGN.md "Mesh simplification").
+
+    Grid: h = fp32(cell) over the box of ALL rows of verts (aminmax, read by the host), nn_index's cell function; more
+    than 2^30 cells on an axis or 2^31 in all raise ValueError, a non-finite coordinate HashmodError.  The vertices
+    that some face uses and that share a cell form a cluster; clusters are numbered by ascending cell key.  Its
+    representative, in fp64 from the fp32 inputs and rounded once: placement="mean", the members' mean m;
+    placement="quadric" (needs normals), the minimiser m + A^-1 b of the members' point-normal quadric regularised
+    towards m (A = sum n n^T + reg k I over the k unit normals, b = sum n (n . (p - m))), clamped per axis to the
+    cell's box widened to hold m.  Its normal is the normalised sum of the members' unit normals (0 when they cancel;
+    a zero or non-finite normal adds nothing); None without normals.  Faces: mapped to clusters, dropped when two
+    corners share one, rotated to smallest-id-first, and of equal triples only the first survives ((a,b,c) and (a,c,b)
+    differ); the survivors keep their order.  Clusters of no surviving face are dropped and the rest renumbered in
+    ascending order; vertex_map[v] is the output row of v's cluster, -1 for a vertex of no face or a dropped cluster.
+    V == 0 or F == 0 gives empty outputs.  Every sum has a fixed order and no atomics: two calls give the same bits.
+
+    Clustering does not preserve manifoldness: a cell that holds two sheets of the surface welds them, and an edge
+    may end up with more than two faces.  A face index outside [0, V) raises HashmodError (reported by the kernel,
+    never dereferenced).  Host reads of the box and of the counts between the launches, so not graph-capturable."""
+    n_faces, n_verts = _check_mesh("mesh_simplify", faces, verts=verts, normals=normals)
+    if not (isinstance(cell, (int, float)) and math.isfinite(cell) and cell > 0):
+        raise ValueError("hashmod mesh_simplify: cell must be a positive finite number")
+    if placement not in ("quadric", "mean"):
+        raise ValueError('hashmod mesh_simplify: placement must be "quadric" or "mean"')
+    if placement == "quadric" and normals is None:
+        raise ValueError('hashmod mesh_simplify: placement="quadric" needs normals')
+    if not (isinstance(reg, (int, float)) and math.isfinite(reg) and reg > 0):
+        raise ValueError("hashmod mesh_simplify: reg must be a positive finite number")
+    dev = faces.device
+
+    i32 = dict(dtype=torch.int32, device=dev)
+
+    def result(nv, nf):
+        """uninitialised outputs of nv vertices and nf faces; the map all -1"""
+        return (torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nf, 3), **i32),
+                None if normals is None else torch.empty((nv, 3), dtype=torch.float32, device=dev),
+                torch.full((n_verts,), -1, **i32))
+
+    if n_verts == 0 or n_faces == 0:
+        return result(0, 0)
+    lo, hi = torch.aminmax(verts, dim=0)
+    box = torch.stack([lo, hi]).tolist()
+    if not all(math.isfinite(v) for v in box[0] + box[1]):
+        raise _lib.HashmodError("hashmod mesh_simplify: a vertex has a non-finite coordinate")
+    h, g = _simplify_grid(box[0], box[1], cell)
+    lo_c, g_c = (C.c_float * 3)(*box[0]), (C.c_int32 * 3)(*g)
+    L = lib()
+    st = stream_ptr(faces)
+
+    # clusters: the sorted keys' runs
+    status = torch.zeros(1, **i32)
+    used = torch.zeros(n_verts, **i32)
+    keys_sorted, head = torch.empty(n_verts, **i32), torch.empty(n_verts, **i32)
+    perm = torch.empty(n_verts, dtype=torch.int64, device=dev)
+    ws = torch.empty(check(L.hm_mesh_simplify_keys_workspace_bytes(n_verts)), dtype=torch.uint8, device=dev)
+    check(L.hm_mesh_simplify_keys(dptr(verts), dptr(faces), n_faces, n_verts, lo_c, h, g_c, dptr(used), dptr(keys_sorted),
+                                  dptr(perm), dptr(head), dptr(ws), ws.numel(), dptr(status), st))
+    start = torch.nonzero(head).reshape(-1)      # a host read of the number of clusters
+    n_clusters = int(start.shape[0])
+    _check_mesh_status("mesh_simplify", status)
+    start = torch.cat([start, used.sum(dtype=torch.int64).reshape(1)])
+    rep = torch.empty((n_clusters, 3), dtype=torch.float32, device=dev)
+    rep_normals = None if normals is None else torch.empty((n_clusters, 3), dtype=torch.float32, device=dev)
+    cluster_of = torch.full((n_verts,), -1, **i32)
+    check(L.hm_mesh_simplify_clusters(dptr(verts), dptr(normals), n_verts, dptr(keys_sorted), dptr(perm), dptr(start),
+                                      n_clusters, lo_c, h, g_c, int(placement == "quadric"), float(reg), dptr(rep),
+                                      dptr(rep_normals), dptr(cluster_of), st))
+
+    # faces: drop the collapsed ones, then the repeats
+    fkeep = torch.empty(n_faces, **i32)
+    check(L.hm_mesh_simplify_face_flags(dptr(faces), n_faces, n_verts, dptr(cluster_of), n_clusters, dptr(fkeep), st))
+    fincl = torch.cumsum(fkeep, 0, dtype=torch.int32)
+    n_tri = int(fincl[-1].item())
+    if n_tri == 0:
+        return result(0, 0)
+    fpre = fincl - fkeep
+    tri = torch.empty((3, n_tri), **i32)
+    tkeep = torch.empty(n_tri, **i32)
+    cused = torch.zeros(n_clusters, **i32)
+    ws = torch.empty(check(L.hm_mesh_simplify_dedupe_workspace_bytes(n_tri)), dtype=torch.uint8, device=dev)
+    check(L.hm_mesh_simplify_dedupe(dptr(faces), n_faces, n_verts, dptr(cluster_of), n_clusters, dptr(fkeep), dptr(fpre),
+                                    n_tri, dptr(tri), dptr(tkeep), dptr(cused), dptr(ws), ws.numel(), st))
+
+    # compaction: the clusters some surviving face uses, renumbered in ascending order
+    cincl = torch.cumsum(cused, 0, dtype=torch.int32)
+    tincl = torch.cumsum(tkeep, 0, dtype=torch.int32)
+    nv, nf = torch.cat([cincl[-1:], tincl[-1:]]).tolist()
+    cpre, tpre = cincl - cused, tincl - tkeep
+    verts_out, faces_out, normals_out, vertex_map = result(nv, nf)
+    check(L.hm_mesh_simplify_emit(dptr(rep), dptr(rep_normals), n_clusters, dptr(cused), dptr(cpre), nv, dptr(tri), n_tri,
+                                  dptr(tkeep), dptr(tpre), nf, dptr(cluster_of), n_verts, dptr(verts_out),
+                                  dptr(normals_out), dptr(faces_out), dptr(vertex_map), st))
+    return verts_out, faces_out, normals_out, vertex_map
+
+
+# =========================================================================================
 # Chamfer evaluation: nearest neighbours, triangle upsampling, the metric (csrc/hm_nn.hip, csrc/hm_mesh_sample.hip)
 # =========================================================================================
 NN_MAX_CELLS = 1 << 26      # cap of the dense cell_start table (256 MiB of int32)

@@ -12,6 +12,8 @@ get_surface_high_res_mesh (plots.py:146-224) runs entirely on this library: the 
 on device-generated lattices, the meshes from ops.marching_cubes (csrc/hm_mesh.hip), and TriMesh stands in for the
 part of trimesh.Trimesh the reference's callers use.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -253,7 +255,8 @@ def _surface_moments(mesh):
     return mean, cov
 
 
-def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False, largest_component=False):
+def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False, largest_component=False,
+                              simplify=None):
     """plots.py:146-224: the zero level set of `sdf` on a lattice aligned with the principal axes of a coarse mesh's
     largest component, `resolution` samples along its shortest axis; a TriMesh in world space, or None without a
     sign change.  Two deliberate deviations (mesh extraction): the principal axes come from the exact
@@ -270,7 +273,15 @@ def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False, 
     areas' argmax - on the device, so that only that component is downloaded: the TriMesh
     max(get_surface_high_res_mesh(...).split(only_watertight=False), key=area), bit for bit.  The component is taken
     from the world-space fp32 vertices, the ones the host split would see: the transform of all vertices is a [V,3] x
-    [3,3] product, and selecting rows afterwards cannot change their bits."""
+    [3,3] product, and selecting rows afterwards cannot change their bits.
+
+    simplify=k (a positive number; None leaves the mesh as it is) decimates the fine mesh by vertex clustering on a grid
+    of k times the fine lattice spacing (ops.mesh_simplify: quadric placement from the SDF normals) on the device, so
+    that only the simplified mesh is downloaded.  It is applied to the world-space mesh, after largest_component when
+    both are given: the component choice sees the full mesh, as eval.py's does.  Clustering does not preserve
+    manifoldness."""
+    if simplify is not None and not (isinstance(simplify, (int, float)) and math.isfinite(simplify) and simplify > 0):
+        raise ValueError("get_surface_high_res_mesh: simplify must be a positive finite number or None")
     lin = np.linspace(-1.0, 1.0, 100)      # the coarse 100^3 grid of get_grid_uniform(100)
     coarse = _mesh_on_lattice(sdf, (lin, lin, lin), device)
     if coarse is None:
@@ -309,4 +320,7 @@ def get_surface_high_res_mesh(sdf, resolution=100, device="cuda", sparse=False, 
     if largest_component:
         verts, faces, normals = ops.mesh_largest_component(verts.contiguous(), faces.contiguous(),
                                                            normals.contiguous())
+    if simplify is not None:
+        verts, faces, normals, _ = ops.mesh_simplify(verts.contiguous(), faces.contiguous(), normals.contiguous(),
+                                                     cell=simplify * float(x[2] - x[1]))
     return TriMesh(verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy())

@@ -824,6 +824,62 @@ HM_API int hm_mesh_select_emit(const float *verts, const float *normals, const i
                                const int32_t *fpre, int64_t n_verts_out, int64_t n_faces_out, float *verts_out,
                                float *normals_out, int32_t *faces_out, void *stream);
 
+/* ---- mesh simplification: vertex clustering on the uniform grid of the Chamfer evaluation ---------
+ * Decimates a mesh to a chosen cell size on the device (DESIGN.md "Mesh simplification" states the contract,
+ * tests/mesh_simplify_cases.py restates it in numpy).  Driver: ops.mesh_simplify, which also takes the prefix sums and
+ * reads the counts between the entry points.  The mesh and the status word are those of the mesh cleanup above; the
+ * grid (lo, h, g) is that of the Chamfer evaluation below: cell = clamp(floor((p - lo) / h), 0, g - 1) per axis in
+ * fp32, key = (cx*g[1] + cy)*g[2] + cz, fewer than 2^31 cells.  No entry point synchronises; no floating-point atomic
+ * is used and every sum has a fixed order, so repeated calls give the same bits (csrc/hm_mesh_simplify.hip).
+ *   hm_mesh_simplify_keys: used [n_verts] int32, zeroed by the caller, gets 1 at every vertex of a face (a face index
+ *                outside [0, n_verts) sets status bit 0 and is never dereferenced).  The used vertices' keys - unused
+ *                ones get the number of cells, above every key - are sorted with hm_sort_pairs_i32 (stable) into
+ *                keys_sorted [n_verts] int32 and perm [n_verts] int64: a cluster is one run, its members in ascending
+ *                vertex id.  head [n_verts] int32 = 1 at the first position of every run of a used key, else 0.
+ *                workspace: hm_mesh_simplify_keys_workspace_bytes(n_verts).
+ *   hm_mesh_simplify_clusters: start [n_clusters + 1] int64 = the positions of head's ones in ascending order and then
+ *                the number of used vertices.  For cluster c with the k members perm[start[c] .. start[c+1]), in fp64
+ *                from the fp32 inputs: m = (sum p)/k; n^ = n/|n|, 0 for a zero or non-finite normal; the
+ *                representative rep [n_clusters, 3] fp32 is m, or with quadric != 0 (normals required, reg > 0)
+ *                m + A^-1 b, A = sum n^ n^T + reg k I, b = sum n^ (n^ . (p - m)), clamped per axis to [min(blo, m),
+ *                max(bhi, m)], blo = lo + cell h, bhi = blo + h; rep_normals [n_clusters, 3] fp32 (with normals) is
+ *                (sum n^)/|sum n^|, or 0 when that length is 0.  One rounding to fp32 at the end.  cluster_of
+ *                [n_verts] int32, filled with -1 by the caller, gets c at every member.  One wave per run.
+ *   hm_mesh_simplify_face_flags: fkeep [n_faces] int32 = 1 for the faces whose three vertices lie in three different
+ *                clusters, else 0.
+ *   hm_mesh_simplify_dedupe: fpre is the exclusive prefix sum of fkeep (int32) and n_tri its total.  tri [3, n_tri]
+ *                int32 receives the kept faces' cluster triples in face order, one row per corner, each triple rotated
+ *                cyclically so that its smallest id comes first.  Three stable sorts by the third, second and first id
+ *                order them; tkeep [n_tri] int32 = 0 for a triple equal to its predecessor in that order (a repeat of
+ *                an earlier face), else 1; cused [n_clusters] int32, zeroed by the caller, gets 1 at the clusters of
+ *                the triples with tkeep = 1.  workspace: hm_mesh_simplify_dedupe_workspace_bytes(n_tri).
+ *   hm_mesh_simplify_emit: cpre / tpre are the exclusive prefix sums of cused / tkeep (int32) and n_verts_out /
+ *                n_faces_out their totals.  verts_out / normals_out [n_verts_out, 3] are the marked clusters' rep /
+ *                rep_normals in ascending order (rep_normals may be NULL), faces_out [n_faces_out, 3] the triples with
+ *                tkeep = 1 in order with id c replaced by cpre[c], vertex_map [n_verts] int32 = cpre of the vertex'
+ *                cluster, or -1 for a vertex of no face or of an unmarked cluster. */
+HM_API int64_t hm_mesh_simplify_keys_workspace_bytes(int64_t n_verts);
+HM_API int hm_mesh_simplify_keys(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                                 const float *lo, float h, const int32_t *g, int32_t *used, int32_t *keys_sorted,
+                                 int64_t *perm, int32_t *head, void *workspace, int64_t workspace_bytes,
+                                 int32_t *status, void *stream);
+HM_API int hm_mesh_simplify_clusters(const float *verts, const float *normals, int64_t n_verts,
+                                     const int32_t *keys_sorted, const int64_t *perm, const int64_t *start,
+                                     int64_t n_clusters, const float *lo, float h, const int32_t *g, int quadric,
+                                     double reg, float *rep, float *rep_normals, int32_t *cluster_of, void *stream);
+HM_API int hm_mesh_simplify_face_flags(const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                                       const int32_t *cluster_of, int64_t n_clusters, int32_t *fkeep, void *stream);
+HM_API int64_t hm_mesh_simplify_dedupe_workspace_bytes(int64_t n_tri);
+HM_API int hm_mesh_simplify_dedupe(const int32_t *faces, int64_t n_faces, int64_t n_verts, const int32_t *cluster_of,
+                                   int64_t n_clusters, const int32_t *fkeep, const int32_t *fpre, int64_t n_tri,
+                                   int32_t *tri, int32_t *tkeep, int32_t *cused, void *workspace,
+                                   int64_t workspace_bytes, void *stream);
+HM_API int hm_mesh_simplify_emit(const float *rep, const float *rep_normals, int64_t n_clusters, const int32_t *cused,
+                                 const int32_t *cpre, int64_t n_verts_out, const int32_t *tri, int64_t n_tri,
+                                 const int32_t *tkeep, const int32_t *tpre, int64_t n_faces_out,
+                                 const int32_t *cluster_of, int64_t n_verts, float *verts_out, float *normals_out,
+                                 int32_t *faces_out, int32_t *vertex_map, void *stream);
+
 /* ---- Chamfer evaluation: exact nearest neighbours on a uniform grid, deterministic triangle upsampling ---------
  * The device side of the reference's DTU Chamfer evaluation (code/evaluation/dtu_eval): upsample every triangle to a
  * point density, nearest-neighbour distances between two clouds.  Driver: ops.nn_index, ops.nearest_neighbors,
