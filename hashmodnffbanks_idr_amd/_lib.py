@@ -147,6 +147,12 @@ SIGNATURES = {
     "hm_image_sqerr": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
     "hm_image_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "hm_image_ssim": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, C.c_double, C.c_double, _p, _p, _p, _p]),
+    # culling by camera masks and visibility: per-vertex view votes, depth maps of the mesh, the keep flags
+    "hm_mesh_mask_votes": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _int, _p, _p, _p]),
+    "hm_mesh_depth_workspace_bytes": (_i64, [_i64, _i64]),
+    "hm_mesh_depth_maps": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    "hm_mesh_visible_votes": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, C.c_float, _int, _p, _p]),
+    "hm_mesh_keep_mark": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p]),
 }
 
 

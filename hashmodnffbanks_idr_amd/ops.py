@@ -1584,12 +1584,22 @@ def mesh_select(verts, faces, normals, label, component_id):
         raise ValueError("hashmod mesh_select: component_id does not fit int32")
     check(L.hm_mesh_select_mark(dptr(faces), n_faces, n_verts, dptr(label), component_id, dptr(vflag), dptr(fflag),
                                 dptr(status), st))
+    return _mesh_emit_flagged("mesh_select", verts, faces, normals, vflag, fflag, status)
+
+
+def _mesh_emit_flagged(what, verts, faces, normals, vflag, fflag, status):
+    """the tail mesh_select and mesh_keep_vertices share: prefix sums of the int32 flags a mark kernel wrote, one host
+    read of the two counts and the status word, hm_mesh_select_emit"""
+    n_faces, n_verts = int(faces.shape[0]), int(verts.shape[0])
+    dev = faces.device
+    L = lib()
+    st = stream_ptr(faces)
     vincl = torch.cumsum(vflag, 0, dtype=torch.int32)
     fincl = torch.cumsum(fflag, 0, dtype=torch.int32)
     zero = torch.zeros(1, dtype=torch.int32, device=dev)
     nv, nf, bad = torch.cat([vincl[-1:] if n_verts else zero, fincl[-1:] if n_faces else zero, status]).tolist()
     if bad:
-        _check_mesh_status("mesh_select", status)
+        _check_mesh_status(what, status)
     vpre, fpre = vincl - vflag, fincl - fflag
     verts_out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     faces_out = torch.empty((nf, 3), dtype=torch.int32, device=dev)
@@ -2213,3 +2223,162 @@ def image_ssim(x, y, data_range=1.0, win=11, sigma=1.5, k1=0.01, k2=0.03, return
     check(lib_.hm_image_ssim(dptr(x), dptr(y), B, H, W, Cn, win, dptr(wdev), c1, c2, dptr(smap), dptr(ws), dptr(out),
                              stream_ptr(x)))
     return (out, smap) if return_map else out
+
+
+# =========================================================================================
+# Mesh culling by camera masks and visibility (csrc/hm_mesh_cull.hip, DESIGN.md "Mesh culling on the device")
+# =========================================================================================
+_CULL_WS = _lib.Workspace("mesh_depth_maps")
+CULL_BIG_FACE = 64          # pixels of a face's clamped bounding box above which one wave draws it instead of one lane
+CULL_MAX_IMAGE = 65536      # H and W; and H*W < 2^31
+CULL_MAX_PAD = 64
+
+
+def _check_views(what, verts, proj, H=None, W=None):
+    """(V, n) after the checks the vote and raster ops share: contiguous fp32 verts [V,3]; proj float64 [n,3,4] as a
+    numpy array or a tensor; the image size, when given, within the kernels' range"""
+    _check_cloud(what, "verts", verts)
+    if isinstance(proj, torch.Tensor):
+        ok = proj.dtype == torch.float64 and proj.dim() == 3 and tuple(proj.shape[1:]) == (3, 4)
+    else:
+        ok = isinstance(proj, np.ndarray) and proj.dtype == np.float64 and proj.ndim == 3 and proj.shape[1:] == (3, 4)
+    if not ok:
+        raise ValueError(f"hashmod {what}: float64 proj [n, 3, 4] expected (evaluation.cull.view_projections)")
+    if H is not None:
+        if not (isinstance(H, int) and isinstance(W, int) and 1 <= H <= CULL_MAX_IMAGE and 1 <= W <= CULL_MAX_IMAGE
+                and H * W < 1 << 31):
+            raise ValueError(f"hashmod {what}: H and W must be integers in [1, {CULL_MAX_IMAGE}] with H*W < 2^31")
+    return int(verts.shape[0]), int(proj.shape[0])
+
+
+def _device_proj(proj, device):
+    if not isinstance(proj, torch.Tensor):
+        proj = torch.from_numpy(np.ascontiguousarray(proj))
+    return proj.to(device).contiguous()
+
+
+def _mask_table(masks):
+    """the summed-area table [n, H+1, W+1] int32 of masks [n, H, W]: table[v, r, c] = the non-zero pixels of view v in
+    rows < r and columns < c (torch plumbing: n*H*W adds, once per scan)"""
+    n, H, W = masks.shape
+    sat = torch.zeros((n, H + 1, W + 1), dtype=torch.int32, device=masks.device)
+    sat[:, 1:, 1:] = torch.cumsum(torch.cumsum(masks != 0, 2, dtype=torch.int32), 1, dtype=torch.int32)
+    return sat
+
+
+def mesh_mask_votes(verts, proj, masks, dilate, table_bytes=1 << 28):
+    """(n_in_image [V] int32, n_in_mask [V] int32) of verts [V,3] fp32 against the views proj [n,3,4] float64 (host or
+    device) and their masks [n,H,W] bool or uint8 on the device.  A view counts in n_in_image iff the vertex is
+    projectable (finite, w finite and > 0, p = P @ (x, y, z, 1) in fp64 rounded once per operation) and its pixel
+    (rint(u), rint(v)), half to even, is in the image; it also counts in n_in_mask iff a mask pixel within `dilate`
+    pixels (a (2 dilate + 1)^2 square, cv2.dilate with ones; zero outside the image) is non-zero.  The masks become a
+    summed-area table by two torch.cumsum calls, `table_bytes` of it at a time, and one lane per vertex loops over the
+    views with four table reads each; no atomics.  tests/mesh_cull_cases.mask_votes_ref gives the same bits."""
+    n_verts, n_views = _check_views("mesh_mask_votes", verts, proj)
+    if (not isinstance(masks, torch.Tensor) or masks.dtype not in (torch.bool, torch.uint8) or masks.dim() != 3
+            or masks.shape[0] != n_views):
+        raise ValueError("hashmod mesh_mask_votes: bool or uint8 masks [n, H, W] expected, one per view")
+    H, W = int(masks.shape[1]), int(masks.shape[2])
+    _check_views("mesh_mask_votes", verts, proj, H, W)
+    if not (isinstance(dilate, int) and not isinstance(dilate, bool) and dilate >= 0):
+        raise ValueError("hashmod mesh_mask_votes: dilate must be an integer >= 0")
+    if masks.device != verts.device:
+        raise ValueError("hashmod mesh_mask_votes: the tensors are on different devices")
+    require_gpu(verts, masks)
+    dev = verts.device
+    proj = _device_proj(proj, dev)
+    n_img = torch.zeros(n_verts, dtype=torch.int32, device=dev)
+    n_msk = torch.zeros(n_verts, dtype=torch.int32, device=dev)
+    per = max(1, int(table_bytes) // (4 * (H + 1) * (W + 1)))
+    for v0 in range(0, n_views, per):
+        sat = _mask_table(masks[v0:v0 + per])
+        check(lib().hm_mesh_mask_votes(dptr(verts), n_verts, dptr(proj[v0:]), int(sat.shape[0]), dptr(sat), H, W,
+                                       min(dilate, CULL_MAX_IMAGE), 1 if v0 else 0, dptr(n_img), dptr(n_msk),
+                                       stream_ptr(verts)))
+    return n_img, n_msk
+
+
+def mesh_depth_maps(verts, faces, proj, H, W, big_face=CULL_BIG_FACE):
+    """(depth [n,H,W] fp32, n_skipped [n] int32): the mesh's nearest surface per pixel of every view, +inf where nothing
+    is drawn.  Per view every vertex is projected once (fixed-point X = rint(256 u), Y = rint(256 v) and 1/w); a face
+    with an unprojectable corner or a position beyond |X|, |Y| < 2^24 is skipped and counted - there is NO clipping:
+    the cameras are expected outside the object.  Coverage: the pixel centres (256 col, 256 row) of the face's clamped
+    bounding box whose three int64 edge functions are all >= 0 or all <= 0 (both windings, inclusive edges; zero area
+    draws nothing).  Depth: perspective-correct, z = 1/((b0/w0 + b1/w1) + b2/w2) in fp64 rounded once per operation,
+    then to fp32, kept when finite and > 0 by an unsigned atomicMin on its bits - the result does not depend on the
+    order of the faces and two calls give the same bits (tests/mesh_cull_cases.depth_map_ref gives them too).  A face
+    whose clamped box exceeds `big_face` pixels is listed and drawn by one wave, any other by one lane.  A face index
+    outside [0, V) raises HashmodError.  One host read of the status word; not graph-capturable."""
+    n_verts, n_views = _check_views("mesh_depth_maps", verts, proj, H, W)
+    if not (isinstance(big_face, int) and big_face >= 1):
+        raise ValueError("hashmod mesh_depth_maps: big_face must be an integer >= 1")
+    n_faces, _ = _check_mesh("mesh_depth_maps", faces, verts=verts, gpu_first=False)
+    dev = verts.device
+    proj = _device_proj(proj, dev)
+    depth = torch.empty((n_views, H, W), dtype=torch.float32, device=dev)
+    n_skipped = torch.empty(n_views, dtype=torch.int32, device=dev)
+    if n_views == 0:
+        return depth, n_skipped
+    L = lib()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _CULL_WS.get(dev, check(L.hm_mesh_depth_workspace_bytes(n_verts, n_faces)))
+    check(L.hm_mesh_depth_maps(dptr(verts), n_verts, dptr(faces), n_faces, dptr(proj), n_views, H, W, big_face,
+                               dptr(depth), dptr(n_skipped), dptr(ws), ws.numel(), dptr(status), stream_ptr(verts)))
+    _check_mesh_status("mesh_depth_maps", status)
+    return depth, n_skipped
+
+
+def mesh_visible_votes(verts, proj, depth, pad=1, tol=0.0, out=None):
+    """n_visible [V] int32: the views of proj [n,3,4] in which the vertex is projectable, in the image, and
+    float32(w) <= m + float32(tol), m = the maximum of depth [n,H,W] (mesh_depth_maps) over the (2 pad + 1)^2 pixels
+    around the vertex' pixel, indices clamped to the image.  The neighbourhood maximum makes the rule conservative: a
+    marching-cubes vertex rarely projects onto the pixel centre its own faces were sampled at, so the single-pixel rule
+    (pad = 0) loses about half of the front-facing vertices, and a depth tolerance does not bring all of them back;
+    with pad = 1, tol = 0 none is lost.  The price is that back-facing vertices within `pad` pixels of the silhouette
+    also count as visible: for culling, keeping too much at the rim is the right direction.  `out` [V] int32, when
+    given, is added to (the next chunk of views) and returned."""
+    n_verts, n_views = _check_views("mesh_visible_votes", verts, proj)
+    if (not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3
+            or depth.shape[0] != n_views or not depth.is_contiguous()):
+        raise ValueError("hashmod mesh_visible_votes: contiguous fp32 depth [n, H, W] expected, one map per view")
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    _check_views("mesh_visible_votes", verts, proj, H, W)
+    if not (isinstance(pad, int) and not isinstance(pad, bool) and 0 <= pad <= CULL_MAX_PAD):
+        raise ValueError(f"hashmod mesh_visible_votes: pad must be an integer in [0, {CULL_MAX_PAD}]")
+    if not (isinstance(tol, (int, float)) and not math.isnan(tol)):
+        raise ValueError("hashmod mesh_visible_votes: tol must be a number")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.shape != (n_verts,)
+                            or not out.is_contiguous()):
+        raise ValueError("hashmod mesh_visible_votes: contiguous int32 out [V] expected")
+    for t in (depth, out):
+        if t is not None and t.device != verts.device:
+            raise ValueError("hashmod mesh_visible_votes: the tensors are on different devices")
+    require_gpu(verts, depth, out)
+    dev = verts.device
+    proj = _device_proj(proj, dev)
+    n_vis = torch.zeros(n_verts, dtype=torch.int32, device=dev) if out is None else out
+    check(lib().hm_mesh_visible_votes(dptr(verts), n_verts, dptr(proj), n_views, dptr(depth), H, W, pad, float(tol),
+                                      0 if out is None else 1, dptr(n_vis), stream_ptr(verts)))
+    return n_vis
+
+
+def mesh_keep_vertices(verts, faces, normals, keep):
+    """(verts, faces, normals or None) of the faces whose three vertices have keep [V] bool set: the surviving vertices
+    are those a surviving face uses, in ascending original order; the faces stay in order and are renumbered; the
+    normals are gathered like the vertices - mesh_select's conventions (np.unique(faces[kept], return_inverse=True)),
+    and its emit kernels.  A face index outside [0, V) raises HashmodError (reported by the kernel, never
+    dereferenced).  One host read of the counts; not graph-capturable."""
+    _check_cloud("mesh_keep_vertices", "verts", verts)
+    if (not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.shape != (verts.shape[0],)
+            or not keep.is_contiguous()):
+        raise ValueError("hashmod mesh_keep_vertices: contiguous bool keep [V] expected")
+    if keep.device != verts.device:
+        raise ValueError("hashmod mesh_keep_vertices: the tensors are on different devices")
+    n_faces, n_verts = _check_mesh("mesh_keep_vertices", faces, verts=verts, normals=normals, gpu_first=False)
+    dev = faces.device
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    vflag = torch.zeros(n_verts, dtype=torch.int32, device=dev)
+    fflag = torch.empty(n_faces, dtype=torch.int32, device=dev)
+    check(lib().hm_mesh_keep_mark(dptr(faces), n_faces, n_verts, dptr(keep), dptr(vflag), dptr(fflag), dptr(status),
+                                  stream_ptr(faces)))
+    return _mesh_emit_flagged("mesh_keep_vertices", verts, faces, normals, vflag, fflag, status)

@@ -1002,6 +1002,54 @@ HM_API int hm_image_ssim(const float *x, const float *y, int64_t B, int64_t H, i
                          const double *weights, double c1, double c2, double *map, double *partial_ws, double *out,
                          void *stream);
 
+/* ---- mesh culling: camera-mask votes, depth maps of the mesh, visibility votes, compaction -------------------------
+ * Removes what no camera could have constrained: geometry that projects outside the (dilated) object masks and geometry
+ * hidden from every camera.  Driver: ops.mesh_mask_votes, ops.mesh_depth_maps, ops.mesh_visible_votes,
+ * ops.mesh_keep_vertices, evaluation.cull.cull_mesh.  csrc/hm_mesh_cull.hip, csrc/hm_view_dev.h.  No entry point
+ * synchronises; n_verts, n_faces, n_views in [0, 2^31); H, W in [1, 65536] with H*W < 2^31.
+ * A view is proj [n_views, 3, 4] DEVICE fp64, P = K[:3,:3] @ inv(pose)[:3,:4]; pixel (col, row) has its centre at
+ * uv = (col, row).  A vertex (fp32, cast to fp64; every operation rounded once, no contraction):
+ *     p_a = ((P[a,0]*x + P[a,1]*y) + P[a,2]*z) + P[a,3],  w = p_2,  u = p_0 / w,  v = p_1 / w
+ *   unprojectable: a non-finite coordinate, or w <= 0, or w not finite
+ *   pixel          col = rint(u), row = rint(v) (half to even); in the image iff 0 <= col < W and 0 <= row < H
+ *   fixed point    X = rint(256 u), Y = rint(256 v), valid iff |X| < 2^24 and |Y| < 2^24; pixel centres at (256 col, 256 row)
+ * every range test is made on doubles before a value becomes an integer: a NaN or a huge value fails it, nothing is read.
+ *   hm_mesh_mask_votes: sat [n_views, H+1, W+1] int32 the summed-area table of the masks (sat[v][r][c] = set pixels in
+ *                rows < r and columns < c).  Per vertex: n_in_image = the views that have it in the image; n_in_mask =
+ *                those where also a mask pixel (c, r') with |c - col| <= dilate and |r' - row| <= dilate inside the
+ *                image is set (a (2 dilate + 1)^2 square element, zero outside the image).  accumulate != 0 adds to the
+ *                arrays (the next chunk of views) instead of writing them.  No atomics.
+ *   hm_mesh_depth_maps: depth [n_views, H, W] fp32 = the nearest surface per pixel, +inf where nothing is drawn;
+ *                n_skipped [n_views] int32.  Per face and view: a face with an unprojectable corner or an invalid
+ *                fixed-point position is skipped and counted (no clipping).  area = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0) in
+ *                int64; 0 draws nothing.  For the pixel centres (Xp, Yp) inside the face's bounding box clamped to the
+ *                image, E_a = (X_c-X_b)(Yp-Y_b) - (Y_c-Y_b)(Xp-X_b), (b, c) = (a+1, a+2) mod 3; covered iff all E_a >= 0
+ *                or all E_a <= 0 (both windings, inclusive edges).  b_a = double(E_a)/double(area), iw_a = 1/w_a,
+ *                z = 1/((b_0 iw_0 + b_1 iw_1) + b_2 iw_2) rounded to fp32, stored when finite and > 0 by an unsigned
+ *                atomicMin on its bits: independent of the order of the faces, two calls give the same bits.  A face
+ *                whose clamped box has more than big_face (>= 1) pixels is drawn by one wave, any other by one lane.
+ *                A face index outside [0, n_verts) sets bit 0 of status [1] int32 and is never dereferenced.
+ *                workspace: hm_mesh_depth_workspace_bytes(n_verts, n_faces) bytes, reused view after view.
+ *   hm_mesh_visible_votes: n_visible = the views that have the vertex in the image with
+ *                float(w) <= m + tol (fp32), m = the maximum of depth over the (2 pad + 1)^2 pixels around (col, row),
+ *                indices clamped to the image; pad in [0, 64].  accumulate as above.
+ *   hm_mesh_keep_mark: fflag [n_faces] int32 = 1 for the faces whose three vertices have keep [n_verts] (bytes) set,
+ *                vflag [n_verts] int32 (zeroed by the caller) = 1 for their vertices; out-of-range indices as above.
+ *                hm_mesh_select_emit then writes the mesh. */
+HM_API int hm_mesh_mask_votes(const float *verts, int64_t n_verts, const double *proj, int64_t n_views,
+                              const int32_t *sat, int64_t H, int64_t W, int64_t dilate, int accumulate,
+                              int32_t *n_in_image, int32_t *n_in_mask, void *stream);
+HM_API int64_t hm_mesh_depth_workspace_bytes(int64_t n_verts, int64_t n_faces);
+HM_API int hm_mesh_depth_maps(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                              const double *proj, int64_t n_views, int64_t H, int64_t W, int64_t big_face, float *depth,
+                              int32_t *n_skipped, void *workspace, int64_t workspace_bytes, int32_t *status,
+                              void *stream);
+HM_API int hm_mesh_visible_votes(const float *verts, int64_t n_verts, const double *proj, int64_t n_views,
+                                 const float *depth, int64_t H, int64_t W, int64_t pad, float tol, int accumulate,
+                                 int32_t *n_visible, void *stream);
+HM_API int hm_mesh_keep_mark(const int32_t *faces, int64_t n_faces, int64_t n_verts, const uint8_t *keep,
+                             int32_t *vflag, int32_t *fflag, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
