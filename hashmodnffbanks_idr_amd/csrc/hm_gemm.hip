@@ -1077,6 +1077,16 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
         off = 0;
         return HM_OK;
     };
+    // deterministic: does the problem's C window overlap one of a problem waiting in the table?
+    auto overlaps_table = [&](const hm_gemm_group_item &it) {
+        for (int p = 0; det && p < t.n; ++p) {
+            uintptr_t a0, a1, b0, b1;
+            window(it, a0, a1);
+            window(items[in_table[p]], b0, b1);
+            if (!(a1 <= b0 || b1 <= a0)) return true;
+        }
+        return false;
+    };
     for (int i = 0; i < n_items; ++i) {
         const hm_gemm_group_item &it = items[i];
         HM_CHECK_ARG(it.M >= 0 && it.N >= 0 && it.K >= 0 && it.M < (1ll << 31) && it.N < (1ll << 31) && it.K < (1ll << 31),
@@ -1085,7 +1095,12 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
         HM_CHECK_ARG(!run || (it.A && it.B && it.C && it.lda >= it.M && it.ldb >= it.N && it.ldc >= it.N),
                      std::string(who) + ": NULL operand or leading dimension");
         if (it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31)) {
-            // no K tail in the pipelined kernel, 32-bit operand offsets: such a problem goes alone
+            // no K tail in the pipelined kernel, 32-bit operand offsets: such a problem goes alone, at once - so the
+            // table goes first when this problem adds into the C of a problem waiting in it (item order)
+            if (overlaps_table(it)) {
+                const int rc = flush();
+                if (rc != HM_OK) return rc;
+            }
             if (det) {
                 const int64_t b = gemm_det_bytes(gemm_plan(1, 0, it.M, it.N, it.K, nullptr, it.lda, nullptr, it.ldb, false), it.M, it.N);
                 if (b > *need) *need = b;
@@ -1097,14 +1112,7 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
             }
             continue;
         }
-        bool overlap = false;
-        for (int p = 0; det && p < t.n && !overlap; ++p) {
-            uintptr_t a0, a1, b0, b1;
-            window(it, a0, a1);
-            window(items[in_table[p]], b0, b1);
-            overlap = !(a1 <= b0 || b1 <= a0);
-        }
-        if (t.n == HM_GEMM_GROUP_MAX || overlap) {
+        if (t.n == HM_GEMM_GROUP_MAX || overlaps_table(it)) {
             const int rc = flush();
             if (rc != HM_OK) return rc;
         }

@@ -606,7 +606,9 @@ HM_API int hm_adam_step_dev(const hm_adam_tensor *tensors, int n_tensors, const 
  * row-major with leading dimensions, C_p [M, N] accumulated with fp32 atomics - the caller zeroes it, like the
  * reference's optimizer.zero_grad()).  Replaces the per-layer grad_weight GEMMs autograd runs for nn.Linear in
  * ImplicitNetwork / RenderingNetwork (implicit_differentiable_renderer.py:102,211-221).  K a multiple of 128 takes the
- * grouped kernel, any other K falls back to hm_gemm_f32 for that item.  items is a [host] array.                     */
+ * grouped kernel, any other K falls back to hm_gemm_f32 for that item, and so does an item whose A or B spans 2 GB or
+ * more (4 * lda * K or 4 * ldb * K >= 2^31: the grouped kernel forms 32-bit operand offsets).  Items with M, N or K
+ * equal to 0 are skipped.  items is a [host] array.                                                                 */
 #define HM_GEMM_GROUP_MAX 16
 typedef struct hm_gemm_group_item {
     const float *A, *B;
@@ -631,8 +633,9 @@ HM_API int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t
                            void *workspace, int64_t workspace_bytes, void *stream);
 /* hm_gemm_f32_group_tn (the weight gradients of one backward pass): the same problem table and k parts, partials of
  * every problem to the workspace in one launch, one reduce launch for all problems.  Items whose C windows overlap
- * (two terms of one weight gradient) go to consecutive launches and are added in item order.  The workspace query
- * returns -1 on a bad item.                                                                                        */
+ * (two terms of one weight gradient) go to consecutive launches and are added in item order - an item that falls back
+ * to hm_gemm_f32_det included: the call gives the bits of consecutive one-item calls.  The workspace query returns -1
+ * on a bad item.                                                                                                    */
 HM_API int64_t hm_gemm_f32_group_tn_det_workspace_bytes(const hm_gemm_group_item *items, int n_items);
 HM_API int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void *workspace,
                                     int64_t workspace_bytes, void *stream);
