@@ -55,6 +55,7 @@ SIGNATURES = {
     "hm_trace_workspace_bytes": (_i64, [_i64, _p]),
     "hm_trace_guard_clear": (_int, [_p, _i64, _p]),
     "hm_trace_guard_tolerances": (_int, [_p, _p]),
+    "hm_trace_scan_pool_plan": (_int, [_i64, _i64, _i64, _int, _int, _i64, _int, _i64, _p, _p]),
     "hm_trace_forward": (_int, [_p, _p, _p, _p, _int, _int, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
                                 _i64, _p, _p]),
     "hm_trace_workspace_bytes_nffb": (_i64, [_i64, _p, _int]),

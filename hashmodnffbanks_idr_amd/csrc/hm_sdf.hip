@@ -59,6 +59,7 @@ __device__ unsigned long long hm_probe_ts[128];
 
 #include "hm_sdf_tile64.h"        // sdf64_run: the 64-point fp32 tile body
 #include "hm_sdf_split_tile.h"    // sdf_split_tile: the 64-point f16x2 / bf16x2 tile body (sdf_refine_scan_kernel)
+#include "hm_scan_pool.h"         // scan_pool_quota: the closest-approach scan's tiles per launch of the guarded search
 
 // ... of the small tiles (pts = 16 or 8 points in the LDS image): two activation images + the embedding in whole
 // 16-blocks.  (The 8-point layout needs half of the 16-point one, which is what every launch asks for.)
@@ -591,40 +592,82 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevel
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Guarded coarse scans (hm_trace.hip): the exact refinement of the sampler's marked samples and the approximate
-// closest-approach scan in ONE launch.  The refinement list is ~90 fp32 tiles, one ~0.47 ms round on a third of the chip;
-// the closest-approach scan (1200 split tiles at the bench workload) depends on neither the sampler's values nor their
-// refinement.  Every workgroup first takes fp32 64-point tiles of the list (sdf64_run with the atomic cursor: the tiles
-// and values of the stand-alone refinement launch), then split tiles of the scan from a second cursor (the tile of
-// sdf_fwd_split_kernel: a tile's values do not depend on the workgroup that runs it).  The workgroups that got no fp32
-// tile start on the scan at once; nothing is exchanged between workgroups.  Both cursors are zero at launch.
-// scan_min: shorter scans ran on the exact small-tile launch in front of this one.
+// Guarded coarse scans (hm_trace.hip): the exact refinement of a list of the sampler's marked samples and split tiles of the
+// approximate closest-approach scan in ONE launch.  The refinement list is ~190 fp32 half tiles, one round on part of the
+// chip; the closest-approach scan (1200 split tiles at the bench workload) depends on neither the sampler's values nor
+// their refinement.  Every workgroup first takes fp32 64-point tiles of the list (sdf64_run with the atomic cursor: the
+// tiles and values of the stand-alone refinement launch), then split tiles of this launch's range of the scan
+// (hm_scan_pool.h: one per workgroup that got no fp32 tile, plus what would not fit under the secant chain) from a second
+// cursor (the tile of sdf_fwd_split_kernel: a tile's values do not depend on the workgroup or the launch that runs it).
+// The workgroups that got no fp32 tile start on the scan at once; nothing is exchanged between workgroups.  Both cursors
+// are zero at launch.  which = 0 / 1: the launch of the list cnt[c_ref1] / of cnt[c_ref2] (lazy sampler, second pass).
+template <int KIND, int FRAC>
+__device__ __forceinline__ void split_scan_range(const HmLevels &lv, const SdfNet &net_split, const float *__restrict__ table,
+                                                 const float *__restrict__ Bf, const TraceArgs &a, int64_t scan_off,
+                                                 int64_t n_scan, int64_t first, int64_t quota, unsigned *cursor, float *lds) {
+    __shared__ unsigned s_scan_tile;
+    if (quota <= 0) return;
+    for (;;) {
+        __syncthreads();   // every thread has read the previous hand-out (and is done with the other tiles' LDS)
+        if (threadIdx.x == 0) s_scan_tile = atomicAdd(cursor, 1u);
+        __syncthreads();
+        const int64_t k = s_scan_tile;
+        if (k >= quota) break;
+        sdf_split_tile<KIND, FRAC>(lv, net_split, a.w.pts + scan_off * 3, n_scan, table, Bf, a.w.vals + scan_off, 1, lds,
+                                   first + k);
+    }
+}
+
 template <int KIND, int FRAC>
 __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_refine_scan_kernel(HmLevels lv, SdfNet net, SdfNet net_split,
                                                                           const float *__restrict__ table,
                                                                           const float *__restrict__ Bf, TraceArgs a,
-                                                                          int c_ref, int64_t scan_off, int64_t scan_min) {
+                                                                          int c_ref1, int c_ref2, int which,
+                                                                          int64_t scan_off, int64_t chain_tiles) {
     extern __shared__ __align__(16) float lds[];
-    __shared__ unsigned s_scan_tile;
-    const int64_t n_ref = min((int64_t)max(a.w.cnt[c_ref], 0), a.w.cap);
+    const int64_t n_ref1 = min((int64_t)max(a.w.cnt[c_ref1], 0), a.w.cap);
+    const int64_t n_ref2 = which ? min((int64_t)max(a.w.cnt[c_ref2], 0), a.w.cap) : 0;   // (not final in the first launch)
+    const int64_t n_ref = which ? n_ref2 : n_ref1;
     const int64_t n_scan = min((int64_t)max(a.w.cnt[C_NSEL_PTS], 0), a.w.cap);
     if (n_ref > 0) {
         const SdfFill none = {nullptr, nullptr, 0, 0};
         sdf64_run<FRAC, true>(lv, net, a.w.ref_pts, n_ref, table, Bf, a.w.ref_vals, 1, 1, lds,
-                              reinterpret_cast<unsigned *>(a.w.cnt + C_XREF_CURSOR), none);
+                              reinterpret_cast<unsigned *>(a.w.cnt + (which ? C_XREF2_CURSOR : C_XREF_CURSOR)), none);
     }
-    if (n_scan < scan_min) return;
-    const int64_t n_tiles = (n_scan + kPS - 1) / kPS;
-    unsigned *cursor = reinterpret_cast<unsigned *>(a.w.cnt + C_XSCAN_CURSOR);
-    for (;;) {
-        __syncthreads();   // every thread has read the previous hand-out (and is done with the fp32 tiles' LDS)
-        if (threadIdx.x == 0) s_scan_tile = atomicAdd(cursor, 1u);
-        __syncthreads();
-        const int64_t tile = s_scan_tile;
-        if (tile >= n_tiles) break;
-        sdf_split_tile<KIND, FRAC>(lv, net_split, a.w.pts + scan_off * 3, n_scan, table, Bf, a.w.vals + scan_off, 1, lds,
-                                   tile);
+    const ScanPool p = scan_pool_quota(n_scan, n_ref1, n_ref2, c_ref2 >= 0, gridDim.x, a.w.cnt[C_NSAMP], chain_tiles);
+    // (constant indices: a run-time index would put the struct into scratch)
+    split_scan_range<KIND, FRAC>(lv, net_split, table, Bf, a, scan_off, n_scan, which ? p.first[1] : p.first[0],
+                                 which ? p.quota[1] : p.quota[0],
+                                 reinterpret_cast<unsigned *>(a.w.cnt + (which ? C_XSCAN2_CURSOR : C_XSCAN_CURSOR)), lds);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Guarded coarse scans: the secant chain and the REST of the closest-approach scan's split tiles in ONE launch.  The chain
+// is eight dependent rounds of ~60 16-point tiles, a pure latency chain of about a millisecond; the scan's tiles that the
+// refine-scan launches in front left over (hm_scan_pool.h: as many as fit under the chain) run on every other workgroup
+// meanwhile, and the secant's workgroups join when their chain is done.  secant_role is sdf_scan_secant_kernel's (the tile
+// rule reads the scan's length, so the secant's values are those of every other form of the search); the tiles are
+// sdf_refine_scan_kernel's.  No workgroup waits for another.  grid_x: workgroups of the refine-scan launches.
+template <int KIND, int FRAC>
+__global__ __launch_bounds__(kThreadsSdf, 2) void sdf_split_scan_secant_kernel(HmLevels lv, SdfNet net, SdfNet net_split,
+                                                                                const float *__restrict__ table,
+                                                                                const float *__restrict__ Bf, TraceArgs a,
+                                                                                int n_iters, int64_t m8_max, int64_t m4_max,
+                                                                                int64_t scan_hide, int c_ref1, int c_ref2,
+                                                                                int grid_x, int64_t scan_off,
+                                                                                int64_t chain_tiles) {
+    extern __shared__ __align__(16) float lds[];
+    const int64_t n_sec = a.w.cnt[C_NSEC];
+    if (n_sec > 0 && n_iters > 0) {
+        const int pts = a.w.cnt[C_NSEL_PTS] >= scan_hide ? 16 : (n_sec <= m4_max ? 4 : (n_sec <= m8_max ? 8 : 16));
+        secant_role<FRAC>(lv, net, table, Bf, a, n_iters, n_sec, pts, lds);
     }
+    const int64_t n_scan = min((int64_t)max(a.w.cnt[C_NSEL_PTS], 0), a.w.cap);
+    const int64_t n_ref1 = min((int64_t)max(a.w.cnt[c_ref1], 0), a.w.cap);
+    const int64_t n_ref2 = c_ref2 >= 0 ? min((int64_t)max(a.w.cnt[c_ref2], 0), a.w.cap) : 0;
+    const ScanPool p = scan_pool_quota(n_scan, n_ref1, n_ref2, c_ref2 >= 0, grid_x, a.w.cnt[C_NSAMP], chain_tiles);
+    split_scan_range<KIND, FRAC>(lv, net_split, table, Bf, a, scan_off, n_scan, p.first[2], p.quota[2],
+                                 reinterpret_cast<unsigned *>(a.w.cnt + C_YSCAN_CURSOR), lds);
 }
 
 // network descriptor -> kernel argument for the exact-fp32 kernels (sdf_net_from_desc)
@@ -670,6 +713,13 @@ static unsigned sdf_small_grid(int64_t n, SmallTiles t, int64_t cap) {
     if (t.m8_max > 0) tiles = max(tiles, ((n < t.m8_max ? n : t.m8_max) + kPts8 - 1) / kPts8);
     if (t.m4_max > 0) tiles = max(tiles, ((n < t.m4_max ? n : t.m4_max) + 3) / 4);
     return (unsigned)(tiles < cap ? tiles : cap);
+}
+
+// workgroups of a refine-scan launch (and of the stand-alone refinement launch it stands for) over a refinement region of
+// `cap` points: up to one 32-point half tile of the list per workgroup
+static unsigned refine_scan_grid(int64_t cap) {
+    const int64_t tiles = (cap + 31) / 32;
+    return (unsigned)(tiles < 256 ? tiles : 256);
 }
 
 // hm_frac_dispatch + the precomputed-embedding form of the kernels (mode kFracEmb)
@@ -849,12 +899,18 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
 // ref_pts -> ref_vals (count cnt[c_ref]) and the approximate closest-approach scan (scan_capacity points at pts + scan_off,
 // count cnt[C_NSEL_PTS]) in one launch (sdf_refine_scan_kernel); scans of <= kSdfSmall points run on the exact small-tile
 // launch in front of it, as in hm_sdf_fwd_split's callers.  tile_points = 0 only.
+// The launch runs its range of the scan's split tiles (hm_scan_pool.h): which = 0 - the launch of the list cnt[c_ref1]
+// (the first one: it also enqueues the small-tile launch); which = 1 - of cnt[c_ref2], the lazy sampler's second pass.
+// c_ref2 < 0: there is no second launch.  chain_tiles: split tiles one workgroup finishes under the secant chain (0: the
+// whole scan runs in front of the chain).
 int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                         int frac_mode, const void *trace_args, int c_ref, int64_t scan_off, int64_t scan_capacity,
-                         void *stream) {
+                         int frac_mode, const void *trace_args, int c_ref1, int c_ref2, int which, int64_t scan_off,
+                         int64_t scan_capacity, int64_t chain_tiles, void *stream) {
     HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_refine_scan: NULL argument");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_refine_scan: bad frac_mode");
-    HM_CHECK_ARG(c_ref >= 0 && c_ref < C_COUNT, "hm_trace_refine_scan: bad list counter");
+    HM_CHECK_ARG(c_ref1 >= 0 && c_ref1 < C_COUNT && c_ref2 < C_COUNT, "hm_trace_refine_scan: bad list counter");
+    HM_CHECK_ARG((which == 0 || which == 1) && (which == 0 || c_ref2 >= 0) && chain_tiles >= 0,
+                 "hm_trace_refine_scan: bad launch index / chain capacity");
     const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
     static_assert(sizeof(HmLevels) + 2 * sizeof(SdfNet) + sizeof(TraceArgs) + 64 <= 4096, "kernel arguments exceed 4 KB");
     SdfNet net, net_split;
@@ -865,21 +921,22 @@ int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
     if (a.n == 0) return HM_OK;
     HM_CHECK_ARG(a.w.pts && a.w.vals && a.w.ref_pts && a.w.ref_vals && a.w.cnt, "hm_trace_refine_scan: NULL workspace pointer");
     HM_CHECK_ARG(scan_off >= 0 && scan_capacity >= 0 && scan_capacity <= a.w.cap, "hm_trace_refine_scan: bad scan region");
-    rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1, frac_mode,
-                    -1, a.w.cnt + C_NSEL_PTS, 0, stream);
-    if (rc != HM_OK) return rc;
+    if (which == 0) {
+        rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1,
+                        frac_mode, -1, a.w.cnt + C_NSEL_PTS, 0, stream);
+        if (rc != HM_OK) return rc;
+    }
     const size_t lds64 = sdf_lds64(net).bytes();
     HM_CHECK_ARG(lds64 <= kLds64Max - kLdsTrace && lds_split <= kLds64Max - kLdsTrace,
                  "hm_trace_refine_scan: network does not fit the LDS tiles");
     const size_t lds = lds_split > lds64 ? lds_split : lds64;
-    const int64_t tiles = (a.w.cap + 31) / 32;     // (up to one 32-point half tile of the list per workgroup)
-    const unsigned grid = (unsigned)(tiles < 256 ? tiles : 256);
+    const unsigned grid = refine_scan_grid(a.w.cap);
     const auto launch = [&](auto kind, auto frac) {
         constexpr auto kernel = sdf_refine_scan_kernel<decltype(kind)::value, decltype(frac)::value>;
         const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
         if (rc != HM_OK) return rc;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, net_split, table,
-                           B_fourier, a, c_ref, scan_off, (int64_t)kSdfSmall + 1);
+                           B_fourier, a, c_ref1, c_ref2, which, scan_off, chain_tiles);
         HM_CHECK_LAUNCH("hm_trace_refine_scan");
         return HM_OK;
     };
@@ -887,6 +944,62 @@ int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
         if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
         return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
     });
+}
+
+// internal entry of the ray search (hm_trace.hip, not exported), guarded coarse scans: the secant refinement and the split
+// tiles of the closest-approach scan that the hm_trace_refine_scan launches in front left over, in one launch
+// (sdf_split_scan_secant_kernel).  c_ref1 / c_ref2 / scan_off / chain_tiles: as given to those launches.
+int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
+                               const float *B_fourier, int frac_mode, const void *trace_args, int n_iters, int c_ref1,
+                               int c_ref2, int64_t scan_off, int64_t scan_capacity, int64_t chain_tiles, void *stream) {
+    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_split_scan_secant: NULL argument");
+    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR,
+                 "hm_trace_split_scan_secant: bad frac_mode");
+    HM_CHECK_ARG(c_ref1 >= 0 && c_ref1 < C_COUNT && c_ref2 < C_COUNT && chain_tiles >= 0,
+                 "hm_trace_split_scan_secant: bad list counter / chain capacity");
+    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
+    SdfNet net, net_split;
+    size_t lds_split = 0;
+    int rc = sdf_net_fp32("hm_trace_split_scan_secant", desc->lv, mlp, 0, kImgM16, net);
+    if (rc == HM_OK) rc = sdf_split_net("hm_trace_split_scan_secant", desc->lv.E, mlp, 0, net_split, &lds_split);
+    if (rc != HM_OK) return rc;
+    if (a.n == 0) return HM_OK;
+    HM_CHECK_ARG(a.w.pts && a.w.vals && a.w.cnt, "hm_trace_split_scan_secant: NULL workspace pointer");
+    HM_CHECK_ARG(scan_off >= 0 && scan_capacity >= 0 && scan_capacity <= a.w.cap, "hm_trace_split_scan_secant: bad scan region");
+    const size_t lds16 = sdf_lds_small(net, desc->lv.E, kPts16).bytes();
+    HM_CHECK_ARG(lds16 <= kLds16Max && lds_split <= kLds64Max - kLdsTrace,
+                 "hm_trace_split_scan_secant: network does not fit the LDS tiles");
+    const size_t lds = lds16 > lds_split ? lds16 : lds_split;
+    const int grid_x = (int)refine_scan_grid(a.w.cap);
+    const SmallTiles t = sdf_small_tiles(0);
+    const auto launch = [&](auto kind, auto frac) {
+        constexpr auto kernel = sdf_split_scan_secant_kernel<decltype(kind)::value, decltype(frac)::value>;
+        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, net_split, table,
+                           B_fourier, a, n_iters, t.m8_max, t.m4_max, (int64_t)kTraceScanHide, c_ref1, c_ref2, grid_x,
+                           scan_off, chain_tiles);
+        HM_CHECK_LAUNCH("hm_trace_split_scan_secant");
+        return HM_OK;
+    };
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
+        return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
+    });
+}
+
+int hm_trace_scan_pool_plan(int64_t n_scan, int64_t n_ref1, int64_t n_ref2, int two_x, int grid_x, int64_t n_sec_bound,
+                            int n_iters, int64_t chain_tiles, int64_t *first, int64_t *quota) {
+    HM_CHECK_ARG(n_scan >= 0 && n_ref1 >= 0 && n_ref2 >= 0 && grid_x >= 1 && grid_x <= 256 && n_sec_bound >= 0 &&
+                     n_iters >= 0 && chain_tiles >= -1 && first && quota,
+                 "hm_trace_scan_pool_plan: bad argument");
+    const ScanPool p = scan_pool_quota(n_scan, n_ref1, n_ref2, two_x != 0, grid_x, n_sec_bound,
+                                       trace_chain_tiles(n_iters, chain_tiles));
+    for (int k = 0; k < 3; ++k) {
+        first[k] = p.first[k];
+        quota[k] = p.quota[k];
+    }
+    return HM_OK;
 }
 
 static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,

@@ -36,10 +36,18 @@ extern "C" int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc 
                                     int small_front, int c_prev1, int grid1, int c_prev2, int grid2, void *stream);
 
 // hm_sdf.hip (not exported), guarded mode: the exact refinement of a list and the approximate closest-approach scan as ONE
-// launch (fp32 tiles of the list first, then split tiles of the scan, each from an atomic cursor)
+// launch (fp32 tiles of the list first, then this launch's range of the scan's split tiles, each from an atomic cursor of
+// its own; which = 0 / 1: the launch of the list cnt[c_ref1] / cnt[c_ref2])
 extern "C" int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                    const float *B_fourier, int frac_mode, const void *trace_args, int c_ref,
-                                    int64_t scan_off, int64_t scan_capacity, void *stream);
+                                    const float *B_fourier, int frac_mode, const void *trace_args, int c_ref1, int c_ref2,
+                                    int which, int64_t scan_off, int64_t scan_capacity, int64_t chain_tiles, void *stream);
+
+// hm_sdf.hip (not exported), guarded mode: the secant refinement and the split tiles of the closest-approach scan that the
+// hm_trace_refine_scan launches left over as ONE launch
+extern "C" int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
+                                          const float *B_fourier, int frac_mode, const void *trace_args, int n_iters,
+                                          int c_ref1, int c_ref2, int64_t scan_off, int64_t scan_capacity,
+                                          int64_t chain_tiles, void *stream);
 
 // hm_sdf.hip (not exported): hm_sdf_fwd whose 64-point launch completes its last round with tiles of a second point set
 extern "C" int hm_sdf_fwd_fill(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n,
@@ -654,6 +662,16 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     // lists are disjoint and the sampler's list is patched before the closest-approach rows are selected, so both lists
     // start at the head of the refinement region.  HM_TRACE_OVERLAP=1: every launch on its own, one list (A/B, tests).
     const bool cosched = guard && overlap_shape && !(e_ov && atoi(e_ov) == 1);
+    // The default shares the closest-approach scan out between the launches (hm_sdf.hip: hm_scan_pool.h): the refinement
+    // launches - both passes' of the lazy sampler - take as many of its split tiles as they have idle workgroups, the
+    // secant chain's launch (sdf_split_scan_secant_kernel) runs the rest beside the chain, and the closest-approach rows
+    // are selected, refined (a plain 64-point launch) and reduced behind it.  HM_TRACE_OVERLAP=2: the sequence above, the
+    // whole scan in front of the chain (A/B, tests).  HM_TRACE_POOL_CHAIN_TILES=k (A/B, tests; read per call): the chain
+    // hides k tiles per workgroup instead of trace_chain_tiles' - 0 leaves the whole scan in front of it.
+    const bool pool = cosched && !(e_ov && atoi(e_ov) == 2);
+    const char *e_ct = getenv("HM_TRACE_POOL_CHAIN_TILES");
+    const int64_t chain_tiles = pool ? trace_chain_tiles(cfg->n_secant_steps, (e_ct && atoi(e_ct) >= 0) ? atoi(e_ct) : -1) : 0;
+    const int c_ref2 = (pool && a.head > 0) ? (int)C_GUARD_N2 : -1;    // list of the second refine-scan launch
 
     hm_zero_u32_async(a.w.cnt, C_COUNT, st);
     const unsigned g_rays = (unsigned)((n_rays + kTB - 1) / kTB);
@@ -794,8 +812,8 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             guard_noise(0, n_rays * cfg->n_steps, c_samp);
             hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
                                (int)C_GUARD_N1);
-            rc = hm_trace_refine_scan(desc, mlp, table, B_fourier, frac_mode, &a, (int)C_GUARD_N1, a.sel_off,
-                                      n_rays * cfg->n_steps, stream);
+            rc = hm_trace_refine_scan(desc, mlp, table, B_fourier, frac_mode, &a, (int)C_GUARD_N1, c_ref2, 0, a.sel_off,
+                                      n_rays * cfg->n_steps, chain_tiles, stream);
             if (rc != HM_OK) return rc;
             guard_patch((int)C_GUARD_N1);
         } else if (guard) {
@@ -824,7 +842,13 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             guard_noise(a.tail_off, n_rays * (cfg->n_steps - a.head - 1), (int)C_TAIL_PTS);
             hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 2, (int)C_TAIL_PTS,
                                sel_own ? c_first : (int)C_BIG_PTS, guard_min, (int)C_GUARD_N2);
-            rc = guard_refine((int)C_GUARD_N2);
+            if (c_ref2 >= 0) {   // (the tiles and values of guard_refine's launch, beside its range of the scan)
+                rc = hm_trace_refine_scan(desc, mlp, table, B_fourier, frac_mode, &a, (int)C_GUARD_N1, c_ref2, 1, a.sel_off,
+                                          n_rays * cfg->n_steps, chain_tiles, stream);
+                guard_patch(c_ref2);
+            } else {
+                rc = guard_refine((int)C_GUARD_N2);
+            }
             if (rc != HM_OK) return rc;
         }
     }
@@ -839,6 +863,19 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps,
                                                 a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, n_rays * cfg->n_steps,
                                                 (int)C_NSEL_PTS, 1, c_first, grid_p1, (int)C_TAIL_PTS, grid_p2, stream);
+            if (rc != HM_OK) return rc;
+            hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
+        } else if (pool) {
+            // the rest of the closest-approach scan runs beside the chain; its rows' marks (selected behind the sampler's
+            // patch: see guard_mark_row) are refined behind it
+            int rc = hm_trace_split_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps,
+                                                (int)C_GUARD_N1, c_ref2, a.sel_off, n_rays * cfg->n_steps, chain_tiles,
+                                                stream);
+            if (rc != HM_OK) return rc;
+            guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
+            hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
+                               (int)C_GUARD_NC);
+            rc = guard_refine((int)C_GUARD_NC);
             if (rc != HM_OK) return rc;
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         } else if (cosched) {

@@ -28,9 +28,13 @@ enum : int32_t {  // counters (device int32 array)
     C_GUARD_N1 = 80,     // ... refinement list of the sampler's first (or only) pass; HM_TRACE_OVERLAP=1 and the sequences
                          //     without a launch of their own for the closest-approach rows: of those rows too
     C_GUARD_N2 = 81,     // ... of the lazy sampler's second pass
-    C_GUARD_NC = 82,     // ... of the closest-approach rows (refined beside the secant chain)
+    C_GUARD_NC = 82,     // ... of the closest-approach rows (refined behind the secant launch; HM_TRACE_OVERLAP=2: beside
+                         //     the chain)
     C_XREF_CURSOR = 83,  // sdf_refine_scan_kernel: next fp32 tile of the refinement list (zero at launch)
-    C_XSCAN_CURSOR = 84, // ... next split tile of the closest-approach scan (zero at launch)
+    C_XSCAN_CURSOR = 84, // ... next split tile of its range of the closest-approach scan (zero at launch; scan_pool_quota)
+    C_XREF2_CURSOR = 85, // the same two cursors of the lazy sampler's second refine-scan launch
+    C_XSCAN2_CURSOR = 86,
+    C_YSCAN_CURSOR = 87, // sdf_split_scan_secant_kernel: next split tile of its range of the closest-approach scan
     C_COUNT = 96
 };
 
@@ -48,6 +52,22 @@ constexpr int32_t kGuardTripped = 0x47554152;      // value of the workspace's s
 // closest-approach scans of at least this many points hide a chain of 16-point secant tiles (sdf_scan_secant_kernel:
 // 8 x 131 us ~ 2.3 rounds of 64-point tiles: 3 rounds of 256 workgroups)
 constexpr int64_t kTraceScanHide = 3 * 256 * 64;
+
+// Guarded scans: split tiles of the closest-approach scan that ONE workgroup finishes in the time of ONE secant round, in
+// thousandths (hm_scan_pool.h: a workgroup without secant rays takes floor(n_iters * this / 1000) tiles under the chain).
+// A tuning value: it moves tiles between launches and cannot change a value.  Measured on the bench step (C2, 2048 rays,
+// profiles/scan_pool_parent_step_kernel_stats.csv): sdf_scan_secant_kernel 1120.4 us / 8 secant rounds = 140.1 us over
+// sdf_fwd_split_kernel 1323.3 us / 8 rounds of tiles = 165.4 us gives 0.85, i.e. 6 tiles under a chain of 8.  The sweep
+// over HM_TRACE_POOL_CHAIN_TILES (profiles/scan_pool_ab.json) has the step at 6.927 / 6.889 / 6.791 / 6.665 / 6.674 ms
+// for 4 / 5 / 6 / 7 / 8 tiles against a spread of 0.02 ms (7 and 8 give the same ranges there): the rule counts the
+// secant's workgroups from the bound of its rays (81 for ~60) and the chain's workgroups join the scan when they are done,
+// so the chain hides more than the ratio says.  Kept: 7 / 8.
+constexpr int64_t kScanTilesPerSecantIterPermille = 875;
+// ... the tiles one workgroup finishes under a chain of n_iters rounds; given >= 0: that many (HM_TRACE_POOL_CHAIN_TILES)
+inline int64_t trace_chain_tiles(int n_iters, int64_t given) {
+    if (n_iters <= 0) return 0;
+    return given >= 0 ? given : n_iters * kScanTilesPerSecantIterPermille / 1000;
+}
 
 enum : uint8_t { ST_WAIT_FIRST = 1, ST_WAIT_MARCH = 2, ST_WAIT_LS = 3, ST_DONE = 4 };
 

@@ -401,6 +401,14 @@ HM_API int64_t hm_trace_workspace_bytes(int64_t n_rays, const hm_trace_cfg *cfg)
  * the workspace, and to re-arm a tripped guard.  hm_trace_guard_tolerances: the guard width tau and the trip threshold. */
 HM_API int hm_trace_guard_clear(void *workspace, int64_t workspace_bytes, void *stream);
 HM_API int hm_trace_guard_tolerances(float *tau, float *tau_trip);
+/* Diagnostic, host only: which split tiles of the closest-approach scan (n_scan points, 64 per tile, none at <= 8192
+ * points) each launch of the guarded search owns - the rule the kernels evaluate from the device counters
+ * (csrc/hm_scan_pool.h).  first[k], quota[k], k = 0, 1, 2: the refine-scan launch of the sampler's first pass (list of
+ * n_ref1 points), of the lazy sampler's second pass (n_ref2 points; two_x = 0: no such launch) and the secant launch.
+ * grid_x: workgroups of the refine-scan launches; n_sec_bound: rays handed to the sampler (the bound of the secant rays);
+ * chain_tiles: tiles one workgroup finishes under the whole secant chain, -1 = derived from n_iters.                 */
+HM_API int hm_trace_scan_pool_plan(int64_t n_scan, int64_t n_ref1, int64_t n_ref2, int two_x, int grid_x,
+                                   int64_t n_sec_bound, int n_iters, int64_t chain_tiles, int64_t *first, int64_t *quota);
 HM_API int hm_trace_forward(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
                             const float *B_fourier, int frac_mode, int tile_points, const hm_trace_cfg *cfg,
                             const float *cam_loc, const float *ray_dirs, const uint8_t *object_mask,
