@@ -154,6 +154,8 @@ SIGNATURES = {
     "hm_mesh_depth_maps": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
     "hm_mesh_visible_votes": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, C.c_float, _int, _p, _p]),
     "hm_mesh_keep_mark": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "hm_mesh_vertex_colors": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, C.c_float, _i64,
+                                     C.c_double, _int, _int, _int, _p, _p, _p]),
 }
 
 

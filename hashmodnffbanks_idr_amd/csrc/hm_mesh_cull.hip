@@ -9,11 +9,12 @@
 //   hm_mesh_visible_votes  one lane per vertex, a loop over the views: w against the largest depth around its pixel
 //   hm_mesh_keep_mark      the face and vertex flags of "all three vertices kept", for hm_mesh_select_emit
 //
-// The projection, the pixel and the fixed-point position are hm_view_dev.h's.  Coverage is decided by int64 edge
-// functions of the fixed-point positions (|X|, |Y| < 2^24 and pixel centres below 2^24: every product is below 2^50), the
-// depth by fp64 operations rounded once, and a pixel keeps the minimum through an unsigned atomicMin on the float's bits
-// (positive floats order like their bits): the depth maps do not depend on the order of the faces and two calls give the
-// same bits.  The votes are written once per vertex, without atomics.  No index is dereferenced before its range check.
+// The projection, the pixel, the fixed-point position and the visibility rule are hm_view_dev.h's (the rule is also the
+// colours': hm_mesh_color.hip).  Coverage is decided by int64 edge functions of the fixed-point positions (|X|, |Y| <
+// 2^24 and pixel centres below 2^24: every product is below 2^50), the depth by fp64 operations rounded once, and a
+// pixel keeps the minimum through an unsigned atomicMin on the float's bits (positive floats order like their bits): the
+// depth maps do not depend on the order of the faces and two calls give the same bits.  The votes are written once per
+// vertex, without atomics.  No index is dereferenced before its range check.
 #include "hm_block_dev.h"
 #include "hm_view_dev.h"
 
@@ -199,13 +200,7 @@ __global__ __launch_bounds__(kVT) void cull_visible_votes_kernel(const float *__
         const HmViewPoint q = hm_view_project(proj + (int64_t)v * 12, x, y, z);
         int32_t col, row;
         if (!hm_view_pixel(q, H, W, col, row)) continue;
-        const float *d = depth + (int64_t)v * H * W;
-        float m = d[(int64_t)row * W + col];
-        for (int dr = -pad; dr <= pad; ++dr) {
-            const int64_t r = min(max(row + dr, 0), H - 1);
-            for (int dc = -pad; dc <= pad; ++dc) m = fmaxf(m, d[r * W + min(max(col + dc, 0), W - 1)]);
-        }
-        n_vis += __double2float_rn(q.w) <= __fadd_rn(m, tol);
+        n_vis += hm_view_visible(q, depth + (int64_t)v * H * W, H, W, col, row, pad, tol);
     }
     n_visible[i] = (accumulate ? n_visible[i] : 0) + n_vis;
 }
@@ -225,15 +220,6 @@ __global__ __launch_bounds__(kVT) void cull_keep_mark_kernel(const int32_t *__re
     }
 }
 
-// the image sizes the kernels' index arithmetic is written for: pixel centres below 2^24, H*W within int32
-int cull_check_image(int64_t n_views, int64_t H, int64_t W, const char *what) {
-    const std::string w(what);
-    HM_CHECK_ARG(n_views >= 0 && n_views < ((int64_t)1 << 31), w + ": n_views must be in [0, 2^31)");
-    HM_CHECK_ARG(H >= 1 && W >= 1 && H <= 65536 && W <= 65536 && H * W < ((int64_t)1 << 31),
-                 w + ": H and W must be in [1, 65536] with H*W < 2^31");
-    return HM_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -242,7 +228,7 @@ int hm_mesh_mask_votes(const float *verts, int64_t n_verts, const double *proj, 
                        int64_t H, int64_t W, int64_t dilate, int accumulate, int32_t *n_in_image, int32_t *n_in_mask,
                        void *stream) {
     if (int rc = hm_check_mesh(0, n_verts, nullptr, "hm_mesh_mask_votes")) return rc;
-    if (int rc = cull_check_image(n_views, H, W, "hm_mesh_mask_votes")) return rc;
+    if (int rc = hm_view_check_image(n_views, H, W, "hm_mesh_mask_votes")) return rc;
     HM_CHECK_ARG(dilate >= 0, "hm_mesh_mask_votes: dilate must be >= 0");
     if (n_verts == 0) return HM_OK;
     HM_CHECK_ARG(verts && n_in_image && n_in_mask && (n_views == 0 || (proj && sat)), "hm_mesh_mask_votes: NULL pointer");
@@ -263,7 +249,7 @@ int hm_mesh_depth_maps(const float *verts, int64_t n_verts, const int32_t *faces
                        int64_t n_views, int64_t H, int64_t W, int64_t big_face, float *depth, int32_t *n_skipped,
                        void *workspace, int64_t workspace_bytes, int32_t *status, void *stream) {
     if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_depth_maps")) return rc;
-    if (int rc = cull_check_image(n_views, H, W, "hm_mesh_depth_maps")) return rc;
+    if (int rc = hm_view_check_image(n_views, H, W, "hm_mesh_depth_maps")) return rc;
     HM_CHECK_ARG(big_face >= 1, "hm_mesh_depth_maps: big_face must be >= 1");
     if (n_views == 0) return HM_OK;
     HM_CHECK_ARG(proj && depth && n_skipped && status && workspace && (n_verts == 0 || verts),
@@ -297,7 +283,7 @@ int hm_mesh_visible_votes(const float *verts, int64_t n_verts, const double *pro
                           int64_t H, int64_t W, int64_t pad, float tol, int accumulate, int32_t *n_visible,
                           void *stream) {
     if (int rc = hm_check_mesh(0, n_verts, nullptr, "hm_mesh_visible_votes")) return rc;
-    if (int rc = cull_check_image(n_views, H, W, "hm_mesh_visible_votes")) return rc;
+    if (int rc = hm_view_check_image(n_views, H, W, "hm_mesh_visible_votes")) return rc;
     HM_CHECK_ARG(pad >= 0 && pad <= 64, "hm_mesh_visible_votes: pad must be in [0, 64]");
     HM_CHECK_ARG(tol == tol, "hm_mesh_visible_votes: tol is NaN");
     if (n_verts == 0) return HM_OK;

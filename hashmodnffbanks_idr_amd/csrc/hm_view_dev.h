@@ -1,9 +1,9 @@
-// hm_view_dev.h - a vertex seen by a view, written once for the culling kernels (hm_mesh_cull.hip): the projection, the
-// pixel and the fixed-point screen position.  A view is a 3x4 projection P in fp64 (K[:3,:3] @ inv(pose)[:3,:4]); pixel
-// (col, row) has its centre at uv = (col, row).  Every operation is fp64 on the fp32 coordinates and rounded once
-// (__dmul_rn and friends: no contraction whatever the build flags say), so the numpy restatement
-// (tests/mesh_cull_cases.py) gives the same bits.  Every range test is made on doubles BEFORE a value becomes an integer:
-// a NaN, an infinity or a huge value fails it and nothing is read.
+// hm_view_dev.h - a vertex seen by a view, written once for the culling and colouring kernels (hm_mesh_cull.hip,
+// hm_mesh_color.hip): the projection, the pixel, the fixed-point screen position and the visibility rule.  A view is a
+// 3x4 projection P in fp64 (K[:3,:3] @ inv(pose)[:3,:4]); pixel (col, row) has its centre at uv = (col, row).  Every
+// operation is fp64 on the fp32 coordinates and rounded once (__dmul_rn and friends: no contraction whatever the build
+// flags say), so the numpy restatement (tests/mesh_cull_cases.py) gives the same bits.  Every range test is made on
+// doubles BEFORE a value becomes an integer: a NaN, an infinity or a huge value fails it and nothing is read.
 #pragma once
 #include <math.h>
 
@@ -51,4 +51,26 @@ __device__ __forceinline__ bool hm_view_fixed(const HmViewPoint &q, int32_t &X, 
     Y = in ? (int32_t)y : 0;
     return in;
 }
+
+// the visibility rule of the votes and of the colours: float32(w) <= m + tol, m = the maximum of the view's depth map d
+// [H, W] over the (2 pad + 1)^2 pixels around the vertex' pixel (col, row), indices clamped to the image.  (col, row)
+// is hm_view_pixel's and in the image.
+__device__ __forceinline__ bool hm_view_visible(const HmViewPoint &q, const float *__restrict__ d, int H, int W,
+                                                int32_t col, int32_t row, int pad, float tol) {
+    float m = d[(int64_t)row * W + col];
+    for (int dr = -pad; dr <= pad; ++dr) {
+        const int64_t r = min(max(row + dr, 0), H - 1);
+        for (int dc = -pad; dc <= pad; ++dc) m = fmaxf(m, d[r * W + min(max(col + dc, 0), W - 1)]);
+    }
+    return __double2float_rn(q.w) <= __fadd_rn(m, tol);
+}
 #endif
+
+// the image sizes the kernels' index arithmetic is written for: pixel centres below 2^24, H*W within int32
+inline int hm_view_check_image(int64_t n_views, int64_t H, int64_t W, const char *what) {
+    const std::string w(what);
+    HM_CHECK_ARG(n_views >= 0 && n_views < ((int64_t)1 << 31), w + ": n_views must be in [0, 2^31)");
+    HM_CHECK_ARG(H >= 1 && W >= 1 && H <= 65536 && W <= 65536 && H * W < ((int64_t)1 << 31),
+                 w + ": H and W must be in [1, 65536] with H*W < 2^31");
+    return HM_OK;
+}

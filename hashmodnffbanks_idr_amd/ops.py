@@ -2382,3 +2382,112 @@ def mesh_keep_vertices(verts, faces, normals, keep):
     check(lib().hm_mesh_keep_mark(dptr(faces), n_faces, n_verts, dptr(keep), dptr(vflag), dptr(fflag), dptr(status),
                                   stream_ptr(faces)))
     return _mesh_emit_flagged("mesh_keep_vertices", verts, faces, normals, vflag, fflag, status)
+
+
+# =========================================================================================
+# Mesh colouring from the input views (csrc/hm_mesh_color.hip, DESIGN.md "Mesh colouring on the device")
+# =========================================================================================
+COLOR_MODES = {"blend": 0, "best": 1}
+COLOR_MAX_POWER = 8
+
+
+def _device_centers(what, centers, n_views, device):
+    if isinstance(centers, torch.Tensor):
+        ok = centers.dtype == torch.float64 and tuple(centers.shape) == (n_views, 3)
+    else:
+        ok = isinstance(centers, np.ndarray) and centers.dtype == np.float64 and centers.shape == (n_views, 3)
+    if not ok:
+        raise ValueError(f"hashmod {what}: float64 centers [n, 3] expected, one camera centre per view")
+    if not isinstance(centers, torch.Tensor):
+        centers = torch.from_numpy(np.ascontiguousarray(centers))
+    return centers.to(device).contiguous()
+
+
+def mesh_vertex_colors(verts, normals, proj, centers, images, depth, *, masks=None, erode=0, pad=1, tol=0.0,
+                       min_cos=0.0, power=1, mode="blend", out=None):
+    """(acc [V,4] float64, n_used [V] int32): the colour each vertex of verts [V,3] fp32 collects from the views
+    proj [n,3,4], centers [n,3] (float64, host or device; the camera centres pose[:, :3, 3]) with images [n,H,W,3] fp32
+    and the mesh's depth maps depth [n,H,W] fp32 (mesh_depth_maps), all on the device.  A view contributes iff the
+    vertex is projectable with its pixel (rint(u), rint(v)) in the image; visible by mesh_visible_votes' rule with
+    `pad` and `tol`; with masks [n,H,W] bool or uint8, every mask pixel of the (2 erode + 1)^2 square around its pixel
+    that lies in the image is set (cv2.erode with its default border; erode >= 1 makes all four taps mask pixels); and,
+    with normals [V,3] fp32, cos(normal, centre - vertex) is finite and > min_cos in [0, 1).  The weight is 1 without
+    normals and cos^power (an integer in [0, 8]) with them; the sample is bilinear at (u, v), taps clamped to the image.
+    mode="blend": acc[:, :3] = the sum of weight * sample, acc[:, 3] = the sum of the weights, added in view order;
+    mode="best": the sample and weight of the view with the largest weight, of equals the first.  n_used counts the
+    contributing views.  out = (acc, n_used), when given, is continued with these views (the next chunk) and returned:
+    the bits do not depend on how the views are split.  fp64 operations rounded once, no atomics:
+    tests/mesh_color_cases.vertex_colors_ref gives the same bits.  mesh_colors_finish turns acc into colours."""
+    what = "mesh_vertex_colors"
+    n_verts, n_views = _check_views(what, verts, proj)
+    if normals is not None:
+        _check_cloud(what, "normals", normals, like=verts)
+        if normals.shape[0] != n_verts:
+            raise ValueError(f"hashmod {what}: normals must have one row per vertex")
+    if (not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.dim() != 4
+            or images.shape[0] != n_views or images.shape[3] != 3 or not images.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous fp32 images [n, H, W, 3] expected, one per view")
+    H, W = int(images.shape[1]), int(images.shape[2])
+    _check_views(what, verts, proj, H, W)
+    if (not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or tuple(depth.shape) != (n_views, H, W)
+            or not depth.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous fp32 depth [n, H, W] expected, one map per view")
+    if masks is not None and (not isinstance(masks, torch.Tensor) or masks.dtype not in (torch.bool, torch.uint8)
+                              or tuple(masks.shape) != (n_views, H, W)):
+        raise ValueError(f"hashmod {what}: bool or uint8 masks [n, H, W] expected, one per view")
+    if not (isinstance(erode, int) and not isinstance(erode, bool) and erode >= 0):
+        raise ValueError(f"hashmod {what}: erode must be an integer >= 0")
+    if not (isinstance(pad, int) and not isinstance(pad, bool) and 0 <= pad <= CULL_MAX_PAD):
+        raise ValueError(f"hashmod {what}: pad must be an integer in [0, {CULL_MAX_PAD}]")
+    if not (isinstance(tol, (int, float)) and not math.isnan(tol)):
+        raise ValueError(f"hashmod {what}: tol must be a number")
+    if not (isinstance(min_cos, (int, float)) and not isinstance(min_cos, bool) and 0.0 <= min_cos < 1.0):
+        raise ValueError(f"hashmod {what}: min_cos must be a number in [0, 1)")
+    if not (isinstance(power, int) and not isinstance(power, bool) and 0 <= power <= COLOR_MAX_POWER):
+        raise ValueError(f"hashmod {what}: power must be an integer in [0, {COLOR_MAX_POWER}]")
+    if mode not in COLOR_MODES:
+        raise ValueError(f"hashmod {what}: mode must be 'blend' or 'best'")
+    if out is not None:
+        if (not isinstance(out, (tuple, list)) or len(out) != 2 or not all(isinstance(t, torch.Tensor) for t in out)
+                or out[0].dtype != torch.float64 or tuple(out[0].shape) != (n_verts, 4) or not out[0].is_contiguous()
+                or out[1].dtype != torch.int32 or tuple(out[1].shape) != (n_verts,) or not out[1].is_contiguous()):
+            raise ValueError(f"hashmod {what}: out must be (contiguous float64 acc [V, 4], contiguous int32 n_used [V])")
+    others = (images, depth, masks) + (tuple(out) if out is not None else ())
+    for t in others:
+        if t is not None and t.device != verts.device:
+            raise ValueError(f"hashmod {what}: the tensors are on different devices")
+    dev = verts.device
+    centers = _device_centers(what, centers, n_views, dev)
+    require_gpu(verts, normals, *others)
+    proj = _device_proj(proj, dev)
+    sat = None if masks is None else _mask_table(masks)
+    if out is None:
+        acc = torch.zeros((n_verts, 4), dtype=torch.float64, device=dev)
+        n_used = torch.zeros(n_verts, dtype=torch.int32, device=dev)
+    else:
+        acc, n_used = out
+    check(lib().hm_mesh_vertex_colors(dptr(verts), dptr(normals), n_verts, dptr(proj), dptr(centers), dptr(images),
+                                      dptr(depth), dptr(sat), n_views, H, W, pad, float(tol),
+                                      min(erode, CULL_MAX_IMAGE), float(min_cos), power, COLOR_MODES[mode],
+                                      0 if out is None else 1, dptr(acc), dptr(n_used), stream_ptr(verts)))
+    return acc, n_used
+
+
+def mesh_colors_finish(acc, n_used, mode, fill=(0.0, 0.0, 0.0)):
+    """colours [V,3] fp32 of mesh_vertex_colors' (acc, n_used): acc[:, :3] / acc[:, 3:] in float64 for mode="blend",
+    acc[:, :3] for mode="best", cast to fp32; `fill` (three numbers) where no view contributed.  Torch plumbing."""
+    if mode not in COLOR_MODES:
+        raise ValueError("hashmod mesh_colors_finish: mode must be 'blend' or 'best'")
+    if (not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or acc.dim() != 2 or acc.shape[1] != 4
+            or not isinstance(n_used, torch.Tensor) or n_used.dtype != torch.int32
+            or tuple(n_used.shape) != (acc.shape[0],) or n_used.device != acc.device):
+        raise ValueError("hashmod mesh_colors_finish: float64 acc [V, 4] and int32 n_used [V] on one device expected")
+    try:
+        fill = [float(c) for c in fill]
+    except (TypeError, ValueError):
+        fill = []
+    if len(fill) != 3:
+        raise ValueError("hashmod mesh_colors_finish: fill must be three numbers")
+    rgb = acc[:, :3] / acc[:, 3:] if mode == "blend" else acc[:, :3]
+    fill = torch.tensor(fill, dtype=torch.float32, device=acc.device)
+    return torch.where((n_used > 0)[:, None], rgb.to(torch.float32), fill)

@@ -99,12 +99,20 @@ def get_surface_mesh(sdf, resolution=100, device="cuda"):
 class TriMesh:
     """The part of trimesh.Trimesh the reference's mesh callers use (eval.py: world transform, largest component,
     .ply export; plots.py: .ply export): vertices [V,3] float64, faces [F,3] int64, vertex_normals [V,3] (the given
-    ones, else area-weighted face normals), area, apply_transform, split, export."""
+    ones, else area-weighted face normals), area, apply_transform, split, export.  vertex_colors [V,3] uint8, optional
+    (evaluation.color.color_mesh and colors_to_uint8 make them): split gathers them, apply_transform keeps them and
+    export writes them after the normals."""
 
-    def __init__(self, vertices, faces, vertex_normals=None):
+    def __init__(self, vertices, faces, vertex_normals=None, vertex_colors=None):
         self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
         self._normals = None if vertex_normals is None else np.asarray(vertex_normals, np.float64).reshape(-1, 3)
+        self.vertex_colors = None
+        if vertex_colors is not None:
+            colors = np.asarray(vertex_colors)
+            if colors.dtype != np.uint8 or colors.shape != self.vertices.shape:
+                raise ValueError("TriMesh: vertex_colors must be uint8 [V, 3] (colors_to_uint8)")
+            self.vertex_colors = colors
 
     def _cross(self):
         v = self.vertices[self.faces]
@@ -169,27 +177,31 @@ class TriMesh:
             ff = f[face_label == lab]
             used, inv = np.unique(ff, return_inverse=True)
             normals = None if self._normals is None else self._normals[used]
-            part = TriMesh(self.vertices[used], inv.reshape(-1, 3), normals)
+            colors = None if self.vertex_colors is None else self.vertex_colors[used]
+            part = TriMesh(self.vertices[used], inv.reshape(-1, 3), normals, colors)
             if not only_watertight or part.is_watertight:
                 out.append(part)
         return out
 
     def export(self, file_obj=None, file_type="ply"):
-        """binary little-endian PLY: float32 x y z (+ nx ny nz), faces as (uchar 3, int32 x3); bytes when file_obj
-        is None, else written to the path or binary file object"""
+        """binary little-endian PLY: float32 x y z nx ny nz (+ uchar red green blue with vertex_colors), faces as
+        (uchar 3, int32 x3); bytes when file_obj is None, else written to the path or binary file object"""
         if file_type != "ply":
             raise ValueError("TriMesh.export: only file_type='ply' is supported")
         names = ["x", "y", "z", "nx", "ny", "nz"]
-        vdt = np.dtype([(n, "<f4") for n in names])
+        rgb = ["red", "green", "blue"] if self.vertex_colors is not None else []
+        vdt = np.dtype([(n, "<f4") for n in names] + [(n, "u1") for n in rgb])
         vert = np.empty(len(self.vertices), vdt)
         cols = np.concatenate([self.vertices, self.vertex_normals], axis=1)
         for c, n in enumerate(names):
             vert[n] = cols[:, c]
+        for c, n in enumerate(rgb):
+            vert[n] = self.vertex_colors[:, c]
         face = np.empty(len(self.faces), np.dtype([("count", "u1"), ("index", "<i4", (3,))]))
         face["count"] = 3
         face["index"] = self.faces
         head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(vert)}"]
-        head += [f"property float {n}" for n in names]
+        head += [f"property float {n}" for n in names] + [f"property uchar {n}" for n in rgb]
         head += [f"element face {len(face)}", "property list uchar int vertex_indices", "end_header", ""]
         data = "\n".join(head).encode("ascii") + vert.tobytes() + face.tobytes()
         if file_obj is None:
@@ -200,6 +212,13 @@ class TriMesh:
             with open(file_obj, "wb") as fh:
                 fh.write(data)
         return None
+
+
+def colors_to_uint8(colors):
+    """uint8 [V,3] of colours in the dataset's [-1, 1] range (a tensor or an array): rint(clip((c + 1) / 2, 0, 1) * 255),
+    half to even; what TriMesh(vertex_colors=) takes"""
+    c = np.asarray(colors.detach().cpu() if isinstance(colors, torch.Tensor) else colors, np.float64)
+    return np.rint(np.clip((c + 1.0) / 2.0, 0.0, 1.0) * 255.0).astype(np.uint8).reshape(-1, 3)
 
 
 @torch.no_grad()

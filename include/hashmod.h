@@ -1061,6 +1061,35 @@ HM_API int hm_mesh_visible_votes(const float *verts, int64_t n_verts, const doub
 HM_API int hm_mesh_keep_mark(const int32_t *faces, int64_t n_faces, int64_t n_verts, const uint8_t *keep,
                              int32_t *vflag, int32_t *fflag, int32_t *status, void *stream);
 
+/* ---- mesh colouring: per-vertex colour from the views that see the vertex ------------------------------------------
+ * Driver: ops.mesh_vertex_colors, ops.mesh_colors_finish, evaluation.color.color_mesh.  csrc/hm_mesh_color.hip,
+ * csrc/hm_view_dev.h.  Does not synchronise; sizes, proj, the projection and the pixel as for mesh culling above.
+ *   hm_mesh_vertex_colors: verts [n_verts, 3] fp32; normals [n_verts, 3] fp32 or NULL; centers [n_views, 3] fp64 the
+ *                camera centres (pose[:, :3, 3]); images [n_views, H, W, 3] fp32; depth [n_views, H, W] fp32 from
+ *                hm_mesh_depth_maps; sat [n_views, H+1, W+1] int32 the masks' summed-area table or NULL.
+ *                One lane per vertex visits the views in ascending order.  A view contributes iff, tested in this order,
+ *                  1. the vertex is projectable and its pixel (col, row) is in the image;
+ *                  2. float(w) <= m + tol, the rule of hm_mesh_visible_votes with the same pad in [0, 64];
+ *                  3. (with sat) every pixel of the (2 erode + 1)^2 square around (col, row) inside the image is set:
+ *                     the window's count from four table reads equals the clamped window's area; erode in [0, 65536];
+ *                  4. (with normals) d = c - double(x) per component, dot = ((nx dx) + (ny dy)) + (nz dz), nn and dd
+ *                     the squared lengths of the normal and of d in the same association, den = sqrt(nn dd),
+ *                     cos = dot / den; den > 0, cos finite and cos > min_cos; min_cos in [0, 1).
+ *                Weight: w = 1 without normals, else cos^power as `power` products from 1.0, left to right; power in
+ *                [0, 8].  Sample: bilinear at (u, v): c0 = floor(u), r0 = floor(v), fu = u - c0, fv = v - r0, the tap
+ *                indices c0, c0 + 1, r0, r0 + 1 clamped to the image; per channel top = (a (1 - fu)) + (b fu), bot
+ *                likewise, val = (top (1 - fv)) + (bot fv).  Every operation is fp64 and rounded once.
+ *                mode 0 (blend): acc[k] += w val[k] (k < 3), acc[3] += w, sequentially in view order.
+ *                mode 1 (best): a view replaces (val, w) iff w > acc[3]: of equal weights the lowest view stays.
+ *                acc [n_verts, 4] fp64, n_used [n_verts] int32 = the contributing views.  accumulate == 0 starts from
+ *                zeros, else from what acc and n_used hold: views [0, n) in one call and [0, k), [k, n) in two give the
+ *                same bits.  No atomics, no workspace.  n_views == 0 writes zeros (accumulate == 0) or nothing. */
+HM_API int hm_mesh_vertex_colors(const float *verts, const float *normals, int64_t n_verts, const double *proj,
+                                 const double *centers, const float *images, const float *depth, const int32_t *sat,
+                                 int64_t n_views, int64_t H, int64_t W, int64_t pad, float tol, int64_t erode,
+                                 double min_cos, int power, int mode, int accumulate, double *acc, int32_t *n_used,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
