@@ -65,6 +65,7 @@ SIGNATURES = {
     "hm_sdf_fwd_bf16": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _int, _p, _i64, _p]),
     "hm_sdf_fwd_emb_bf16": (_int, [_p, _p, _i64, _int, _i64, _p, _i64, _p, _i64, _p]),
     "hm_pack_mlp_layer_split": (_int, [_p, _i64, _int, _int, _int, C.c_float, C.c_float, _int, _p, _p]),
+    "hm_pack_mlp_layers_split": (_int, [_p, _int, _int, _p]),
     "hm_sdf_fwd_split": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _int, _p, _i64, _p]),
     "hm_sdf_fwd_emb_split": (_int, [_p, _p, _i64, _int, _i64, _p, _i64, _p, _i64, _p]),
     "hm_pack_mlp_layers": (_int, [_p, _int, _p]),
@@ -196,6 +197,12 @@ class PackItem(C.Structure):
     _fields_ = [("W", C.c_void_p), ("bias", C.c_void_p), ("w_packed", C.c_void_p), ("w_packed_m16", C.c_void_p),
                 ("bias_padded", C.c_void_p), ("ldw", C.c_int64), ("out_dim", C.c_int32), ("seg_width0", C.c_int32),
                 ("seg_width1", C.c_int32), ("pad_", C.c_int32)]
+
+
+class PackSplitItem(C.Structure):
+    _fields_ = [("W", C.c_void_p), ("w_packed_split", C.c_void_p), ("ldw", C.c_int64), ("out_dim", C.c_int32),
+                ("seg_width0", C.c_int32), ("seg_width1", C.c_int32), ("seg_scale0", C.c_float), ("seg_scale1", C.c_float),
+                ("pad_", C.c_int32)]
 
 
 class CopyItem(C.Structure):

@@ -204,6 +204,29 @@ template <int FRAC>
 __device__ __forceinline__ void hm_level_features(const HmLevels &lv, const float *__restrict__ table, int l, float x0,
                                                   float x1, float x2, float (&acc)[8]) {
     const int F = lv.F;
+    if (F == 2 && (reinterpret_cast<uintptr_t>(table) & 7) == 0) {
+        // two features per row: a corner's row is ONE 8-byte load, and the sums live in two named registers (the
+        // generic path below fetches a dword at a time and indexes acc[] with a run-time f); same adds in the same order
+        const float2 *tl2 = reinterpret_cast<const float2 *>(table) + lv.row_off[l];
+        float a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            uint32_t ux, uy, uz;
+            float wx, wy, wz;
+            hm_corner<FRAC>(x0, lv.res[l], c & 1, ux, wx);
+            hm_corner<FRAC>(x1, lv.res[l], (c >> 1) & 1, uy, wy);
+            hm_corner<FRAC>(x2, lv.res[l], (c >> 2) & 1, uz, wz);
+            const float w = __fmul_rn(__fmul_rn(wx, wy), wz);
+            if (w != 0.0f) {
+                const float2 r = tl2[hm_mod_rows(hm_hash3(ux, uy, uz), lv.rows[l], lv.magic[l])];
+                a0 = __fadd_rn(a0, __fmul_rn(r.x, w));
+                a1 = __fadd_rn(a1, __fmul_rn(r.y, w));
+            }
+        }
+        acc[0] = a0;
+        acc[1] = a1;
+        return;
+    }
     for (int f = 0; f < F; ++f) acc[f] = 0.0f;
     const float *tl = table + (size_t)lv.row_off[l] * F;
 #pragma unroll

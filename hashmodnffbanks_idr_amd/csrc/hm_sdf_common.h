@@ -211,6 +211,16 @@ __device__ __forceinline__ void embed_fourier(const float *__restrict__ Bf, int 
     put(3 + c, sn);
     put(3 + L + c, cs);
 }
+// a level's F features -> put(e0 + f, .)  (F == 2, the usual table: no run-time index into acc[])
+template <class Put>
+__device__ __forceinline__ void put_features(int e0, int F, const float (&acc)[8], Put &put) {
+    if (F == 2) {
+        put(e0, acc[0]);
+        put(e0 + 1, acc[1]);
+    } else {
+        for (int f = 0; f < F; ++f) put(e0 + f, acc[f]);
+    }
+}
 // the thread owns slots first, first + step, ... of its point (Fourier channels and levels walked separately)
 template <int FRAC, class Put>
 __device__ __forceinline__ void embed_point(const HmLevels &lv, const float *__restrict__ table,
@@ -225,7 +235,7 @@ __device__ __forceinline__ void embed_point(const HmLevels &lv, const float *__r
     for (int l = first; l < L; l += step) {
         float acc[8];
         hm_level_features<FRAC>(lv, table, l, x0, x1, x2, acc);
-        for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
+        put_features(3 + 2 * L + l * F, F, acc, put);
     }
 }
 
@@ -244,7 +254,7 @@ __device__ __forceinline__ void embed_slot(const HmLevels &lv, const float *__re
         const int l = slot - L - 1, F = lv.F;
         float acc[8];
         hm_level_features<FRAC>(lv, table, l, x0, x1, x2, acc);
-        for (int f = 0; f < F; ++f) put(3 + 2 * L + l * F + f, acc[f]);
+        put_features(3 + 2 * L + l * F, F, acc, put);
     }
 }
 

@@ -24,8 +24,10 @@
 // matrix rate: stream and pipe are about balanced, as in the bf16 kernel.  fp32: accumulators, bias, Softplus, the
 // sqrt(2) of the layer before the skip, the last layer's dot product and the clamp.  The 1/sqrt(2) of the skip
 // layer's EMBEDDING segment is folded into that segment's weights at pack time (hm_pack_mlp_layer_split).
-// Point load, encode, weight stream (WeightRing<4, 4, 2048>: hi and lo part of two feature tiles per 2-KB block), quad
-// epilogue, last-layer finish and the LDS layout (sdf_lds_split) are the stages of hm_sdf_common.h.
+// Point load, encode (one slot per wave and pass: level parameters are scalar loads), weight stream (WeightRing<4, 4,
+// 2048>: hi and lo part of two feature tiles per 2-KB block), last-layer finish and the LDS layout (sdf_lds_split) are
+// the stages of hm_sdf_common.h; the quad epilogue (split_quad: one instance per layer kind, bias fetched ahead of the
+// k-loop) is hm_sdf_split_tile.h's own.
 #include "hm_common.h"
 
 #include <math.h>
@@ -33,6 +35,18 @@
 namespace {
 
 #include "hm_sdf_common.h"
+#ifdef HM_SPLIT_PHASE_PROBE
+// scripts/split_phase_probe.py: 100 MHz stamps of one tile's phases (workgroup 0, thread 0, its second tile) -> ts[i], and
+// the shader clock over the same tile -> ts[120], ts[121]
+__device__ unsigned long long hm_split_probe_ts[128];
+#define HM_SPLIT_PROBE(i_)                                                                            \
+    do {                                                                                              \
+        if (blockIdx.x == 0 && threadIdx.x == 0 && tile == (int64_t)gridDim.x) {                      \
+            if ((i_) < 120) hm_split_probe_ts[(i_)] = wall_clock64();                                 \
+            if ((i_) == 0 || (i_) == 100) hm_split_probe_ts[120 + ((i_) != 0)] = clock64();           \
+        }                                                                                             \
+    } while (0)
+#endif
 #include "hm_sdf_split_tile.h"   // Split<KIND>, the LDS layout, sdf_split_tile: one 64-point tile, and the launch checks
 
 template <int KIND, int FRAC>
@@ -52,15 +66,16 @@ __global__ __launch_bounds__(kTS, 2) void sdf_fwd_split_kernel(HmLevels lv, SdfN
 
 struct PackSplitArgs {
     const float *W;
+    void *img;
     int64_t ldw;
     int32_t out_dim, n_tiles, w0, w1, p16_0, nb;
     float scale0, scale1;
 };
 
+// element d of a layer's split image
 template <int KIND>
-__global__ __launch_bounds__(256) void pack_layer_split_kernel(PackSplitArgs a, typename Split<KIND>::T *img) {
+__device__ __forceinline__ void pack_split_body(const PackSplitArgs a, int64_t d) {
     // img[(((u*nb + t)*2 + part)*64 + l)*8 + jj] = part(scale * W[32u + (l&31)][16t + 8(l>>5) + jj])
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)a.n_tiles * a.nb * 512;
     if (d >= total) return;
     const int jj = d & 7, l = (d >> 3) & 63;
@@ -80,9 +95,41 @@ __global__ __launch_bounds__(256) void pack_layer_split_kernel(PackSplitArgs a, 
     const float w = (row < a.out_dim && col >= 0) ? __fmul_rn(a.W[(int64_t)row * a.ldw + col], sc) : 0.0f;
     typename Split<KIND>::T hi, lo;
     split_val<KIND>(w * Split<KIND>::ws, hi, lo);
+    typename Split<KIND>::T *img = static_cast<typename Split<KIND>::T *>(a.img);
     const int64_t o = (blk * 2) * 512 + l * 8 + jj;
     img[o] = hi;
     img[o + 512] = lo;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_layer_split_kernel(PackSplitArgs a) {
+    pack_split_body<KIND>(a, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// every layer of a network in ONE launch (blockIdx.y = layer), as pack_layer_multi_kernel does for the fp32 images
+struct PackSplitTable {
+    PackSplitArgs a[HM_MAX_LAYERS];
+};
+template <int KIND>
+__global__ __launch_bounds__(256) void pack_layer_split_multi_kernel(PackSplitTable t) {
+    pack_split_body<KIND>(t.a[blockIdx.y], (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// the checks and kernel arguments of one layer's split image; *total = its 2-byte (hi, lo) element pairs
+static int fill_pack_split_args(const char *who, PackSplitArgs &a, const float *W, int64_t ldw, int out_dim, int seg_width0,
+                                int seg_width1, float seg_scale0, float seg_scale1, void *w_packed_split, int64_t &total) {
+    HM_CHECK_ARG(W && w_packed_split, std::string(who) + ": NULL pointer");
+    HM_CHECK_ARG(out_dim >= 1 && seg_width0 >= 1 && seg_width1 >= 0 && ldw >= seg_width0 + seg_width1,
+                 std::string(who) + ": bad shape");
+    a = {};
+    a.W = W; a.img = w_packed_split; a.ldw = ldw; a.out_dim = out_dim;
+    a.n_tiles = (out_dim + 31) / 32;
+    a.w0 = seg_width0; a.w1 = seg_width1;
+    a.p16_0 = (seg_width0 + 15) / 16 * 16;
+    a.nb = a.p16_0 / 16 + (seg_width1 + 15) / 16;
+    a.scale0 = seg_scale0; a.scale1 = seg_scale1;
+    total = (int64_t)a.n_tiles * a.nb * 512;
+    return HM_OK;
 }
 
 static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float *x, int64_t emb_stride, int64_t n,
@@ -118,6 +165,12 @@ static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const floa
 
 extern "C" {
 
+#ifdef HM_SPLIT_PHASE_PROBE
+HM_API int hm_split_probe_read(unsigned long long *out, int n) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(hm_split_probe_ts), sizeof(unsigned long long) * (size_t)(n < 128 ? n : 128)) == hipSuccess ? 0 : -1;
+}
+#endif
+
 // (internal: hm_sdf_net_fits / hm_diag_sdf_lds, HM_SDF_SPLIT; regions may be NULL)
 int sdf_split_fits(const hm_mlp_desc *mlp, int E, int32_t *regions) {
     SdfNet net;
@@ -127,26 +180,42 @@ int sdf_split_fits(const hm_mlp_desc *mlp, int E, int32_t *regions) {
 
 int hm_pack_mlp_layer_split(const float *W, int64_t ldw, int out_dim, int seg_width0, int seg_width1, float seg_scale0,
                             float seg_scale1, int split_kind, void *w_packed_split, void *stream) {
-    HM_CHECK_ARG(W && w_packed_split, "hm_pack_mlp_layer_split: NULL pointer");
-    HM_CHECK_ARG(out_dim >= 1 && seg_width0 >= 1 && seg_width1 >= 0 && ldw >= seg_width0 + seg_width1,
-                 "hm_pack_mlp_layer_split: bad shape");
     HM_CHECK_ARG(split_kind == HM_SPLIT_BF16X2 || split_kind == HM_SPLIT_F16X2, "hm_pack_mlp_layer_split: bad split_kind");
-    PackSplitArgs a = {};
-    a.W = W; a.ldw = ldw; a.out_dim = out_dim;
-    a.n_tiles = (out_dim + 31) / 32;
-    a.w0 = seg_width0; a.w1 = seg_width1;
-    a.p16_0 = (seg_width0 + 15) / 16 * 16;
-    a.nb = a.p16_0 / 16 + (seg_width1 + 15) / 16;
-    a.scale0 = seg_scale0; a.scale1 = seg_scale1;
-    const int64_t total = (int64_t)a.n_tiles * a.nb * 512;
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    PackSplitArgs a;
+    int64_t total = 0;
+    const int rc = fill_pack_split_args("hm_pack_mlp_layer_split", a, W, ldw, out_dim, seg_width0, seg_width1, seg_scale0,
+                                        seg_scale1, w_packed_split, total);
+    if (rc != HM_OK) return rc;
+    const dim3 grid((unsigned)((total + 255) / 256));
     if (split_kind == HM_SPLIT_BF16X2)
-        hipLaunchKernelGGL(pack_layer_split_kernel<HM_SPLIT_BF16X2>, dim3(grid), dim3(256), 0, as_stream(stream), a,
-                           static_cast<__bf16 *>(w_packed_split));
+        hipLaunchKernelGGL(pack_layer_split_kernel<HM_SPLIT_BF16X2>, grid, dim3(256), 0, as_stream(stream), a);
     else
-        hipLaunchKernelGGL(pack_layer_split_kernel<HM_SPLIT_F16X2>, dim3(grid), dim3(256), 0, as_stream(stream), a,
-                           static_cast<_Float16 *>(w_packed_split));
+        hipLaunchKernelGGL(pack_layer_split_kernel<HM_SPLIT_F16X2>, grid, dim3(256), 0, as_stream(stream), a);
     HM_CHECK_LAUNCH("hm_pack_mlp_layer_split");
+    return HM_OK;
+}
+
+int hm_pack_mlp_layers_split(const hm_pack_split_item *items, int n_items, int split_kind, void *stream) {
+    HM_CHECK_ARG(n_items >= 0 && n_items <= HM_MAX_LAYERS && (n_items == 0 || items), "hm_pack_mlp_layers_split: bad argument");
+    HM_CHECK_ARG(split_kind == HM_SPLIT_BF16X2 || split_kind == HM_SPLIT_F16X2, "hm_pack_mlp_layers_split: bad split_kind");
+    if (n_items == 0) return HM_OK;
+    PackSplitTable t;
+    int64_t max_total = 0;
+    for (int i = 0; i < n_items; ++i) {
+        int64_t total = 0;
+        const hm_pack_split_item &I = items[i];
+        const int rc = fill_pack_split_args("hm_pack_mlp_layers_split", t.a[i], I.W, I.ldw, I.out_dim, I.seg_width0,
+                                            I.seg_width1, I.seg_scale0, I.seg_scale1, I.w_packed_split, total);
+        if (rc != HM_OK) return rc;
+        max_total = total > max_total ? total : max_total;
+    }
+    for (int i = n_items; i < HM_MAX_LAYERS; ++i) t.a[i] = t.a[0];
+    const dim3 grid((unsigned)((max_total + 255) / 256), (unsigned)n_items);
+    if (split_kind == HM_SPLIT_BF16X2)
+        hipLaunchKernelGGL(pack_layer_split_multi_kernel<HM_SPLIT_BF16X2>, grid, dim3(256), 0, as_stream(stream), t);
+    else
+        hipLaunchKernelGGL(pack_layer_split_multi_kernel<HM_SPLIT_F16X2>, grid, dim3(256), 0, as_stream(stream), t);
+    HM_CHECK_LAUNCH("hm_pack_mlp_layers_split");
     return HM_OK;
 }
 

@@ -2,6 +2,9 @@
 // its operand kinds, LDS layout and launch checks, shared by sdf_fwd_split_kernel (hm_sdf_split.hip) and the ray search's
 // sdf_refine_scan_kernel (hm_sdf.hip).  Included inside each file's anonymous namespace, behind hm_sdf_common.h.
 #pragma once
+#ifndef HM_SPLIT_PROBE   // hm_sdf_split.hip's phase-probe stamps (scripts/split_phase_probe.py), never in the product build
+#define HM_SPLIT_PROBE(i_) do { } while (0)
+#endif
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -12,6 +15,7 @@ template <> struct Split<HM_SPLIT_BF16X2> {
     typedef __bf16 T;
     typedef bf16x8 V8;
     typedef bf16x4 V4;
+    typedef __bf16 V2 __attribute__((ext_vector_type(2)));
     static constexpr float xs = 1.0f, ws = 1.0f, inv = 1.0f;   // operand scales (bf16 has fp32's exponent range: none)
     static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -21,6 +25,7 @@ template <> struct Split<HM_SPLIT_F16X2> {
     typedef _Float16 T;
     typedef f16x8 V8;
     typedef f16x4 V4;
+    typedef _Float16 V2 __attribute__((ext_vector_type(2)));
     // fp16 lo parts are ~2^-11 of their value: activations are stored scaled by 2^4 and weights by 2^8 so that the lo
     // parts of ordinary magnitudes (|x| >= 0.008, |w| >= 5e-4) are NORMAL fp16 numbers; smaller ones become subnormal,
     // which the MFMA keeps (scripts/f16_denorm_probe.hip) - their absolute error stays below 2^-25 / scale.  The
@@ -37,6 +42,41 @@ __device__ __forceinline__ void split_val(float v, typename Split<KIND>::T &hi, 
     typedef typename Split<KIND>::T T;
     hi = (T)v;                                              // round to nearest even
     lo = (T)__fsub_rn(v, (float)hi);
+}
+
+// Epilogue of one register quad that already carries its bias: Softplus(100) (ACT), the /sqrt(2) in front of the skip layer
+// (DIV), then the four values -> (hi, lo).  The arithmetic is softplus100_x2's and split_val's, operation for operation;
+// written out so that hipcc takes the short forms: -|a| as source modifiers of the multiply, max(a, 0) on the scalar FMA
+// result (no canonicalising v_max in front of it), and both pairs of the quad on the packed multiply / convert / subtract.
+template <int KIND, bool ACT, bool DIV>
+__device__ __forceinline__ void split_quad(float (&v)[4], typename Split<KIND>::V4 &oh, typename Split<KIND>::V4 &ol) {
+    typedef Split<KIND> S;
+    typedef typename S::V2 V2;
+    if (ACT) {
+#pragma unroll
+        for (int i = 0; i < 4; i += 2) {
+            f32x2p t = {__builtin_amdgcn_exp2f(-fabsf(v[i]) * 144.26950408889634f),          // -|100 a| log2(e)
+                        __builtin_amdgcn_exp2f(-fabsf(v[i + 1]) * 144.26950408889634f)};
+            t = t + 1.0f;
+            const f32x2p lg = {__builtin_amdgcn_logf(t.x), __builtin_amdgcn_logf(t.y)};
+            const f32x2p mx = {fmaxf(v[i], 0.0f), fmaxf(v[i + 1], 0.0f)};
+            const f32x2p r = __builtin_elementwise_fma(lg, (f32x2p){0.006931471805599453f, 0.006931471805599453f}, mx);
+            v[i] = r.x;
+            v[i + 1] = r.y;
+        }
+    }
+    if (DIV) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = __fdiv_rn(v[i], kSqrt2);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {
+        const f32x2p s = (f32x2p){v[i], v[i + 1]} * S::xs;
+        const V2 hi = __builtin_convertvector(s, V2);                                  // round to nearest even
+        const V2 lo = __builtin_convertvector(s - __builtin_convertvector(hi, f32x2p), V2);
+        oh[i] = hi.x; oh[i + 1] = hi.y;
+        ol[i] = lo.x; ol[i + 1] = lo.y;
+    }
 }
 
 constexpr int kPS = 64;            // points per workgroup tile
@@ -88,9 +128,11 @@ __device__ __forceinline__ void sdf_split_tile(const HmLevels &lv, const SdfNet 
     {
         const int64_t base = tile * kPS;
         const int cnt = (int)min((int64_t)kPS, n - base);
+        HM_SPLIT_PROBE(0);
         __syncthreads();
         load_points(net.emb_stride == 0, SX, x, base, cnt, kPS, tid);
         __syncthreads();
+        HM_SPLIT_PROBE(1);
 
         // ---------------- embedding (fp32 arithmetic) -> split planes EH / EL ---------------------------------
         if (net.emb_stride > 0) {
@@ -100,13 +142,15 @@ __device__ __forceinline__ void sdf_split_tile(const HmLevels &lv, const SdfNet 
             }
         } else {
             const int n_slot = 2 * L + 1;
-            for (int idx = tid; idx < kPS * n_slot; idx += kTS) {
-                const int p = idx % kPS, slot = idx / kPS;
-                embed_slot<FRAC>(lv, table, Bf, SX[p * 3], SX[p * 3 + 1], SX[p * 3 + 2], slot, e_pad,
-                                 [&](int e, float v) { put(p, e, v); });
-            }
+            // task (point, slot) = (lane, wave + 8 i): the slot is the WAVE's, so its kind is a scalar branch and the
+            // level's res / rows / magic / row_off are scalar loads from the kernel arguments
+            static_assert(kPS == 64, "one point per lane");
+            const float x0 = SX[lane * 3], x1 = SX[lane * 3 + 1], x2 = SX[lane * 3 + 2];
+            for (int slot = wave; slot < n_slot; slot += kWS)
+                embed_slot<FRAC>(lv, table, Bf, x0, x1, x2, slot, e_pad, [&](int e, float v) { put(lane, e, v); });
         }
         __syncthreads();
+        HM_SPLIT_PROBE(2);
 
         // ---------------- layers ------------------------------------------------------------------------------
         // weight ring (WeightRing, hm_sdf_common.h): 4 slots, 3 blocks of 2 KB in flight per feature tile; it lives across
@@ -146,6 +190,7 @@ __device__ __forceinline__ void sdf_split_tile(const HmLevels &lv, const SdfNet 
                 }
                 RED[sl * kPS + p] = part;
                 sdf_last_finish(RED, kWS, kPS, cnt, Ly.bias, net.beta, out, base, out_stride, tid);
+                HM_SPLIT_PROBE(100);
                 break;
             }
             const int nt = Ly.n_tiles;
@@ -156,6 +201,15 @@ __device__ __forceinline__ void sdf_split_tile(const HmLevels &lv, const SdfNet 
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) acc[a][q] = f32x16{0};
+            // the epilogue's bias quads, requested in front of the k-loop: behind the barrier they would be one exposed
+            // round trip to memory per layer, with every wave of the workgroup waiting at the same moment.  (Unconditional,
+            // on a tile index clamped into the padded bias [nt][32], for the waves that own fewer than two tiles.)
+            float4 bias4[2][4];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    bias4[a][q] = *reinterpret_cast<const float4 *>(Ly.bias + 32 * min(t0 + a, nt - 1) + 8 * q + 4 * h);
             if (ntw > 0) {
                 const int nb = Ly.seg_blocks16[0] + Ly.seg_blocks16[1];
                 int blk0 = 0;
@@ -197,42 +251,45 @@ __device__ __forceinline__ void sdf_split_tile(const HmLevels &lv, const SdfNet 
                 }
             }
             if (li + 1 < net.n_layers - 1) ring_ready = prefetch_layer(li + 1);
+            HM_SPLIT_PROBE(3 + 4 * li);
             __syncthreads();  // every wave has finished reading the planes for this layer
+            HM_SPLIT_PROBE(4 + 4 * li);
 
-            // epilogue: registers 4q..4q+3 of a tile = features 8q + 4h + {0..3} -> 4 elements of one k-octet of the next layer
-            const bool act = Ly.activation != 0;
-            const bool div = Ly.post_div_sqrt2 != 0;
+            // epilogue: registers 4q..4q+3 of a tile = features 8q + 4h + {0..3} -> 4 elements of one k-octet of the next layer.
+            // The layer's activation / division flags pick ONE instance of the quad loops (no branch inside them: the
+            // scheduler interleaves the transcendentals of neighbouring quads).
+            auto epilogue = [&](auto act, auto div) {
 #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                if (a >= ntw) continue;
-                const int fbase = 32 * (t0 + a);
-#pragma unroll
-                for (int pt = 0; pt < 2; ++pt) {
+                for (int a = 0; a < 2; ++a) {
+                    if (a >= ntw) continue;
+                    const int fbase = 32 * (t0 + a);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int f = fbase + 8 * q + 4 * h;
-                        const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
-                        float v[4];
+                        const float4 bb = bias4[a][q];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[a][pt][4 * q + e];
-                        v[0] = __fmaf_rn(v[0], S::inv, bb.x); v[1] = __fmaf_rn(v[1], S::inv, bb.y);
-                        v[2] = __fmaf_rn(v[2], S::inv, bb.z); v[3] = __fmaf_rn(v[3], S::inv, bb.w);
-                        V4 oh, ol;
-                        act_quads(v, act, div);
+                        for (int pt = 0; pt < 2; ++pt) {
+                            float v[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            T hi, lo;
-                            split_val<KIND>(v[e] * S::xs, hi, lo);
-                            oh[e] = hi;
-                            ol[e] = lo;
+                            for (int e = 0; e < 4; ++e) v[e] = acc[a][pt][4 * q + e];
+                            v[0] = __fmaf_rn(v[0], S::inv, bb.x); v[1] = __fmaf_rn(v[1], S::inv, bb.y);
+                            v[2] = __fmaf_rn(v[2], S::inv, bb.z); v[3] = __fmaf_rn(v[3], S::inv, bb.w);
+                            V4 oh, ol;
+                            split_quad<KIND, decltype(act)::value, decltype(div)::value>(v, oh, ol);
+                            const size_t o = (size_t)(f >> 3) * kOctE + (32 * pt + j) * 8 + 4 * h;
+                            *reinterpret_cast<V4 *>(XH + o) = oh;
+                            *reinterpret_cast<V4 *>(XL + o) = ol;
                         }
-                        const size_t o = (size_t)(f >> 3) * kOctE + (32 * pt + j) * 8 + 4 * h;
-                        *reinterpret_cast<V4 *>(XH + o) = oh;
-                        *reinterpret_cast<V4 *>(XL + o) = ol;
                     }
                 }
-            }
+            };
+            const auto with_div = [&](auto act) {
+                if (Ly.post_div_sqrt2 != 0) epilogue(act, std::true_type{}); else epilogue(act, std::false_type{});
+            };
+            if (Ly.activation != 0) with_div(std::true_type{}); else with_div(std::false_type{});
+            HM_SPLIT_PROBE(5 + 4 * li);
             __syncthreads();
+            HM_SPLIT_PROBE(6 + 4 * li);
         }
     }
 }

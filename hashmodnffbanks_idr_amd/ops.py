@@ -612,7 +612,7 @@ class PackedSdf:
     """Device-resident packed weights + the [host] hm_mlp_desc for hm_sdf_fwd.
 
     The image buffers are allocated once (stable pointers, so the descriptor stays valid across
-    optimizer steps and inside captured graphs); update() re-packs them with one kernel per layer."""
+    optimizer steps and inside captured graphs); update() re-packs them with one launch per image family."""
 
     def __init__(self, weights, biases, E, skip_in, beta, with_bf16=False, split=None):
         n = len(weights)
@@ -685,6 +685,7 @@ class PackedSdf:
     def update(self, weights, biases, beta):
         self.desc.beta = float(beta)
         items = (_lib.PackItem * len(self.bufs))()
+        split_items = (_lib.PackSplitItem * len(self.bufs))()
         self.keep = []
         for l, (img8, img16, bpad) in enumerate(self.bufs):
             out_dim, w0, w1 = self.segs[l]
@@ -703,9 +704,12 @@ class PackedSdf:
                                                    stream_ptr(W)))
             if self.split is not None:
                 s0, s1 = self.split_scales[l]
-                check(lib().hm_pack_mlp_layer_split(dptr(W), W.stride(0), out_dim, w0, w1, s0, s1, self.desc.split_kind,
-                                                    dptr(self.split_imgs[l]), stream_ptr(W)))
-        # all fp32 operand images (8-k, 16-k) and padded biases in ONE launch
+                split_items[l] = _lib.PackSplitItem(W.data_ptr(), self.split_imgs[l].data_ptr(), W.stride(0), out_dim, w0,
+                                                    w1, s0, s1, 0)
+        # all split images in ONE launch; all fp32 operand images (8-k, 16-k) and padded biases in another
+        if self.split is not None:
+            check(lib().hm_pack_mlp_layers_split(C.cast(split_items, C.c_void_p), len(self.bufs), self.desc.split_kind,
+                                                 stream_ptr(self.bufs[0][0])))
         check(lib().hm_pack_mlp_layers(C.cast(items, C.c_void_p), len(self.bufs), stream_ptr(self.bufs[0][0])))
 
 

@@ -293,6 +293,17 @@ HM_API int hm_sdf_fwd_emb_bf16(const hm_mlp_desc *mlp, const float *emb, int64_t
 HM_API int hm_pack_mlp_layer_split(const float *W, int64_t ldw, int out_dim, int seg_width0, int seg_width1,
                                    float seg_scale0, float seg_scale1, int split_kind, void *w_packed_split,
                                    void *stream);
+/* the same for every layer of a network in ONE launch (the per-step re-pack); items is a [host] array of at most
+ * HM_MAX_LAYERS entries with the arguments of hm_pack_mlp_layer_split, all of the kind split_kind                 */
+typedef struct hm_pack_split_item {
+    const float *W;
+    void *w_packed_split;
+    int64_t ldw;
+    int32_t out_dim, seg_width0, seg_width1;
+    float seg_scale0, seg_scale1;
+    int32_t pad_;
+} hm_pack_split_item;
+HM_API int hm_pack_mlp_layers_split(const hm_pack_split_item *items, int n_items, int split_kind, void *stream);
 HM_API int hm_sdf_fwd_split(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n,
                             const float *table, const float *B_fourier, float *out, int64_t out_stride, int frac_mode,
                             const int32_t *n_dev, int64_t run_min, void *stream);

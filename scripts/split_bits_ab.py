@@ -1,5 +1,5 @@
 """Did a change of csrc/hm_sdf_split.hip move any bit?  Runs hm_sdf_fwd_split and hm_sdf_fwd_emb_split, both kinds
-(bf16x2, f16x2), on the `c2`, `odd_tiles`, `w32`, `ragged` and `depth1` networks of tests/sdf_shapes.py over seeded points,
+(bf16x2, f16x2), the grid form in both frac modes, on the `c2`, `odd_tiles`, `w32`, `ragged` and `depth1` networks of tests/sdf_shapes.py over seeded points,
 once on the library in the tree and once on another build of the same ABI (HM_LIB_PATH, e.g. the parent commit's
 libhashmod.so), each in a child process of its own, and compares the SHA-256 of every output.
 
@@ -43,6 +43,7 @@ def child():
                     net.coarse_split = kind
                     pk = net.packed_weights()
                     for form, t in (("grid", ops.sdf_fwd_split(desc, pk, x, table, B, frac)),
+                                    ("grid-trilinear", ops.sdf_fwd_split(desc, pk, x, table, B, 1)),
                                     ("emb", ops.sdf_fwd_emb_split(pk, e))):
                         out[f"{name} n={n} {kind} {form}"] = hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()
     torch.cuda.synchronize()
