@@ -67,7 +67,9 @@ __host__ __device__ inline SdfLds sdf_lds_small(const SdfNet &net, int E, int pt
     return sdf_lds(pts, 2, net.x_groups * pts * 4, 1, (E + 15) / 16 * 4 * pts * 4, kWaves);
 }
 
-template <int FRAC>
+// QUARTER: the launch with quarter tiles enabled (HM_SDF_TILE64_QUARTER) - a kernel of its own, so that the third tile
+// form costs the launches without it nothing
+template <int FRAC, bool QUARTER>
 __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_fwd_kernel(HmLevels lv, SdfNet net,
                                                                   const float *__restrict__ x, int64_t n,
                                                                   const float *__restrict__ table,
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_fwd_kernel(HmLevels lv, Sd
         if (fa.prev_dev)
             fb.tile0 = fill_quota(max(*fa.prev_dev, 0), fa.prev_grid, (fb.n + kPts - 1) / kPts, run_min);
     }
-    sdf64_run<FRAC, false>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, nullptr, fb);
+    sdf64_run<FRAC, false, QUARTER>(lv, net, x, n, table, Bf, out, out_stride, out_cols, lds, nullptr, fb);
 }
 
 
@@ -1008,9 +1010,12 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
                         const SdfFillArgs *fill, int *grid64_out) {
     HM_CHECK_ARG(n >= 0, "hm_sdf_fwd: n < 0");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_sdf_fwd: bad frac_mode");
+    // the 64-point launch with quarter tiles enabled
+    const bool quarter = tile_points == HM_SDF_TILE64_QUARTER;
+    if (quarter) tile_points = 64;
     HM_CHECK_ARG(tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16 || tile_points == 64 ||
                      tile_points == -1,
-                 "hm_sdf_fwd: tile_points must be -1, 0, 4, 8, 16 or 64");
+                 "hm_sdf_fwd: tile_points must be -1, 0, 4, 8, 16, 64 or HM_SDF_TILE64_QUARTER");
     SdfNet net;
     bool have16 = true;
     {
@@ -1062,19 +1067,23 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
     if (run64) {
         const size_t lds = sdf_lds64(net).bytes();
         HM_CHECK_ARG(lds <= kLds64Max, "hm_sdf_fwd: network does not fit the 160 KB LDS tile");
-        const int64_t tiles = (n + 31) / 32;      // (up to cap * 32 points: one 32-point half tile per workgroup)
+        // (up to cap * 32 points: one 32-point half tile per workgroup - or one quarter tile of 16)
+        const int64_t tiles = quarter ? (n + 15) / 16 : (n + 31) / 32;
         const int64_t grid = tiles < cap ? tiles : cap;
         // filler tiles only where every launch of the chain applies the same lower bound (fill_quota's run_min)
         const SdfFillArgs none = {nullptr, nullptr, nullptr, nullptr, 0, 0};
         const SdfFillArgs fa = (fill && lo64 == kSdfSmall + 1 && out_cols == 1 && out_stride == 1) ? *fill : none;
         if (grid64_out && fa.n_dev) *grid64_out = (int)grid;
-        const int rc = sdf_dispatch(mode, [&](auto frac) {
-            constexpr auto kernel = sdf_fwd_kernel<decltype(frac)::value>;
+        const auto launch = [&](auto frac, auto q) {
+            constexpr auto kernel = sdf_fwd_kernel<decltype(frac)::value, decltype(q)::value>;
             const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024);
             if (rc == HM_OK)
                 hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kThreadsSdf), lds, as_stream(stream), lv, net, x, n,
                                    table, B_fourier, out, out_stride, out_cols, n_dev, lo64, hi64, fa);
             return rc;
+        };
+        const int rc = sdf_dispatch(mode, [&](auto frac) {
+            return quarter ? launch(frac, std::true_type{}) : launch(frac, std::false_type{});
         });
         if (rc != HM_OK) return rc;
     }

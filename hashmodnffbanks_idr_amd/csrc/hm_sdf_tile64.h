@@ -16,6 +16,15 @@ constexpr int kPts = 64;        // points per workgroup tile
 constexpr int kThreadsSdf = 512;
 constexpr int kWaves = 8;
 constexpr int kGroupFloats = kPts * 4;  // floats per k-group row of X: [point][4]
+typedef float f32x4q __attribute__((ext_vector_type(4)));   // accumulator of a 16x16x4 MFMA (quarter tile)
+
+// v_permlane32_swap: lanes 32..63 of a change places with lanes 0..31 of b -> a = (a[0..31] | b[0..31]), b = (a[32..63] |
+// b[32..63]), each in lane order
+__device__ __forceinline__ void lane32_swap(float &a, float &b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    a = __uint_as_float(r[0]);
+    b = __uint_as_float(r[1]);
+}
 
 // dynamic LDS of the 64-point tile: X, the embedding (kept for the skip connection), 8 partial sums per point
 __host__ __device__ inline SdfLds sdf_lds64(const SdfNet &net) {
@@ -53,7 +62,9 @@ __device__ __forceinline__ int64_t fill_quota(int64_t n_own, int64_t grid, int64
 // The 64-point tile loop of sdf_fwd_kernel / sdf_scan_secant_kernel.  DYN = false: the static schedule below
 // (tile = round * grid + workgroup); DYN = true: the SAME tiles in the same enumeration, handed out by an atomic cursor
 // (zero at launch) - workgroups that start late (they carried secant rays first) simply take fewer of them.
-template <int FRAC, bool DYN>
+// QUARTER (static schedule, no filler set): a launch of at most 16 points per workgroup runs QUARTER tiles of <= 16 points
+// on v_mfma_f32_16x16x4_f32 - see the k-loop below; every other count keeps the schedule of QUARTER = false.
+template <int FRAC, bool DYN, bool QUARTER = false>
 __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net, const float *__restrict__ x, int64_t n,
                                           const float *__restrict__ table, const float *__restrict__ Bf,
                                           float *__restrict__ out, int64_t out_stride, int out_cols, float *lds,
@@ -70,6 +81,8 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
     const int lane = tid & 63;
     const int j = lane & 31;  // point within a 32-point tile / feature row within a 32-feature tile
     const int h = lane >> 5;
+    const int m = lane & 15;  // quarter tile: point / feature row within a 16-feature sub-tile
+    const int q = lane >> 4;  //               K slot of the 16x16x4 MFMA; feature quad of its result
     const int E = lv.E;
     // Tile schedule: `rounds` full rounds of 64-point tiles (tile = round * grid + workgroup), then ONE remainder tile
     // per workgroup.  When the remainder fits 32 points per workgroup it is cut into 32-point HALF tiles (the MFMAs of
@@ -82,7 +95,9 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
     const int64_t n_fill = DYN ? 0 : fill_quota(n, G, max((fb.n + kPts - 1) / kPts - fb.tile0, (int64_t)0), 0);
     const int64_t rounds = n_fill > 0 ? (TA + n_fill) / G : (n / kPts) / G;
     const int64_t rem_base = rounds * G * kPts;
-    const int64_t rem_step = (n - rem_base <= G * 32) ? 32 : kPts;
+    // quarter tiles: the whole launch is one remainder round of 16-point tiles
+    const bool qt = QUARTER && !DYN && n_fill == 0 && n <= G * 16;
+    const int64_t rem_step = qt ? 16 : (n - rem_base <= G * 32) ? 32 : kPts;
 
     for (int64_t it = 0;; ++it) {
         int64_t itr = it, wg = blockIdx.x;
@@ -127,21 +142,38 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
 
         // ---------------- encode -> EMB[(e/4)][p][e%4] ------------------------------------
         if constexpr (FRAC == kFracEmb) {
-            load_emb_tile(EMB, xs, net.emb_stride, base, cnt, E, net.emb_groups, kPts, kGroupFloats, tid, kThreadsSdf);
+            load_emb_tile(EMB, xs, net.emb_stride, base, cnt, E, net.emb_groups, qt ? 16 : kPts, kGroupFloats, tid,
+                          kThreadsSdf);
         } else {
-            const int p = tid & (kPts - 1);
-            const int grp = tid >> 6;  // 0..7
+            // (quarter tile: 16 points, so 32 threads share a point's slots; rows 16.. of the image are never read by a
+            //  lane whose value is kept)
+            const int p = qt ? (tid & 15) : (tid & (kPts - 1));
+            const int grp = qt ? (tid >> 4) : (tid >> 6);  // 0..31 / 0..7
             const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, grp, kWaves, net.emb_groups * 4,
+            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, grp, qt ? kThreadsSdf / 16 : kWaves, net.emb_groups * 4,
                               [&](int e, float v) { EMB[(e >> 2) * kGroupFloats + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
         HM_PROBE(1);
 
         // ---------------- layers ------------------------------------------------------------
+        // (a generic lambda: the quarter tile's copy of the layer loop is compiled beside the other two forms', not into
+        //  them - with the three k-loops in one loop body the registers of all of them were live together)
+        auto run_layers = [&](auto qt_c) {
+        constexpr bool QT = decltype(qt_c)::value;
         // weight ring (WeightRing, hm_sdf_common.h: 4 slots, 3 octets = 6 KB per wave in flight); it lives across layers
         WeightRing<4, 2> ring;
-        ring.voff = lane * 16;
+        // Quarter tile: the SAME image and the same two 16-byte loads per octet.  Octet g of a 32-feature tile holds, in
+        // image lane (feature j, h), W[j][8g + 4h + 0..3], and the 32x32x2 loop below hands an accumulator k = 8g + 0, 4,
+        // 1, 5, 2, 6, 3, 7 in that order (component x of h = 0 / 1, then y, z, w).  On 16x16x4 that chain is two MFMAs per
+        // octet and 16-feature sub-tile u with K slots (k0, k4, k1, k5) and (k2, k6, k3, k7): lane (row m, slot q) needs
+        // components q >> 1 and 2 + (q >> 1) of image lane (16 u + m, h = q & 1) for u = 0 and 1.  It loads image lane
+        // (16 (q >> 1) + m, h = q & 1) - every lane another 16 bytes, as in the other forms - and holds the components its
+        // partner lane ^ 32 needs of that sub-tile where the partner holds what it needs of the other one:
+        // v_permlane32_swap on (x, y) and on (z, w) leaves sub-tile 0's operands of both MFMAs in x / z and sub-tile 1's in
+        // y / w.  Four VALU instructions per octet and no load a lane does not use (dword loads of single components,
+        // eight per octet, were bound by the texture addresser: 0.43 instead of 0.26 ms for the bench's list).
+        ring.voff = QT ? (16 * (q >> 1) + m + 32 * (q & 1)) * 16 : lane * 16;
         bool ring_ready = false;
         auto prefetch64 = [&](int l) {
             const hm_mlp_layer &Lp = net.layer[l];
@@ -184,7 +216,48 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
             const int t0 = 2 * wave;
             const int ntw = max(0, min(2, nt - t0));
             f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
-            if (ntw > 0) {
+            f32x4q aq[4] = {{0}, {0}, {0}, {0}};      // quarter tile: [feature tile][16-feature sub-tile]
+            if constexpr (QT) {
+                if (ntw > 0) {
+                    const __amdgpu_buffer_rsrc_t rsA = w_rsrc(Ly.w_packed + ((size_t)t0 * n_oct) * 256);
+                    const int so[2] = {0, ntw > 1 ? n_oct * 1024 : 0};
+                    const int no0 = Ly.seg_octets[0];
+                    const float *src0 = ((Ly.seg_src[0] == 0) ? X : EMB) + (q & 1) * kGroupFloats + m * 4 + (q >> 1);
+                    const float *src1 = ((Ly.seg_src[1] == 0) ? X : EMB) + (q & 1) * kGroupFloats + m * 4 + (q >> 1);
+                    if (!ring_ready) prefetch64(li);
+                    ring_ready = false;
+                    auto loadBq = [&](int gg, float &b0, float &b1) {
+                        const int gc = min(gg, n_oct - 1);
+                        const float *src = (gc < no0) ? src0 + 2 * gc * kGroupFloats : src1 + 2 * (gc - no0) * kGroupFloats;
+                        b0 = src[0];
+                        b1 = src[2];
+                    };
+                    // (the slot is consumed: x / z become sub-tile 0's operands of the two MFMAs, y / w sub-tile 1's)
+                    auto mfma8 = [&](float4 (&w)[2], float b0, float b1) {
+#pragma unroll
+                        for (int ft = 0; ft < 2; ++ft) {
+                            lane32_swap(w[ft].x, w[ft].y);
+                            lane32_swap(w[ft].z, w[ft].w);
+                        }
+                        aq[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[0].x, b0, aq[0], 0, 0, 0);
+                        aq[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[0].y, b0, aq[1], 0, 0, 0);
+                        aq[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[1].x, b0, aq[2], 0, 0, 0);
+                        aq[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[1].y, b0, aq[3], 0, 0, 0);
+                        aq[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[0].z, b1, aq[0], 0, 0, 0);
+                        aq[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[0].w, b1, aq[1], 0, 0, 0);
+                        aq[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[1].z, b1, aq[2], 0, 0, 0);
+                        aq[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[1].w, b1, aq[3], 0, 0, 0);
+                        // (the next octet's loads stay below: hoisted into this slot's registers while its last MFMAs
+                        //  still read them, they cost a copy behind a vmcnt(0) per octet)
+                        __builtin_amdgcn_sched_barrier(0);
+                    };
+                    float bA0, bA1, bB0, bB1;       // B components: even octets in set A, odd octets in set B
+                    loadBq(0, bA0, bA1);
+                    ring.run(rsA, so, n_oct,
+                             [&](int gg, int u) { if (u & 1) loadBq(gg + 1, bA0, bA1); else loadBq(gg + 1, bB0, bB1); },
+                             [&](int, int u, float4 (&w)[2]) { if (u & 1) mfma8(w, bB0, bB1); else mfma8(w, bA0, bA1); });
+                }
+            } else if (ntw > 0) {
                 const __amdgpu_buffer_rsrc_t rsA = w_rsrc(Ly.w_packed + ((size_t)t0 * n_oct) * 256);
                 const int so[2] = {0, ntw > 1 ? n_oct * 1024 : 0};     // byte offsets of the wave's two feature tiles
                 const int no0 = Ly.seg_octets[0];
@@ -274,19 +347,36 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
                         make_float4(v[0], v[1], v[2], v[3]);
                 }
             };
-            if (ntw > 0) {
-                store_tile(acc00, 0, 0);
-                if (!half) store_tile(acc01, 0, 1);
-            }
-            if (ntw > 1) {
-                store_tile(acc10, 1, 0);
-                if (!half) store_tile(acc11, 1, 1);
+            // quarter tile: registers 0..3 of sub-tile a = features 16 a + 4q + {0..3} of the wave's tiles, point m
+            auto store_quarter = [&](const f32x4q &acc, int a) {
+                const int f = 32 * t0 + 16 * a + 4 * q;
+                const float4 bb = *reinterpret_cast<const float4 *>(Ly.bias + f);
+                float v[4] = {acc[0] + bb.x, acc[1] + bb.y, acc[2] + bb.z, acc[3] + bb.w};
+                act_quads(v, act, div);
+                *reinterpret_cast<float4 *>(X + (f >> 2) * kGroupFloats + m * 4) = make_float4(v[0], v[1], v[2], v[3]);
+            };
+            if constexpr (QT) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+                    if (a < 2 * ntw) store_quarter(aq[a], a);
+            } else {
+                if (ntw > 0) {
+                    store_tile(acc00, 0, 0);
+                    if (!half) store_tile(acc01, 0, 1);
+                }
+                if (ntw > 1) {
+                    store_tile(acc10, 1, 0);
+                    if (!half) store_tile(acc11, 1, 1);
+                }
             }
             if (li == 0 && net.emb_groups > 0) rescale_emb(EMB, net.emb_groups * kGroupFloats, tid, kThreadsSdf);
             HM_PROBE(4 + 4 * li);
             __syncthreads();
             HM_PROBE(5 + 4 * li);
         }
+        };
+        if (QUARTER && qt) run_layers(std::true_type{});
+        else run_layers(std::false_type{});
         HM_PROBE(100);
 
         // ---------------- output: X[(f/4)][p][f%4] -> out[p][f] -----------------------------

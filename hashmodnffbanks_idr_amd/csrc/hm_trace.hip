@@ -743,9 +743,12 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     auto guard_patch = [&](int c_ref) {
         hipLaunchKernelGGL(guard_patch_kernel, dim3((unsigned)((L.cap + kTB - 1) / kTB)), dim3(kTB), 0, st, a, c_ref);
     };
-    auto guard_refine = [&](int c_ref) -> int {
+    // quarter: a list of at most 16 points per workgroup runs quarter tiles (the same values in two thirds of the time of the half
+    // tiles; only where the launch stands alone - the closest-approach rows' list behind the secant chain)
+    auto guard_refine = [&](int c_ref, bool quarter = false) -> int {
         const int rc = hm_sdf_fwd(desc, mlp, a.w.ref_pts, L.cap, table, B_fourier, a.w.ref_vals, 1, 1, frac_mode,
-                                  tile_points == 0 ? 64 : tile_points, a.w.cnt + c_ref, 0, stream);
+                                  tile_points == 0 ? (quarter ? HM_SDF_TILE64_QUARTER : 64) : tile_points,
+                                  a.w.cnt + c_ref, 0, stream);
         if (rc != HM_OK) return rc;
         guard_patch(c_ref);
         return HM_OK;
@@ -875,7 +878,7 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
             hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
                                (int)C_GUARD_NC);
-            rc = guard_refine((int)C_GUARD_NC);
+            rc = guard_refine((int)C_GUARD_NC, true);
             if (rc != HM_OK) return rc;
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         } else if (cosched) {

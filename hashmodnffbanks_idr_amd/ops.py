@@ -13,6 +13,8 @@ from . import _lib
 from ._lib import check, dptr, lib, require_gpu, stream_ptr
 
 FRAC_MODES = {"reference": 0, "trilinear": 1}
+# sdf_fwd / sdf_fwd_emb tile_points: the 64-point launch with quarter tiles enabled (hashmod.h: HM_SDF_TILE64_QUARTER)
+TILE64_QUARTER = 1664
 
 
 # =========================================================================================

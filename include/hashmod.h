@@ -259,9 +259,13 @@ HM_API int hm_pack_mlp_layer_bf16(const float *W, int64_t ldw, int out_dim, int 
  * tile_points: 64 (one 8-wave workgroup per CU), 16 (small batches),
  * 8 or 4 (<= 2048 / 1024 points: bound by the weight stream alone), 0 = choose by n (on the device when n_dev is given),
  * -1 = like 0 but ONLY for n <= 8192 (larger batches are left to another launch, e.g. hm_sdf_fwd_bf16 with run_min 8193).
+ * HM_SDF_TILE64_QUARTER = the 64-point launch with quarter tiles enabled: a live count of at most 16 points per workgroup
+ * runs tiles of <= 16 points on v_mfma_f32_16x16x4_f32 in the 64-point tile's accumulation order (the values of
+ * tile_points = 64 bit for bit, in about two thirds of the time of its 32-point half tiles); larger counts run as with 64.
  * n_dev: optional DEVICE int32; when non-NULL the kernel evaluates min(n, *n_dev) points, so a
  *        caller that compacts work on the device needs no host synchronisation (n is the capacity).
  * max_workgroups <= 0: fill the chip once (persistent grid-stride over tiles).                    */
+#define HM_SDF_TILE64_QUARTER 1664
 HM_API int hm_sdf_fwd(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n,
                       const float *table, const float *B_fourier, float *out, int64_t out_stride, int out_cols,
                       int frac_mode, int tile_points, const int32_t *n_dev, int max_workgroups, void *stream);
