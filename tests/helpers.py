@@ -152,6 +152,24 @@ def nffb_conf(embed_type):
     return Conf(c)
 
 
+def make_implicit_nffb(embed_type, L, hidden, fvs, seed, bias=0.6, device="cuda"):
+    """ImplicitNetwork on a filter-bank embedder ('FFB' / 'StyleModNFFB') of L levels (embedding width 3 + 8 + 8 L) with
+    seeded parameters: params.make_sdf_params(seed + 7, ..) and params.make_nffb_params(seed + 3, ..)"""
+    from hashmodnffbanks_idr_amd.model.implicit_differentiable_renderer import ImplicitNetwork
+    net = ImplicitNetwork(fvs, 3, 1, list(hidden), True, 0.6, [4], True, multires=L, embed_type=embed_type,
+                          log2_max_hash_size=5, max_points_per_entry=2, base_resolution=16, desired_resolution=512,
+                          bound=1.0)
+    sd = net.state_dict()
+    prm = dict(P.make_sdf_params(seed + 7, 3 + 8 + 8 * L, tuple(hidden), 1 + fvs, (4,), bias, 0.1, 0.1))
+    for k, v in P.make_nffb_params(seed + 3, L, embed_type == "StyleModNFFB", 0.3).items():
+        prm["embed_model.embedder_obj." + k] = v
+    for k, v in prm.items():
+        assert sd[k].shape == v.shape, (k, sd[k].shape, v.shape)
+        sd[k] = torch.from_numpy(v)
+    net.load_state_dict(sd)
+    return net.to(device)
+
+
 def make_idr_nffb(embed_type, seed, device="cuda"):
     """IDRNetwork on a filter-bank embedder with the seeded parameters make_goldens.gen_idr_step_nffb gave the reference."""
     from hashmodnffbanks_idr_amd.model.implicit_differentiable_renderer import IDRNetwork

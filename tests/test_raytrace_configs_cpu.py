@@ -176,6 +176,19 @@ def test_radius_and_threshold_cases(layout):
     assert thr0["sampler"] > bench["sampler"]                                # fewer rays converge by the threshold
 
 
+def test_filter_bank_layouts_stay_within_the_small_embedder_launch():
+    """no launch of either tracer holds more than rays * max(n_steps, 2) points: with these layouts every launch of every
+    configuration runs the embedder's lanes-per-point kernel (test_raytrace_nffb_gpu.py, all-VALU regime)"""
+    assert set(TC.NFFB_LAYOUTS) == {"1x1", "3x21", "1x63"}
+    for layout, (B, P) in TC.NFFB_LAYOUTS.items():
+        cam, dirs, om = TC.nffb_rays(layout)
+        assert cam.shape == (B, 3) and dirs.shape == (B, P, 3) and om.shape == (B, P)
+        for name, case in TC.CONFIGS.items():
+            assert B * P * max(case.n_steps, 2) <= TC.NFFB_SMALL_LAUNCH, (layout, name)
+    assert 63 * TC.CONFIGS["n130"].n_steps == 8190      # the largest: two points below the kernel switch
+    assert TC.LAYOUTS == {"1x300": (1, 300), "3x77": (3, 77), "1x1": (1, 1)}     # the hash-grid tests' own set
+
+
 def test_layouts_and_table():
     cam, dirs, om = TC.rays("3x77")
     assert cam.shape == (3, 3) and dirs.shape == (3, 77, 3) and om.shape == (3, 77)

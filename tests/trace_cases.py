@@ -4,6 +4,7 @@ settings, the ray layouts, object masks and injected closest-approach fractions,
   CONFIGS            name -> (TraceCase: the seven constructor arguments + the branch the entry exists for)
   LAYOUTS            name -> (cameras, rays per camera)
   rays(layout)       (cam_loc [B,3], ray_dirs [B,P,3], object_mask [B,P]) as torch CPU tensors
+  NFFB_LAYOUTS       the same for the filter-bank tests, with nffb_rays(layout)
   steps(n_steps)     the injected U(0,1) fractions of the closest-approach search
   SDFS               name -> analytic elementwise fp32 SDF (CPU test only)
 
@@ -54,6 +55,14 @@ CONFIGS = {
 LAYOUTS = {"1x300": (1, 300), "3x77": (3, 77), "1x1": (1, 1)}
 _LAYOUT_SEED = {"1x300": 100, "3x77": 200, "1x1": 300}
 
+# Filter-bank networks (tests/test_raytrace_nffb_gpu.py): the fused embedder picks its kernel by the live count of a launch
+# (<= 8192 points: the lanes-per-point kernel), so these layouts keep rays * max(n_steps, 2) - the tracer's largest launch
+# - within 8192 for every entry of CONFIGS (n130: 63 * 130 = 8190; asserted in test_raytrace_configs_cpu.py).  A table of
+# its own: the hash-grid tests keep their parameter sets.
+NFFB_LAYOUTS = {"1x1": (1, 1), "3x21": (3, 21), "1x63": (1, 63)}
+_NFFB_LAYOUT_SEED = {"1x1": 400, "3x21": 500, "1x63": 600}
+NFFB_SMALL_LAUNCH = 8192
+
 
 def tracer_args(case):
     return tuple(case[:7])
@@ -70,6 +79,12 @@ def make_rays(cameras, per_camera, seed):
 def rays(layout):
     B, n = LAYOUTS[layout]
     return make_rays(B, n, _LAYOUT_SEED[layout])
+
+
+@functools.lru_cache(maxsize=None)
+def nffb_rays(layout):
+    B, n = NFFB_LAYOUTS[layout]
+    return make_rays(B, n, _NFFB_LAYOUT_SEED[layout])
 
 
 @functools.lru_cache(maxsize=None)
