@@ -157,6 +157,10 @@ SIGNATURES = {
     "hm_mesh_keep_mark": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p]),
     "hm_mesh_vertex_colors": (_int, [_p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, C.c_float, _i64,
                                      C.c_double, _int, _int, _int, _p, _p, _p]),
+    # the mesh through a camera: the visibility buffer (nearest face per pixel) resolved with vertex attributes
+    "hm_mesh_render_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "hm_mesh_render": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p,
+                              _i64, _p, _p]),
 }
 
 

@@ -10,42 +10,22 @@
 //   hm_mesh_keep_mark      the face and vertex flags of "all three vertices kept", for hm_mesh_select_emit
 //
 // The projection, the pixel, the fixed-point position and the visibility rule are hm_view_dev.h's (the rule is also the
-// colours': hm_mesh_color.hip).  Coverage is decided by int64 edge functions of the fixed-point positions (|X|, |Y| <
-// 2^24 and pixel centres below 2^24: every product is below 2^50), the depth by fp64 operations rounded once, and a
-// pixel keeps the minimum through an unsigned atomicMin on the float's bits (positive floats order like their bits): the
+// colours': hm_mesh_color.hip); the projection kernel, the face set-up, the coverage test and the depth of a covered
+// pixel are hm_raster_dev.h's, shared with the renderer (hm_mesh_render.hip).  Coverage is decided by int64 edge
+// functions of the fixed-point positions, the depth by fp64 operations rounded once, and a pixel keeps the minimum through an unsigned atomicMin on the float's bits (positive floats order like their bits): the
 // depth maps do not depend on the order of the faces and two calls give the same bits.  The votes are written once per
 // vertex, without atomics.  No index is dereferenced before its range check.
-#include "hm_block_dev.h"
-#include "hm_view_dev.h"
+#include "hm_raster_dev.h"
 
 namespace {
 
-constexpr int kVT = 256;
-constexpr int kBigBlocks = 1024;          // workgroups of cull_raster_big: 4096 waves stride over the list
+constexpr int kVT = kRasterVT;
+constexpr int kBigBlocks = kRasterBigBlocks;
 constexpr uint32_t kInfBits = 0x7f800000u;
-
-// a vertex as one view sees it: 16 bytes, one load per face corner.  X == kBadX: the face is skipped
-struct __align__(16) ViewVert {
-    int32_t X, Y;
-    double iw;
-};
-constexpr int32_t kBadX = INT32_MIN;
-
-struct CullWs {
-    ViewVert *pv;        // [n_verts]
-    int32_t *list;       // [n_faces] the faces of the current view whose box exceeds big_face
-    uint32_t *count;     // [1]
-    int64_t bytes;
-};
 
 CullWs cull_layout(void *ws, int64_t n_verts, int64_t n_faces) {
     HmCarve c(ws);
-    CullWs w;
-    w.pv = c.take<ViewVert>(n_verts > 0 ? n_verts : 1);
-    w.list = c.take<int32_t>(n_faces > 0 ? n_faces : 1);
-    w.count = c.take<uint32_t>(1);
-    w.bytes = c.bytes;
-    return w;
+    return cull_layout(c, n_verts, n_faces);
 }
 
 __global__ __launch_bounds__(kVT) void cull_fill_kernel(uint32_t *__restrict__ p, int64_t n, uint32_t value) {
@@ -78,69 +58,9 @@ __global__ __launch_bounds__(kVT) void cull_mask_votes_kernel(const float *__res
     n_in_mask[i] = (accumulate ? n_in_mask[i] : 0) + n_msk;
 }
 
-__global__ __launch_bounds__(kVT) void cull_project_kernel(const float *__restrict__ verts, int64_t n_verts,
-                                                           const double *__restrict__ P, ViewVert *__restrict__ pv,
-                                                           uint32_t *__restrict__ count) {
-    const int64_t i = (int64_t)blockIdx.x * kVT + threadIdx.x;
-    if (i == 0) *count = 0u;   // the list of the view before this one has been consumed: the stream orders the launches
-    if (i >= n_verts) return;
-    const HmViewPoint q = hm_view_project(P, verts[i * 3], verts[i * 3 + 1], verts[i * 3 + 2]);
-    ViewVert o;
-    if (!hm_view_fixed(q, o.X, o.Y)) o.X = kBadX;
-    o.iw = __ddiv_rn(1.0, q.w);
-    pv[i] = o;
-}
-
-// a face of one view, ready to be drawn: its corners, its doubled area and the pixels of its clamped bounding box
-struct Tri {
-    int64_t X[3], Y[3], area;
-    double iw[3];
-    int c0, c1, r0, r1;   // columns c0..c1 and rows r0..r1, inclusive
-};
-
-enum { kTriNone = 0, kTriDraw = 1, kTriSkipped = 2 };
-
-// kTriSkipped: a corner is unprojectable or out of the fixed-point range; kTriNone: zero area or no pixel centre in the box
-__device__ __forceinline__ int cull_tri(const ViewVert *__restrict__ pv, const int32_t (&id)[3], int H, int W, Tri &t) {
-    bool ok = true;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        const ViewVert q = pv[id[m]];
-        ok = ok && q.X != kBadX;
-        t.X[m] = q.X;
-        t.Y[m] = q.Y;
-        t.iw[m] = q.iw;
-    }
-    if (!ok) return kTriSkipped;
-    t.area = (t.X[1] - t.X[0]) * (t.Y[2] - t.Y[0]) - (t.Y[1] - t.Y[0]) * (t.X[2] - t.X[0]);
-    if (t.area == 0) return kTriNone;
-    const int64_t xlo = min(t.X[0], min(t.X[1], t.X[2])), xhi = max(t.X[0], max(t.X[1], t.X[2]));
-    const int64_t ylo = min(t.Y[0], min(t.Y[1], t.Y[2])), yhi = max(t.Y[0], max(t.Y[1], t.Y[2]));
-    // the centres 256*col inside [xlo, xhi]: ceil and floor by arithmetic shifts (exact for negative values too)
-    t.c0 = (int)max((xlo + (kViewSub - 1)) >> 8, (int64_t)0);
-    t.c1 = (int)min(xhi >> 8, (int64_t)W - 1);
-    t.r0 = (int)max((ylo + (kViewSub - 1)) >> 8, (int64_t)0);
-    t.r1 = (int)min(yhi >> 8, (int64_t)H - 1);
-    return (t.c0 <= t.c1 && t.r0 <= t.r1) ? kTriDraw : kTriNone;
-}
-
 // the pixel (col, row) of the box: covered iff E_0, E_1, E_2 are all >= 0 or all <= 0; then depth = min(depth, z)
 __device__ __forceinline__ void cull_pixel(const Tri &t, int col, int row, int W, uint32_t *__restrict__ depth) {
-    const int64_t Xp = (int64_t)col * kViewSub, Yp = (int64_t)row * kViewSub;
-    int64_t E[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const int b = (a + 1) % 3, c = (a + 2) % 3;
-        E[a] = (t.X[c] - t.X[b]) * (Yp - t.Y[b]) - (t.Y[c] - t.Y[b]) * (Xp - t.X[b]);
-    }
-    const bool covered = (E[0] >= 0 && E[1] >= 0 && E[2] >= 0) || (E[0] <= 0 && E[1] <= 0 && E[2] <= 0);
-    if (!covered) return;
-    const double area = (double)t.area;
-    const double b0 = __ddiv_rn((double)E[0], area), b1 = __ddiv_rn((double)E[1], area),
-                 b2 = __ddiv_rn((double)E[2], area);
-    const double s = __dadd_rn(__dadd_rn(__dmul_rn(b0, t.iw[0]), __dmul_rn(b1, t.iw[1])), __dmul_rn(b2, t.iw[2]));
-    const float z = __double2float_rn(__ddiv_rn(1.0, s));
-    if (isfinite(z) && z > 0.0f) atomicMin(depth + (int64_t)row * W + col, __float_as_uint(z));
+    raster_pixel(t, col, row, [&](float z) { atomicMin(depth + (int64_t)row * W + col, __float_as_uint(z)); });
 }
 
 __global__ __launch_bounds__(kVT) void cull_raster_kernel(const ViewVert *__restrict__ pv,

@@ -5,6 +5,7 @@ stream; torch supplies device memory only.  CPU tensors raise (no fallback).
 """
 import ctypes as C
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -2388,6 +2389,76 @@ def mesh_keep_vertices(verts, faces, normals, keep):
     check(lib().hm_mesh_keep_mark(dptr(faces), n_faces, n_verts, dptr(keep), dptr(vflag), dptr(fflag), dptr(status),
                                   stream_ptr(faces)))
     return _mesh_emit_flagged("mesh_keep_vertices", verts, faces, normals, vflag, fflag, status)
+
+
+# =========================================================================================
+# The mesh through a camera (csrc/hm_mesh_render.hip, DESIGN.md "Rendering the mesh")
+# =========================================================================================
+RENDER_MAX_ATTR = 16
+MeshRender = namedtuple("MeshRender", ["face_id", "depth", "weights", "image", "n_skipped"])
+
+
+def mesh_render(verts, faces, proj, H, W, attrs=None, background=0.0, big_face=CULL_BIG_FACE, return_weights=False):
+    """MeshRender(face_id [n,H,W] int32, depth [n,H,W] fp32, weights [n,H,W,3] fp32 or None, image [n,H,W,C] fp32 or
+    None, n_skipped [n] int32): the mesh seen by every view, with the vertex attributes attrs [V,C] fp32 (0 <= C <= 16)
+    interpolated over the visible faces.
+
+    Visibility.  The projection, the skipped and counted faces (NO clipping), the coverage of a pixel centre and the
+    depth z of a covered pixel are mesh_depth_maps' - the same device functions - and so are `depth`'s bits.  A pixel
+    keeps the smallest 64-bit key (float_bits(z) << 32) | face over the samples with z finite and > 0, by an unsigned
+    64-bit atomicMin: the nearest sample and, among equal depths, the smallest face index, whatever the order in which
+    the faces are drawn; two calls give the same bits.  A face whose clamped box exceeds `big_face` pixels is drawn by
+    one wave, any other by one lane.
+
+    Resolve (one lane per pixel, no atomics).  Nothing drawn: face_id = -1, depth = +inf, weights = 0, image =
+    `background` (a float, or C floats).  Else, with b_m = E_m / area the screen-space barycentric weights of the face's
+    corners and iw_m = 1 / w_m:  t_m = b_m iw_m,  s = (t_0 + t_1) + t_2,  weights[m] = float32(t_m / s),
+    image[c] = float32((((t_0 a_0c) + (t_1 a_1c)) + (t_2 a_2c)) / s) - perspective-correct, every operation fp64 and
+    rounded once, in this order; a NaN attribute propagates.  No anti-aliasing, no lighting.
+    tests/mesh_render_cases.render_ref gives the same bits.
+
+    A face index outside [0, V) raises HashmodError (reported by the kernel, never dereferenced).  One host read of
+    the status word; not graph-capturable."""
+    what = "mesh_render"
+    n_verts, n_views = _check_views(what, verts, proj, H, W)
+    if not (isinstance(big_face, int) and big_face >= 1):
+        raise ValueError(f"hashmod {what}: big_face must be an integer >= 1")
+    n_attr = 0
+    if attrs is not None:
+        if (not isinstance(attrs, torch.Tensor) or attrs.dtype != torch.float32 or attrs.dim() != 2
+                or attrs.shape[0] != n_verts or attrs.shape[1] > RENDER_MAX_ATTR or not attrs.is_contiguous()):
+            raise ValueError(f"hashmod {what}: contiguous fp32 attrs [V, C] with C <= {RENDER_MAX_ATTR} expected")
+        if attrs.device != verts.device:
+            raise ValueError(f"hashmod {what}: the tensors are on different devices")
+        n_attr = int(attrs.shape[1])
+    try:
+        bg = np.asarray(background, np.float32)
+        bg = np.ascontiguousarray(np.broadcast_to(bg, (n_attr,)) if bg.ndim == 0 else bg)
+    except (TypeError, ValueError):
+        bg = None
+    if background is None or bg is None or bg.shape != (n_attr,):
+        raise ValueError(f"hashmod {what}: background must be a float or a sequence of C floats")
+    n_faces, _ = _check_mesh(what, faces, verts=verts, gpu_first=False)
+    require_gpu(attrs)
+    dev = verts.device
+    proj = _device_proj(proj, dev)
+    face_id = torch.empty((n_views, H, W), dtype=torch.int32, device=dev)
+    depth = torch.empty((n_views, H, W), dtype=torch.float32, device=dev)
+    weights = torch.empty((n_views, H, W, 3), dtype=torch.float32, device=dev) if return_weights else None
+    image = None if attrs is None else torch.empty((n_views, H, W, n_attr), dtype=torch.float32, device=dev)
+    n_skipped = torch.empty(n_views, dtype=torch.int32, device=dev)
+    if n_views == 0:
+        return MeshRender(face_id, depth, weights, image, n_skipped)
+    L = lib()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _CULL_WS.get(dev, check(L.hm_mesh_render_workspace_bytes(n_verts, n_faces, H, W)))
+    given = n_attr > 0                 # C == 0: an empty tensor has no address; the kernel then has no image to write
+    check(L.hm_mesh_render(dptr(verts), n_verts, dptr(faces), n_faces, dptr(proj), n_views, H, W, big_face,
+                           dptr(attrs) if given else None, n_attr, bg.ctypes.data_as(C.c_void_p) if given else None,
+                           dptr(face_id), dptr(depth), dptr(weights), dptr(image) if given else None,
+                           dptr(n_skipped), dptr(ws), ws.numel(), dptr(status), stream_ptr(verts)))
+    _check_mesh_status(what, status)
+    return MeshRender(face_id, depth, weights, image, n_skipped)
 
 
 # =========================================================================================

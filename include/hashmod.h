@@ -1105,6 +1105,33 @@ HM_API int hm_mesh_vertex_colors(const float *verts, const float *normals, int64
                                  double min_cos, int power, int mode, int accumulate, double *acc, int32_t *n_used,
                                  void *stream);
 
+/* ---- mesh rendering: a visibility buffer of the mesh per view, resolved with interpolated vertex attributes ---------
+ * Driver: ops.mesh_render, evaluation.mesh_views.  csrc/hm_mesh_render.hip, csrc/hm_raster_dev.h.  Does not
+ * synchronise; sizes, proj, the projection, the fixed-point position, the skipped faces, coverage, b_a, iw_a and the
+ * depth z of a covered pixel as for hm_mesh_depth_maps above (the same device functions).
+ *   hm_mesh_render: per view, every pixel starts with the 64-bit key of all ones; a covered pixel whose z is finite and
+ *                > 0 takes key = min(key, (uint64(float_bits(z)) << 32) | uint32(face)) by an unsigned 64-bit atomic
+ *                minimum: the nearest sample and, among equal depths, the smallest face index, independent of the order
+ *                of the faces.  Then, per pixel (written once, no atomics): an all-ones key gives face_id = -1,
+ *                depth = +inf, weights = 0, image = background; any other key gives face_id = its low word, depth = its
+ *                high word as a float, and with that face's corners m = 0, 1, 2:
+ *                  t_m = b_m * iw_m,  s = (t_0 + t_1) + t_2,  weights[m] = float(t_m / s),
+ *                  image[c] = float((((t_0 * a_0c) + (t_1 * a_1c)) + (t_2 * a_2c)) / s),  a_mc = double(attrs[v_m][c]),
+ *                every operation fp64 and rounded once, in this order; a NaN attribute propagates.
+ *                attrs [n_verts, n_attr] fp32 with n_attr in [0, 16], or NULL; background [n_attr] fp32 on the HOST
+ *                (read before the launches) or NULL for zeros; face_id [n_views, H, W] int32; depth [n_views, H, W]
+ *                fp32; weights [n_views, H, W, 3] fp32 or NULL; image [n_views, H, W, n_attr] fp32, NULL iff attrs is;
+ *                n_skipped [n_views] int32.  A face whose clamped box has more than big_face (>= 1) pixels is drawn by
+ *                one wave, any other by one lane.  A face index outside [0, n_verts) sets bit 0 of status [1] int32
+ *                and is never dereferenced.  No clipping, no anti-aliasing, no lighting.
+ *                workspace: hm_mesh_render_workspace_bytes(n_verts, n_faces, H, W) bytes, reused view after view. */
+HM_API int64_t hm_mesh_render_workspace_bytes(int64_t n_verts, int64_t n_faces, int64_t H, int64_t W);
+HM_API int hm_mesh_render(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                          const double *proj, int64_t n_views, int64_t H, int64_t W, int64_t big_face,
+                          const float *attrs, int64_t n_attr, const float *background, int32_t *face_id, float *depth,
+                          float *weights, float *image, int32_t *n_skipped, void *workspace, int64_t workspace_bytes,
+                          int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
