@@ -161,6 +161,13 @@ SIGNATURES = {
     "hm_mesh_render_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "hm_mesh_render": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p,
                               _i64, _p, _p]),
+    # point-to-mesh distance: the triangle grid and the exact closest point
+    "hm_mesh_dist_workspace_bytes": (_i64, [_i64]),
+    "hm_mesh_dist_count": (_int, [_p, _p, _i64, _i64, _p, C.c_float, _p, _i64, _p, _p, _p, _p]),
+    "hm_mesh_dist_build": (_int, [_p, _p, _i64, _i64, _p, C.c_float, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _i64,
+                                  _p]),
+    "hm_mesh_dist_query": (_int, [_p, _i64, _p, _i64, _i64, _p, _p, C.c_float, _p, C.c_float, _p, _p, _p, _p, _p, _i64,
+                                  _p, _p, _p]),
 }
 
 

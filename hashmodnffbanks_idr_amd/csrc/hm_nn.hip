@@ -16,7 +16,8 @@
 // under the total order (d2, original index): it does not depend on which wave or box the query fell into.
 // Lanes that are not finished (stopping rule at nn_face_low) make the wave grow the box on all sides by a doubling
 // ring; only the new shell is scanned.  A box that covers the grid has no faces left and ends the search.
-// The grid record, the cell function and the host-side grid check are in hm_nn_dev.h, shared with hm_nn_radius.hip.
+// The grid record, the cell function, the host-side grid check, the key and cell-table kernels and the stopping rule's
+// checked faces (nn_face_low) are in hm_nn_dev.h, shared with hm_nn_radius.hip and hm_mesh_dist.hip.
 #include <math.h>
 
 #include "hm_block_dev.h"
@@ -27,21 +28,6 @@ namespace {
 constexpr int kChunk = 256;   // records staged in LDS per pass (4 KiB)
 constexpr int32_t kNoIndex = 0x7fffffff;
 
-__global__ __launch_bounds__(kNT) void nn_key_kernel(const float *__restrict__ p, int64_t n, NnGrid G,
-                                                     int32_t *__restrict__ key, int32_t *status, int32_t bit) {
-    const int64_t i = (int64_t)blockIdx.x * kNT + threadIdx.x;
-    if (i >= n) return;
-    const float x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-    if (!nn_finite3(x, y, z)) {
-        atomicOr(status, bit);
-        key[i] = 0;
-        return;
-    }
-    const int32_t cx = nn_cell(x, G.lo[0], G.h, G.g[0]), cy = nn_cell(y, G.lo[1], G.h, G.g[1]),
-                  cz = nn_cell(z, G.lo[2], G.h, G.g[2]);
-    key[i] = (cx * G.g[1] + cy) * G.g[2] + cz;
-}
-
 __global__ __launch_bounds__(kNT) void nn_records_kernel(const float *__restrict__ p, int64_t n,
                                                          const int64_t *__restrict__ perm, float4 *__restrict__ rec) {
     const int64_t r = (int64_t)blockIdx.x * kNT + threadIdx.x;
@@ -49,51 +35,6 @@ __global__ __launch_bounds__(kNT) void nn_records_kernel(const float *__restrict
     int64_t i = perm[r];
     if ((uint64_t)i >= (uint64_t)n) i = 0;
     rec[r] = make_float4(p[i * 3], p[i * 3 + 1], p[i * 3 + 2], __int_as_float((int32_t)i));
-}
-
-// cell_start[c] for c in [0, cells]: the first position of keys_sorted[0..n) that is >= c (n for c == cells)
-__global__ __launch_bounds__(kNT) void nn_cell_start_kernel(const int32_t *__restrict__ keys_sorted, int64_t n,
-                                                            int64_t cells, int32_t *__restrict__ cell_start) {
-    const int64_t c = (int64_t)blockIdx.x * kNT + threadIdx.x;
-    if (c > cells) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if ((int64_t)keys_sorted[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    cell_start[c] = (int32_t)lo;
-}
-
-// THE STOPPING RULE.  A lane is finished when its best d2 is strictly below b2 = min over the box's faces that have
-// cells beyond them of fl(fl(|q - F|)^2), F the face's coordinate as found here.  Argument: nn_cell is a composition
-// of monotone steps (fp32 subtraction, division by h > 0, floor, clamp), so it is monotone in p.  nn_face_low returns
-// an F that it has CHECKED to satisfy nn_cell(F) >= k; hence every point whose cell is < k - every point beyond the
-// low face of a box that starts at cell k - has p < F, whatever the rounding of the cell assignment did, and that
-// includes a point lying exactly on the face lo + k*h (it is wherever nn_cell put it, and F is on the same side).
-// For such a point and q >= F, rounding being monotone too: fl(q - p) >= fl(q - F) >= 0, fl(dx*dx) >= fl(fl(q - F)^2),
-// and adding the non-negative fl(dy*dy), fl(dz*dz) never rounds below the first term.  So the point's d2 as the
-// kernel computes it is >= b2 > best: it is neither a better minimum nor a tie.  (q < F gives the bound 0, which
-// finishes nothing.)  The starting guess lo + k*h is nudged by doubling steps of a few ulp until the check holds;
-// if it never does the face is put at infinity, the bound is 0 and the search runs on until the box covers the grid.
-__device__ __forceinline__ float nn_face_low(float lo, float h, int32_t g, int32_t k) {
-    float F = __fadd_rn(lo, __fmul_rn((float)k, h));
-    float step = fmaxf(fmaxf(fabsf(F), fabsf(lo)), h) * 2.3841858e-7f;
-    for (int it = 0; it < 48 && nn_cell(F, lo, h, g) < k; ++it) {
-        F = __fadd_rn(F, step);
-        step = __fmul_rn(step, 2.0f);
-    }
-    return nn_cell(F, lo, h, g) >= k ? F : INFINITY;
-}
-// the mirror image: an F with nn_cell(F) <= k, so that every point whose cell is > k has p > F
-__device__ __forceinline__ float nn_face_high(float lo, float h, int32_t g, int32_t k) {
-    float F = __fadd_rn(lo, __fmul_rn((float)k + 1.0f, h));
-    float step = fmaxf(fmaxf(fabsf(F), fabsf(lo)), h) * 2.3841858e-7f;
-    for (int it = 0; it < 48 && nn_cell(F, lo, h, g) > k; ++it) {
-        F = __fsub_rn(F, step);
-        step = __fmul_rn(step, 2.0f);
-    }
-    return nn_cell(F, lo, h, g) <= k ? F : -INFINITY;
 }
 
 __global__ __launch_bounds__(64) void nn_query_kernel(const float *__restrict__ query, int64_t m,
@@ -244,16 +185,6 @@ __global__ __launch_bounds__(64) void nn_query_kernel(const float *__restrict__ 
         d2_out[src] = hit ? best : INFINITY;
         idx_out[src] = hit ? best_i : -1;
     }
-}
-
-// keys of the n rows of p, sorted: w.keys_sorted, w.perm
-int nn_sorted_keys(const float *p, int64_t n, const NnGrid &G, int64_t cells, const HmKeySortWs &w, int32_t *status,
-                   int32_t bit, void *stream) {
-    hipLaunchKernelGGL(nn_key_kernel, dim3(hm_grid(n, kNT)), dim3(kNT), 0, as_stream(stream), p, n, G, w.key, status,
-                       bit);
-    int key_bits = 1;
-    while (key_bits < 31 && ((int64_t)1 << key_bits) < cells) ++key_bits;
-    return hm_sort_pairs_i32(w.key, n, key_bits, w.keys_sorted, w.perm, w.sort_ws, w.sort_bytes, stream);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 """Evaluation of a reconstructed mesh and of rendered views on the device (reference: code/evaluation)."""
-from .chamfer import dtu_chamfer, load_dtu_scan, mesh_chamfer  # noqa: F401
+from .chamfer import dtu_chamfer, load_dtu_scan, mesh_chamfer, mesh_to_mesh  # noqa: F401
 from .color import ColorStats, color_mesh, color_mesh_for_dataset  # noqa: F401
 from .cull import CullStats, cull_mesh, cull_mesh_for_dataset, view_projections  # noqa: F401
 from .images import evaluate_views, render_view, view_metrics  # noqa: F401

@@ -1,7 +1,8 @@
 """The reference's DTU Chamfer evaluation (code/evaluation/dtu_eval) of a mesh against a point cloud, on the device.
 
 mesh_chamfer: upsample every triangle to a point density, nearest-neighbour distances both ways, means below a
-cut-off.  dtu_chamfer: the whole DTU protocol - the sampled cloud is shuffled and thinned by the greedy radius rule
+cut-off; with surface=True the completeness side is the exact distance to the triangles.  mesh_to_mesh: the points of
+each mesh against the triangles of the other (ops.mesh_closest_point), means and maxima.  dtu_chamfer: the whole DTU protocol - the sampled cloud is shuffled and thinned by the greedy radius rule
 (ops.radius_downsample), cut to the scan's padded bounding box and observation mask (ops.dtu_point_flags), the scan is
 cut at its ground plane, and accuracy and completeness are the one-sided means (ops.one_sided_distance) between what
 is left.  load_dtu_scan reads a scan's mask and plane files.  DESIGN.md "Chamfer evaluation on the device" states the
@@ -27,19 +28,62 @@ def _device_mesh(mesh, device):
     raise ValueError("hashmod mesh_chamfer: mesh must be a TriMesh or a (verts, faces[, normals]) tuple")
 
 
-def mesh_chamfer(mesh, target_points, density, max_dist=None):
+def mesh_chamfer(mesh, target_points, density, max_dist=None, surface=False):
     """ops.ChamferResult (with n_cloud) of a mesh against target_points [T,3] fp32 on the GPU.  `mesh` is a
     (verts, faces[, normals]) tuple of device tensors as ops.marching_cubes or ops.mesh_largest_component return
     them, or a TriMesh, which is uploaded to the target's device.  The mesh's cloud is cat(verts,
     ops.mesh_sample_surface(verts, faces, density)) - the DTU order - and the result is ops.chamfer_distance(cloud,
-    target_points, max_dist): mean_a2b is mesh -> target (accuracy), mean_b2a target -> mesh (completeness).  Only the
-    scalars come back to the host."""
+    target_points, max_dist): mean_a2b is mesh -> target (accuracy), mean_b2a target -> mesh (completeness).  With
+    surface=True the completeness side is ops.point_mesh_distance(target_points, mesh, max_dist): the exact distance
+    to the triangles instead of the distance to the sampled cloud, which cannot see below the sampling density; the
+    accuracy side is the same bits (ops.one_sided_distance).  Only the scalars come back to the host."""
     if not isinstance(target_points, torch.Tensor):
         raise ValueError("hashmod mesh_chamfer: target_points must be a tensor")
+    if not isinstance(surface, bool):
+        raise ValueError("hashmod mesh_chamfer: surface must be a bool")
     verts, faces = _device_mesh(mesh, target_points.device)
     cloud = torch.cat([verts, ops.mesh_sample_surface(verts, faces, density)])
-    r = ops.chamfer_distance(cloud, target_points, max_dist)
-    return ops.ChamferResult(r.mean_a2b, r.mean_b2a, r.n_a2b, r.n_b2a, int(cloud.shape[0]))
+    if not surface:
+        r = ops.chamfer_distance(cloud, target_points, max_dist)
+        return ops.ChamferResult(r.mean_a2b, r.mean_b2a, r.n_a2b, r.n_b2a, int(cloud.shape[0]))
+    ops._check_cloud("mesh_chamfer", "target_points", target_points, cloud)
+    if cloud.shape[0] < 1 or target_points.shape[0] < 1:
+        raise ValueError("hashmod mesh_chamfer: the mesh's cloud and the target need at least one point")
+    acc, n_acc = ops.one_sided_distance(cloud, target_points, max_dist)
+    comp, n_comp = ops.point_mesh_distance(target_points, (verts, faces), max_dist)
+    return ops.ChamferResult(acc, comp, n_acc, n_comp, int(cloud.shape[0]))
+
+
+MeshToMeshResult = namedtuple("MeshToMeshResult", ["mean_a2b", "mean_b2a", "max_a2b", "max_b2a", "n_a2b", "n_b2a"])
+
+
+def mesh_to_mesh(mesh_a, mesh_b, density, max_dist=None):
+    """MeshToMeshResult of two meshes (each as for mesh_chamfer; device tensors of one GPU, or TriMeshes with
+    device tensors on the other side): the points of each mesh - cat(verts, ops.mesh_sample_surface(verts, faces,
+    density)) - against the TRIANGLES of the other (ops.mesh_closest_point).  mean_a2b is the mean exact distance from
+    a's points to b's surface over the distances < max_dist (strict; all for None), max_a2b the largest of them (a
+    sampled one-sided Hausdorff distance), n_a2b their number; the b2a fields the other way.  The distances are the
+    fp64 square roots of the exact fp32 d2, so that - unlike a distance between two sampled clouds - the figures do
+    not stop at the sampling density of the side measured against.  No distance below max_dist gives nan and count 0.
+    Only the scalars come to the host."""
+    if not (isinstance(density, (int, float)) and math.isfinite(density) and density > 0):
+        raise ValueError("hashmod mesh_to_mesh: density must be a positive finite number")
+    if max_dist is not None and not (isinstance(max_dist, (int, float)) and max_dist > 0):
+        raise ValueError("hashmod mesh_to_mesh: max_dist must be a positive number (or None)")
+    dev = next((t.device for m in (mesh_a, mesh_b) if isinstance(m, (tuple, list)) for t in m[:1]
+                if isinstance(t, torch.Tensor)), None)
+    if dev is None:
+        raise ValueError("hashmod mesh_to_mesh: at least one mesh must be a tuple of device tensors")
+    sides = []
+    for mesh in (mesh_a, mesh_b):
+        verts, faces = _device_mesh(mesh, dev)
+        sides.append((torch.cat([verts, ops.mesh_sample_surface(verts, faces, density)]),
+                      ops.mesh_index(verts, faces)))
+    (pa, ia), (pb, ib) = sides
+    sa, ca, ma, sb, cb, mb = torch.cat([ops._point_mesh_sums(pa, ib, max_dist)[0],
+                                        ops._point_mesh_sums(pb, ia, max_dist)[0]]).tolist()
+    return MeshToMeshResult(sa / ca if ca else math.nan, sb / cb if cb else math.nan, ma if ca else math.nan,
+                            mb if cb else math.nan, int(ca), int(cb))
 
 
 DtuChamferResult = namedtuple("DtuChamferResult", ["accuracy", "completeness", "overall", "n_cloud", "n_down", "n_in",

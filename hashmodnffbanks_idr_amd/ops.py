@@ -1782,17 +1782,18 @@ def _check_cloud(what, name, t, like=None):
         raise ValueError(f"hashmod {what}: the tensors are on different devices")
 
 
-def _nn_grid(lo, hi, n, cell):
+def _nn_grid(lo, hi, n, cell, what="nn_index", per_cell=_NN_PER_CELL):
     """(h as fp32, g[3]) of the grid over the box [lo, hi] (float lists): the cell edge a surface-like cloud of n points
-    needs for _NN_PER_CELL points per occupied cell - its area taken as half the box's - unless `cell` gives it, grown
-    until the grid has at most NN_MAX_CELLS cells; a zero extent gives one cell on that axis"""
+    needs for per_cell = _NN_PER_CELL points per occupied cell - its area taken as half the box's - unless `cell` gives
+    it, grown until the grid has at most NN_MAX_CELLS cells; a zero extent gives one cell on that axis.  `what` names
+    the caller in the error messages"""
     ext = [max(float(b) - float(a), 0.0) for a, b in zip(lo, hi)]
     if cell is None:
         area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2]
         if area > 0.0:
-            h = math.sqrt(_NN_PER_CELL * area / n)
+            h = math.sqrt(per_cell * area / n)
         elif max(ext) > 0.0:
-            h = _NN_PER_CELL * max(ext) / n
+            h = per_cell * max(ext) / n
         else:
             h = 1.0
         h = max(h, max(ext) * 2.0 ** -20)
@@ -1801,12 +1802,12 @@ def _nn_grid(lo, hi, n, cell):
     while True:
         h = float(np.float32(h))
         if not (h > 0.0 and math.isfinite(h)):
-            raise ValueError("hashmod nn_index: the cell edge must be positive and finite in fp32")
+            raise ValueError(f"hashmod {what}: the cell edge must be positive and finite in fp32")
         g = [int(math.floor(e / h)) + 1 for e in ext]
         if max(g) <= 1 << 30 and g[0] * g[1] * g[2] <= NN_MAX_CELLS:
             return h, g
         if cell is not None:
-            raise ValueError(f"hashmod nn_index: cell={cell} gives a grid of {g[0]}x{g[1]}x{g[2]} cells, more than "
+            raise ValueError(f"hashmod {what}: cell={cell} gives a grid of {g[0]}x{g[1]}x{g[2]} cells, more than "
                              f"NN_MAX_CELLS = {NN_MAX_CELLS}")
         h *= 1.125
 
@@ -2017,6 +2018,200 @@ def one_sided_distance(src, dst, max_dist=None, cell=None):
         return math.nan, 0
     s, c = _one_sided(src, NNIndex(dst, cell), max_dist, _search_bound2(max_dist)).tolist()
     return (s / c if c else math.nan), int(c)
+
+
+# =========================================================================================
+# Point-to-mesh distance: the triangle grid and the exact closest point (csrc/hm_mesh_dist.hip)
+# =========================================================================================
+MESH_DIST_BIG_FACE = 64     # cells of a face's cell box above which the face goes to the list every wave tests in full
+_MD_PER_CELL = 32.0         # mean face areas per cell face the default cell edge aims at
+_MD_WS = _lib.Workspace("mesh_closest_point")
+
+
+def _check_on_gpu(what, *tensors):
+    """the mesh-distance ops reject a CPU tensor as an argument error (a ValueError and a HashmodError) before the
+    library is touched"""
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise _lib.HashmodArgumentError(f"hashmod {what}: the tensors must be on a GPU; there is no CPU path")
+
+
+class MeshIndex:
+    """The uniform grid over a triangle mesh that ops.mesh_index builds: every face listed in the cells of its
+    bounding box as 48-byte records ordered by cell (ascending face inside a cell), the big faces as a run of records
+    behind them, and the dense cell_start table.  query() answers closest-point queries against it."""
+
+    def __init__(self, verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE):
+        if cell is not None and not (isinstance(cell, (int, float)) and not isinstance(cell, bool)
+                                     and math.isfinite(cell) and cell > 0):
+            raise ValueError("hashmod mesh_index: cell must be a positive finite number")
+        if not (isinstance(big_face, int) and not isinstance(big_face, bool) and 1 <= big_face < 1 << 62):
+            raise ValueError("hashmod mesh_index: big_face must be an integer >= 1")
+        if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
+            raise ValueError("hashmod mesh_index: verts and faces must be tensors")
+        if faces.dim() == 2 and faces.shape[0] < 1:
+            raise ValueError("hashmod mesh_index: at least one face is needed")
+        _check_on_gpu("mesh_index", verts, faces)
+        n_faces, n_verts = _check_mesh("mesh_index", faces, verts=verts, gpu_first=False)
+        dev = faces.device
+        if n_verts < 1:
+            raise _lib.HashmodError("hashmod mesh_index: a face index lies outside [0, n_verts)")
+        lo, hi = torch.aminmax(verts, dim=0)
+        box = torch.stack([lo, hi]).tolist()
+        if not all(math.isfinite(v) for v in box[0] + box[1]):
+            raise _lib.HashmodError("hashmod mesh_index: a vertex has a non-finite coordinate")
+        self.h, self.g = _nn_grid(box[0], box[1], n_faces, cell, "mesh_index", _MD_PER_CELL)
+        self.lo = box[0]
+        self.n_faces, self.n_verts = n_faces, n_verts
+        self.big_face = big_face
+        self.device = dev
+        cells = self.g[0] * self.g[1] * self.g[2]
+        L = lib()
+        st = stream_ptr(faces)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        count = torch.empty(n_faces, dtype=torch.int32, device=dev)
+        big = torch.empty(n_faces, dtype=torch.int32, device=dev)
+        check(L.hm_mesh_dist_count(dptr(verts), dptr(faces), n_faces, n_verts, self._lo(), self.h, self._g(), big_face,
+                                   dptr(count), dptr(big), dptr(status), st))
+        # bookkeeping between the launches: positions from the counts, the totals and the status word to the host
+        cincl = torch.cumsum(count, 0, dtype=torch.int64)
+        bincl = torch.cumsum(big, 0, dtype=torch.int64)
+        n_pairs, n_big, bad = torch.stack([cincl[-1], bincl[-1], status[0].to(torch.int64)]).tolist()
+        if bad & 1:
+            _check_mesh_status("mesh_index", status)
+        if bad:
+            raise _lib.HashmodError("hashmod mesh_index: a vertex of a face has a non-finite coordinate")
+        if n_pairs + n_big >= 1 << 31:
+            raise ValueError(f"hashmod mesh_index: the faces fill {n_pairs} cells of the grid, 2^31 or more; use a "
+                             "larger cell or a smaller big_face")
+        self.n_pairs, self.n_big = n_pairs, n_big
+        prefix = (cincl - count).to(torch.int32)
+        big_prefix = (bincl - big).to(torch.int32)
+        self.cell_start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
+        self.records = torch.empty((n_pairs + n_big, 12), dtype=torch.float32, device=dev)
+        ws = _MD_WS.get(dev, check(L.hm_mesh_dist_workspace_bytes(n_pairs)))
+        check(L.hm_mesh_dist_build(dptr(verts), dptr(faces), n_faces, n_verts, self._lo(), self.h, self._g(),
+                                   dptr(count), dptr(big), dptr(prefix), n_pairs, dptr(big_prefix), n_big,
+                                   dptr(self.cell_start), dptr(self.records), dptr(ws), ws.numel(), st))
+
+    def _lo(self):
+        return (C.c_float * 3)(*self.lo)
+
+    def _g(self):
+        return (C.c_int32 * 3)(*self.g)
+
+    def _query(self, query, max_dist2, return_point=True, return_feature=False, stats=None):
+        """(d2, face, point or None, feature or None); stats: a dict that receives "candidate_tests", the launch's
+        number of (query, face) tests (one more host read; for scripts/mesh_distance_time.py)"""
+        _check_cloud("mesh_closest_point", "query", query, self.records)
+        _check_on_gpu("mesh_closest_point", query)
+        m = int(query.shape[0])
+        dev = self.device
+        d2 = torch.empty(m, dtype=torch.float32, device=dev)
+        face = torch.empty(m, dtype=torch.int32, device=dev)
+        point = torch.empty((m, 3), dtype=torch.float32, device=dev) if return_point else None
+        feature = torch.empty(m, dtype=torch.int32, device=dev) if return_feature else None
+        if m == 0:
+            return d2, face, point, feature
+        L = lib()
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _MD_WS.get(dev, check(L.hm_mesh_dist_workspace_bytes(m)))
+        tests = None if stats is None else torch.zeros(1, dtype=torch.int64, device=dev)
+        check(L.hm_mesh_dist_query(dptr(query), m, dptr(self.records), self.n_pairs, self.n_big, dptr(self.cell_start),
+                                   self._lo(), self.h, self._g(), max_dist2, dptr(d2), dptr(face), dptr(point),
+                                   dptr(feature), dptr(ws), ws.numel(), dptr(status), dptr(tests), stream_ptr(query)))
+        if stats is not None:
+            stats["candidate_tests"] = int(tests.item())
+        if int(status.item()):
+            raise _lib.HashmodError("hashmod mesh_closest_point: a query has a non-finite coordinate")
+        return d2, face, point, feature
+
+    def query(self, query, max_dist=None, return_point=True, return_feature=False):
+        """mesh_closest_point's outputs for the rows of query [m,3] against this mesh"""
+        _check_flags("mesh_closest_point", return_point=return_point, return_feature=return_feature)
+        out = self._query(query, _max_dist2("mesh_closest_point", max_dist), return_point, return_feature)
+        return tuple(t for t in out if t is not None)
+
+
+def _check_flags(what, **flags):
+    for name, value in flags.items():
+        if not isinstance(value, bool):
+            raise ValueError(f"hashmod {what}: {name} must be a bool")
+
+
+def mesh_index(verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE):
+    """The search structure of mesh_closest_point over the mesh verts [V,3] fp32, faces [F,3] int32 (F >= 1), to be
+    queried many times: a uniform grid of cell edge `cell` over the vertices' bounding box (read by the host through
+    aminmax), every face listed in all cells of its own bounding box.  Without `cell` the edge is sqrt(32 A / F) with A
+    half the box's surface area - a cell face with the area of 32 mean faces of a surface-like mesh, about three
+    bounding-box edges of a marching-cubes face: small cells list a face many times and make far queries walk many
+    rings, large cells make near queries test many faces, and scripts/mesh_distance_time.py's mesh and cloud put the
+    best compromise between two and four lattice spacings (DESIGN.md has the sweep); the dense cell table is capped
+    at NN_MAX_CELLS = 2^26 cells (the edge grows to fit; an explicit `cell` that does not fit raises ValueError).  A
+    face whose cell box has more than `big_face` cells (default MESH_DIST_BIG_FACE = 64: a face more than about three
+    cells across on every axis) is not listed in the grid but in a separate run that every query wave tests in full,
+    so that one large face among many small ones does not fill the table.  The pairs are ordered by cell with the
+    library's stable radix sort.  A non-finite vertex or a face index outside [0, V) raises HashmodError (reported by
+    the kernel's status word, never dereferenced).  The grid changes the speed of a query, never its result.  Host
+    reads of the box, the totals and the status word, so not graph-capturable."""
+    return MeshIndex(verts, faces, cell, big_face)
+
+
+def mesh_closest_point(query, verts, faces, max_dist=None, cell=None, big_face=MESH_DIST_BIG_FACE, return_point=True,
+                       return_feature=False):
+    """(d2 [m] fp32, face [m] int32, then point [m,3] fp32 with return_point, then feature [m] int32 with
+    return_feature): for every row of query [m,3] the exact closest point of the triangle mesh, the face it lies on,
+    that face's feature (0 the interior, 1, 2, 3 the edges (a,b), (b,c), (c,a) with their end points) and the squared
+    distance.  The result is the brute-force fp32 argmin of the per-face value that include/hashmod.h defines
+    (tests/mesh_dist_cases.closest_ref is its numpy restatement), the lowest face index among equal d2, bit for bit:
+    independent of the grid, of big_face, of m and of the thread order.  With max_dist, a query whose d2 exceeds
+    fp32(max_dist)^2 (squared in fp32) gets d2 = inf, face -1, a NaN point and feature -1; d2 equal to the bound is
+    reported (nearest_neighbors' rule).  m = 0 gives empty outputs; F >= 1; contiguous tensors on one GPU (else
+    ValueError); a non-finite coordinate or a face index outside [0, V) raises HashmodError.  mesh_index(verts, faces,
+    cell, big_face).query(query, max_dist, ...) is the same in two steps.  Not graph-capturable."""
+    _check_cloud("mesh_closest_point", "query", query)
+    _check_flags("mesh_closest_point", return_point=return_point, return_feature=return_feature)
+    md2 = _max_dist2("mesh_closest_point", max_dist)
+    index = MeshIndex(verts, faces, cell, big_face)
+    if query.device != index.device:
+        raise ValueError("hashmod mesh_closest_point: the tensors are on different devices")
+    return tuple(t for t in index._query(query, md2, return_point, return_feature) if t is not None)
+
+
+def _point_mesh_sums(src, index, max_dist):
+    """(sum, count, max) as one fp64 [3] device tensor of the distances src -> the index's mesh below max_dist, and
+    d2; the rule and the reduction of _one_sided"""
+    d2 = index._query(src, _search_bound2(max_dist), return_point=False)[0]
+    d = torch.sqrt(d2.to(torch.float64))
+    keep = d < max_dist if max_dist is not None else torch.ones_like(d, dtype=torch.bool)
+    zero = torch.zeros((), dtype=torch.float64, device=d.device)
+    kept = torch.where(keep, d, zero)
+    return torch.stack([kept.sum(), keep.sum().to(torch.float64), kept.max()]), d2
+
+
+def point_mesh_distance(src, mesh_or_index, max_dist=None):
+    """(mean, count): the mean over the rows of src [m,3] of the exact distance to the mesh - a MeshIndex or a
+    (verts, faces) pair - over the distances < max_dist (strict; all for None), and how many entered: what
+    one_sided_distance is against a cloud, against the triangles themselves, so that it can stand in the same
+    formulas.  The distances are the fp64 square roots of mesh_closest_point's exact fp32 d2, summed by the same
+    fixed-order fp64 device reduction.  An empty src, or no distance below max_dist, gives (nan, 0).  Host scalars;
+    not graph-capturable."""
+    _check_cloud("point_mesh_distance", "src", src)
+    if max_dist is not None and not (isinstance(max_dist, (int, float)) and max_dist > 0):
+        raise ValueError("hashmod point_mesh_distance: max_dist must be a positive number (or None)")
+    index = _as_mesh_index("point_mesh_distance", mesh_or_index)
+    if src.shape[0] < 1:
+        return math.nan, 0
+    s, c, _ = _point_mesh_sums(src, index, max_dist)[0].tolist()
+    return (s / c if c else math.nan), int(c)
+
+
+def _as_mesh_index(what, mesh_or_index):
+    if isinstance(mesh_or_index, MeshIndex):
+        return mesh_or_index
+    if isinstance(mesh_or_index, (tuple, list)) and len(mesh_or_index) == 2:
+        return MeshIndex(mesh_or_index[0], mesh_or_index[1])
+    raise ValueError(f"hashmod {what}: the mesh must be a MeshIndex or a (verts, faces) pair")
 
 
 # =========================================================================================

@@ -1132,6 +1132,61 @@ HM_API int hm_mesh_render(const float *verts, int64_t n_verts, const int32_t *fa
                           float *weights, float *image, int32_t *n_skipped, void *workspace, int64_t workspace_bytes,
                           int32_t *status, void *stream);
 
+/* ---- point-to-mesh distance: the exact closest point of a triangle mesh on a uniform grid ------------------------
+ * For a query point the nearest point of the mesh, the face it lies on, the face's feature and the squared distance.
+ * Driver: ops.mesh_index, ops.mesh_closest_point, ops.point_mesh_distance, evaluation.chamfer.mesh_to_mesh and
+ * mesh_chamfer(surface=True).  csrc/hm_mesh_dist.hip (it states the stopping rule of the search).  No entry point
+ * synchronises, none uses floating-point atomics, no atomic decides a position.  status is one device int32 the CALLER
+ * has zeroed.  The grid (lo, h, g) is hm_nn_build's above.
+ *
+ * THE DEFINITION.  The result is the brute-force fp32 argmin of the following, bit for bit, whatever the grid,
+ * big_face, m and the thread order.  Every fp32 operation rounds once (no fused multiply-add);
+ * dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z; cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x).
+ * For a query q and a face with fp32 vertices a, b, c: lo, hi are the face's per-axis bounding box,
+ * clamp(p) = min(max(p, lo), hi) per axis (min and max return the other operand for a NaN, so clamp(p) is always in
+ * the box), d2_to(p) = dot(q - clamp(p), q - clamp(p)).  The face's value is the first minimum, in this order, of
+ *   candidate 0, the interior: n = cross(b - a, c - a), nn = dot(n, n), wa = a - q, wb = b - q, wc = c - q; it exists
+ *       iff nn > 0 and dot(n, cross(wa, wb)) >= 0 and dot(n, cross(wb, wc)) >= 0 and dot(n, cross(wc, wa)) >= 0; its
+ *       point is q + (dot(wa, n) / nn) * n;
+ *   candidates 1, 2, 3, the segments (a, b), (b, c), (c, a): for (p0, p1), e = p1 - p0, ee = dot(e, e),
+ *       t = ee > 0 ? dot(q - p0, e) / ee : 0, clamped to [0, 1]; its point is p0 + t*e;
+ * each with the value d2_to(point).  The face's closest point is the CLAMPED point of the winning candidate, its
+ * feature the candidate's number.  Over the mesh the result is the minimum d2 and, among equal d2, the lowest face
+ * index.  A segment always exists, so a zero-area face, a repeated vertex and a sliver all have a finite value.
+ *   hm_mesh_dist_workspace_bytes(n): the scratch of hm_mesh_dist_build over n pairs, and of hm_mesh_dist_query over
+ *                n queries.
+ *   hm_mesh_dist_count: per face, its cell box (the cells of lo and of hi per axis) and count [n_faces] int32 = the
+ *                number of cells in it - unless that exceeds big_face (>= 1): then count = 0 and big [n_faces] int32
+ *                = 1 (else 0).  A face index outside [0, n_verts) sets status bit 0, a non-finite vertex of a face
+ *                bit 1; such a face gets count 0, big 0, and no vertex is read through an unchecked index.
+ *   hm_mesh_dist_build: prefix, big_prefix [n_faces] int32 = the exclusive prefix sums of count and big, n_pairs and
+ *                n_big their totals (n_pairs + n_big in [1, 2^31)).  Writes the (cell key, face) pairs in ascending
+ *                face order, sorts them with the library's stable sort, and writes records [n_pairs + n_big, 12] fp32:
+ *                record r = ax ay az bx by bz cx cy cz, the face index as the int32 bits of word 9, two zero words -
+ *                first the pairs in sorted order (ascending face inside a cell), then the big faces, ascending; and
+ *                cell_start [cells + 1] int32 (the records of cell c are [cell_start[c], cell_start[c+1])).  Every
+ *                store is checked against n_pairs and n_big.
+ *   hm_mesh_dist_query: query [m,3] fp32, m >= 0.  Writes d2 [m] fp32 and face [m] int32 and, unless NULL,
+ *                point [m,3] fp32 and feature [m] int32 (0 interior, 1..3 the segments).  max_dist2 (fp32, +inf =
+ *                none): a query whose minimum is > max_dist2 gets d2 +inf, face -1, a NaN point and feature -1;
+ *                == max_dist2 is reported.  A non-finite query coordinate sets status bit 2.  n_tests (may be NULL;
+ *                a measurement aid): a device counter the caller has zeroed, receives the number of (query lane,
+ *                face record) pairs the launch visited; a pair whose face's bounding box is farther than the lane's
+ *                best is rejected after the box test, which cannot change the result (csrc/hm_mesh_dist.hip). */
+HM_API int64_t hm_mesh_dist_workspace_bytes(int64_t n);
+HM_API int hm_mesh_dist_count(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                              const float *lo, float h, const int32_t *g, int64_t big_face, int32_t *count,
+                              int32_t *big, int32_t *status, void *stream);
+HM_API int hm_mesh_dist_build(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                              const float *lo, float h, const int32_t *g, const int32_t *count, const int32_t *big,
+                              const int32_t *prefix, int64_t n_pairs, const int32_t *big_prefix, int64_t n_big,
+                              int32_t *cell_start, float *records, void *workspace, int64_t workspace_bytes,
+                              void *stream);
+HM_API int hm_mesh_dist_query(const float *query, int64_t m, const float *records, int64_t n_pairs, int64_t n_big,
+                              const int32_t *cell_start, const float *lo, float h, const int32_t *g, float max_dist2,
+                              float *d2, int32_t *face, float *point, int32_t *feature, void *workspace,
+                              int64_t workspace_bytes, int32_t *status, uint64_t *n_tests, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
