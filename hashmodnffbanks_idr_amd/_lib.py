@@ -168,6 +168,12 @@ SIGNATURES = {
                                   _p]),
     "hm_mesh_dist_query": (_int, [_p, _i64, _p, _i64, _i64, _p, _p, C.c_float, _p, C.c_float, _p, _p, _p, _p, _p, _i64,
                                   _p, _p, _p]),
+    # rays against the mesh: the index with a pad, the first hit of a ray
+    "hm_mesh_index_count": (_int, [_p, _p, _i64, _i64, _p, C.c_float, _p, C.c_float, _i64, _p, _p, _p, _p]),
+    "hm_mesh_index_build": (_int, [_p, _p, _i64, _i64, _p, C.c_float, _p, C.c_float, _p, _p, _p, _i64, _p, _i64, _p, _p,
+                                   _p, _i64, _p]),
+    "hm_mesh_ray_cast": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _p, C.c_float, _p, C.c_float, _p, _p, _p, _p,
+                                _p, _p, _p]),
 }
 
 

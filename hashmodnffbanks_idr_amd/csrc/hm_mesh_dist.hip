@@ -5,6 +5,10 @@
 //
 //   hm_mesh_dist_count  md_count   one lane per face: its cell box nn_cell(lo) .. nn_cell(hi) per axis; count[f] = the
 //                                  cells of the box, or 0 and big[f] = 1 when there are more than big_face of them
+//                                  (hm_mesh_index_count / hm_mesh_index_build: the same with the box grown by a pad,
+//                                  nn_cell(fl(lo - pad)) .. nn_cell(fl(hi + pad)), the index hm_mesh_ray.hip walks; the
+//                                  hm_mesh_dist_* entry points forward with pad = 0.  A padded index lists a superset
+//                                  of the cells, which the stopping rule below allows: it needs AT LEAST the box's)
 //   (caller)                       exclusive prefix sums of count and big, their totals read by the host
 //   hm_mesh_dist_build  md_emit    (cell key, face) pairs, faces ascending, a face's cells in key order; the big faces'
 //                                  records, ascending, behind the pair records
@@ -40,32 +44,14 @@
 #include <math.h>
 
 #include "hm_block_dev.h"
+#include "hm_mesh_rec_dev.h"
 #include "hm_nn_dev.h"
 
 namespace {
 
 constexpr int kChunk = 256;   // records staged in LDS per pass (12 KiB)
-constexpr int kRecVec = 3;    // float4 per record: ax ay az bx | by bz cx cy | cz face 0 0
-constexpr int32_t kNoFace = 0x7fffffff;
 
-// ---- the face value (include/hashmod.h), every operation rounded once --------------------------------------------
-struct MdVec {
-    float x, y, z;
-};
-__device__ __forceinline__ MdVec md_sub(MdVec u, MdVec v) {
-    return {__fsub_rn(u.x, v.x), __fsub_rn(u.y, v.y), __fsub_rn(u.z, v.z)};
-}
-__device__ __forceinline__ float md_dot(MdVec u, MdVec v) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(u.x, v.x), __fmul_rn(u.y, v.y)), __fmul_rn(u.z, v.z));
-}
-__device__ __forceinline__ MdVec md_cross(MdVec u, MdVec v) {
-    return {__fsub_rn(__fmul_rn(u.y, v.z), __fmul_rn(u.z, v.y)), __fsub_rn(__fmul_rn(u.z, v.x), __fmul_rn(u.x, v.z)),
-            __fsub_rn(__fmul_rn(u.x, v.y), __fmul_rn(u.y, v.x))};
-}
-// p0 + t*d
-__device__ __forceinline__ MdVec md_along(MdVec p0, float t, MdVec d) {
-    return {__fadd_rn(p0.x, __fmul_rn(t, d.x)), __fadd_rn(p0.y, __fmul_rn(t, d.y)), __fadd_rn(p0.z, __fmul_rn(t, d.z))};
-}
+// ---- the face value (include/hashmod.h), every operation rounded once: the vector operations are hm_mesh_rec_dev.h's
 // min(max(p, lo), hi) per axis; fmaxf / fminf return the other operand for a NaN, so the result is always in the box
 __device__ __forceinline__ MdVec md_clamp(MdVec p, MdVec lo, MdVec hi) {
     return {fminf(fmaxf(p.x, lo.x), hi.x), fminf(fmaxf(p.y, lo.y), hi.y), fminf(fmaxf(p.z, lo.z), hi.z)};
@@ -136,10 +122,11 @@ __device__ __forceinline__ void md_test(MdVec q, MdVec a, MdVec b, MdVec c, int3
 }
 
 // ---- build ---------------------------------------------------------------------------------------------------------
-// the vertices of face f and its cell box; false (and a status bit: 1 an index outside [0, n_verts), 2 a non-finite
+// the vertices of face f and its cell box, the cells of fl(min - pad) .. fl(max + pad) per axis (pad = 0: of the
+// bounding box itself, x - 0 being x); false (and a status bit: 1 an index outside [0, n_verts), 2 a non-finite
 // vertex) for a face that is not to be listed.  No vertex is read through an index that was not checked.
 __device__ __forceinline__ bool md_face(const float *__restrict__ verts, const int32_t *__restrict__ faces, int64_t f,
-                                        int64_t n_verts, const NnGrid &G, int32_t *status, float (&v)[9],
+                                        int64_t n_verts, const NnGrid &G, float pad, int32_t *status, float (&v)[9],
                                         int32_t (&c0)[3], int32_t (&c1)[3]) {
     int32_t id[3];
     const bool in_range = status ? hm_face_ids(faces, f, n_verts, id, status) : hm_face_ids(faces, f, n_verts, id);
@@ -157,15 +144,15 @@ __device__ __forceinline__ bool md_face(const float *__restrict__ verts, const i
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        c0[a] = nn_cell(fminf(fminf(v[a], v[3 + a]), v[6 + a]), G.lo[a], G.h, G.g[a]);
-        c1[a] = nn_cell(fmaxf(fmaxf(v[a], v[3 + a]), v[6 + a]), G.lo[a], G.h, G.g[a]);
+        c0[a] = nn_cell(__fsub_rn(fminf(fminf(v[a], v[3 + a]), v[6 + a]), pad), G.lo[a], G.h, G.g[a]);
+        c1[a] = nn_cell(__fadd_rn(fmaxf(fmaxf(v[a], v[3 + a]), v[6 + a]), pad), G.lo[a], G.h, G.g[a]);
     }
     return true;
 }
 
 __global__ __launch_bounds__(kNT) void md_count_kernel(const float *__restrict__ verts,
                                                        const int32_t *__restrict__ faces, int64_t n_faces,
-                                                       int64_t n_verts, NnGrid G, int64_t big_face,
+                                                       int64_t n_verts, NnGrid G, float pad, int64_t big_face,
                                                        int32_t *__restrict__ count, int32_t *__restrict__ big,
                                                        int32_t *status) {
     const int64_t f = (int64_t)blockIdx.x * kNT + threadIdx.x;
@@ -173,7 +160,7 @@ __global__ __launch_bounds__(kNT) void md_count_kernel(const float *__restrict__
     float v[9];
     int32_t c0[3], c1[3];
     int32_t n = 0, is_big = 0;
-    if (md_face(verts, faces, f, n_verts, G, status, v, c0, c1)) {
+    if (md_face(verts, faces, f, n_verts, G, pad, status, v, c0, c1)) {
         // at most the cells of the grid: < 2^31
         const int64_t cells = (int64_t)(c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1);
         is_big = cells > big_face ? 1 : 0;
@@ -194,7 +181,8 @@ __device__ __forceinline__ void md_store_record(float4 *__restrict__ rec, int64_
 // send a store outside key / pair_face / rec
 __global__ __launch_bounds__(kNT) void md_emit_kernel(const float *__restrict__ verts,
                                                       const int32_t *__restrict__ faces, int64_t n_faces,
-                                                      int64_t n_verts, NnGrid G, const int32_t *__restrict__ count,
+                                                      int64_t n_verts, NnGrid G, float pad,
+                                                      const int32_t *__restrict__ count,
                                                       const int32_t *__restrict__ big,
                                                       const int32_t *__restrict__ prefix, int64_t n_pairs,
                                                       const int32_t *__restrict__ big_prefix, int64_t n_big,
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(kNT) void md_emit_kernel(const float *__restrict__ 
     if (!is_big && count[f] <= 0) return;
     float v[9];
     int32_t c0[3], c1[3];
-    if (!md_face(verts, faces, f, n_verts, G, nullptr, v, c0, c1)) return;
+    if (!md_face(verts, faces, f, n_verts, G, pad, nullptr, v, c0, c1)) return;
     if (is_big) {
         const int64_t o = big_prefix[f];
         if (o >= 0 && o < n_big) md_store_record(rec, n_pairs + o, v, (int32_t)f);
@@ -443,13 +431,6 @@ MdWs md_layout(void *ws, int64_t n) {
     return w;
 }
 
-int md_check_counts(int64_t n_pairs, int64_t n_big, const char *what) {
-    const std::string w(what);
-    HM_CHECK_ARG(n_pairs >= 0 && n_big >= 0 && n_pairs + n_big >= 1 && n_pairs + n_big < ((int64_t)1 << 31),
-                 w + ": n_pairs and n_big must be >= 0 and their sum in [1, 2^31)");
-    return HM_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -460,40 +441,43 @@ int64_t hm_mesh_dist_workspace_bytes(int64_t n) {
     return md_layout(nullptr, n).bytes;
 }
 
-int hm_mesh_dist_count(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, const float *lo,
-                       float h, const int32_t *g, int64_t big_face, int32_t *count, int32_t *big, int32_t *status,
-                       void *stream) {
-    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_dist_count")) return rc;
-    HM_CHECK_ARG(n_faces >= 1, "hm_mesh_dist_count: at least one face is needed");
+int hm_mesh_index_count(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, const float *lo,
+                        float h, const int32_t *g, float pad, int64_t big_face, int32_t *count, int32_t *big,
+                        int32_t *status, void *stream) {
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_index_count")) return rc;
+    HM_CHECK_ARG(n_faces >= 1, "hm_mesh_index_count: at least one face is needed");
     NnGrid G;
     int64_t cells;
-    if (int rc = nn_grid(lo, h, g, "hm_mesh_dist_count", G, cells)) return rc;
-    HM_CHECK_ARG(big_face >= 1, "hm_mesh_dist_count: big_face must be >= 1");
-    HM_CHECK_ARG((verts || n_verts == 0) && count && big && status, "hm_mesh_dist_count: NULL pointer");
+    if (int rc = nn_grid(lo, h, g, "hm_mesh_index_count", G, cells)) return rc;
+    HM_CHECK_ARG(big_face >= 1, "hm_mesh_index_count: big_face must be >= 1");
+    HM_CHECK_ARG(std::isfinite(pad) && pad >= 0.0f, "hm_mesh_index_count: pad must be finite and >= 0");
+    HM_CHECK_ARG((verts || n_verts == 0) && count && big && status, "hm_mesh_index_count: NULL pointer");
     hipLaunchKernelGGL(md_count_kernel, dim3(hm_grid(n_faces, kNT)), dim3(kNT), 0, as_stream(stream), verts, faces,
-                       n_faces, n_verts, G, big_face, count, big, status);
-    HM_CHECK_LAUNCH("hm_mesh_dist_count");
+                       n_faces, n_verts, G, pad, big_face, count, big, status);
+    HM_CHECK_LAUNCH("hm_mesh_index_count");
     return HM_OK;
 }
 
-int hm_mesh_dist_build(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, const float *lo,
-                       float h, const int32_t *g, const int32_t *count, const int32_t *big, const int32_t *prefix,
-                       int64_t n_pairs, const int32_t *big_prefix, int64_t n_big, int32_t *cell_start, float *records,
-                       void *workspace, int64_t workspace_bytes, void *stream) {
-    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_dist_build")) return rc;
-    HM_CHECK_ARG(n_faces >= 1, "hm_mesh_dist_build: at least one face is needed");
+int hm_mesh_index_build(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, const float *lo,
+                        float h, const int32_t *g, float pad, const int32_t *count, const int32_t *big,
+                        const int32_t *prefix, int64_t n_pairs, const int32_t *big_prefix, int64_t n_big,
+                        int32_t *cell_start, float *records, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (int rc = hm_check_mesh(n_faces, n_verts, faces, "hm_mesh_index_build")) return rc;
+    HM_CHECK_ARG(n_faces >= 1, "hm_mesh_index_build: at least one face is needed");
     NnGrid G;
     int64_t cells;
-    if (int rc = nn_grid(lo, h, g, "hm_mesh_dist_build", G, cells)) return rc;
-    if (int rc = md_check_counts(n_pairs, n_big, "hm_mesh_dist_build")) return rc;
+    if (int rc = nn_grid(lo, h, g, "hm_mesh_index_build", G, cells)) return rc;
+    if (int rc = md_check_counts(n_pairs, n_big, "hm_mesh_index_build")) return rc;
+    HM_CHECK_ARG(std::isfinite(pad) && pad >= 0.0f, "hm_mesh_index_build: pad must be finite and >= 0");
     HM_CHECK_ARG(verts && count && big && prefix && big_prefix && cell_start && records && workspace,
-                 "hm_mesh_dist_build: NULL pointer");
-    HM_CHECK_ARG(workspace_bytes >= hm_mesh_dist_workspace_bytes(n_pairs), "hm_mesh_dist_build: workspace too small");
+                 "hm_mesh_index_build: NULL pointer");
+    HM_CHECK_ARG(workspace_bytes >= hm_mesh_dist_workspace_bytes(n_pairs),
+                 "hm_mesh_index_build: workspace too small");
     const MdWs w = md_layout(workspace, n_pairs);
     hipStream_t st = as_stream(stream);
     float4 *rec = reinterpret_cast<float4 *>(records);
     hipLaunchKernelGGL(md_emit_kernel, dim3(hm_grid(n_faces, kNT)), dim3(kNT), 0, st, verts, faces, n_faces, n_verts, G,
-                       count, big, prefix, n_pairs, big_prefix, n_big, w.sort.key, w.pair_face, rec);
+                       pad, count, big, prefix, n_pairs, big_prefix, n_big, w.sort.key, w.pair_face, rec);
     if (n_pairs > 0) {
         int key_bits = 1;
         while (key_bits < 31 && ((int64_t)1 << key_bits) < cells) ++key_bits;
@@ -506,8 +490,23 @@ int hm_mesh_dist_build(const float *verts, const int32_t *faces, int64_t n_faces
     }
     hipLaunchKernelGGL(nn_cell_start_kernel, dim3(hm_grid(cells + 1, kNT)), dim3(kNT), 0, st,
                        static_cast<const int32_t *>(w.sort.keys_sorted), n_pairs, cells, cell_start);
-    HM_CHECK_LAUNCH("hm_mesh_dist_build");
+    HM_CHECK_LAUNCH("hm_mesh_index_build");
     return HM_OK;
+}
+
+// the index without a pad: the cells of the faces' own bounding boxes
+int hm_mesh_dist_count(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, const float *lo,
+                       float h, const int32_t *g, int64_t big_face, int32_t *count, int32_t *big, int32_t *status,
+                       void *stream) {
+    return hm_mesh_index_count(verts, faces, n_faces, n_verts, lo, h, g, 0.0f, big_face, count, big, status, stream);
+}
+
+int hm_mesh_dist_build(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts, const float *lo,
+                       float h, const int32_t *g, const int32_t *count, const int32_t *big, const int32_t *prefix,
+                       int64_t n_pairs, const int32_t *big_prefix, int64_t n_big, int32_t *cell_start, float *records,
+                       void *workspace, int64_t workspace_bytes, void *stream) {
+    return hm_mesh_index_build(verts, faces, n_faces, n_verts, lo, h, g, 0.0f, count, big, prefix, n_pairs, big_prefix,
+                               n_big, cell_start, records, workspace, workspace_bytes, stream);
 }
 
 int hm_mesh_dist_query(const float *query, int64_t m, const float *records, int64_t n_pairs, int64_t n_big,

@@ -4,3 +4,4 @@ from .color import ColorStats, color_mesh, color_mesh_for_dataset  # noqa: F401
 from .cull import CullStats, cull_mesh, cull_mesh_for_dataset, view_projections  # noqa: F401
 from .images import evaluate_views, render_view, view_metrics  # noqa: F401
 from .mesh_views import MeshViews, evaluate_mesh_views, render_mesh  # noqa: F401
+from .mesh_rays import DepthAgreement, cast_camera_rays, depth_agreement  # noqa: F401

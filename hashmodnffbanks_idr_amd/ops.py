@@ -2026,6 +2026,8 @@ def one_sided_distance(src, dst, max_dist=None, cell=None):
 MESH_DIST_BIG_FACE = 64     # cells of a face's cell box above which the face goes to the list every wave tests in full
 _MD_PER_CELL = 32.0         # mean face areas per cell face the default cell edge aims at
 _MD_WS = _lib.Workspace("mesh_closest_point")
+_MR_PER_CELL = 24.0         # the aim of mesh_ray_cast's default cell edge, about 2.75 lattice spacings of a marching-
+                            # cubes mesh: scripts/mesh_ray_time.py's sweep is fastest between 2 and 3
 
 
 def _check_on_gpu(what, *tensors):
@@ -2038,15 +2040,18 @@ def _check_on_gpu(what, *tensors):
 
 class MeshIndex:
     """The uniform grid over a triangle mesh that ops.mesh_index builds: every face listed in the cells of its
-    bounding box as 48-byte records ordered by cell (ascending face inside a cell), the big faces as a run of records
-    behind them, and the dense cell_start table.  query() answers closest-point queries against it."""
+    bounding box - grown by `pad` on every side - as 48-byte records ordered by cell (ascending face inside a cell), the
+    big faces as a run of records behind them, and the dense cell_start table.  query() answers closest-point queries
+    against it, ray_cast() first-hit queries."""
 
-    def __init__(self, verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE):
+    def __init__(self, verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE, pad=0.0, _per_cell=_MD_PER_CELL,
+                 _auto_pad=False):
         if cell is not None and not (isinstance(cell, (int, float)) and not isinstance(cell, bool)
                                      and math.isfinite(cell) and cell > 0):
             raise ValueError("hashmod mesh_index: cell must be a positive finite number")
         if not (isinstance(big_face, int) and not isinstance(big_face, bool) and 1 <= big_face < 1 << 62):
             raise ValueError("hashmod mesh_index: big_face must be an integer >= 1")
+        self.pad = None if _auto_pad and pad is None else _ray_pad("mesh_index", pad)
         if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
             raise ValueError("hashmod mesh_index: verts and faces must be tensors")
         if faces.dim() == 2 and faces.shape[0] < 1:
@@ -2060,8 +2065,10 @@ class MeshIndex:
         box = torch.stack([lo, hi]).tolist()
         if not all(math.isfinite(v) for v in box[0] + box[1]):
             raise _lib.HashmodError("hashmod mesh_index: a vertex has a non-finite coordinate")
-        self.h, self.g = _nn_grid(box[0], box[1], n_faces, cell, "mesh_index", _MD_PER_CELL)
+        self.h, self.g = _nn_grid(box[0], box[1], n_faces, cell, "mesh_index", _per_cell)
         self.lo = box[0]
+        if self.pad is None:                # mesh_ray_cast's default, from the box already read: mesh_ray_pad's value
+            self.pad = _default_ray_pad(box)
         self.n_faces, self.n_verts = n_faces, n_verts
         self.big_face = big_face
         self.device = dev
@@ -2071,8 +2078,8 @@ class MeshIndex:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         count = torch.empty(n_faces, dtype=torch.int32, device=dev)
         big = torch.empty(n_faces, dtype=torch.int32, device=dev)
-        check(L.hm_mesh_dist_count(dptr(verts), dptr(faces), n_faces, n_verts, self._lo(), self.h, self._g(), big_face,
-                                   dptr(count), dptr(big), dptr(status), st))
+        check(L.hm_mesh_index_count(dptr(verts), dptr(faces), n_faces, n_verts, self._lo(), self.h, self._g(), self.pad,
+                                    big_face, dptr(count), dptr(big), dptr(status), st))
         # bookkeeping between the launches: positions from the counts, the totals and the status word to the host
         cincl = torch.cumsum(count, 0, dtype=torch.int64)
         bincl = torch.cumsum(big, 0, dtype=torch.int64)
@@ -2090,9 +2097,9 @@ class MeshIndex:
         self.cell_start = torch.empty(cells + 1, dtype=torch.int32, device=dev)
         self.records = torch.empty((n_pairs + n_big, 12), dtype=torch.float32, device=dev)
         ws = _MD_WS.get(dev, check(L.hm_mesh_dist_workspace_bytes(n_pairs)))
-        check(L.hm_mesh_dist_build(dptr(verts), dptr(faces), n_faces, n_verts, self._lo(), self.h, self._g(),
-                                   dptr(count), dptr(big), dptr(prefix), n_pairs, dptr(big_prefix), n_big,
-                                   dptr(self.cell_start), dptr(self.records), dptr(ws), ws.numel(), st))
+        check(L.hm_mesh_index_build(dptr(verts), dptr(faces), n_faces, n_verts, self._lo(), self.h, self._g(), self.pad,
+                                    dptr(count), dptr(big), dptr(prefix), n_pairs, dptr(big_prefix), n_big,
+                                    dptr(self.cell_start), dptr(self.records), dptr(ws), ws.numel(), st))
 
     def _lo(self):
         return (C.c_float * 3)(*self.lo)
@@ -2132,6 +2139,85 @@ class MeshIndex:
         out = self._query(query, _max_dist2("mesh_closest_point", max_dist), return_point, return_feature)
         return tuple(t for t in out if t is not None)
 
+    def ray_cast(self, origins, dirs, t_min=0.0, t_max=math.inf, return_uv=True, return_point=False, stats=None):
+        """mesh_ray_cast's outputs for the rays (origins, dirs) [m,3] against this mesh, with the index's own pad;
+        stats: a dict that receives "face_tests", the launch's number of (ray, face) tests (one more host read; for
+        scripts/mesh_ray_time.py)"""
+        what = "mesh_ray_cast"
+        _check_cloud(what, "origins", origins)
+        _check_cloud(what, "dirs", dirs, origins)
+        m = int(origins.shape[0])
+        if int(dirs.shape[0]) != m:
+            raise ValueError(f"hashmod {what}: origins and dirs must have the same number of rows")
+        _check_flags(what, return_uv=return_uv, return_point=return_point)
+        if stats is not None and not isinstance(stats, dict):
+            raise ValueError(f"hashmod {what}: stats must be a dict (or None)")
+        bounds = [_ray_bound(what, "t_min", t_min, 0.0, m, origins),
+                  _ray_bound(what, "t_max", t_max, math.inf, m, origins)]
+        _check_on_gpu(what, origins, dirs)
+        if origins.device != self.device:
+            raise ValueError(f"hashmod {what}: the tensors are on different devices")
+        dev = self.device
+        t = torch.empty(m, dtype=torch.float32, device=dev)
+        face = torch.empty(m, dtype=torch.int32, device=dev)
+        uv = torch.empty((m, 2), dtype=torch.float32, device=dev) if return_uv else None
+        point = torch.empty((m, 3), dtype=torch.float32, device=dev) if return_point else None
+        out = tuple(x for x in (t, face, uv, point) if x is not None)
+        if stats is not None:
+            stats["face_tests"] = 0
+        if m == 0:
+            return out
+        for k, b in enumerate(bounds):      # a number other than the default becomes a filled tensor
+            if isinstance(b, float):
+                bounds[k] = torch.full((m,), b, dtype=torch.float32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        tests = None if stats is None else torch.zeros(1, dtype=torch.int64, device=dev)
+        check(lib().hm_mesh_ray_cast(dptr(origins), dptr(dirs), dptr(bounds[0]), dptr(bounds[1]), m, dptr(self.records),
+                                     self.n_pairs, self.n_big, dptr(self.cell_start), self._lo(), self.h, self._g(),
+                                     self.pad, dptr(t), dptr(face), dptr(uv), dptr(point), dptr(status), dptr(tests),
+                                     stream_ptr(origins)))
+        if stats is not None:
+            stats["face_tests"] = int(tests.item())
+        if int(status.item()):
+            raise _lib.HashmodError(f"hashmod {what}: a ray has a non-finite origin, direction or t_min, or a NaN "
+                                    "t_max")
+        return out
+
+
+def _default_ray_pad(box):
+    ext = max(np.float32(b) - np.float32(a) for a, b in zip(box[0], box[1]))
+    return float(np.float32(2.0 ** -12) * ext)
+
+
+def _ray_pad(what, pad):
+    """pad as the fp32 value the kernels use"""
+    if not (isinstance(pad, (int, float)) and not isinstance(pad, bool) and math.isfinite(pad) and pad >= 0):
+        raise ValueError(f"hashmod {what}: pad must be a finite number >= 0")
+    with np.errstate(over="ignore"):
+        pad = float(np.float32(pad))
+    if not math.isfinite(pad):
+        raise ValueError(f"hashmod {what}: pad must be finite in fp32")
+    return pad
+
+
+def _ray_bound(what, name, value, default, m, like):
+    """a range end of the rays: None for the default (the kernel's NULL), a float to be filled in, or the [m] fp32
+    tensor itself"""
+    if isinstance(value, torch.Tensor):
+        if value.dtype != torch.float32 or value.dim() != 1 or not value.is_contiguous():
+            raise ValueError(f"hashmod {what}: {name} must be a number or a contiguous fp32 tensor [m]")
+        if int(value.shape[0]) != m:
+            raise ValueError(f"hashmod {what}: {name} must have one entry per ray")
+        if value.device != like.device:
+            raise ValueError(f"hashmod {what}: the tensors are on different devices")
+        return value
+    if not isinstance(value, (int, float)) or isinstance(value, bool):
+        raise ValueError(f"hashmod {what}: {name} must be a number or a contiguous fp32 tensor [m]")
+    value = float(value)
+    if value != value or (name == "t_min" and math.isinf(value)):
+        raise ValueError(f"hashmod {what}: {name} must not be NaN" + (" or infinite" if name == "t_min" else ""))
+    return None if value == default else value
+
 
 def _check_flags(what, **flags):
     for name, value in flags.items():
@@ -2139,9 +2225,9 @@ def _check_flags(what, **flags):
             raise ValueError(f"hashmod {what}: {name} must be a bool")
 
 
-def mesh_index(verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE):
-    """The search structure of mesh_closest_point over the mesh verts [V,3] fp32, faces [F,3] int32 (F >= 1), to be
-    queried many times: a uniform grid of cell edge `cell` over the vertices' bounding box (read by the host through
+def mesh_index(verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE, pad=0.0):
+    """The search structure of mesh_closest_point (and, with a pad, of ray casting) over the mesh verts [V,3] fp32,
+    faces [F,3] int32 (F >= 1), to be queried many times: a uniform grid of cell edge `cell` over the vertices' bounding box (read by the host through
     aminmax), every face listed in all cells of its own bounding box.  Without `cell` the edge is sqrt(32 A / F) with A
     half the box's surface area - a cell face with the area of 32 mean faces of a surface-like mesh, about three
     bounding-box edges of a marching-cubes face: small cells list a face many times and make far queries walk many
@@ -2152,9 +2238,59 @@ def mesh_index(verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE):
     cells across on every axis) is not listed in the grid but in a separate run that every query wave tests in full,
     so that one large face among many small ones does not fill the table.  The pairs are ordered by cell with the
     library's stable radix sort.  A non-finite vertex or a face index outside [0, V) raises HashmodError (reported by
-    the kernel's status word, never dereferenced).  The grid changes the speed of a query, never its result.  Host
-    reads of the box, the totals and the status word, so not graph-capturable."""
-    return MeshIndex(verts, faces, cell, big_face)
+    the kernel's status word, never dereferenced).  The grid changes the speed of a query, never its result.  `pad`
+    (a finite number >= 0, kept as index.pad in fp32) lists every face over its bounding box grown by pad on every
+    side: index.ray_cast needs it (mesh_ray_pad gives the usual value) and its result depends on it, the closest-point
+    query stays exact on a padded index, and pad = 0 is the index without one, tensor for tensor.  Host reads of the
+    box, the totals and the status word, so not graph-capturable."""
+    return MeshIndex(verts, faces, cell, big_face, pad)
+
+
+def mesh_ray_pad(verts):
+    """The default pad of ray casting: fp32(2^-12 * the largest bounding-box extent of verts [V,3]) - far above fp32
+    rounding, a few percent of a default cell.  One host read."""
+    if (not isinstance(verts, torch.Tensor) or verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3
+            or verts.shape[0] < 1 or not verts.is_contiguous()):
+        raise ValueError("hashmod mesh_ray_pad: contiguous fp32 verts [V,3] with V >= 1 expected")
+    box = torch.stack(torch.aminmax(verts, dim=0)).tolist()
+    if not all(math.isfinite(v) for v in box[0] + box[1]):
+        raise _lib.HashmodError("hashmod mesh_ray_pad: a vertex has a non-finite coordinate")
+    return _default_ray_pad(box)
+
+
+def mesh_ray_index(verts, faces, cell=None, big_face=MESH_DIST_BIG_FACE, pad=None):
+    """The MeshIndex that mesh_ray_cast builds, to be cast at many times: mesh_index with the defaults of ray casting -
+    pad = mesh_ray_pad(verts) for None (taken from the box the build reads anyway), and without `cell` the edge
+    sqrt(24 A / F), about 2.75 bounding-box edges of a marching-cubes face, where scripts/mesh_ray_time.py's sweep is
+    fastest.  Neither changes a result for a given pad."""
+    return MeshIndex(verts, faces, cell, big_face, pad, _per_cell=_MR_PER_CELL, _auto_pad=True)
+
+
+def mesh_ray_cast(origins, dirs, verts, faces, t_min=0.0, t_max=math.inf, pad=None, cell=None,
+                  big_face=MESH_DIST_BIG_FACE, return_uv=True, return_point=False):
+    """(t [m] fp32, face [m] int32, then uv [m,2] fp32 with return_uv, then point [m,3] fp32 with return_point): for
+    every ray origins[i] + t * dirs[i], t_min <= t <= t_max (numbers or [m] fp32 tensors, both ends inclusive, t_max
+    may be inf), the first face of the triangle mesh it meets: the ray parameter t (the Euclidean distance for a unit
+    direction), the face, its barycentric (u, v) (the hit is (1-u-v) a + u b + v c) and the point o + t d.  The result
+    is the brute-force fp32 argmin of the per-face value that include/hashmod.h defines (tests/mesh_ray_cases.ray_ref
+    is its numpy restatement): the smallest t, the lowest face index among equal t, bit for bit, independent of the
+    grid, of big_face, of m and of the ray and thread order.  Both windings hit; a miss (a zero direction included)
+    gives t = inf, face -1, NaN uv and point.  `pad` is part of the definition (a hit point must lie in its face's
+    bounding box grown by pad): None takes mesh_ray_pad(verts).  No claim of watertightness.  m = 0 gives empty
+    outputs; contiguous fp32 tensors on one GPU (else ValueError); a non-finite origin, direction or t_min, or a NaN
+    t_max, raises HashmodError.  mesh_ray_index(verts, faces, cell, big_face, pad).ray_cast(origins, dirs, ...) is the
+    same in two steps.  Not graph-capturable."""
+    _check_cloud("mesh_ray_cast", "origins", origins)
+    _check_cloud("mesh_ray_cast", "dirs", dirs, origins)
+    _check_flags("mesh_ray_cast", return_uv=return_uv, return_point=return_point)
+    if pad is not None:
+        pad = _ray_pad("mesh_ray_cast", pad)
+    if origins.shape[0] != dirs.shape[0]:
+        raise ValueError("hashmod mesh_ray_cast: origins and dirs must have the same number of rows")
+    for name, value, default in (("t_min", t_min, 0.0), ("t_max", t_max, math.inf)):
+        _ray_bound("mesh_ray_cast", name, value, default, int(origins.shape[0]), origins)
+    index = mesh_ray_index(verts, faces, cell, big_face, pad)
+    return index.ray_cast(origins, dirs, t_min, t_max, return_uv, return_point)
 
 
 def mesh_closest_point(query, verts, faces, max_dist=None, cell=None, big_face=MESH_DIST_BIG_FACE, return_point=True,

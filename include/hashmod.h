@@ -1187,6 +1187,52 @@ HM_API int hm_mesh_dist_query(const float *query, int64_t m, const float *record
                               float *d2, int32_t *face, float *point, int32_t *feature, void *workspace,
                               int64_t workspace_bytes, int32_t *status, uint64_t *n_tests, void *stream);
 
+/* ---- rays against the mesh: the first hit of a ray on the triangle grid ------------------------------------------
+ * For a ray (o, d, t_min, t_max) the nearest face it meets, the ray parameter t (a Euclidean distance when d has unit
+ * length), the barycentric (u, v) and the hit point.  Driver: ops.mesh_index(pad=...).ray_cast, ops.mesh_ray_cast,
+ * evaluation.mesh_rays.cast_camera_rays.  csrc/hm_mesh_ray.hip (it states why the walk over the grid is exact).  No
+ * entry point synchronises, none uses floating-point atomics.  status is one device int32 the CALLER has zeroed.
+ *
+ * THE PADDED INDEX.  hm_mesh_index_count / hm_mesh_index_build are hm_mesh_dist_count / hm_mesh_dist_build with a
+ * pad (fp32, finite, >= 0): a face is listed in the cells of fl(min - pad) .. fl(max + pad) per axis instead of its
+ * bounding box's.  pad = 0 gives the same counts, pairs, records and cell_start, bit for bit, and that is what the
+ * hm_mesh_dist_* entry points forward.  The records do not depend on pad.  A padded index lists a superset of the
+ * cells, so hm_mesh_dist_query stays exact on it (its stopping rule needs a face to be listed in AT LEAST the cells
+ * of its box).  hm_mesh_ray_cast must be given the pad its index was built with, or a smaller one.
+ *
+ * THE DEFINITION.  The result is the brute-force argmin over all faces of the following, bit for bit, whatever the
+ * grid, big_face, m, the ray order and the thread order.  Every fp32 operation rounds once; dot and cross are those
+ * of the point-to-mesh distance above.  For a face with fp32 vertices a, b, c:
+ *   lo = fl(min(a, b, c) - pad), hi = fl(max(a, b, c) + pad) per axis;
+ *   e1 = b - a, e2 = c - a, pv = cross(d, e2), det = dot(e1, pv), tv = o - a, u = dot(tv, pv) / det,
+ *   qv = cross(tv, e1), v = dot(d, qv) / det, t = dot(e2, qv) / det, p = fl(o + fl(t * d)) per axis;
+ *   hit <=> det != 0 and u >= 0 and v >= 0 and fl(u + v) <= 1 and t_min <= t <= t_max and lo <= p <= hi on every axis.
+ * Both windings hit; any NaN makes a comparison false, a miss; both range ends are inclusive and t_max = +inf is
+ * allowed; a zero direction misses.  The winner is the smallest t and, among equal t, the lowest face index.  The
+ * last clause ties the hit point to the face's (padded) box: it makes the grid walk provably exact and discards the
+ * garbage t of slivers; with pad = 0 a face that is flat along an axis is almost never hit, so ray casting wants
+ * pad > 0 (ops.mesh_ray_pad: 2^-12 of the largest extent).  pad is part of the definition.  No claim of
+ * watertightness: the edge tests of neighbouring faces are separate fp32 expressions.
+ *   hm_mesh_ray_cast: origins, dirs [m,3] fp32, m >= 0 (m = 0 returns at once); t_min, t_max [m] fp32, or NULL for
+ *                0 and +inf.  records, n_pairs, n_big, cell_start, lo, h, g: the index.  Writes t [m] fp32 and
+ *                face [m] int32 and, unless NULL, uv [m,2] fp32 and point [m,3] fp32 (= p); a miss gets +inf, -1,
+ *                NaN, NaN.  A non-finite origin or direction, a non-finite t_min or a NaN t_max sets status bit 2.
+ *                n_tests (may be NULL; a measurement aid): a device counter the caller has zeroed, receives the
+ *                number of (ray, face record) tests.  Every index read from cell_start is clamped into
+ *                [0, n_pairs]. */
+HM_API int hm_mesh_index_count(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                               const float *lo, float h, const int32_t *g, float pad, int64_t big_face,
+                               int32_t *count, int32_t *big, int32_t *status, void *stream);
+HM_API int hm_mesh_index_build(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                               const float *lo, float h, const int32_t *g, float pad, const int32_t *count,
+                               const int32_t *big, const int32_t *prefix, int64_t n_pairs, const int32_t *big_prefix,
+                               int64_t n_big, int32_t *cell_start, float *records, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+HM_API int hm_mesh_ray_cast(const float *origins, const float *dirs, const float *t_min, const float *t_max, int64_t m,
+                            const float *records, int64_t n_pairs, int64_t n_big, const int32_t *cell_start,
+                            const float *lo, float h, const int32_t *g, float pad, float *t, int32_t *face, float *uv,
+                            float *point, int32_t *status, uint64_t *n_tests, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
