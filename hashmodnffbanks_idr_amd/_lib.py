@@ -174,6 +174,10 @@ SIGNATURES = {
                                    _p, _i64, _p]),
     "hm_mesh_ray_cast": (_int, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _p, _p, C.c_float, _p, C.c_float, _p, _p, _p, _p,
                                 _p, _p, _p]),
+    # signed distance to the mesh: the pseudo-normal tables and the sign of a closest-point result
+    "hm_mesh_topology_workspace_bytes": (_i64, [_i64]),
+    "hm_mesh_topology_build": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p]),
+    "hm_mesh_sign": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
 }
 
 

@@ -2183,6 +2183,18 @@ class MeshIndex:
                                     "t_max")
         return out
 
+    def signed_distance(self, query, topology, max_dist=None, return_sign=False, return_face=False,
+                        return_point=False):
+        """mesh_signed_distance's outputs for the rows of query [m,3] against this mesh; `topology` is
+        ops.mesh_topology(verts, faces) of the same mesh (its n_faces, n_verts and device must be the index's, else
+        ValueError)"""
+        what = "mesh_signed_distance"
+        _check_flags(what, return_sign=return_sign, return_face=return_face, return_point=return_point)
+        sd, sign, _, face, point = _mesh_sign(self, topology, query, _max_dist2(what, max_dist), return_sign)
+        out = tuple(t for t, wanted in ((sd, True), (sign, return_sign), (face, return_face), (point, return_point))
+                    if wanted)
+        return out if len(out) > 1 else sd
+
 
 def _default_ray_pad(box):
     ext = max(np.float32(b) - np.float32(a) for a, b in zip(box[0], box[1]))
@@ -2348,6 +2360,136 @@ def _as_mesh_index(what, mesh_or_index):
     if isinstance(mesh_or_index, (tuple, list)) and len(mesh_or_index) == 2:
         return MeshIndex(mesh_or_index[0], mesh_or_index[1])
     raise ValueError(f"hashmod {what}: the mesh must be a MeshIndex or a (verts, faces) pair")
+
+
+# =========================================================================================
+# Signed distance to the mesh: pseudo-normal tables and the sign of a closest-point result (csrc/hm_mesh_topo.hip)
+# =========================================================================================
+_MT_WS = _lib.Workspace("mesh_topology")
+_MT_MAX_FACES = ((1 << 31) - 1) // 3
+
+
+class MeshTopology:
+    """The two pseudo-normal tables of a triangle mesh that ops.mesh_topology builds - vertex_normals [V,3] fp64 (the
+    angle-weighted sum of the unit normals of a vertex's faces, zero for a vertex no face names) and edge_normals
+    [F,3,3] fp64 (per half-edge, the sum of the unit normals of ALL faces on its edge) - and what the half-edges say
+    about the mesh: boundary_edges (edges of one face), nonmanifold_edges (of more than two), flipped_edges (of two
+    faces that traverse it in the same direction), and closed, true when all three are 0.  It keeps verts and faces
+    (not copies): MeshIndex.signed_distance reads the winning face's vertices from them."""
+
+    def __init__(self, verts, faces):
+        what = "mesh_topology"
+        if not isinstance(verts, torch.Tensor) or not isinstance(faces, torch.Tensor):
+            raise ValueError(f"hashmod {what}: verts and faces must be tensors")
+        if faces.dim() == 2 and faces.shape[0] < 1:
+            raise ValueError(f"hashmod {what}: at least one face is needed")
+        if faces.dim() == 2 and faces.shape[0] > _MT_MAX_FACES:
+            raise ValueError(f"hashmod {what}: 3 F must be below 2^31")
+        _check_on_gpu(what, verts, faces)
+        n_faces, n_verts = _check_mesh(what, faces, verts=verts, gpu_first=False)
+        dev = faces.device
+        if n_verts < 1:
+            raise _lib.HashmodError(f"hashmod {what}: a face index lies outside [0, n_verts)")
+        self.verts, self.faces = verts, faces
+        self.n_faces, self.n_verts = n_faces, n_verts
+        self.device = dev
+        self.vertex_normals = torch.empty((n_verts, 3), dtype=torch.float64, device=dev)
+        self.edge_normals = torch.empty((n_faces, 3, 3), dtype=torch.float64, device=dev)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        L = lib()
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = _MT_WS.get(dev, check(L.hm_mesh_topology_workspace_bytes(n_faces)))
+        check(L.hm_mesh_topology_build(dptr(verts), dptr(faces), n_faces, n_verts, dptr(self.vertex_normals),
+                                       dptr(self.edge_normals), dptr(counts), dptr(ws), ws.numel(), dptr(status),
+                                       stream_ptr(faces)))
+        # one host read: the three counts and the status word
+        b, n, f, bad = torch.cat([counts, status.to(torch.int64)]).tolist()
+        if bad & 1:
+            _check_mesh_status(what, status)
+        if bad:
+            raise _lib.HashmodError(f"hashmod {what}: a vertex of a face has a non-finite coordinate")
+        self.boundary_edges, self.nonmanifold_edges, self.flipped_edges = b, n, f
+        self.closed = b == 0 and n == 0 and f == 0
+
+    def __repr__(self):
+        return (f"MeshTopology(n_verts={self.n_verts}, n_faces={self.n_faces}, boundary_edges={self.boundary_edges}, "
+                f"nonmanifold_edges={self.nonmanifold_edges}, flipped_edges={self.flipped_edges})")
+
+
+def mesh_topology(verts, faces):
+    """The MeshTopology of the mesh verts [V,3] fp32, faces [F,3] int32 (F >= 1, 3 F < 2^31): the angle-weighted
+    pseudo-normals of Baerentzen and Aanaes as two fp64 tables and the counts of boundary, non-manifold and flipped
+    edges, by the definition of include/hashmod.h (tests/mesh_sign_cases.topology_ref is its numpy restatement).  The
+    corners are sorted by vertex and the half-edges by their vertex pair with the library's stable radix sort, and one
+    lane sums each run in sorted order: no floating-point atomics, the same bits whatever the thread order; the edge
+    table and the counts equal the restatement bit for bit, the vertex table up to the device's atan2.  Contiguous
+    tensors on one GPU (else ValueError); a face index outside [0, V) or a non-finite vertex of a face raises
+    HashmodError (reported by the kernel's status word, never dereferenced).  One host read, so not
+    graph-capturable."""
+    return MeshTopology(verts, faces)
+
+
+def _mesh_sign(index, topology, query, max_dist2, want_sign):
+    """(sd, sign or None, d2, face, point) of the queries: the closest-point query, then the sign kernel"""
+    what = "mesh_signed_distance"
+    if not isinstance(topology, MeshTopology):
+        raise ValueError(f"hashmod {what}: topology must be a MeshTopology (ops.mesh_topology)")
+    if (topology.n_faces != index.n_faces or topology.n_verts != index.n_verts or topology.device != index.device):
+        raise ValueError(f"hashmod {what}: the topology is not of the index's mesh (n_faces, n_verts and device must "
+                         "agree)")
+    d2, face, point, feature = index._query(query, max_dist2, True, True)
+    m = int(query.shape[0])
+    dev = index.device
+    sd = torch.empty(m, dtype=torch.float32, device=dev)
+    sign = torch.empty(m, dtype=torch.int32, device=dev) if want_sign else None
+    if m:
+        check(lib().hm_mesh_sign(dptr(query), m, dptr(face), dptr(feature), dptr(point), dptr(d2),
+                                 dptr(topology.verts), dptr(topology.faces), topology.n_faces, topology.n_verts,
+                                 dptr(topology.vertex_normals), dptr(topology.edge_normals), dptr(sd), dptr(sign),
+                                 stream_ptr(query)))
+    return sd, sign, d2, face, point
+
+
+def mesh_signed_distance(query, verts, faces, max_dist=None, cell=None, big_face=MESH_DIST_BIG_FACE, return_sign=False,
+                         return_face=False, return_point=False):
+    """sd [m] fp32 (then sign [m] int32 with return_sign, face [m] int32 with return_face, point [m,3] fp32 with
+    return_point; a tuple when more than sd is asked for): for every row of query [m,3] the signed distance to the
+    triangle mesh, negative inside.  |sd| is the fp32 square root of mesh_closest_point's exact d2; the sign is the
+    sign of dot(q - closest point, N), N the angle-weighted pseudo-normal of the feature the closest point lies on -
+    the face's normal, its edge's, or its vertex's (Baerentzen and Aanaes) - by the definition of include/hashmod.h
+    (tests/mesh_sign_cases.sign_ref is its numpy restatement): a function of the closest-point result and
+    mesh_topology's two tables and of nothing else, so independent of the grid, of big_face, of m and of the thread
+    order.  It is the inside/outside of a closed, consistently wound mesh (MeshTopology.closed); elsewhere it is
+    still defined - above an open sheet is +, below it -.  A zero dot product is outside (+1): a query on the surface,
+    a zero pseudo-normal.  A query cut by max_dist gets sd = +inf, sign 0.  m = 0 gives empty outputs.  mesh_index(...)
+    .signed_distance(query, mesh_topology(verts, faces), ...) is the same in two steps.  Not graph-capturable."""
+    _check_cloud("mesh_signed_distance", "query", query)
+    _check_flags("mesh_signed_distance", return_sign=return_sign, return_face=return_face, return_point=return_point)
+    _max_dist2("mesh_signed_distance", max_dist)
+    index = MeshIndex(verts, faces, cell, big_face)
+    if query.device != index.device:
+        raise ValueError("hashmod mesh_signed_distance: the tensors are on different devices")
+    return index.signed_distance(query, MeshTopology(verts, faces), max_dist, return_sign, return_face, return_point)
+
+
+def _as_signed_mesh(what, mesh):
+    """(MeshIndex, MeshTopology) of a (MeshIndex, MeshTopology) or a (verts, faces) pair"""
+    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        if isinstance(mesh[0], MeshIndex) and isinstance(mesh[1], MeshTopology):
+            return mesh[0], mesh[1]
+        if isinstance(mesh[0], torch.Tensor) and isinstance(mesh[1], torch.Tensor):
+            return MeshIndex(mesh[0], mesh[1]), MeshTopology(mesh[0], mesh[1])
+    raise ValueError(f"hashmod {what}: the mesh must be a (MeshIndex, MeshTopology) or a (verts, faces) pair")
+
+
+def mesh_contains(query, mesh):
+    """inside [m] bool: mesh_signed_distance's sign < 0 for the rows of query [m,3]; `mesh` is a (MeshIndex,
+    MeshTopology) pair of one mesh or a (verts, faces) pair.  A query on the surface is outside.  Meaningful for a
+    closed mesh (MeshTopology.closed).  An index built with a pad gives the same result: the closest-point query is
+    exact on it."""
+    _check_cloud("mesh_contains", "query", query)
+    index, topology = _as_signed_mesh("mesh_contains", mesh)
+    return _mesh_sign(index, topology, query, math.inf, True)[1] < 0
 
 
 # =========================================================================================

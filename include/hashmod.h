@@ -1233,6 +1233,60 @@ HM_API int hm_mesh_ray_cast(const float *origins, const float *dirs, const float
                             const float *lo, float h, const int32_t *g, float pad, float *t, int32_t *face, float *uv,
                             float *point, int32_t *status, uint64_t *n_tests, void *stream);
 
+/* ---- signed distance to the mesh: angle-weighted pseudo-normals and the sign of a closest-point result -----------
+ * On which side of the surface a query lies, from the closest-point result above and two tables of the mesh's
+ * topology (Baerentzen and Aanaes, "Signed distance computation using the angle weighted pseudonormal"): no second
+ * search, no ray parity.  Driver: ops.mesh_topology, ops.MeshIndex.signed_distance, ops.mesh_signed_distance,
+ * ops.mesh_contains, evaluation.mesh_sdf.  csrc/hm_mesh_topo.hip.  No entry point synchronises, none uses
+ * floating-point atomics; the three counts use integer atomics.  status is one device int32 the CALLER has zeroed.
+ *
+ * THE DEFINITION (numpy restatement: tests/mesh_sign_cases.topology_ref, sign_ref).
+ * Per-face quantities, fp64 from the fp32 vertices a, b, c, every operation rounded once, no contraction, dot and
+ * cross of the shape stated for the point-to-mesh distance:
+ *   n = cross(b - a, c - a);  nu = n / sqrt(dot(n, n)), the zero vector when dot(n, n) == 0;
+ *   the angle at corner p with neighbours p1, p2: atan2(sqrt(dot(x, x)), dot(e1, e2)), x = cross(e1, e2), e1 = p1 - p,
+ *   e2 = p2 - p (corner a: b, c; corner b: c, a; corner c: a, b).
+ * VN[v], the vertex pseudo-normal: the sum of angle * nu over all (face, corner) pairs with that vertex, in ascending
+ *   face, then ascending corner order, starting from 0; zero for a vertex no face names.
+ * EN[f][k], the edge pseudo-normal of half-edge k of face f (k = 0, 1, 2 for (a,b), (b,c), (c,a)): the sum of nu over
+ *   ALL half-edges with the same unordered vertex pair - a run - in ascending (face, k) order, starting from 0; every
+ *   member of a run stores the same sum.  A boundary edge gets its own face's normal, a non-manifold edge the sum of
+ *   all its faces' normals; a face with a repeated vertex contributes its half-edges like any other (its nu is zero).
+ * counts: boundary_edges = runs of length 1; nonmanifold_edges = runs longer than 2; flipped_edges = runs of length 2
+ *   whose two half-edges traverse the pair in the SAME direction (first index > second index for both or for
+ *   neither).  The mesh is closed when all three are 0.
+ * The sign of a query q with closest-point result (face, feature, point, d2), a, b, c the face's fp32 vertices:
+ *   feature 0: w = q - a (fp32, rounded once, then widened), N = n of the face (fp64, not normalised);
+ *   feature k in 1..3 with end points p0, p1: t as the distance definition computes it in fp32, e = p1 - p0,
+ *       ee = dot(e, e), t = ee > 0 ? dot(q - p0, e) / ee : 0;  t <= 0: N = VN[index of p0];  t >= 1: N = VN[index of
+ *       p1];  otherwise N = EN[face][k-1];  in all three cases w = q - point (fp32, rounded once, then widened);
+ *   s = (w.x*N.x + w.y*N.y) + w.z*N.z in fp64;  sign = -1 if s < 0, else +1 (a zero or NaN s - d2 == 0, a zero
+ *   pseudo-normal - is outside);  sd = sign * sqrt(d2), the fp32 square root rounded once.
+ *   A query that max_dist cut (face -1) gets sd = +inf, sign = 0.
+ * The magnitude is the exact d2 of the closest-point query; the sign is a function of (face, feature, point) and the
+ * two tables and of nothing else.  The tables do not depend on the thread order; VN depends on the device's atan2.
+ *   hm_mesh_topology_workspace_bytes(n_faces): the scratch of hm_mesh_topology_build; 3 * n_faces < 2^31.
+ *   hm_mesh_topology_build: verts [n_verts,3] fp32, faces [n_faces,3] int32, n_faces >= 1.  Writes
+ *                vertex_normals [n_verts,3] fp64, edge_normals [n_faces,3,3] fp64 and counts [3] int64 (boundary,
+ *                non-manifold, flipped).  The corners are sorted by vertex and the half-edges by two passes (max, then
+ *                min) of the library's stable sort; the lane of every run head walks its run in sorted order and
+ *                writes the sum to every member.  A face index outside [0, n_verts) sets status bit 0, a non-finite
+ *                vertex of a face bit 1; no vertex is read through an unchecked index, and the outputs of such a call
+ *                mean nothing.
+ *   hm_mesh_sign: query [m,3] fp32, and face [m] int32, feature [m] int32, point [m,3] fp32, d2 [m] fp32 as
+ *                hm_mesh_dist_query wrote them for the same mesh; m >= 0 (m = 0 returns at once).  Reads the face's
+ *                indices and vertices from faces / verts.  Writes sd [m] fp32 and, unless NULL, sign [m] int32.  A
+ *                face outside [0, n_faces), a feature outside [0, 3] or a face index outside [0, n_verts) is treated
+ *                as a cut query. */
+HM_API int64_t hm_mesh_topology_workspace_bytes(int64_t n_faces);
+HM_API int hm_mesh_topology_build(const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                                  double *vertex_normals, double *edge_normals, int64_t *counts, void *workspace,
+                                  int64_t workspace_bytes, int32_t *status, void *stream);
+HM_API int hm_mesh_sign(const float *query, int64_t m, const int32_t *face, const int32_t *feature, const float *point,
+                        const float *d2, const float *verts, const int32_t *faces, int64_t n_faces, int64_t n_verts,
+                        const double *vertex_normals, const double *edge_normals, float *sd, int32_t *sign,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
