@@ -92,6 +92,9 @@ SIGNATURES = {
     "hm_gemm_f32_det": (_int, [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _int, _p, _i64, _p]),
     "hm_gemm_f32_group_tn_det_workspace_bytes": (_i64, [_p, _int]),
     "hm_gemm_f32_group_tn_det": (_int, [_p, _int, _p, _i64, _p]),
+    "hm_gemm_f32_group_tn_add": (_int, [_p, _int, _p]),
+    "hm_gemm_f32_group_tn_add_det_workspace_bytes": (_i64, [_p, _int]),
+    "hm_gemm_f32_group_tn_add_det": (_int, [_p, _int, _p, _i64, _p]),
     "hm_colsum_det_workspace_bytes": (_i64, [_i64, _i64]),
     "hm_colsum_det": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p]),
     "hm_colsum_acc_det": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _p]),
@@ -208,6 +211,11 @@ class AdamTensor(C.Structure):
 class GemmGroupItem(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64),
                 ("K", C.c_int64), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64)]
+
+
+class GemmGroupAddItem(C.Structure):
+    _fields_ = GemmGroupItem._fields_ + [("A2", C.c_void_p), ("B2", C.c_void_p), ("lda2", C.c_int64), ("ldb2", C.c_int64),
+                                         ("a_k0", C.c_int64), ("a_k1", C.c_int64), ("b_k0", C.c_int64), ("b_k1", C.c_int64)]
 
 
 class ColsumItem(C.Structure):

@@ -486,6 +486,48 @@ __device__ __forceinline__ void pipe_mask_tail(float4 (&x)[PER], const int (&kli
     }
 }
 
+// Addends of the grouped TN form (gemm_f32_pipe2_group_add_kernel): rows k in [a_k0, a_k1) of A are used as
+// A[k] + A2[k - a_k0], likewise B.  The kernel sees each addend as a buffer descriptor over EXACTLY its rows (nrec bytes
+// from A2 / B2; 0 = no addend) and the row offset of k = 0 relative to it, so that every k-group outside the range -
+// a negative offset is a huge unsigned one - reads zeros and the K loop needs no condition: the trick of the K tail.
+struct GemmAddend {
+    const float *A2, *B2;
+    int32_t lda2, ldb2;      // leading dimensions (floats)
+    int32_t a_k0, b_k0;      // first row of A / B the addend covers (multiples of 4: whole k-groups)
+    int32_t a_k1, b_k1;      // end of the range (== k0: no addend)
+    int32_t nrecA2, nrecB2;  // bytes of the descriptors: 4 * ((k1 - k0 - 1) * ld2 + rows of the tile's dimension)
+};
+
+// one stage's addend k-groups (k the slow dimension: four dwords).  The range check must see the STAGE's offset too, so
+// it is added to the thread's offset on the VALU (one add per operand and stage) and only the k-group's own rows -
+// 0 .. 3 * ld, which never leave a range of whole k-groups - go to the scalar offset.
+template <int PER>
+__device__ __forceinline__ void pipe_fetch_add(const __amdgpu_buffer_rsrc_t &rs, const int (&voff)[PER], int stage_off,
+                                               int ld4, float4 (&x)[PER]) {
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int v = voff[i] + stage_off;
+        x[i] = make_float4(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, v, 0, 0)),
+                           __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, v, ld4, 0)),
+                           __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, v, 2 * ld4, 0)),
+                           __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, v, 3 * ld4, 0)));
+    }
+}
+// operand + addend, one fp32 add per element, where the ring slot goes to LDS (like pipe_mask_tail).  The empty asm
+// statement pins the add to this place: without it hipcc adds each addend in the stage after its fetch - that frees the
+// addend's registers early, and waits vmcnt(0) for loads issued one stage before instead of three.
+template <int PER>
+__device__ __forceinline__ void pipe_add(float4 (&x)[PER], float4 (&q)[PER]) {
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        asm volatile("" : "+v"(q[i].x), "+v"(q[i].y), "+v"(q[i].z), "+v"(q[i].w));
+        x[i].x = __fadd_rn(x[i].x, q[i].x);
+        x[i].y = __fadd_rn(x[i].y, q[i].y);
+        x[i].z = __fadd_rn(x[i].z, q[i].z);
+        x[i].w = __fadd_rn(x[i].w, q[i].w);
+    }
+}
+
 template <int OCT, int AROWS>
 __device__ __forceinline__ void pipe_read_ops(const float *as, const float *bs, int arow, int brow, int h,
                                               float4 (&xa)[OCT], float4 (&xb)[OCT]) {
@@ -511,13 +553,27 @@ __device__ __forceinline__ void pipe_mfma_oct(const float4 &a, const float4 &b, 
 // with one - but exactly 256 of 96 x 64.  The B panel is staged by the first 512 threads.
 // KT: the K range has a tail (see the descriptors below); the k-contiguous operand's k >= K elements are zeroed before
 // they go to LDS.  A separate instantiation, so that the K-whole loop keeps its instructions.
-template <bool AKC, bool BKC, bool EP, int WM = 2, bool PART = false, bool KT = false>
-__device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int by, int bz) {
+// ADD: the operands have addends over row ranges (*ad, see GemmAddend; both operands row-contiguous), fetched into a ring
+// of their own beside the operands' and added when the slot goes to LDS.  Bit 0: A has one, bit 1: B has one - separate
+// instantiations for the same reason, and so that a workgroup whose k part meets only one operand's range (the caller
+// chooses, gemm_group_body) issues only that operand's extra loads.  These instances stage through the launch's DYNAMIC
+// LDS (2 * BK * (BM + BN) floats), which the instances inlined into one kernel share; the others keep their static arrays.
+template <bool AKC, bool BKC, bool EP, int WM = 2, bool PART = false, bool KT = false, int ADD = 0>
+__device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int by, int bz, const GemmAddend *ad = nullptr) {
     constexpr int BM = 32 * WM, BN = 64, BK = kPipeBK, NT = 256 * WM, NTB = 512, PER = BM * BK / 4 / NT, KG = BK / 4,
                   OCT = BK / 8 / 2;   // OCT: octets of a stage per wave group
     static_assert(PER == 1 && BN * BK / 4 / NTB == 1, "one k-group per thread and operand");
-    __shared__ __align__(16) float As[2][BK * BM];
-    __shared__ __align__(16) float Bs[2][BK * BN];
+    __shared__ __align__(16) float As_static[ADD ? 1 : 2][ADD ? 4 : BK * BM];
+    __shared__ __align__(16) float Bs_static[ADD ? 1 : 2][ADD ? 4 : BK * BN];
+    float (*As)[BK * BM], (*Bs)[BK * BN];
+    if constexpr (ADD != 0) {
+        extern __shared__ __align__(16) float hm_pipe_dyn_lds[];
+        As = reinterpret_cast<float (*)[BK * BM]>(hm_pipe_dyn_lds);
+        Bs = reinterpret_cast<float (*)[BK * BN]>(hm_pipe_dyn_lds + 2 * BK * BM);
+    } else {
+        As = As_static;
+        Bs = Bs_static;
+    }
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int kpart = wave / (2 * WM), wsub = wave % (2 * WM);   // two wave groups split the octets of every stage
@@ -558,12 +614,35 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
             klb[i] = g.K - kbeg - (eb % KG) * 4;
         }
     }
-#define HM_PIPE_MASK(S_, RA_, RB_)                                                                  \
+    // ADD: the addends' descriptors and the threads' offsets into them at k = kbeg (negative in front of the range)
+    __amdgpu_buffer_rsrc_t rsA2 = rsA, rsB2 = rsB;
+    int va2[PER], vb2[PER];
+    int sa2 = 0, sb2 = 0, lda24 = 0, ldb24 = 0;
+    if constexpr (ADD != 0) {
+        static_assert(!AKC && !BKC && !KT, "addends are built for the grouped TN form");
+        rsA2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ad->A2), 0, ad->nrecA2, 0x00020000);
+        rsB2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ad->B2), 0, ad->nrecB2, 0x00020000);
+        lda24 = 4 * ad->lda2;
+        ldb24 = 4 * ad->ldb2;
+        sa2 = BK * lda24;
+        sb2 = BK * ldb24;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int e = tid + NT * i;
+            const int eb = (tid % NTB) + NTB * i;
+            const int am = min(m0 + e % BM, g.M - 1), bn = min(n0 + eb % BN, g.N - 1);
+            va2[i] = 4 * ((kbeg + (e / BM) * 4 - ad->a_k0) * ad->lda2 + am);   // (|.| < 2^31: host)
+            vb2[i] = 4 * ((kbeg + (eb / BN) * 4 - ad->b_k0) * ad->ldb2 + bn);
+        }
+    }
+#define HM_PIPE_MASK(S_, N_)                                                                        \
     do {                                                                                            \
         if (KT) {                                                                                   \
-            pipe_mask_tail<AKC, PER>(RA_, kla, (S_) * BK);                                          \
-            pipe_mask_tail<BKC, PER>(RB_, klb, (S_) * BK);                                          \
+            pipe_mask_tail<AKC, PER>(ra##N_, kla, (S_) * BK);                                       \
+            pipe_mask_tail<BKC, PER>(rb##N_, klb, (S_) * BK);                                       \
         }                                                                                           \
+        if constexpr ((ADD & 1) != 0) pipe_add<PER>(ra##N_, qa##N_);                                \
+        if constexpr ((ADD & 2) != 0) pipe_add<PER>(rb##N_, qb##N_);                                \
     } while (0)
     const bool stage_b = NT == NTB || tid < NTB;
     const int sa = 4 * (AKC ? BK : BK * (int)g.lda), sb = 4 * (BKC ? BK : BK * (int)g.ldb);   // bytes per stage
@@ -575,17 +654,20 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
     // the unrolled loop was demoted to scratch memory by hipcc)
     static_assert(kPipeD == 4, "the stage macro below is written out for a 4-deep ring (8-deep measured no faster)");
     float4 ra0[PER], ra1[PER], ra2[PER], ra3[PER], rb0[PER], rb1[PER], rb2[PER], rb3[PER];
+    float4 qa0[PER], qa1[PER], qa2[PER], qa3[PER], qb0[PER], qb1[PER], qb2[PER], qb3[PER];   // ADD: the addends' ring
     float4 opa0[OCT], opa1[OCT], opb0[OCT], opb1[OCT];
-#define HM_PIPE_FETCH(S_, RA_, RB_)                                                                 \
+#define HM_PIPE_FETCH(S_, F_)                                                                       \
     do {                                                                                            \
         const int sc_ = min((S_), stages - 1); /* past the end: re-read the last stage, never multiplied */ \
-        pipe_fetch_buf<AKC, PER>(rsA, va, sc_ * sa, lda4, RA_);                                     \
-        pipe_fetch_buf<BKC, PER>(rsB, vb, sc_ * sb, ldb4, RB_);                                     \
+        pipe_fetch_buf<AKC, PER>(rsA, va, sc_ * sa, lda4, ra##F_);                                  \
+        pipe_fetch_buf<BKC, PER>(rsB, vb, sc_ * sb, ldb4, rb##F_);                                  \
+        if constexpr ((ADD & 1) != 0) pipe_fetch_add<PER>(rsA2, va2, sc_ * sa2, lda24, qa##F_);     \
+        if constexpr ((ADD & 2) != 0) pipe_fetch_add<PER>(rsB2, vb2, sc_ * sb2, ldb24, qb##F_);     \
     } while (0)
-    HM_PIPE_FETCH(0, ra0, rb0);
-    HM_PIPE_FETCH(1, ra1, rb1);
-    HM_PIPE_FETCH(2, ra2, rb2);
-    HM_PIPE_MASK(0, ra0, rb0);
+    HM_PIPE_FETCH(0, 0);
+    HM_PIPE_FETCH(1, 1);
+    HM_PIPE_FETCH(2, 2);
+    HM_PIPE_MASK(0, 0);
     store_tile<BM, BK, NT>(As[0], AKC, tid, ra0);
     if (stage_b) store_tile<BN, BK, NTB>(Bs[0], BKC, tid, rb0);
     __syncthreads();
@@ -595,9 +677,9 @@ __device__ __forceinline__ void gemm_pipe2_body(const GemmArgs &g, int bx, int b
 // s+1) through LDS buffer NB into operand set X
 #define HM_PIPE_STAGE(S_, F_, N_, C_, X_, NB_)                                                      \
     do {                                                                                            \
-        HM_PIPE_FETCH((S_) + kPipeD - 1, ra##F_, rb##F_);                                                    \
+        HM_PIPE_FETCH((S_) + kPipeD - 1, F_);                                                       \
         pipe_mfma_oct(opa##C_[0], opb##C_[0], acc);                                                 \
-        HM_PIPE_MASK((S_) + 1, ra##N_, rb##N_);                                                     \
+        HM_PIPE_MASK((S_) + 1, N_);                                                                 \
         store_tile<BM, BK, NT>(As[NB_], AKC, tid, ra##N_);                                          \
         if (stage_b) store_tile<BN, BK, NTB>(Bs[NB_], BKC, tid, rb##N_);                            \
         HM_GEMM_LOOP_BARRIER();                                                                     \
@@ -712,8 +794,13 @@ struct GemmGroupTable {
 };
 // PART: deterministic form - every problem's E.C is its workspace slab base (E.ldc = N), partials go there with plain
 // stores and gemm_part_reduce_kernel adds them to the real C in k-part order.
-template <bool PART>
-__device__ __forceinline__ void gemm_group_body(const GemmGroupTable &t) {
+// the grouped form with addends: the same table plus one GemmAddend per problem
+struct GemmGroupAddTable {
+    GemmGroupTable t;
+    GemmAddend ad[HM_GEMM_GROUP_MAX];
+};
+template <bool PART, bool ADD = false>
+__device__ __forceinline__ void gemm_group_body(const GemmGroupTable &t, const GemmAddend *ads = nullptr) {
     int p = 0;
     while (p + 1 < t.n && (int)blockIdx.x >= t.start[p + 1]) ++p;       // (uniform: <= 16 problems)
     const GemmGroupEntry &E = t.e[p];
@@ -732,13 +819,32 @@ __device__ __forceinline__ void gemm_group_body(const GemmGroupTable &t) {
     g.vec_out = 0;   // (atomics, or the slabs of the deterministic form: dword stores)
     g.nrecA = g.nrecB = 0x7fffffff;
     g.ep.mode = HM_EPI_NONE;
-    gemm_pipe2_body<false, false, false, 2, PART>(g, bx, by, bz);
+    if constexpr (ADD) {
+        // which addend can this workgroup's k part meet?  Uniform, decided in front of the K loop: on the training step
+        // A's range (z-bar rows) and B's (v-bar rows) lie in different k parts, so a workgroup fetches one of them
+        const GemmAddend &D = ads[p];
+        const int kbeg = bz * E.k_chunk, kend = kbeg + E.k_chunk;
+        const bool oa = D.a_k0 < kend && D.a_k1 > kbeg, ob = D.b_k0 < kend && D.b_k1 > kbeg;
+        if (oa && ob)
+            gemm_pipe2_body<false, false, false, 2, PART, false, 3>(g, bx, by, bz, &D);
+        else if (ob)
+            gemm_pipe2_body<false, false, false, 2, PART, false, 2>(g, bx, by, bz, &D);
+        else   // (neither: A's descriptor is empty or never met - zeros)
+            gemm_pipe2_body<false, false, false, 2, PART, false, 1>(g, bx, by, bz, &D);
+    } else
+        gemm_pipe2_body<false, false, false, 2, PART>(g, bx, by, bz);
 }
 __global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_kernel(GemmGroupTable t) {
     gemm_group_body<false>(t);
 }
 __global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_part_kernel(GemmGroupTable t) {
     gemm_group_body<true>(t);
+}
+__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_add_kernel(GemmGroupAddTable t) {
+    gemm_group_body<false, true>(t.t, t.ad);
+}
+__global__ __launch_bounds__(512, 4) void gemm_f32_pipe2_group_add_part_kernel(GemmGroupAddTable t) {
+    gemm_group_body<true, true>(t.t, t.ad);
 }
 
 // Deterministic split-K, second pass: C = C_old + (((p0 + p1) + p2) + ...) (accumulate) or C = ((p0 + p1) + ...),
@@ -778,6 +884,7 @@ __global__ __launch_bounds__(256) void zero_window_kernel(float *C, int64_t ldc,
     C[m * ldc + n] = 0.0f;
 }
 
+constexpr unsigned kGroupAddLds = 4 * 2 * kPipeBK * (64 + 64);   // dynamic LDS of the grouped addend kernels (bytes)
 constexpr int64_t kSplitTarget = 512;   // split-K: workgroups to aim for when the tile grid alone leaves the chip idle
 
 }  // namespace
@@ -1031,6 +1138,8 @@ int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t K, con
                      static_cast<float *>(workspace), workspace_bytes);
 }
 
+}  // extern "C"
+
 // The grouped calls: ONE routine builds the problem table, so that the deterministic mode sums the partials of the very
 // k parts the default mode adds with atomics.  Default (det = false): every table of up to HM_GEMM_GROUP_MAX problems
 // is one gemm_f32_pipe2_group_kernel launch that adds into the callers' C (overlapping C windows are fine: atomics).
@@ -1038,20 +1147,26 @@ int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t K, con
 // problems of the table.  With run = false only the workspace need is computed
 // (hm_gemm_f32_group_tn_det_workspace_bytes): the largest table's slabs, or the largest need of a problem that goes
 // alone - the launches of a call follow each other on one stream, so they share the buffer.  who: the entry point.
-static int group_tn(const char *who, const hm_gemm_group_item *items, int n_items, bool det, float *ws, int64_t ws_bytes,
+// Item = hm_gemm_group_add_item: the same routine for items with addends (hm_gemm_f32_group_tn_add*); a table in which
+// some problem has a non-empty addend range goes to the kernels' addend instances, every other table to the plain ones.
+template <class Item>
+static int group_tn(const char *who, const Item *items, int n_items, bool det, float *ws, int64_t ws_bytes,
                     void *stream, bool run, int64_t *need) {
+    constexpr bool ADD = std::is_same<Item, hm_gemm_group_add_item>::value;
     HM_CHECK_ARG(n_items >= 0 && (n_items == 0 || items), std::string(who) + ": bad argument");
     *need = 0;
     // byte window of a problem's C: the reduce kernel gives every C element ONE thread, so two problems of one table
     // must not overlap - a problem that overlaps one already in the table starts the next table (the two sums are then
     // added in item order, by two launches)
-    auto window = [](const hm_gemm_group_item &it, uintptr_t &w0, uintptr_t &w1) {
+    auto window = [](const Item &it, uintptr_t &w0, uintptr_t &w1) {
         w0 = reinterpret_cast<uintptr_t>(it.C);
         w1 = w0 + 4 * ((it.M - 1) * it.ldc + it.N);
     };
     int in_table[HM_GEMM_GROUP_MAX];   // item index of every table entry
-    GemmGroupTable t;
+    GemmGroupAddTable ta;   // (ta.ad is used by the addend form only)
+    GemmGroupTable &t = ta.t;
     GemmReduceTable r;
+    bool table_adds = false;   // some problem of the current table has a non-empty addend range
     int64_t off = 0;   // floats of workspace the current table uses (deterministic)
     t.n = r.n = 0;
     t.start[0] = 0;
@@ -1064,13 +1179,19 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
                 HM_CHECK_ARG(ws != nullptr && ws_bytes >= 4 * off, std::string(who) + ": workspace too small");
                 for (int p = 0; p < t.n; ++p) t.e[p].C = ws + reinterpret_cast<uintptr_t>(t.e[p].C);   // slab offsets -> pointers
                 for (int p = 0; p < r.n; ++p) r.e[p].P = ws + reinterpret_cast<uintptr_t>(r.e[p].P);
-                hipLaunchKernelGGL(gemm_f32_pipe2_group_part_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
+                if (table_adds)
+                    hipLaunchKernelGGL(gemm_f32_pipe2_group_add_part_kernel, dim3((unsigned)t.start[t.n]), dim3(512), kGroupAddLds, st, ta);
+                else
+                    hipLaunchKernelGGL(gemm_f32_pipe2_group_part_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
                 const int rc = launch_part_reduce(r, st);
                 if (rc != HM_OK) return rc;
-            } else
+            } else if (table_adds)
+                hipLaunchKernelGGL(gemm_f32_pipe2_group_add_kernel, dim3((unsigned)t.start[t.n]), dim3(512), kGroupAddLds, st, ta);
+            else
                 hipLaunchKernelGGL(gemm_f32_pipe2_group_kernel, dim3((unsigned)t.start[t.n]), dim3(512), 0, st, t);
             HM_CHECK_LAUNCH(who);
         }
+        table_adds = false;
         t.n = r.n = 0;
         t.start[0] = 0;
         r.end = 0;
@@ -1078,7 +1199,7 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
         return HM_OK;
     };
     // deterministic: does the problem's C window overlap one of a problem waiting in the table?
-    auto overlaps_table = [&](const hm_gemm_group_item &it) {
+    auto overlaps_table = [&](const Item &it) {
         for (int p = 0; det && p < t.n; ++p) {
             uintptr_t a0, a1, b0, b1;
             window(it, a0, a1);
@@ -1088,13 +1209,29 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
         return false;
     };
     for (int i = 0; i < n_items; ++i) {
-        const hm_gemm_group_item &it = items[i];
+        const Item &it = items[i];
         HM_CHECK_ARG(it.M >= 0 && it.N >= 0 && it.K >= 0 && it.M < (1ll << 31) && it.N < (1ll << 31) && it.K < (1ll << 31),
                      std::string(who) + ": bad dimension");
         if (it.M == 0 || it.N == 0 || it.K == 0) continue;
         HM_CHECK_ARG(!run || (it.A && it.B && it.C && it.lda >= it.M && it.ldb >= it.N && it.ldc >= it.N),
                      std::string(who) + ": NULL operand or leading dimension");
-        if (it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31)) {
+        const bool grouped = !(it.K % (kPipeBK * kPipeD) != 0 || 4 * it.lda * it.K >= (1ll << 31) || 4 * it.ldb * it.K >= (1ll << 31));
+        bool add_a = false, add_b = false;
+        if constexpr (ADD) {
+            HM_CHECK_ARG(it.a_k0 >= 0 && it.a_k0 <= it.a_k1 && it.a_k1 <= it.K && it.b_k0 >= 0 && it.b_k0 <= it.b_k1 &&
+                         it.b_k1 <= it.K, std::string(who) + ": addend range outside [0, K]");
+            add_a = it.a_k1 > it.a_k0;
+            add_b = it.b_k1 > it.b_k0;
+            // an addend runs in the grouped kernel only, over whole k-groups and with 32-bit offsets (the caller pre-adds
+            // what does not qualify: ops.gemm_group_tn_add)
+            auto ok = [&](bool on, const float *P2, int64_t ld2, int64_t rows, int64_t k0, int64_t k1) {
+                return !on || (grouped && (!run || P2) && ld2 >= rows && k0 % 4 == 0 && k1 % 4 == 0 && 4 * ld2 * it.K < (1ll << 31));
+            };
+            HM_CHECK_ARG(ok(add_a, it.A2, it.lda2, it.M, it.a_k0, it.a_k1) && ok(add_b, it.B2, it.ldb2, it.N, it.b_k0, it.b_k1),
+                         std::string(who) + ": addend on an item the grouped kernel does not take, range no multiple of 4, or "
+                                            "leading dimension");
+        }
+        if (!grouped) {
             // no K tail in the pipelined kernel, 32-bit operand offsets: such a problem goes alone, at once - so the
             // table goes first when this problem adds into the C of a problem waiting in it (item order)
             if (overlaps_table(it)) {
@@ -1131,6 +1268,21 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
         E.tiles_n = (int32_t)((it.N + 63) / 64);
         E.split = (int32_t)split;
         E.k_chunk = (int32_t)(it.K / split);
+        if constexpr (ADD) {
+            // no addend: an empty descriptor on the operand itself - every read through it returns zero
+            GemmAddend &D = ta.ad[t.n];
+            D.A2 = add_a ? it.A2 : it.A;
+            D.B2 = add_b ? it.B2 : it.B;
+            D.lda2 = add_a ? (int32_t)it.lda2 : 0;
+            D.ldb2 = add_b ? (int32_t)it.ldb2 : 0;
+            D.a_k0 = add_a ? (int32_t)it.a_k0 : 0;
+            D.b_k0 = add_b ? (int32_t)it.b_k0 : 0;
+            D.a_k1 = add_a ? (int32_t)it.a_k1 : 0;
+            D.b_k1 = add_b ? (int32_t)it.b_k1 : 0;
+            D.nrecA2 = add_a ? (int32_t)(4 * ((it.a_k1 - it.a_k0 - 1) * it.lda2 + it.M)) : 0;
+            D.nrecB2 = add_b ? (int32_t)(4 * ((it.b_k1 - it.b_k0 - 1) * it.ldb2 + it.N)) : 0;
+            table_adds = table_adds || add_a || add_b;
+        }
         t.start[t.n + 1] = t.start[t.n] + E.tiles_m * E.tiles_n * E.split;
         ++t.n;
         if (det) {
@@ -1143,6 +1295,8 @@ static int group_tn(const char *who, const hm_gemm_group_item *items, int n_item
     }
     return flush();
 }
+
+extern "C" {
 
 int hm_gemm_f32_group_tn(const hm_gemm_group_item *items, int n_items, void *stream) {
     int64_t need = 0;
@@ -1159,6 +1313,24 @@ int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void 
                              void *stream) {
     int64_t need = 0;
     return group_tn("hm_gemm_f32_group_tn_det", items, n_items, true, static_cast<float *>(workspace), workspace_bytes,
+                    stream, true, &need);
+}
+
+int hm_gemm_f32_group_tn_add(const hm_gemm_group_add_item *items, int n_items, void *stream) {
+    int64_t need = 0;
+    return group_tn("hm_gemm_f32_group_tn_add", items, n_items, false, nullptr, 0, stream, true, &need);
+}
+
+int64_t hm_gemm_f32_group_tn_add_det_workspace_bytes(const hm_gemm_group_add_item *items, int n_items) {
+    int64_t need = 0;
+    if (group_tn("hm_gemm_f32_group_tn_add_det", items, n_items, true, nullptr, 0, nullptr, false, &need) != HM_OK) return -1;
+    return need;
+}
+
+int hm_gemm_f32_group_tn_add_det(const hm_gemm_group_add_item *items, int n_items, void *workspace, int64_t workspace_bytes,
+                                 void *stream) {
+    int64_t need = 0;
+    return group_tn("hm_gemm_f32_group_tn_add_det", items, n_items, true, static_cast<float *>(workspace), workspace_bytes,
                     stream, true, &need);
 }
 

@@ -24,7 +24,7 @@ import torch
 
 from . import ops
 from .ops import (EPI_ADJOINT, EPI_RELU, EPI_RELUMASK, EPI_S1MUL, EPI_SOFTPLUS, _softplus_call, colsum_into_multi, gemm,
-                  gemm_ep, gemm_group_tn)
+                  gemm_ep, gemm_group_tn, gemm_group_tn_add)
 
 _SQRT2 = math.sqrt(2.0)
 
@@ -96,7 +96,8 @@ class _SdfMlp(torch.autograd.Function):
         ctx.shared = cache_out        # (weight / bias gradient accumulators shared with a _SdfMlpRows node, see there)
         if cache_out is not None:     # lets a second node over a ROW RANGE of this batch skip its forward (_SdfMlpRows)
             cache_out.update(meta=ctx.meta, out=out, g_e=g_e, sdf=sdf, c=c, denom=denom, a_list=a_list, z_list=z_list,
-                             v_list=v_list, Ws=Ws)
+                             v_list=v_list, Ws=Ws,
+                             need=(tuple(ctx.needs_input_grad[6:6 + L]), tuple(ctx.needs_input_grad[6 + L:6 + 2 * L])))
         return out, g_e
 
     @staticmethod
@@ -109,7 +110,7 @@ class _SdfMlp(torch.autograd.Function):
         return (grads[0], None, None, None, None, None, *grads[1:])
 
 
-def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shared=None, owner=True):
+def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shared=None, owner=True, rows=None):
     """Analytic reverse-over-reverse of the forward sweep and the gradient sweep (see the module docstring).
     stack: the forward's [2N, in_l] buffers (weight gradients as ONE stacked product per layer), or None (a node that
     reuses another node's saved activations, _SdfMlpRows: u^T v-bar and z-bar^T a are two entries of the grouped launch).
@@ -117,7 +118,14 @@ def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shar
     weight / bias gradients into ONE set of buffers kept in the dict `shared`: the companion (owner = False; its
     backward always runs first - its input depends on the owner's output) allocates and zeroes them and returns no
     weight gradients, the owner adds its own share and returns the sums - autograd then has nothing to add up (18
-    elementwise launches per step) and the buffers are zeroed once."""
+    elementwise launches per step) and the buffers are zeroed once.
+    rows = (row0, n), companion only: merge its hidden layers' weight-gradient products into the owner's.  Both nodes
+    multiply the same saved u_l and a_l of rows [row0, row0 + n) by their own cotangents, and
+        [u; z-bar_o]^T [v-bar_o; a]  +  u[rows]^T v-bar_c + z-bar_c^T a[rows]
+            =  [u; z-bar_o + pad(z-bar_c)]^T [v-bar_o + pad(v-bar_c); a],
+    so the companion appends no product for such a layer, asks for no u_l, and leaves v-bar_c and z-bar_c in
+    shared["row_cot"]; the owner's stacked product takes them as addends of its operands' row ranges
+    (ops.gemm_group_tn_add).  Only when both nodes want the same gradients (the sets the accumulators are shared on)."""
     L, skip_layer, beta_sp, thr_sp, E = meta
     e, sdf, c, denom = sv[0], sv[1], sv[2], sv[3]
     Ws = sv[4:4 + L]
@@ -145,6 +153,11 @@ def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shar
                     dW[l].add_(acc[0][l])
                 if db[l] is not None and acc[1][l] is not None:
                     db[l].add_(acc[1][l])
+    needs = (tuple(bool(w) for w in need_w), tuple(bool(b) for b in need_b))
+    merge = (rows is not None and shared is not None and not owner and d_ge is not None
+             and tuple(tuple(bool(x) for x in t) for t in shared.get("need", ((), ()))) == needs)
+    cot = {}              # companion, merged layers: l -> [v-bar_c, z-bar_c]
+    pend = shared.pop("row_cot", None) if (shared is not None and owner) else None
     zx = [None] * L       # extra z-bar from the adjoint of the gradient sweep
     ustack = [None] * L   # [u_l; z-bar_l] of the layers whose weight gradient is one stacked GEMM
     cb = None
@@ -171,6 +184,9 @@ def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shar
                 nxt = l + 1
                 dst = stack[nxt][:N] if (use_stack and nxt < L - 1 and nxt != skip_layer and need_w[nxt]) else None
                 loose = (not stacked) and bool(need_w[l])    # u_l as a tensor of its own: u^T v-bar joins the grouped launch
+                if loose and merge:
+                    cot[l] = [vb, None]                      # ... or v-bar_c joins the owner's stacked product
+                    loose = False
                 vb_h, zx[l], u_l = gemm_ep(vb, Ws[l], None, False, True, EPI_ADJOINT, beta_sp, thr_sp,
                                            z=z_list[l], g=v_list[l + 1], out1=dst,
                                            out3=ustack[l][:N] if stacked else None, want_out3=loose)
@@ -191,8 +207,14 @@ def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shar
     de = None
     for l in range(L - 1, -1, -1):
         if need_w[l]:
-            if ustack[l] is not None:                        # zb IS ustack[l][N:] (written by layer l+1 below)
-                wgrad.append((ustack[l], stack[l], dW[l]))                                  # [u; z-bar]^T [v-bar; a]
+            if l in cot:
+                cot[l][1] = zb                               # the owner's product adds it to its z-bar rows
+            elif ustack[l] is not None:                      # zb IS ustack[l][N:] (written by layer l+1 below)
+                if pend is not None and l in pend[2]:
+                    row0, n, (vb_c, zb_c) = pend[0], pend[1], pend[2].pop(l)
+                    wgrad.append((ustack[l], stack[l], dW[l], (zb_c, N + row0), (vb_c, row0)))
+                else:
+                    wgrad.append((ustack[l], stack[l], dW[l]))                              # [u; z-bar]^T [v-bar; a]
             else:
                 wgrad.append((zb, a_list[l], dW[l]))
         if need_b[l]:
@@ -210,9 +232,16 @@ def _sdf_mlp_backward(meta, sv, stack, need_e, need_w, need_b, d_out, d_ge, shar
         else:
             ab = gemm(zb, Ws[l], None, False, False)
             de = ab if de is None else de + ab
-    gemm_group_tn(wgrad)
+    if pend is not None and pend[2]:
+        raise RuntimeError("hashmod: a _SdfMlpRows node left cotangents for weight gradients this pass does not form")
+    if any(len(w) == 5 for w in wgrad):
+        gemm_group_tn_add([w if len(w) == 5 else (*w, None, None) for w in wgrad])
+    else:
+        gemm_group_tn(wgrad)
     colsum_into_multi(bgrad)
     d_e = de if need_e else None
+    if cot:
+        shared["row_cot"] = (rows[0], rows[1], cot)
     if shared is not None and not owner:
         # hand the sums to the owner's backward pass; autograd sees no weight gradient from this node
         shared["wgrad_acc"] = (dW, db, (tuple(bool(w) for w in need_w), tuple(bool(b) for b in need_b)))
@@ -229,7 +258,7 @@ class _SdfMlpRows(torch.autograd.Function):
     the second evaluation's 17 forward GEMMs disappear, its gradient flow (through its own embedding e2) is unchanged."""
 
     @staticmethod
-    def forward(ctx, e2, cache, row0, n, *params):
+    def forward(ctx, e2, cache, row0, n, merge_wgrad, *params):
         L = cache["meta"][0]
         sl = slice(int(row0), int(row0) + int(n))
         cp = lambda t: ops.dcopy_(torch.empty_like(t), t)    # noqa: E731  (kernel copy: no MEMCPY graph node)
@@ -237,6 +266,7 @@ class _SdfMlpRows(torch.autograd.Function):
         g_e = cp(cache["g_e"][sl])
         ctx.meta = cache["meta"]
         ctx.shared = cache            # weight / bias gradients are accumulated with the owner's (_sdf_mlp_backward)
+        ctx.rows = (int(row0), int(n)) if merge_wgrad else None
         Ws = params[:L]
         if any(w.data_ptr() != cw.data_ptr() for w, cw in zip(Ws, cache["Ws"])):
             raise RuntimeError("hashmod: _SdfMlpRows must see the weights of the evaluation it reuses")
@@ -250,9 +280,9 @@ class _SdfMlpRows(torch.autograd.Function):
     def backward(ctx, d_out, d_ge):
         L = ctx.meta[0]
         grads = _sdf_mlp_backward(ctx.meta, ctx.saved_tensors, None, ctx.needs_input_grad[0],
-                                  ctx.needs_input_grad[4:4 + L], ctx.needs_input_grad[4 + L:4 + 2 * L], d_out, d_ge,
-                                  shared=ctx.shared, owner=False)
-        return (grads[0], None, None, None, *grads[1:])
+                                  ctx.needs_input_grad[5:5 + L], ctx.needs_input_grad[5 + L:5 + 2 * L], d_out, d_ge,
+                                  shared=ctx.shared, owner=False, rows=ctx.rows)
+        return (grads[0], None, None, None, None, *grads[1:])
 
 
 def sdf_mlp(e, weights, biases, skip_layer, beta_sp, thr_sp, beta_rho, cache_out=None):
@@ -263,13 +293,14 @@ def sdf_mlp(e, weights, biases, skip_layer, beta_sp, thr_sp, beta_rho, cache_out
                          *weights, *biases)
 
 
-def sdf_mlp_rows(e2, cache, row0, n, weights, biases):
+def sdf_mlp_rows(e2, cache, row0, n, weights, biases, merge_wgrad=True):
     """the same pair for rows [row0, row0 + n) of the batch `cache` was filled by (same weights, e2 == that batch's
-    embedding rows in value): no forward work, own backward (through e2)."""
+    embedding rows in value): no forward work, own backward (through e2).  merge_wgrad: the hidden layers' weight
+    gradients of this node are formed inside the other node's products (_sdf_mlp_backward); False: products of their own."""
     ops.require_gpu(e2)
     if e2.shape[0] != n or row0 < 0 or row0 + n > cache["out"].shape[0]:
         raise ValueError("hashmod sdf_mlp_rows: row range does not match")
-    return _SdfMlpRows.apply(e2.contiguous(), cache, int(row0), int(n), *weights, *biases)
+    return _SdfMlpRows.apply(e2.contiguous(), cache, int(row0), int(n), bool(merge_wgrad), *weights, *biases)
 
 
 class _ReluMlp(torch.autograd.Function):

@@ -109,6 +109,14 @@ class ImplicitNetwork(nn.Module):
         for p in self.parameters():
             p.requires_grad = True
         self.use_fused_mlp_grad = True
+        # forward_with_gradient(reuse=...): the row node's hidden-layer weight gradients are formed inside the products of
+        # the evaluation it reuses (mlp_grad._sdf_mlp_backward); False: two products of its own per layer (A/B, tests).
+        # Restriction: the row node decides alone (same gradient sets on both nodes) and then relies on the evaluation's
+        # backward pass running after its own in the same backward - as the shared accumulators already do - and
+        # forming the stacked products; a pass that does not (it cannot happen through autograd, which materialises
+        # both incoming gradients) raises instead of dropping the row node's share.  The cotangents live in the
+        # per-forward cache dict until that pass takes them, or until the graph of the forward is freed.
+        self.merge_row_wgrad = True
         self._packed = None
         self._packed_key = None
         self._force_repack = False
@@ -283,7 +291,8 @@ class ImplicitNetwork(nn.Module):
             bs = [lin.bias for lin in lins]
             skip = self.skip_in[0] if self.skip_in else -1
             if reuse is not None and reuse[0]:
-                out, g_e = mlp_grad.sdf_mlp_rows(e, reuse[0], reuse[1], reuse[2], Ws, bs)
+                out, g_e = mlp_grad.sdf_mlp_rows(e, reuse[0], reuse[1], reuse[2], Ws, bs,
+                                                 merge_wgrad=self.merge_row_wgrad)
             else:
                 out, g_e = mlp_grad.sdf_mlp(e, Ws, bs, skip, self.softplus.beta, self.softplus.threshold,
                                             self._beta_value(), cache_out=cache_out)

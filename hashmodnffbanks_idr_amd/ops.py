@@ -445,6 +445,64 @@ def gemm_group_tn(problems):
     check(lib().hm_gemm_f32_group_tn(C.cast(items, C.c_void_p), len(problems), stream_ptr(problems[0][0])))
 
 
+def _group_tn_takes(K, lda, ldb):
+    """does the grouped kernel take a problem (else hm_gemm_f32 runs it)?  The rule of group_tn in csrc/hm_gemm.hip,
+    pinned to the library by tests/test_gemm_group_add_cpu.py."""
+    return K % 128 == 0 and 4 * lda * K < 2 ** 31 and 4 * ldb * K < 2 ** 31
+
+
+def gemm_group_tn_add(problems):
+    """gemm_group_tn over operands with ADDENDS: every problem is (A [K, M], B [K, N], C [M, N], a_add, b_add) with
+    a_add = None or (A2 [rows, M], k0): rows [k0, k0 + rows) of A are used as A[k] + A2[k - k0] (one fp32 add per
+    element); b_add likewise for B.  The sum is formed where the grouped kernel stages its operands
+    (hm_gemm_f32_group_tn_add), so the products of two autograd nodes over the same saved rows cost one.  An addend the
+    kernel does not take - a range that is no multiple of 4, a non-unit column stride, a problem that runs on the plain
+    GEMM (K no multiple of 128, operands of 2 GB) - is added to a copy of its operand beforehand: the same values (and,
+    in deterministic mode, the same bits) from the existing paths."""
+    if not problems:
+        return
+    items = (_lib.GemmGroupAddItem * len(problems))()
+    keep = []
+    for i, (a, b, c, a_add, b_add) in enumerate(problems):
+        require_gpu(a, b, c)
+        a, b = _rowmajor(a), _rowmajor(b)
+        if c.stride(-1) != 1 or a.dtype != torch.float32 or b.dtype != torch.float32 or c.dtype != torch.float32:
+            raise ValueError("hashmod gemm_group_tn_add: fp32 row-major operands expected")
+        K, M = a.shape
+        Kb, N = b.shape
+        if K != Kb or tuple(c.shape) != (M, N):
+            raise ValueError(f"hashmod gemm_group_tn_add: shapes {tuple(a.shape)}^T @ {tuple(b.shape)} -> {tuple(c.shape)}")
+        grouped = _group_tn_takes(K, _ld(a), _ld(b))
+
+        def addend(x, add):
+            """(operand, addend or None, ld2, k0, k1): the addend as the kernel takes it, or added beforehand"""
+            if add is None or add[0].shape[0] == 0:
+                return x, None, 0, 0, 0
+            x2, k0 = add
+            require_gpu(x2)
+            k0, rows = int(k0), x2.shape[0]
+            if x2.dtype != torch.float32 or x2.dim() != 2 or x2.shape[1] != x.shape[1] or k0 < 0 or k0 + rows > K:
+                raise ValueError(f"hashmod gemm_group_tn_add: addend {tuple(x2.shape)} at row {k0} of {tuple(x.shape)}")
+            if grouped and k0 % 4 == 0 and rows % 4 == 0 and x2.stride(1) == 1 and 4 * _ld(x2) * K < 2 ** 31:
+                return x, x2, _ld(x2), k0, k0 + rows
+            x = x.clone()
+            x[k0:k0 + rows] += x2
+            return x, None, 0, 0, 0
+
+        a, a2, lda2, a_k0, a_k1 = addend(a, a_add)
+        b, b2, ldb2, b_k0, b_k1 = addend(b, b_add)
+        keep += [a, b, a2, b2]
+        items[i] = _lib.GemmGroupAddItem(a.data_ptr(), b.data_ptr(), c.data_ptr(), M, N, K, _ld(a), _ld(b), _ld(c),
+                                         dptr(a2), dptr(b2), lda2, ldb2, a_k0, a_k1, b_k0, b_k1)
+    dev = problems[0][0]
+    if is_deterministic():
+        need = check(lib().hm_gemm_f32_group_tn_add_det_workspace_bytes(C.cast(items, C.c_void_p), len(problems)))
+        ws, nb = _det_workspace(dev.device, need)
+        check(lib().hm_gemm_f32_group_tn_add_det(C.cast(items, C.c_void_p), len(problems), ws, nb, stream_ptr(dev)))
+        return
+    check(lib().hm_gemm_f32_group_tn_add(C.cast(items, C.c_void_p), len(problems), stream_ptr(dev)))
+
+
 EPI_SOFTPLUS, EPI_S1MUL, EPI_ADJOINT, EPI_RELU, EPI_RELUMASK = 1, 2, 3, 4, 5
 
 

@@ -662,6 +662,27 @@ HM_API int hm_gemm_f32_det(int transA, int transB, int64_t M, int64_t N, int64_t
 HM_API int64_t hm_gemm_f32_group_tn_det_workspace_bytes(const hm_gemm_group_item *items, int n_items);
 HM_API int hm_gemm_f32_group_tn_det(const hm_gemm_group_item *items, int n_items, void *workspace,
                                     int64_t workspace_bytes, void *stream);
+/* The grouped product over operands with ADDENDS on a row range each: rows k in [a_k0, a_k1) of A are used as
+ * A[k] + A2[k - a_k0] (A2 [a_k1 - a_k0, M], leading dimension lda2), rows [b_k0, b_k1) of B as B[k] + B2[k - b_k0] -
+ * one fp32 add per element, formed where the kernel stages its operands, so the sum of two products over the same rows
+ * (the weight gradients of two autograd nodes over shared activations) costs one.  An empty range (k0 == k1) is no
+ * addend; A2 / B2 are then not read.  Everything else - tables, k parts, fall-back of an item to hm_gemm_f32, overlapping
+ * C windows, the deterministic forms and their workspace - is hm_gemm_f32_group_tn's and hm_gemm_f32_group_tn_det's: a
+ * call gives the values (deterministic: the bits) of that entry point on operands added beforehand.  A non-empty range
+ * needs both ends multiples of 4, lda2 >= M (ldb2 >= N), 4 * ld2 * K < 2^31 and an item the grouped kernel takes (K a
+ * multiple of 128, operands below 2 GB); otherwise the call fails with HM_ERR_INVALID at that item
+ * (ops.gemm_group_tn_add adds such an addend beforehand).                                                          */
+typedef struct hm_gemm_group_add_item {
+    const float *A, *B;
+    float *C;
+    int64_t M, N, K, lda, ldb, ldc;
+    const float *A2, *B2;
+    int64_t lda2, ldb2, a_k0, a_k1, b_k0, b_k1;
+} hm_gemm_group_add_item;
+HM_API int hm_gemm_f32_group_tn_add(const hm_gemm_group_add_item *items, int n_items, void *stream);
+HM_API int64_t hm_gemm_f32_group_tn_add_det_workspace_bytes(const hm_gemm_group_add_item *items, int n_items);
+HM_API int hm_gemm_f32_group_tn_add_det(const hm_gemm_group_add_item *items, int n_items, void *workspace,
+                                        int64_t workspace_bytes, void *stream);
 /* hm_colsum / hm_colsum_acc / hm_colsum_acc_multi (nn.Linear bias gradients): slab partials to the workspace, then
  * summed per column in slab order - two launches per call (per HM_COLSUM_MAX_ITEMS items for the list form).       */
 HM_API int64_t hm_colsum_det_workspace_bytes(int64_t M, int64_t N);
