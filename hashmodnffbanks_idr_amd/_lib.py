@@ -181,6 +181,9 @@ SIGNATURES = {
     "hm_mesh_topology_workspace_bytes": (_i64, [_i64]),
     "hm_mesh_topology_build": (_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _p]),
     "hm_mesh_sign": (_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    # a per-face texture atlas: the texels' points on the faces, and the sampler from (face, weights) back to texels
+    "hm_mesh_texture_points": (_int, [_p, _p, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "hm_mesh_texture_sample": (_int, [_p, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p]),
 }
 
 

@@ -12,22 +12,13 @@
 // range check: the taps come from floor(u), floor(v) of a vertex whose pixel rint(u), rint(v) is in the image, so they
 // are in [-1, W - 1] x [-1, H - 1] before the clamp.
 #include "hm_block_dev.h"
+#include "hm_color_dev.h"
 #include "hm_view_dev.h"
 
 namespace {
 
 constexpr int kVT = 256;
 constexpr int kColorMaxPower = 8;
-
-// ((ax bx) + (ay by)) + (az bz)
-__device__ __forceinline__ double color_dot(double ax, double ay, double az, double bx, double by, double bz) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(ax, bx), __dmul_rn(ay, by)), __dmul_rn(az, bz));
-}
-
-// (a (1 - f)) + (b f)
-__device__ __forceinline__ double color_lerp(double a, double b, double f) {
-    return __dadd_rn(__dmul_rn(a, __dsub_rn(1.0, f)), __dmul_rn(b, f));
-}
 
 // MODE 0 blends the views by their weights, MODE 1 keeps the view of the largest weight (the first of equals)
 template <int MODE, bool FACING, bool MASKED>

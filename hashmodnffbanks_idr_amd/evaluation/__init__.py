@@ -6,3 +6,4 @@ from .images import evaluate_views, render_view, view_metrics  # noqa: F401
 from .mesh_views import MeshViews, evaluate_mesh_views, render_mesh  # noqa: F401
 from .mesh_rays import DepthAgreement, cast_camera_rays, depth_agreement  # noqa: F401
 from .mesh_sdf import SdfAgreement, mesh_sdf_agreement, sdf_agreement, volume_iou  # noqa: F401
+from .texture import TextureStats, texture_mesh, texture_mesh_for_dataset  # noqa: F401

@@ -3099,3 +3099,180 @@ def mesh_colors_finish(acc, n_used, mode, fill=(0.0, 0.0, 0.0)):
     rgb = acc[:, :3] / acc[:, 3:] if mode == "blend" else acc[:, :3]
     fill = torch.tensor(fill, dtype=torch.float32, device=acc.device)
     return torch.where((n_used > 0)[:, None], rgb.to(torch.float32), fill)
+
+
+# =========================================================================================
+# Per-face texture atlases (csrc/hm_mesh_texture.hip, DESIGN.md "Texturing the mesh")
+# =========================================================================================
+TEXTURE_MAX_RES = 4096
+TEXTURE_MAX_TEXELS = 1 << 40
+
+
+def texture_block_shape(res):
+    """(Hb, Wb) = (res + 2, res + 3): the texels of a block, which holds two faces"""
+    return res + 2, res + 3
+
+
+def _check_texture_res(what, res, n_faces):
+    if not (isinstance(res, int) and not isinstance(res, bool) and 1 <= res <= TEXTURE_MAX_RES):
+        raise ValueError(f"hashmod {what}: res must be an integer in [1, {TEXTURE_MAX_RES}]")
+    if not (isinstance(n_faces, int) and not isinstance(n_faces, bool) and 0 <= n_faces < 1 << 31):
+        raise ValueError(f"hashmod {what}: n_faces must be an integer in [0, 2^31)")
+    Hb, Wb = texture_block_shape(res)
+    if (n_faces + 1) // 2 * Hb * Wb >= TEXTURE_MAX_TEXELS:
+        raise ValueError(f"hashmod {what}: the atlas must have fewer than 2^40 texels (res too large for the mesh)")
+    return (n_faces + 1) // 2, Hb, Wb
+
+
+def mesh_texture_points(verts, faces, res, normals=None):
+    """(points [T,3] fp32, normals [T,3] fp32 or None, face [T] int32): the point on its face, the interpolated vertex
+    normal (not normalised) and the face of every texel of the mesh's atlas at `res` texel steps per face edge.
+
+    The atlas (include/hashmod.h states it once): two faces per block of (res + 2) x (res + 3) texels, block b = faces
+    2b and 2b + 1, T = ceil(F / 2) (res + 2) (res + 3) texels in block-major order.  A texel's barycentrics are small
+    integers over 2 res - the lattice point inside the face, the nearest point of the hypotenuse on the gutter - and
+    its point is float32(((b0 A) + (b1 B)) + (b2 C)) in fp64, rounded once per operation.  The texels of the absent
+    upper half of the last block (odd F) have face -1 and NaN point and normal, which mesh_vertex_colors cannot
+    project.  tests/mesh_texture_cases.texel_points_ref gives the same bits.  A face index outside [0, V) raises
+    HashmodError (reported by the kernel, never dereferenced).  One host read of the status word."""
+    what = "mesh_texture_points"
+    _check_texture_res(what, res, 0)
+    n_faces, n_verts = _check_mesh(what, faces, verts=verts, normals=normals, gpu_first=False)
+    n_blocks, Hb, Wb = _check_texture_res(what, res, n_faces)
+    dev = verts.device
+    T = n_blocks * Hb * Wb
+    points = torch.empty((T, 3), dtype=torch.float32, device=dev)
+    tex_normals = None if normals is None else torch.empty((T, 3), dtype=torch.float32, device=dev)
+    face = torch.empty(T, dtype=torch.int32, device=dev)
+    if T == 0:
+        return points, tex_normals, face
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().hm_mesh_texture_points(dptr(verts), dptr(normals), n_verts, dptr(faces), n_faces, res, dptr(points),
+                                       dptr(tex_normals), dptr(face), dptr(status), stream_ptr(verts)))
+    _check_mesh_status(what, status)
+    return points, tex_normals, face
+
+
+def _background3(what, background):
+    try:
+        bg = np.asarray(background, np.float32)
+        bg = np.ascontiguousarray(np.broadcast_to(bg, (3,)) if bg.ndim == 0 else bg)
+    except (TypeError, ValueError):
+        bg = None
+    if background is None or bg is None or bg.shape != (3,):
+        raise ValueError(f"hashmod {what}: background must be a float or three floats")
+    return bg
+
+
+def mesh_texture_sample(texels, res, n_faces, face_id, weights, background=0.0):
+    """colours [..., 3] fp32 of the samples face_id [...] int32, weights [..., 3] fp32 (mesh_render's, of any leading
+    shape) in the atlas texels [n_blocks, res + 2, res + 3, 3] fp32 of a mesh of n_faces faces.
+
+    face_id < 0 or a non-finite weight gives `background` (a float or three).  Else the position in the face's half
+    block is (w1 res, w2 res), point-mirrored to (res + 2 - w1 res, res + 1 - w2 res) for an odd face, clamped to the
+    block as doubles before any integer is formed; four taps, interpolated along x and then along y in fp64 with
+    (a (1 - f)) + (b f), rounded once to fp32.  Weights exactly at a corner return that corner's texel.
+    tests/mesh_texture_cases.texture_sample_ref gives the same bits; two calls give the same bits.  A face_id >=
+    n_faces raises HashmodError (reported by the kernel, nothing is read).  One host read of the status word."""
+    what = "mesh_texture_sample"
+    n_blocks, Hb, Wb = _check_texture_res(what, res, n_faces)
+    if (not isinstance(texels, torch.Tensor) or texels.dtype != torch.float32
+            or tuple(texels.shape) != (n_blocks, Hb, Wb, 3) or not texels.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous fp32 texels [ceil(n_faces / 2), res + 2, res + 3, 3] expected")
+    if not isinstance(face_id, torch.Tensor) or face_id.dtype != torch.int32 or not face_id.is_contiguous():
+        raise ValueError(f"hashmod {what}: contiguous int32 face_id [...] expected")
+    if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32
+            or tuple(weights.shape) != tuple(face_id.shape) + (3,) or not weights.is_contiguous()):
+        raise ValueError(f"hashmod {what}: contiguous fp32 weights [..., 3] expected, three per face_id")
+    if face_id.numel() >= TEXTURE_MAX_TEXELS:
+        raise ValueError(f"hashmod {what}: face_id must have fewer than 2^40 samples")
+    bg = _background3(what, background)
+    for t in (face_id, weights):
+        if t.device != texels.device:
+            raise ValueError(f"hashmod {what}: the tensors are on different devices")
+    require_gpu(texels, face_id, weights)
+    dev = texels.device
+    out = torch.empty(tuple(face_id.shape) + (3,), dtype=torch.float32, device=dev)
+    if face_id.numel() == 0:
+        return out
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().hm_mesh_texture_sample(dptr(texels) if n_blocks else None, res, n_faces, dptr(face_id), dptr(weights),
+                                       face_id.numel(), bg.ctypes.data_as(C.c_void_p), dptr(out), dptr(status),
+                                       stream_ptr(texels)))
+    if int(status.item()):
+        raise _lib.HashmodError(f"hashmod {what}: a face_id lies outside [-inf, n_faces): the samples are not of this "
+                                "atlas' mesh")
+    return out
+
+
+class TextureAtlas:
+    """A baked per-face texture: res, n_faces, block_shape = (Hb, Wb), texels [n_blocks,Hb,Wb,3] fp32 (the dataset's
+    [-1, 1] range when evaluation.texture.texture_mesh made them), used [n_blocks,Hb,Wb] bool (a view coloured the
+    texel) and fill, the three floats of the unused rest of the 2-D image.  sample() is mesh_texture_sample over it;
+    image() and face_uvs() lay the blocks out for an export (torch plumbing, no kernel)."""
+
+    def __init__(self, res, n_faces, texels, used=None, fill=(0.0, 0.0, 0.0)):
+        n_blocks, Hb, Wb = _check_texture_res("TextureAtlas", res, n_faces)
+        if (not isinstance(texels, torch.Tensor) or texels.dtype != torch.float32
+                or tuple(texels.shape) != (n_blocks, Hb, Wb, 3) or not texels.is_contiguous()):
+            raise ValueError("hashmod TextureAtlas: contiguous fp32 texels [ceil(n_faces / 2), res + 2, res + 3, 3] "
+                             "expected")
+        if used is None:
+            used = torch.ones((n_blocks, Hb, Wb), dtype=torch.bool, device=texels.device)
+        if (not isinstance(used, torch.Tensor) or used.dtype != torch.bool or tuple(used.shape) != (n_blocks, Hb, Wb)
+                or used.device != texels.device):
+            raise ValueError("hashmod TextureAtlas: bool used [n_blocks, res + 2, res + 3] on the texels' device "
+                             "expected")
+        try:
+            fill = tuple(float(c) for c in fill)
+        except (TypeError, ValueError):
+            fill = ()
+        if len(fill) != 3:
+            raise ValueError("hashmod TextureAtlas: fill must be three numbers")
+        self.res, self.n_faces, self.block_shape = res, n_faces, (Hb, Wb)
+        self.texels, self.used, self.fill = texels, used, fill
+
+    @property
+    def n_blocks(self):
+        return int(self.texels.shape[0])
+
+    def sample(self, face_id, weights, background=0.0):
+        return mesh_texture_sample(self.texels, self.res, self.n_faces, face_id, weights, background)
+
+    def atlas_shape(self, blocks_per_row=None):
+        """(bw, Ha, Wa): bw blocks per row, Wa = bw Wb, Ha = ceil(n_blocks / bw) Hb.  The default bw is, of the
+        integers within one of sqrt(n_blocks Hb / Wb), the one whose image is nearest a square"""
+        Hb, Wb = self.block_shape
+        nb = max(self.n_blocks, 1)
+        if blocks_per_row is None:
+            k = math.isqrt(nb * Hb // Wb)
+            blocks_per_row = min((b for b in (k - 1, k, k + 1, k + 2) if b >= 1),
+                                 key=lambda b: (abs(b * Wb - -(-nb // b) * Hb), b))
+        if not (isinstance(blocks_per_row, int) and not isinstance(blocks_per_row, bool) and blocks_per_row >= 1):
+            raise ValueError("hashmod TextureAtlas: blocks_per_row must be an integer >= 1")
+        return blocks_per_row, -(-nb // blocks_per_row) * Hb, blocks_per_row * Wb
+
+    def image(self, blocks_per_row=None):
+        """[Ha,Wa,3] fp32 on the texels' device: block b at column (b mod bw) Wb and row (b div bw) Hb, row 0 on top;
+        the unused tail of the last block row holds `fill`"""
+        Hb, Wb = self.block_shape
+        bw, Ha, Wa = self.atlas_shape(blocks_per_row)
+        rows = Ha // Hb
+        grid = torch.tensor(self.fill, dtype=torch.float32, device=self.texels.device).repeat(rows * bw, Hb, Wb, 1)
+        grid[:self.n_blocks] = self.texels
+        return grid.reshape(rows, bw, Hb, Wb, 3).permute(0, 2, 1, 3, 4).reshape(Ha, Wa, 3).contiguous()
+
+    def face_uvs(self, blocks_per_row=None):
+        """float64 numpy [F,3,2]: the corners' texture coordinates vt = ((x + 0.5) / Wa, 1 - (y + 0.5) / Ha) at their
+        texel centres - (x0, y0), (x0 + n, y0), (x0, y0 + n) for an even face of the block at (x0, y0) and
+        (x0 + n + 2, y0 + n + 1), (x0 + 2, y0 + n + 1), (x0 + n + 2, y0 + 1) for an odd one - so that a standard
+        bilinear texture fetch reads the texels mesh_texture_sample reads"""
+        Hb, Wb = self.block_shape
+        n = self.res
+        bw, Ha, Wa = self.atlas_shape(blocks_per_row)
+        f = np.arange(self.n_faces, dtype=np.int64)
+        origin = np.stack([((f >> 1) % bw) * Wb, ((f >> 1) // bw) * Hb], 1)[:, None, :]
+        lower = np.array([[0, 0], [n, 0], [0, n]], np.int64)
+        upper = np.array([[n + 2, n + 1], [2, n + 1], [n + 2, 1]], np.int64)
+        xy = (origin + np.where(((f & 1) == 1)[:, None, None], upper[None], lower[None])).astype(np.float64)
+        return np.stack([(xy[..., 0] + 0.5) / Wa, 1.0 - (xy[..., 1] + 0.5) / Ha], -1)

@@ -13,6 +13,7 @@ on device-generated lattices, the meshes from ops.marching_cubes (csrc/hm_mesh.h
 part of trimesh.Trimesh the reference's callers use.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -101,9 +102,11 @@ class TriMesh:
     .ply export; plots.py: .ply export): vertices [V,3] float64, faces [F,3] int64, vertex_normals [V,3] (the given
     ones, else area-weighted face normals), area, apply_transform, split, export.  vertex_colors [V,3] uint8, optional
     (evaluation.color.color_mesh and colors_to_uint8 make them): split gathers them, apply_transform keeps them and
-    export writes them after the normals."""
+    export writes them after the normals.  texture [Ha,Wa,3] uint8 with face_uvs [F,3,2] (ops.TextureAtlas.image
+    through colors_to_uint8, and .face_uvs), optional and given together: split gathers the faces' coordinates,
+    export_obj writes them; the .ply export does not carry them."""
 
-    def __init__(self, vertices, faces, vertex_normals=None, vertex_colors=None):
+    def __init__(self, vertices, faces, vertex_normals=None, vertex_colors=None, texture=None, face_uvs=None):
         self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
         self._normals = None if vertex_normals is None else np.asarray(vertex_normals, np.float64).reshape(-1, 3)
@@ -113,6 +116,15 @@ class TriMesh:
             if colors.dtype != np.uint8 or colors.shape != self.vertices.shape:
                 raise ValueError("TriMesh: vertex_colors must be uint8 [V, 3] (colors_to_uint8)")
             self.vertex_colors = colors
+        self.texture = self.face_uvs = None
+        if texture is not None or face_uvs is not None:
+            tex = None if texture is None else np.asarray(texture)
+            uvs = None if face_uvs is None else np.asarray(face_uvs, np.float64)
+            if tex is None or tex.dtype != np.uint8 or tex.ndim != 3 or tex.shape[2] != 3 or 0 in tex.shape:
+                raise ValueError("TriMesh: texture must be uint8 [Ha, Wa, 3], given together with face_uvs")
+            if uvs is None or uvs.shape != (len(self.faces), 3, 2):
+                raise ValueError("TriMesh: face_uvs must be [F, 3, 2], given together with texture")
+            self.texture, self.face_uvs = tex, uvs
 
     def _cross(self):
         v = self.vertices[self.faces]
@@ -178,7 +190,8 @@ class TriMesh:
             used, inv = np.unique(ff, return_inverse=True)
             normals = None if self._normals is None else self._normals[used]
             colors = None if self.vertex_colors is None else self.vertex_colors[used]
-            part = TriMesh(self.vertices[used], inv.reshape(-1, 3), normals, colors)
+            uvs = None if self.face_uvs is None else self.face_uvs[face_label == lab]
+            part = TriMesh(self.vertices[used], inv.reshape(-1, 3), normals, colors, self.texture, uvs)
             if not only_watertight or part.is_watertight:
                 out.append(part)
         return out
@@ -212,6 +225,29 @@ class TriMesh:
             with open(file_obj, "wb") as fh:
                 fh.write(data)
         return None
+
+    def export_obj(self, path):
+        """the textured mesh as Wavefront OBJ: `path`.obj (v, vn, vt, f a/t/n with one vt per face corner; %.9g keeps
+        every fp32 value), `path`.mtl (one material whose map_Kd is the image) and `path`.png (the texture, row 0 on
+        top; vt's v axis points up).  `path` is taken without its .obj suffix.  Returns the three paths."""
+        if self.texture is None:
+            raise ValueError("TriMesh.export_obj: the mesh has no texture (TriMesh(texture=, face_uvs=))")
+        from PIL import Image
+        base = path[:-4] if str(path).lower().endswith(".obj") else str(path)
+        name = os.path.basename(base)
+        Image.fromarray(np.ascontiguousarray(self.texture)).save(base + ".png")
+        with open(base + ".mtl", "w") as fh:
+            fh.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+        a = self.faces + 1
+        t = np.arange(1, 3 * len(a) + 1, dtype=np.int64).reshape(-1, 3)
+        lines = [f"mtllib {name}.mtl", f"usemtl {name}"]
+        lines += ["v %.9g %.9g %.9g" % tuple(v) for v in self.vertices]
+        lines += ["vn %.9g %.9g %.9g" % tuple(v) for v in self.vertex_normals]
+        lines += ["vt %.17g %.17g" % tuple(v) for v in self.face_uvs.reshape(-1, 2)]
+        lines += ["f " + " ".join(f"{a[i, m]}/{t[i, m]}/{a[i, m]}" for m in range(3)) for i in range(len(a))]
+        with open(base + ".obj", "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        return base + ".obj", base + ".mtl", base + ".png"
 
 
 def colors_to_uint8(colors):

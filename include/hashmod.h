@@ -1308,6 +1308,49 @@ HM_API int hm_mesh_sign(const float *query, int64_t m, const int32_t *face, cons
                         const double *vertex_normals, const double *edge_normals, float *sd, int32_t *sign,
                         void *stream);
 
+/* ---- mesh texturing: a per-face texture atlas, its texels' points on the faces and its sampler -------------------
+ * Driver: ops.mesh_texture_points, ops.mesh_texture_sample, ops.TextureAtlas, evaluation.texture.texture_mesh,
+ * evaluation.mesh_views.render_mesh(texture=).  csrc/hm_mesh_texture.hip, csrc/hm_color_dev.h.  No entry point
+ * synchronises; no atomics but the status word's, no workspace; two calls give the same bits.  status is one device
+ * int32 the CALLER has zeroed.  Numpy restatement: tests/mesh_texture_cases.py.
+ *
+ * THE ATLAS.  n = res in [1, 4096] texel steps along a face edge, the same for every face.  Faces are packed two per
+ * block: block b holds face 2b (lower) and face 2b + 1 (upper; absent in the last block of an odd face count);
+ * n_blocks = (n_faces + 1) / 2 and n_blocks Hb Wb < 2^40.  A block is Wb = n + 3 texels wide and Hb = n + 2 high.
+ * Texel (i, j) = (column, row) belongs to the lower face iff i + j <= n + 1, else to the upper face, which uses the
+ * point-mirrored coordinates (i', j') = (n + 2 - i, n + 1 - j) and then the lower face's rule:
+ *   the lower face's corners A, B, C sit at the texel centres (0, 0), (n, 0), (0, n); its texels with i + j = n + 1
+ *   are its gutter.  Barycentric numerators (exact small integers): i + j <= n: S = 2i, T = 2j; otherwise
+ *   S = clamp(2i - 1, 0, 2n), T = 2n - S, the nearest point of the hypotenuse.  b1 = S / 2n, b2 = T / 2n,
+ *   b0 = (2n - S - T) / 2n, one fp64 division each.
+ * Texel point: p_c = float(((b0 A_c) + (b1 B_c)) + (b2 C_c)), fp64 operations on the fp32 corners, each rounded
+ * once, in this order; texel normal: the same expression over the corners' vertex normals, NOT normalised.
+ * Storage is block-major: texel t = (b Hb + j) Wb + i.
+ *   hm_mesh_texture_points: verts [n_verts, 3] fp32; normals [n_verts, 3] fp32 or NULL; faces [n_faces, 3] int32.
+ *                Writes points [T, 3] fp32, tex_normals [T, 3] fp32 (NULL iff normals is) and face [T] int32,
+ *                T = n_blocks Hb Wb; one lane per texel.  A texel of the absent face gets face = -1 and NaN point and
+ *                normal: hm_mesh_vertex_colors cannot project it, so it collects nothing.  A face index outside
+ *                [0, n_verts) sets bit 0 of status and is never dereferenced (its texels are written as absent).
+ *   hm_mesh_texture_sample: texels [n_blocks, Hb, Wb, 3] fp32; face_id [n_samples] int32 and weights [n_samples, 3]
+ *                fp32 as hm_mesh_render writes them; background [3] fp32 on the HOST (read before the launch) or NULL
+ *                for zeros.  Writes out [n_samples, 3] fp32; one lane per sample:
+ *                  1. face_id < 0 or a non-finite weight gives background;
+ *                  2. face_id >= n_faces sets bit 0 of status (and gives background; nothing is read);
+ *                  3. s = w1 n, t = w2 n in fp64 (w1, w2 = weights[1], weights[2] widened);
+ *                  4. lower face (even): (px, py) = (s, t); upper face (odd): (px, py) = ((n + 2) - s, (n + 1) - t);
+ *                  5. px is clamped to [0, Wb - 1] and py to [0, Hb - 1] as doubles, before any integer is formed;
+ *                  6. the taps are x0 = floor(px), x1 = min(x0 + 1, Wb - 1), fx = px - x0, and y likewise;
+ *                  7. per channel top = (a (1 - fx)) + (b fx) over row y0, bot likewise over row y1,
+ *                     val = (top (1 - fy)) + (bot fy); every operation fp64 and rounded once; out = float(val).
+ *                Weights exactly at a corner return that corner's texel; a point inside a face reads no texel of the
+ *                other face with a weight above rounding. */
+HM_API int hm_mesh_texture_points(const float *verts, const float *normals, int64_t n_verts, const int32_t *faces,
+                                  int64_t n_faces, int64_t res, float *points, float *tex_normals, int32_t *face,
+                                  int32_t *status, void *stream);
+HM_API int hm_mesh_texture_sample(const float *texels, int64_t res, int64_t n_faces, const int32_t *face_id,
+                                  const float *weights, int64_t n_samples, const float *background, float *out,
+                                  int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
