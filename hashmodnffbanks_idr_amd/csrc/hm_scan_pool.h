@@ -13,6 +13,11 @@
 //   takes what does not fit under the chain: capacity = (256 - secant workgroups) * chain_tiles, chain_tiles = the tiles
 //   one workgroup finishes while the chain runs (host: floor(n_iters * kScanTilesPerSecantIterPermille / 1000), or
 //   HM_TRACE_POOL_CHAIN_TILES).  Y takes the rest.  chain_tiles = 0 (or no secant ray): everything in front of the chain.
+//   Where the chain is cut in two launches (hm_trace.hip: k_tail), Y is the FIRST of them: the scan must be complete
+//   before the closest-approach rows are selected, which happens between the two, so the second launch (the chain's last
+//   rounds beside those rows' refinement list) owns no tile of the scan.  The ranges stay those of the whole chain
+//   (n_iters = its length): what Y's shorter chain does not cover is a last round of all of Y's workgroups, which costs
+//   less than the same tiles in front of the chain (measured: profiles/chain_tail_ab.json).
 // The number of secant rays is not known before the sampler's values are patched and reduced, i.e. behind X1 and X2; the
 // rule reads its upper bound, the rays handed to the sampler (cnt[C_NSAMP]; training refines those of them that hit inside
 // the object mask), in every launch.

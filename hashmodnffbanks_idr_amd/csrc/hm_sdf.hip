@@ -514,12 +514,15 @@ __device__ __attribute__((noinline)) void secant_step_ray(const TraceArgs &a, in
     secant_advance_ray(a, q, last);
 }
 
+// The chain's state (pts, vals, the bracket arrays) lives in global memory between iterations, so a launch may run any
+// RANGE of them: iterations [it_first, it_first + it_count) of a chain of it_total (the last one of the whole chain
+// writes the results).
 template <int FRAC>
 __device__ __forceinline__ void secant_role(const HmLevels &lv, const SdfNet &net, const float *__restrict__ table,
-                                            const float *__restrict__ Bf, const TraceArgs &a, int n_iters, int64_t n,
-                                            int pts, float *lds) {
+                                            const float *__restrict__ Bf, const TraceArgs &a, int it_first, int it_count,
+                                            int it_total, int64_t n, int pts, float *lds) {
     const int64_t n_tiles = (n + pts - 1) / pts;
-    for (int it = 0; it < n_iters; ++it) {
+    for (int it = it_first; it < it_first + it_count; ++it) {
         if (pts == 4)
             sdf_small_body<FRAC, Tile8<4>>(lv, net, a.w.pts, n, table, Bf, a.w.vals, 1, 1, lds, blockIdx.x, gridDim.x);
         else if (pts == 8)
@@ -529,7 +532,7 @@ __device__ __forceinline__ void secant_role(const HmLevels &lv, const SdfNet &ne
         __syncthreads();       // the tile's values (global stores of this workgroup) are visible to its threads
         for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
             const int64_t q = tile * pts + threadIdx.x;
-            if ((int)threadIdx.x < pts && q < n) secant_step_ray(a, q, it == n_iters - 1 ? 1 : 0);
+            if ((int)threadIdx.x < pts && q < n) secant_step_ray(a, q, it == it_total - 1 ? 1 : 0);
         }
         __syncthreads();       // the next iteration's points are written
     }
@@ -547,7 +550,7 @@ __global__ __launch_bounds__(kThreadsSdf, 1) void trace_secant_kernel(HmLevels l
     // scan_hide > 0: the tile rule of sdf_scan_secant_kernel, so that both forms of the search give the same values
     const bool as_scan = scan_hide > 0 && a.w.cnt[C_NSEL_PTS] >= scan_hide;
     const int pts = as_scan ? 16 : (n <= m4_max ? 4 : (n <= m8_max ? 8 : 16));
-    secant_role<FRAC>(lv, net, table, Bf, a, n_iters, n, pts, lds);
+    secant_role<FRAC>(lv, net, table, Bf, a, 0, n_iters, n_iters, n, pts, lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -563,11 +566,16 @@ __global__ __launch_bounds__(kThreadsSdf, 1) void trace_secant_kernel(HmLevels l
 // The guarded mode runs the same kernel with another scan: scan_x -> scan_out, cnt[c_scan] points = the refinement list of
 // the closest-approach rows' marked samples (any length on the 64-point body: scan_min 1), whose ~60 tiles fit beside the
 // secant tiles; the secant's tile rule still reads the closest-approach scan's length.
-template <int FRAC>
+// The launch runs iterations [it_first, it_first + n_iters) of a chain of it_total (secant_role).  QUARTER: the list runs
+// on the tile schedule of sdf_fwd_kernel<FRAC, true> (quarter tiles up to 16 points per workgroup, else its half / full
+// tiles) - the LAST rounds of a chain that was cut in two launches, with the list's one round under them; the workgroups
+// that own secant tiles join the list afterwards if a tile is left.  No secant ray: the launch is the list's alone.
+template <int FRAC, bool QUARTER>
 __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevels lv, SdfNet net,
                                                                           const float *__restrict__ table,
                                                                           const float *__restrict__ Bf, TraceArgs a,
-                                                                          int n_iters, int64_t m8_max, int64_t m4_max,
+                                                                          int it_first, int n_iters, int it_total,
+                                                                          int64_t m8_max, int64_t m4_max,
                                                                           const float *__restrict__ scan_x,
                                                                           float *__restrict__ scan_out, int c_scan,
                                                                           int64_t scan_cap, int64_t scan_min,
@@ -579,9 +587,9 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevel
     if (n_sec > 0 && n_iters > 0) {
         // (the secant's tiles follow the closest-approach scan's length also where the scan of this launch is another list)
         const int pts = a.w.cnt[C_NSEL_PTS] >= scan_hide ? 16 : (n_sec <= m4_max ? 4 : (n_sec <= m8_max ? 8 : 16));
-        secant_role<FRAC>(lv, net, table, Bf, a, n_iters, n_sec, pts, lds);
+        secant_role<FRAC>(lv, net, table, Bf, a, it_first, n_iters, it_total, n_sec, pts, lds);
     }
-    if (n_scan < scan_min) return;        // (a short scan is the small-tile launch's job; an empty list is nobody's)
+    if (n_scan < scan_min) return;      // (a short scan is the small-tile launch's job; an empty list is nobody's)
     // the scan's first tiles completed the last rounds of the sampler's launches (filler tiles, see fill_quota)
     const int64_t tb = (n_scan + kPts - 1) / kPts;
     int64_t done = c_prev1 >= 0 ? fill_quota(max(a.w.cnt[c_prev1], 0), grid1, tb, scan_min) : 0;
@@ -589,8 +597,8 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_scan_secant_kernel(HmLevel
     const int64_t skip = done * kPts;
     if (skip >= n_scan) return;
     const SdfFill none = {nullptr, nullptr, 0, 0};
-    sdf64_run<FRAC, true>(lv, net, scan_x + skip * 3, n_scan - skip, table, Bf, scan_out + skip, 1, 1, lds,
-                          reinterpret_cast<unsigned *>(a.w.cnt + C_TILE_CURSOR), none);
+    sdf64_run<FRAC, true, QUARTER>(lv, net, scan_x + skip * 3, n_scan - skip, table, Bf, scan_out + skip, 1, 1, lds,
+                                   reinterpret_cast<unsigned *>(a.w.cnt + C_TILE_CURSOR), none);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -650,11 +658,14 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_refine_scan_kernel(HmLevel
 // meanwhile, and the secant's workgroups join when their chain is done.  secant_role is sdf_scan_secant_kernel's (the tile
 // rule reads the scan's length, so the secant's values are those of every other form of the search); the tiles are
 // sdf_refine_scan_kernel's.  No workgroup waits for another.  grid_x: workgroups of the refine-scan launches.
+// The launch runs iterations [it_first, it_first + n_iters) of a chain of it_total (secant_role): where the chain is cut,
+// its first rounds, with ALL remaining tiles of the scan - the closest-approach rows are selected behind this launch.
 template <int KIND, int FRAC>
 __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_split_scan_secant_kernel(HmLevels lv, SdfNet net, SdfNet net_split,
                                                                                 const float *__restrict__ table,
                                                                                 const float *__restrict__ Bf, TraceArgs a,
-                                                                                int n_iters, int64_t m8_max, int64_t m4_max,
+                                                                                int it_first, int n_iters, int it_total,
+                                                                                int64_t m8_max, int64_t m4_max,
                                                                                 int64_t scan_hide, int c_ref1, int c_ref2,
                                                                                 int grid_x, int64_t scan_off,
                                                                                 int64_t chain_tiles) {
@@ -662,7 +673,7 @@ __global__ __launch_bounds__(kThreadsSdf, 2) void sdf_split_scan_secant_kernel(H
     const int64_t n_sec = a.w.cnt[C_NSEC];
     if (n_sec > 0 && n_iters > 0) {
         const int pts = a.w.cnt[C_NSEL_PTS] >= scan_hide ? 16 : (n_sec <= m4_max ? 4 : (n_sec <= m8_max ? 8 : 16));
-        secant_role<FRAC>(lv, net, table, Bf, a, n_iters, n_sec, pts, lds);
+        secant_role<FRAC>(lv, net, table, Bf, a, it_first, n_iters, it_total, n_sec, pts, lds);
     }
     const int64_t n_scan = min((int64_t)max(a.w.cnt[C_NSEL_PTS], 0), a.w.cap);
     const int64_t n_ref1 = min((int64_t)max(a.w.cnt[c_ref1], 0), a.w.cap);
@@ -855,11 +866,15 @@ int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
 // one launch (sdf_scan_secant_kernel).  tile_points = 0 only.  small_front != 0 - the closest-approach scan of the exact
 // mode: scans of <= kSdfSmall points run on the small-tile launch in front of it; 0 - a refinement list of the guarded
 // mode: every count runs on the 64-point body, and no sampler launch took tiles of it (c_prev* = -1).
+// The launch runs iterations [it_first, it_first + n_iters) of a secant chain of it_total.  quarter != 0 (a refinement list
+// only): the list on the tile schedule of hm_sdf_fwd with HM_SDF_TILE64_QUARTER.
 int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                         int frac_mode, const void *trace_args, int n_iters, const float *scan_x, float *scan_out,
-                         int64_t scan_capacity, int c_scan, int small_front, int c_prev1, int grid1, int c_prev2, int grid2,
-                         void *stream) {
+                         int frac_mode, const void *trace_args, int it_first, int n_iters, int it_total, int quarter,
+                         const float *scan_x, float *scan_out, int64_t scan_capacity, int c_scan, int small_front,
+                         int c_prev1, int grid1, int c_prev2, int grid2, void *stream) {
     HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_scan_secant: NULL argument");
+    HM_CHECK_ARG(it_first >= 0 && n_iters >= 0 && it_first + n_iters <= it_total, "hm_trace_scan_secant: bad iteration range");
+    HM_CHECK_ARG(!quarter || !small_front, "hm_trace_scan_secant: quarter tiles are a refinement list's");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_scan_secant: bad frac_mode");
     HM_CHECK_ARG(c_scan >= 0 && c_scan < C_COUNT && scan_capacity >= 0, "hm_trace_scan_secant: bad scan counter / capacity");
     HM_CHECK_ARG(small_front || (grid1 <= 0 && grid2 <= 0), "hm_trace_scan_secant: a refinement list has no filler tiles");
@@ -885,15 +900,21 @@ int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
     // c_prev*: counters holding the own-point counts of the sampler launches that took filler tiles of this scan (-1: none)
     const int p1 = grid1 > 0 ? c_prev1 : -1, p2 = grid2 > 0 ? c_prev2 : -1;
     const SmallTiles t = sdf_small_tiles(0);
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        constexpr auto kernel = sdf_scan_secant_kernel<decltype(frac)::value>;
+    // (quarter: the grid of the stand-alone launch it stands for, sdf_fwd_impl - one quarter tile per workgroup at most)
+    const int64_t qtiles = (scan_capacity + 15) / 16;
+    const unsigned grid = quarter && qtiles < 256 ? (unsigned)(qtiles > 0 ? qtiles : 1) : 256u;
+    const auto launch = [&](auto frac, auto q) {
+        constexpr auto kernel = sdf_scan_secant_kernel<decltype(frac)::value, decltype(q)::value>;
         const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
         if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier, a,
-                           n_iters, t.m8_max, t.m4_max, scan_x, scan_out, c_scan, scan_capacity,
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier, a,
+                           it_first, n_iters, it_total, t.m8_max, t.m4_max, scan_x, scan_out, c_scan, scan_capacity,
                            (int64_t)(small_front ? kSdfSmall + 1 : 1), scan_hide, p1, grid1, p2, grid2);
         HM_CHECK_LAUNCH("hm_trace_scan_secant");
         return HM_OK;
+    };
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        return quarter ? launch(frac, std::true_type{}) : launch(frac, std::false_type{});
     });
 }
 
@@ -950,11 +971,15 @@ int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const
 
 // internal entry of the ray search (hm_trace.hip, not exported), guarded coarse scans: the secant refinement and the split
 // tiles of the closest-approach scan that the hm_trace_refine_scan launches in front left over, in one launch
-// (sdf_split_scan_secant_kernel).  c_ref1 / c_ref2 / scan_off / chain_tiles: as given to those launches.
+// (sdf_split_scan_secant_kernel).  c_ref1 / c_ref2 / scan_off / chain_tiles: as given to those launches.  The launch runs
+// iterations [it_first, it_first + n_iters) of a secant chain of it_total.
 int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                               const float *B_fourier, int frac_mode, const void *trace_args, int n_iters, int c_ref1,
-                               int c_ref2, int64_t scan_off, int64_t scan_capacity, int64_t chain_tiles, void *stream) {
+                               const float *B_fourier, int frac_mode, const void *trace_args, int it_first, int n_iters,
+                               int it_total, int c_ref1, int c_ref2, int64_t scan_off, int64_t scan_capacity,
+                               int64_t chain_tiles, void *stream) {
     HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_split_scan_secant: NULL argument");
+    HM_CHECK_ARG(it_first >= 0 && n_iters >= 0 && it_first + n_iters <= it_total,
+                 "hm_trace_split_scan_secant: bad iteration range");
     HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR,
                  "hm_trace_split_scan_secant: bad frac_mode");
     HM_CHECK_ARG(c_ref1 >= 0 && c_ref1 < C_COUNT && c_ref2 < C_COUNT && chain_tiles >= 0,
@@ -979,7 +1004,8 @@ int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp,
         const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
         if (rc != HM_OK) return rc;
         hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, net_split, table,
-                           B_fourier, a, n_iters, t.m8_max, t.m4_max, (int64_t)kTraceScanHide, c_ref1, c_ref2, grid_x,
+                           B_fourier, a, it_first, n_iters, it_total, t.m8_max, t.m4_max, (int64_t)kTraceScanHide, c_ref1,
+                           c_ref2, grid_x,
                            scan_off, chain_tiles);
         HM_CHECK_LAUNCH("hm_trace_split_scan_secant");
         return HM_OK;

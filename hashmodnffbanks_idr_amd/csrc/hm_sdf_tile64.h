@@ -62,8 +62,9 @@ __device__ __forceinline__ int64_t fill_quota(int64_t n_own, int64_t grid, int64
 // The 64-point tile loop of sdf_fwd_kernel / sdf_scan_secant_kernel.  DYN = false: the static schedule below
 // (tile = round * grid + workgroup); DYN = true: the SAME tiles in the same enumeration, handed out by an atomic cursor
 // (zero at launch) - workgroups that start late (they carried secant rays first) simply take fewer of them.
-// QUARTER (static schedule, no filler set): a launch of at most 16 points per workgroup runs QUARTER tiles of <= 16 points
-// on v_mfma_f32_16x16x4_f32 - see the k-loop below; every other count keeps the schedule of QUARTER = false.
+// QUARTER (no filler set): a launch of at most 16 points per workgroup runs QUARTER tiles of <= 16 points
+// on v_mfma_f32_16x16x4_f32 - see the k-loop below; every other count keeps the schedule of QUARTER = false.  With DYN the
+// quarter tiles are the static schedule's (tile u = points [16 u, 16 u + 16)), handed out by the cursor.
 template <int FRAC, bool DYN, bool QUARTER = false>
 __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net, const float *__restrict__ x, int64_t n,
                                           const float *__restrict__ table, const float *__restrict__ Bf,
@@ -96,7 +97,7 @@ __device__ __forceinline__ void sdf64_run(const HmLevels &lv, const SdfNet &net,
     const int64_t rounds = n_fill > 0 ? (TA + n_fill) / G : (n / kPts) / G;
     const int64_t rem_base = rounds * G * kPts;
     // quarter tiles: the whole launch is one remainder round of 16-point tiles
-    const bool qt = QUARTER && !DYN && n_fill == 0 && n <= G * 16;
+    const bool qt = QUARTER && n_fill == 0 && n <= G * 16;
     const int64_t rem_step = qt ? 16 : (n - rem_base <= G * 32) ? 32 : kPts;
 
     for (int64_t it = 0;; ++it) {

@@ -29,11 +29,13 @@ extern "C" int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp
 
 // hm_sdf.hip (not exported): a 64-point-tile scan (the closest-approach scan of the exact mode, or a refinement list of the
 // guarded mode) and the secant refinement as ONE launch (workgroups without secant rays start on the scan at once, 64-point
-// tiles handed out by an atomic cursor)
+// tiles handed out by an atomic cursor).  Iterations [it_first, it_first + n_iters) of a chain of it_total; quarter: the
+// list on the quarter-tile schedule
 extern "C" int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                    const float *B_fourier, int frac_mode, const void *trace_args, int n_iters,
-                                    const float *scan_x, float *scan_out, int64_t scan_capacity, int c_scan,
-                                    int small_front, int c_prev1, int grid1, int c_prev2, int grid2, void *stream);
+                                    const float *B_fourier, int frac_mode, const void *trace_args, int it_first,
+                                    int n_iters, int it_total, int quarter, const float *scan_x, float *scan_out,
+                                    int64_t scan_capacity, int c_scan, int small_front, int c_prev1, int grid1,
+                                    int c_prev2, int grid2, void *stream);
 
 // hm_sdf.hip (not exported), guarded mode: the exact refinement of a list and the approximate closest-approach scan as ONE
 // launch (fp32 tiles of the list first, then this launch's range of the scan's split tiles, each from an atomic cursor of
@@ -45,9 +47,9 @@ extern "C" int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc 
 // hm_sdf.hip (not exported), guarded mode: the secant refinement and the split tiles of the closest-approach scan that the
 // hm_trace_refine_scan launches left over as ONE launch
 extern "C" int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                          const float *B_fourier, int frac_mode, const void *trace_args, int n_iters,
-                                          int c_ref1, int c_ref2, int64_t scan_off, int64_t scan_capacity,
-                                          int64_t chain_tiles, void *stream);
+                                          const float *B_fourier, int frac_mode, const void *trace_args, int it_first,
+                                          int n_iters, int it_total, int c_ref1, int c_ref2, int64_t scan_off,
+                                          int64_t scan_capacity, int64_t chain_tiles, void *stream);
 
 // hm_sdf.hip (not exported): hm_sdf_fwd whose 64-point launch completes its last round with tiles of a second point set
 extern "C" int hm_sdf_fwd_fill(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n,
@@ -670,6 +672,19 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     // hides k tiles per workgroup instead of trace_chain_tiles' - 0 leaves the whole scan in front of it.
     const bool pool = cosched && !(e_ov && atoi(e_ov) == 2);
     const char *e_ct = getenv("HM_TRACE_POOL_CHAIN_TILES");
+    // The pooled sequence cuts the secant chain in two launches: the first rounds beside ALL remaining tiles of the scan,
+    // then - behind the selection of the closest-approach rows - the last k_tail rounds with the one round of exact tiles
+    // that refines those rows' marks under them (sdf_scan_secant_kernel<., true>), on the workgroups that own no secant tile.
+    // The chain's state lives in global memory between rounds, so the cut changes no value.  Chains of at most k_tail
+    // rounds run whole in front of the refinement.  HM_TRACE_CHAIN_TAIL=r (A/B, tests; read per call): r rounds behind the
+    // cut, 0 = none.
+    const char *e_tl = getenv("HM_TRACE_CHAIN_TAIL");
+    const int tail_want = (e_tl && atoi(e_tl) >= 0) ? atoi(e_tl) : kTraceChainTail;
+    const int k_tail = (pool && tail_want > 0 && cfg->n_secant_steps > tail_want) ? tail_want : 0;
+    // (The scan's ranges do not follow the cut: the first launch keeps the tiles the whole chain would hide and runs the
+    //  ones its shorter chain does not cover as a last round of all its workgroups, ~165 us.  Counting only the rounds in
+    //  front of the cut sends them to the refine-scan launch instead, whose fp32 workgroups reach the scan late: +290 us
+    //  there on the bench step, profiles/chain_tail_ab.json.)
     const int64_t chain_tiles = pool ? trace_chain_tiles(cfg->n_secant_steps, (e_ct && atoi(e_ct) >= 0) ? atoi(e_ct) : -1) : 0;
     const int c_ref2 = (pool && a.head > 0) ? (int)C_GUARD_N2 : -1;    // list of the second refine-scan launch
 
@@ -863,22 +878,31 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
         // (hm_sdf.hip: trace_secant_kernel; with the closest-approach scan in the same launch: sdf_scan_secant_kernel);
         // otherwise an (SDF launch, update launch) pair per iteration
         if (overlap) {
-            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps,
-                                                a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, n_rays * cfg->n_steps,
+            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, 0, cfg->n_secant_steps,
+                                                cfg->n_secant_steps, 0, a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, n_rays * cfg->n_steps,
                                                 (int)C_NSEL_PTS, 1, c_first, grid_p1, (int)C_TAIL_PTS, grid_p2, stream);
             if (rc != HM_OK) return rc;
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         } else if (pool) {
             // the rest of the closest-approach scan runs beside the chain; its rows' marks (selected behind the sampler's
             // patch: see guard_mark_row) are refined behind it
-            int rc = hm_trace_split_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps,
+            const int n_front = cfg->n_secant_steps - k_tail;
+            int rc = hm_trace_split_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, 0, n_front, cfg->n_secant_steps,
                                                 (int)C_GUARD_N1, c_ref2, a.sel_off, n_rays * cfg->n_steps, chain_tiles,
                                                 stream);
             if (rc != HM_OK) return rc;
             guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
             hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
                                (int)C_GUARD_NC);
-            rc = guard_refine((int)C_GUARD_NC, true);
+            if (k_tail > 0) {
+                // the chain's last rounds with the list under them: the tiles and values of guard_refine's quarter launch
+                // (no secant ray, which only the device knows: that launch alone)
+                rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, n_front, k_tail, cfg->n_secant_steps, 1,
+                                          a.w.ref_pts, a.w.ref_vals, L.cap, (int)C_GUARD_NC, 0, -1, 0, -1, 0, stream);
+                if (rc == HM_OK) guard_patch((int)C_GUARD_NC);
+            } else {
+                rc = guard_refine((int)C_GUARD_NC, true);
+            }
             if (rc != HM_OK) return rc;
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
         } else if (cosched) {
@@ -887,8 +911,8 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
             guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
             hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
                                (int)C_GUARD_NC);
-            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, cfg->n_secant_steps, a.w.ref_pts,
-                                                a.w.ref_vals, L.cap, (int)C_GUARD_NC, 0, -1, 0, -1, 0, stream);
+            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, 0, cfg->n_secant_steps,
+                                                cfg->n_secant_steps, 0, a.w.ref_pts, a.w.ref_vals, L.cap, (int)C_GUARD_NC, 0, -1, 0, -1, 0, stream);
             if (rc != HM_OK) return rc;
             guard_patch((int)C_GUARD_NC);
             hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);

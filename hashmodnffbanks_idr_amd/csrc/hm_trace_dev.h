@@ -69,6 +69,13 @@ inline int64_t trace_chain_tiles(int n_iters, int64_t given) {
     return given >= 0 ? given : n_iters * kScanTilesPerSecantIterPermille / 1000;
 }
 
+// Guarded scans, pooled sequence: secant rounds that run BEHIND the selection of the closest-approach rows, in the launch
+// that refines those rows' marks (hm_trace.hip: k_tail; HM_TRACE_CHAIN_TAIL).  The list is one round of quarter tiles
+// (~175 us) on the workgroups without a secant tile; two chain rounds (2 x ~140 us) cover it.  A tuning value: it moves
+// rounds between launches and cannot change a value.  Measured on the bench step (profiles/chain_tail_ab.json): 6.43 /
+// 6.30 / 6.27 / 6.38 ms for 0 / 1 / 2 / 3 rounds.
+constexpr int kTraceChainTail = 2;
+
 enum : uint8_t { ST_WAIT_FIRST = 1, ST_WAIT_MARCH = 2, ST_WAIT_LS = 3, ST_DONE = 4 };
 
 struct TraceWs {
