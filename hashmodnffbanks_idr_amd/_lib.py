@@ -56,6 +56,7 @@ SIGNATURES = {
     "hm_trace_guard_clear": (_int, [_p, _i64, _p]),
     "hm_trace_guard_tolerances": (_int, [_p, _p]),
     "hm_trace_scan_pool_plan": (_int, [_i64, _i64, _i64, _int, _int, _i64, _int, _i64, _p, _p]),
+    "hm_diag_trace_plan": (_int, [_i64, _p, _int, _int, _p]),
     "hm_trace_forward": (_int, [_p, _p, _p, _p, _int, _int, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p,
                                 _i64, _p, _p]),
     "hm_trace_workspace_bytes_nffb": (_i64, [_i64, _p, _int]),
@@ -246,6 +247,14 @@ class TraceCfg(C.Structure):
                 ("line_step_iters", C.c_int32), ("sphere_tracing_iters", C.c_int32), ("n_steps", C.c_int32),
                 ("n_secant_steps", C.c_int32), ("training", C.c_int32), ("coarse_bf16", C.c_int32),
                 ("sampler_head", C.c_int32)]
+
+
+class TracePlanInfo(C.Structure):
+    _fields_ = [("sequence", C.c_int32), ("sel_own", C.c_int32), ("head", C.c_int32), ("per_ray", C.c_int32),
+                ("c_first", C.c_int32), ("k_tail", C.c_int32), ("c_ref2", C.c_int32), ("march_tail", C.c_int32),
+                ("march_launched", C.c_int32), ("march_rounds", C.c_int32), ("secant", C.c_int32),
+                ("scan_rule", C.c_int32), ("noise_nan", C.c_int32), ("noise_amp", C.c_float),
+                ("chain_tiles", C.c_int64), ("guard_min", C.c_int64)]
 
 
 class WnLayer(C.Structure):

@@ -39,6 +39,13 @@ int hm_fail(int code, const std::string &msg);
         if (e__ != hipSuccess) return hm_fail(HM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
+// a step of a launch sequence: its error code ends the sequence
+#define HM_TRY(call)                      \
+    do {                                  \
+        const int rc__ = (call);          \
+        if (rc__ != HM_OK) return rc__;   \
+    } while (0)
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Carves a workspace into its parts: take<T>(count) is the next 256-byte-aligned block of count elements of T, `bytes`

@@ -23,6 +23,7 @@
 // The stages all tile bodies share - point load, weight stream (WeightRing), quad epilogue, embedding rescale, last-layer
 // finish, output rows, LDS layout (SdfLds) - are in hm_sdf_common.h; sdf64_run (hm_sdf_tile64.h) is the 64-point body.
 #include "hm_common.h"
+#include "hm_trace_host.h"   // the ray search's entries into this file
 
 #include <math.h>
 #include <stdlib.h>
@@ -742,6 +743,51 @@ int sdf_dispatch(int mode, F &&f) {
     return hm_frac_dispatch(mode, f);
 }
 
+// The host half that the ray search's fused launches share (hm_trace_host.h).  TILES = the tile bodies the entry's kernel
+// runs: they decide which networks are built, which LDS tiles must fit and the launch's dynamic LDS - the largest of them
+// plus `own` bytes that the kernel keeps behind the tile.  An entry opens it (argument checks, networks), makes its own
+// range checks and returns if the call is empty, then launches: every kernel's arguments start with
+// (lv, net[, net_split], table, B_fourier, TraceArgs).
+enum : unsigned { kTile16 = 1, kTile64 = 2, kTileSplit = 4 };
+template <unsigned TILES>
+struct TraceLaunch {
+    const char *who; const HmTraceCtx *cx; const TraceArgs *a;
+    SdfNet net, net_split;
+    size_t lds16 = 0, lds64 = 0, lds_split = 0, own = 0;
+
+    int fail(const char *what) const { return hm_fail(HM_ERR_INVALID, std::string(who) + ": " + what); }
+
+    int open(const char *who_, const HmTraceCtx *cx_, const void *trace_args, size_t own_ = 0) {
+        who = who_; cx = cx_; own = own_;
+        a = static_cast<const TraceArgs *>(trace_args);
+        if (!(cx && cx->desc && cx->mlp && cx->table && cx->B_fourier && a)) return fail("NULL argument");
+        if (cx->frac_mode != HM_FRAC_REFERENCE && cx->frac_mode != HM_FRAC_TRILINEAR) return fail("bad frac_mode");
+        int rc = sdf_net_fp32(who, cx->desc->lv, cx->mlp, 0, kImgM16, net);
+        if (rc == HM_OK && (TILES & kTileSplit)) rc = sdf_split_net(who, cx->desc->lv.E, cx->mlp, 0, net_split, &lds_split);
+        if (rc != HM_OK) return rc;
+        if (TILES & kTile16) lds16 = sdf_lds_small(net, cx->desc->lv.E, kPts16).bytes();
+        if (TILES & kTile64) lds64 = sdf_lds64(net).bytes();
+        return HM_OK;
+    }
+
+    template <auto Kernel, class... A>
+    int launch(unsigned grid, A... args) const {
+        constexpr bool only16 = TILES == kTile16;
+        if (lds16 + own > kLds16Max || lds64 > kLds64Max - kLdsTrace || lds_split > kLds64Max - kLdsTrace)
+            return fail(only16 ? "network does not fit the 16-point LDS tile" : "network does not fit the LDS tiles");
+        const size_t lds64s = lds64 > lds_split ? lds64 : lds_split, lds = (lds16 > lds64s ? lds16 : lds64s) + own;
+        HM_TRY(hm_allow_dynamic_lds<Kernel>((int)(only16 ? kLds16Max : kLds64Max - kLdsTrace)));
+        if constexpr ((TILES & kTileSplit) != 0)
+            hipLaunchKernelGGL(Kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(cx->stream), cx->desc->lv, net, net_split,
+                               cx->table, cx->B_fourier, *a, args...);
+        else
+            hipLaunchKernelGGL(Kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(cx->stream), cx->desc->lv, net, cx->table,
+                               cx->B_fourier, *a, args...);
+        HM_CHECK_LAUNCH(who);
+        return HM_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -767,19 +813,16 @@ static int sdf_fwd_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const float 
 int sdf_bf16_fits(const hm_mlp_desc *mlp, int E, int32_t *regions);
 int sdf_split_fits(const hm_mlp_desc *mlp, int E, int32_t *regions);
 
-// hm_sdf_fwd for the ray search's sampler launches (not exported): the 64-point launch completes its last round with
-// tiles of a second point set (fill_quota; x_fill / out_fill / n_fill_dev: the closest-approach scan's points, values and
-// device-side count; prev_dev / prev_grid: own-point count and grid of the launch that took filler tiles before this one).
-// *grid64_out = the 64-point launch's grid (0: there was none), for the next launch of the chain.
-int hm_sdf_fwd_fill(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n, const float *table,
-                    const float *B_fourier, float *out, int frac_mode, const int32_t *n_dev, const float *x_fill,
-                    float *out_fill, const int32_t *n_fill_dev, const int32_t *prev_dev, int prev_grid, int *grid64_out,
-                    void *stream) {
-    HM_CHECK_ARG(desc && mlp, "hm_sdf_fwd_fill: NULL descriptor");
-    HM_CHECK_ARG(n == 0 || (table && B_fourier && n_dev && x_fill && out_fill && n_fill_dev), "hm_sdf_fwd_fill: NULL pointer");
+// hm_sdf_fwd for the ray search's sampler launches (hm_trace_host.h)
+int hm_sdf_fwd_fill(const HmTraceCtx *cx, const float *x, int64_t n, float *out, const int32_t *n_dev, const float *x_fill,
+                    float *out_fill, const int32_t *n_fill_dev, const int32_t *prev_dev, int prev_grid, int *grid64_out) {
+    HM_CHECK_ARG(cx && cx->desc && cx->mlp, "hm_sdf_fwd_fill: NULL descriptor");
+    HM_CHECK_ARG(n == 0 || (cx->table && cx->B_fourier && n_dev && x_fill && out_fill && n_fill_dev),
+                 "hm_sdf_fwd_fill: NULL pointer");
     SdfFillArgs fa = {x_fill, out_fill, n_fill_dev, prev_grid > 0 ? prev_dev : nullptr, prev_grid, 0};
     if (grid64_out) *grid64_out = 0;
-    return sdf_fwd_impl(desc->lv, mlp, x, 0, n, table, B_fourier, out, 1, 1, frac_mode, 0, n_dev, 0, stream, &fa, grid64_out);
+    return sdf_fwd_impl(cx->desc->lv, cx->mlp, x, 0, n, cx->table, cx->B_fourier, out, 1, 1, cx->frac_mode, 0, n_dev, 0,
+                        cx->stream, &fa, grid64_out);
 }
 
 int hm_sdf_fwd(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n, const float *table,
@@ -802,217 +845,109 @@ int hm_sdf_fwd_emb(const hm_mlp_desc *mlp, const float *emb, int64_t emb_stride,
                         tile_points, n_dev, max_workgroups, stream);
 }
 
-// internal entry of the ray search (hm_trace.hip, not exported): rounds [first, rounds) of the sphere-tracing march as
-// ONE launch (trace_march_tail_kernel).  `trace_args` = a TraceArgs of hm_trace_dev.h.
-int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                        int frac_mode, int body16, const void *trace_args, int first, int rounds, void *stream) {
-    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_march_tail: NULL argument");
-    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_march_tail: bad frac_mode");
+// ---- the ray search's fused launches (hm_trace_host.h, where each entry is described) ----------------------------------
+int hm_trace_march_tail(const HmTraceCtx *cx, const void *trace_args, int first, int rounds) {
+    TraceLaunch<kTile16> L;
+    HM_TRY(L.open("hm_trace_march_tail", cx, trace_args, kLdsTrace));
     HM_CHECK_ARG(first >= 1 && first < 64 && rounds <= 64, "hm_trace_march_tail: bad round range");
-    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
-    SdfNet net;
-    const int rc = sdf_net_fp32("hm_trace_march_tail", desc->lv, mlp, 0, kImgM16, net);
-    if (rc != HM_OK) return rc;
+    const TraceArgs &a = *L.a;
     if (a.n == 0 || first >= rounds) return HM_OK;
     HM_CHECK_ARG(a.w.cap >= ((a.n + 7) / 8) * 16, "hm_trace_march_tail: point buffer too small");
-    const int lds_floats = (int)(sdf_lds_small(net, desc->lv.E, kPts16).bytes() / sizeof(float));
-    const size_t lds = sizeof(float) * (size_t)lds_floats + kLdsTrace;
-    HM_CHECK_ARG(lds <= kLds16Max, "hm_trace_march_tail: network does not fit the 16-point LDS tile");
-    const unsigned grid = (unsigned)((a.n + 7) / 8);
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        constexpr auto kernel = trace_march_tail_kernel<decltype(frac)::value>;
-        const int rc = hm_allow_dynamic_lds<kernel>(96 * 1024);
-        if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table,
-                           B_fourier, a, first, rounds, lds_floats, body16);
-        HM_CHECK_LAUNCH("hm_trace_march_tail");
-        return HM_OK;
+    return hm_frac_dispatch(cx->frac_mode, [&](auto frac) {
+        return L.launch<trace_march_tail_kernel<decltype(frac)::value>>(
+            (unsigned)((a.n + 7) / 8), first, rounds, (int)(L.lds16 / sizeof(float)), cx->tile_points == 16 ? 1 : 0);
     });
 }
 
-// internal entry of the ray search (hm_trace.hip, not exported): all secant iterations as ONE launch
-// (trace_secant_kernel).  tile_points 0 = the tile size follows the list's length as in hm_sdf_fwd; 4 / 8 / 16 = fixed.
-// scan_rule != 0 (tile_points 0 only): 16-point tiles when the closest-approach scan has at least kTraceScanHide points,
-// as hm_trace_scan_secant chooses them.
-int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                               int frac_mode, int tile_points, const void *trace_args, int n_iters, int scan_rule,
-                               void *stream) {
-    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_secant_persistent: NULL argument");
-    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_secant_persistent: bad frac_mode");
-    HM_CHECK_ARG(tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16,
-                 "hm_trace_secant_persistent: tile_points must be 0, 4, 8 or 16");
-    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
-    SdfNet net;
-    const int rc = sdf_net_fp32("hm_trace_secant_persistent", desc->lv, mlp, 0, kImgM16, net);
-    if (rc != HM_OK) return rc;
-    if (a.n == 0 || n_iters <= 0) return HM_OK;
-    const size_t lds = sdf_lds_small(net, desc->lv.E, kPts16).bytes();
-    HM_CHECK_ARG(lds <= kLds16Max, "hm_trace_secant_persistent: network does not fit the 16-point LDS tile");
-    const SmallTiles t = sdf_small_tiles(tile_points);
+int hm_trace_secant_persistent(const HmTraceCtx *cx, const void *trace_args, int n_iters, int scan_rule) {
+    TraceLaunch<kTile16> L;
+    HM_TRY(L.open("hm_trace_secant_persistent", cx, trace_args));
+    const int tp = cx->tile_points;
+    HM_CHECK_ARG(tp == 0 || tp == 4 || tp == 8 || tp == 16, "hm_trace_secant_persistent: tile_points must be 0, 4, 8 or 16");
+    if (L.a->n == 0 || n_iters <= 0) return HM_OK;
+    const SmallTiles t = sdf_small_tiles(tp);
     // workgroups for the longest list the call can see (every ray a secant ray), one tile each up to one per CU
-    const unsigned grid = sdf_small_grid(a.n, t, 256);
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        constexpr auto kernel = trace_secant_kernel<decltype(frac)::value>;
-        const int rc = hm_allow_dynamic_lds<kernel>(96 * 1024);
-        if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier,
-                           a, n_iters, t.m8_max, t.m4_max, (int64_t)((scan_rule && tile_points == 0) ? kTraceScanHide : 0));
-        HM_CHECK_LAUNCH("hm_trace_secant_persistent");
-        return HM_OK;
+    const unsigned grid = sdf_small_grid(L.a->n, t, 256);
+    return hm_frac_dispatch(cx->frac_mode, [&](auto frac) {
+        return L.launch<trace_secant_kernel<decltype(frac)::value>>(
+            grid, n_iters, t.m8_max, t.m4_max, (int64_t)((scan_rule && tp == 0) ? kTraceScanHide : 0));
     });
 }
 
-// A 64-point-tile scan (scan_capacity points at scan_x, values to scan_out, count cnt[c_scan]) and the secant refinement in
-// one launch (sdf_scan_secant_kernel).  tile_points = 0 only.  small_front != 0 - the closest-approach scan of the exact
-// mode: scans of <= kSdfSmall points run on the small-tile launch in front of it; 0 - a refinement list of the guarded
-// mode: every count runs on the 64-point body, and no sampler launch took tiles of it (c_prev* = -1).
-// The launch runs iterations [it_first, it_first + n_iters) of a secant chain of it_total.  quarter != 0 (a refinement list
-// only): the list on the tile schedule of hm_sdf_fwd with HM_SDF_TILE64_QUARTER.
-int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                         int frac_mode, const void *trace_args, int it_first, int n_iters, int it_total, int quarter,
+int hm_trace_scan_secant(const HmTraceCtx *cx, const void *trace_args, int it_first, int n_iters, int it_total, int quarter,
                          const float *scan_x, float *scan_out, int64_t scan_capacity, int c_scan, int small_front,
-                         int c_prev1, int grid1, int c_prev2, int grid2, void *stream) {
-    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_scan_secant: NULL argument");
+                         int c_prev1, int grid1, int c_prev2, int grid2) {
+    TraceLaunch<kTile16 | kTile64> L;
+    HM_TRY(L.open("hm_trace_scan_secant", cx, trace_args));
     HM_CHECK_ARG(it_first >= 0 && n_iters >= 0 && it_first + n_iters <= it_total, "hm_trace_scan_secant: bad iteration range");
     HM_CHECK_ARG(!quarter || !small_front, "hm_trace_scan_secant: quarter tiles are a refinement list's");
-    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_scan_secant: bad frac_mode");
     HM_CHECK_ARG(c_scan >= 0 && c_scan < C_COUNT && scan_capacity >= 0, "hm_trace_scan_secant: bad scan counter / capacity");
     HM_CHECK_ARG(small_front || (grid1 <= 0 && grid2 <= 0), "hm_trace_scan_secant: a refinement list has no filler tiles");
-    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
-    SdfNet net;
-    int rc = sdf_net_fp32("hm_trace_scan_secant", desc->lv, mlp, 0, kImgM16, net);
-    if (rc != HM_OK) return rc;
+    const TraceArgs &a = *L.a;
     if (a.n == 0) return HM_OK;
     HM_CHECK_ARG(scan_x && scan_out, "hm_trace_scan_secant: NULL scan pointer");
     if (small_front) {
         // the scan's small-count form (tile_points -1: returns at once above kSdfSmall live points)
-        rc = hm_sdf_fwd(desc, mlp, scan_x, scan_capacity, table, B_fourier, scan_out, 1, 1, frac_mode, -1, a.w.cnt + c_scan, 0,
-                        stream);
-        if (rc != HM_OK) return rc;
+        HM_TRY(hm_sdf_fwd(cx->desc, cx->mlp, scan_x, scan_capacity, cx->table, cx->B_fourier, scan_out, 1, 1, cx->frac_mode, -1,
+                          a.w.cnt + c_scan, 0, cx->stream));
     }
-    const size_t lds16 = sdf_lds_small(net, desc->lv.E, kPts16).bytes(), lds64 = sdf_lds64(net).bytes();
-    HM_CHECK_ARG(lds16 <= kLds16Max && lds64 <= kLds64Max - kLdsTrace, "hm_trace_scan_secant: network does not fit the LDS tiles");
-    const size_t lds = lds16 > lds64 ? lds16 : lds64;
     // 16-point secant tiles once the scan keeps the chip busy for longer than their chain takes (8 x 131 us ~ 2.3 rounds
     // of 64-point tiles: 3 rounds = 49 152 points)
     static_assert(kTraceScanHide == 3 * 256 * kPts, "kTraceScanHide counts rounds of 64-point tiles");
-    const int64_t scan_hide = kTraceScanHide;
     // c_prev*: counters holding the own-point counts of the sampler launches that took filler tiles of this scan (-1: none)
     const int p1 = grid1 > 0 ? c_prev1 : -1, p2 = grid2 > 0 ? c_prev2 : -1;
     const SmallTiles t = sdf_small_tiles(0);
     // (quarter: the grid of the stand-alone launch it stands for, sdf_fwd_impl - one quarter tile per workgroup at most)
     const int64_t qtiles = (scan_capacity + 15) / 16;
     const unsigned grid = quarter && qtiles < 256 ? (unsigned)(qtiles > 0 ? qtiles : 1) : 256u;
-    const auto launch = [&](auto frac, auto q) {
-        constexpr auto kernel = sdf_scan_secant_kernel<decltype(frac)::value, decltype(q)::value>;
-        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
-        if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, table, B_fourier, a,
-                           it_first, n_iters, it_total, t.m8_max, t.m4_max, scan_x, scan_out, c_scan, scan_capacity,
-                           (int64_t)(small_front ? kSdfSmall + 1 : 1), scan_hide, p1, grid1, p2, grid2);
-        HM_CHECK_LAUNCH("hm_trace_scan_secant");
-        return HM_OK;
-    };
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        return quarter ? launch(frac, std::true_type{}) : launch(frac, std::false_type{});
+    return hm_frac_dispatch(cx->frac_mode, [&](auto frac) {
+        return hm_bool_dispatch(quarter != 0, [&](auto q) {
+            return L.launch<sdf_scan_secant_kernel<decltype(frac)::value, decltype(q)::value>>(
+                grid, it_first, n_iters, it_total, t.m8_max, t.m4_max, scan_x, scan_out, c_scan, scan_capacity,
+                (int64_t)(small_front ? kSdfSmall + 1 : 1), (int64_t)kTraceScanHide, p1, grid1, p2, grid2);
+        });
     });
 }
 
-// internal entry of the ray search (hm_trace.hip, not exported), guarded coarse scans: the exact refinement of the list
-// ref_pts -> ref_vals (count cnt[c_ref]) and the approximate closest-approach scan (scan_capacity points at pts + scan_off,
-// count cnt[C_NSEL_PTS]) in one launch (sdf_refine_scan_kernel); scans of <= kSdfSmall points run on the exact small-tile
-// launch in front of it, as in hm_sdf_fwd_split's callers.  tile_points = 0 only.
-// The launch runs its range of the scan's split tiles (hm_scan_pool.h): which = 0 - the launch of the list cnt[c_ref1]
-// (the first one: it also enqueues the small-tile launch); which = 1 - of cnt[c_ref2], the lazy sampler's second pass.
-// c_ref2 < 0: there is no second launch.  chain_tiles: split tiles one workgroup finishes under the secant chain (0: the
-// whole scan runs in front of the chain).
-int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                         int frac_mode, const void *trace_args, int c_ref1, int c_ref2, int which, int64_t scan_off,
-                         int64_t scan_capacity, int64_t chain_tiles, void *stream) {
-    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_refine_scan: NULL argument");
-    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR, "hm_trace_refine_scan: bad frac_mode");
+int hm_trace_refine_scan(const HmTraceCtx *cx, const void *trace_args, int c_ref1, int c_ref2, int which, int64_t scan_off,
+                         int64_t scan_capacity, int64_t chain_tiles) {
+    static_assert(sizeof(HmLevels) + 2 * sizeof(SdfNet) + sizeof(TraceArgs) + 64 <= 4096, "kernel arguments exceed 4 KB");
+    TraceLaunch<kTile64 | kTileSplit> L;
+    HM_TRY(L.open("hm_trace_refine_scan", cx, trace_args));
     HM_CHECK_ARG(c_ref1 >= 0 && c_ref1 < C_COUNT && c_ref2 < C_COUNT, "hm_trace_refine_scan: bad list counter");
     HM_CHECK_ARG((which == 0 || which == 1) && (which == 0 || c_ref2 >= 0) && chain_tiles >= 0,
                  "hm_trace_refine_scan: bad launch index / chain capacity");
-    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
-    static_assert(sizeof(HmLevels) + 2 * sizeof(SdfNet) + sizeof(TraceArgs) + 64 <= 4096, "kernel arguments exceed 4 KB");
-    SdfNet net, net_split;
-    size_t lds_split = 0;
-    int rc = sdf_net_fp32("hm_trace_refine_scan", desc->lv, mlp, 0, kImgM16, net);
-    if (rc == HM_OK) rc = sdf_split_net("hm_trace_refine_scan", desc->lv.E, mlp, 0, net_split, &lds_split);
-    if (rc != HM_OK) return rc;
+    const TraceArgs &a = *L.a;
     if (a.n == 0) return HM_OK;
     HM_CHECK_ARG(a.w.pts && a.w.vals && a.w.ref_pts && a.w.ref_vals && a.w.cnt, "hm_trace_refine_scan: NULL workspace pointer");
     HM_CHECK_ARG(scan_off >= 0 && scan_capacity >= 0 && scan_capacity <= a.w.cap, "hm_trace_refine_scan: bad scan region");
-    if (which == 0) {
-        rc = hm_sdf_fwd(desc, mlp, a.w.pts + scan_off * 3, scan_capacity, table, B_fourier, a.w.vals + scan_off, 1, 1,
-                        frac_mode, -1, a.w.cnt + C_NSEL_PTS, 0, stream);
-        if (rc != HM_OK) return rc;
-    }
-    const size_t lds64 = sdf_lds64(net).bytes();
-    HM_CHECK_ARG(lds64 <= kLds64Max - kLdsTrace && lds_split <= kLds64Max - kLdsTrace,
-                 "hm_trace_refine_scan: network does not fit the LDS tiles");
-    const size_t lds = lds_split > lds64 ? lds_split : lds64;
-    const unsigned grid = refine_scan_grid(a.w.cap);
-    const auto launch = [&](auto kind, auto frac) {
-        constexpr auto kernel = sdf_refine_scan_kernel<decltype(kind)::value, decltype(frac)::value>;
-        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
-        if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, net_split, table,
-                           B_fourier, a, c_ref1, c_ref2, which, scan_off, chain_tiles);
-        HM_CHECK_LAUNCH("hm_trace_refine_scan");
-        return HM_OK;
-    };
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
-        return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
+    if (which == 0)
+        HM_TRY(hm_sdf_fwd(cx->desc, cx->mlp, a.w.pts + scan_off * 3, scan_capacity, cx->table, cx->B_fourier,
+                          a.w.vals + scan_off, 1, 1, cx->frac_mode, -1, a.w.cnt + C_NSEL_PTS, 0, cx->stream));
+    return sdf_split_dispatch(cx->mlp, cx->frac_mode, [&](auto kind, auto frac) {
+        return L.launch<sdf_refine_scan_kernel<decltype(kind)::value, decltype(frac)::value>>(
+            refine_scan_grid(a.w.cap), c_ref1, c_ref2, which, scan_off, chain_tiles);
     });
 }
 
-// internal entry of the ray search (hm_trace.hip, not exported), guarded coarse scans: the secant refinement and the split
-// tiles of the closest-approach scan that the hm_trace_refine_scan launches in front left over, in one launch
-// (sdf_split_scan_secant_kernel).  c_ref1 / c_ref2 / scan_off / chain_tiles: as given to those launches.  The launch runs
-// iterations [it_first, it_first + n_iters) of a secant chain of it_total.
-int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                               const float *B_fourier, int frac_mode, const void *trace_args, int it_first, int n_iters,
-                               int it_total, int c_ref1, int c_ref2, int64_t scan_off, int64_t scan_capacity,
-                               int64_t chain_tiles, void *stream) {
-    HM_CHECK_ARG(desc && mlp && table && B_fourier && trace_args, "hm_trace_split_scan_secant: NULL argument");
+int hm_trace_split_scan_secant(const HmTraceCtx *cx, const void *trace_args, int it_first, int n_iters, int it_total,
+                               int c_ref1, int c_ref2, int64_t scan_off, int64_t scan_capacity, int64_t chain_tiles) {
+    TraceLaunch<kTile16 | kTileSplit> L;
+    HM_TRY(L.open("hm_trace_split_scan_secant", cx, trace_args));
     HM_CHECK_ARG(it_first >= 0 && n_iters >= 0 && it_first + n_iters <= it_total,
                  "hm_trace_split_scan_secant: bad iteration range");
-    HM_CHECK_ARG(frac_mode == HM_FRAC_REFERENCE || frac_mode == HM_FRAC_TRILINEAR,
-                 "hm_trace_split_scan_secant: bad frac_mode");
     HM_CHECK_ARG(c_ref1 >= 0 && c_ref1 < C_COUNT && c_ref2 < C_COUNT && chain_tiles >= 0,
                  "hm_trace_split_scan_secant: bad list counter / chain capacity");
-    const TraceArgs &a = *static_cast<const TraceArgs *>(trace_args);
-    SdfNet net, net_split;
-    size_t lds_split = 0;
-    int rc = sdf_net_fp32("hm_trace_split_scan_secant", desc->lv, mlp, 0, kImgM16, net);
-    if (rc == HM_OK) rc = sdf_split_net("hm_trace_split_scan_secant", desc->lv.E, mlp, 0, net_split, &lds_split);
-    if (rc != HM_OK) return rc;
+    const TraceArgs &a = *L.a;
     if (a.n == 0) return HM_OK;
     HM_CHECK_ARG(a.w.pts && a.w.vals && a.w.cnt, "hm_trace_split_scan_secant: NULL workspace pointer");
     HM_CHECK_ARG(scan_off >= 0 && scan_capacity >= 0 && scan_capacity <= a.w.cap, "hm_trace_split_scan_secant: bad scan region");
-    const size_t lds16 = sdf_lds_small(net, desc->lv.E, kPts16).bytes();
-    HM_CHECK_ARG(lds16 <= kLds16Max && lds_split <= kLds64Max - kLdsTrace,
-                 "hm_trace_split_scan_secant: network does not fit the LDS tiles");
-    const size_t lds = lds16 > lds_split ? lds16 : lds_split;
-    const int grid_x = (int)refine_scan_grid(a.w.cap);
+    const int grid_x = (int)refine_scan_grid(a.w.cap);     // workgroups of the refine-scan launches
     const SmallTiles t = sdf_small_tiles(0);
-    const auto launch = [&](auto kind, auto frac) {
-        constexpr auto kernel = sdf_split_scan_secant_kernel<decltype(kind)::value, decltype(frac)::value>;
-        const int rc = hm_allow_dynamic_lds<kernel>(160 * 1024 - 64);
-        if (rc != HM_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3(256), dim3(kThreadsSdf), lds, as_stream(stream), desc->lv, net, net_split, table,
-                           B_fourier, a, it_first, n_iters, it_total, t.m8_max, t.m4_max, (int64_t)kTraceScanHide, c_ref1,
-                           c_ref2, grid_x,
-                           scan_off, chain_tiles);
-        HM_CHECK_LAUNCH("hm_trace_split_scan_secant");
-        return HM_OK;
-    };
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
-        return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
+    return sdf_split_dispatch(cx->mlp, cx->frac_mode, [&](auto kind, auto frac) {
+        return L.launch<sdf_split_scan_secant_kernel<decltype(kind)::value, decltype(frac)::value>>(
+            256u, it_first, n_iters, it_total, t.m8_max, t.m4_max, (int64_t)kTraceScanHide, c_ref1, c_ref2, grid_x, scan_off,
+            chain_tiles);
     });
 }
 

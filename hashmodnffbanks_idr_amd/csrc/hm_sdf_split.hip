@@ -155,10 +155,7 @@ static int sdf_split_impl(const HmLevels &lv, const hm_mlp_desc *mlp, const floa
         HM_CHECK_LAUNCH("hm_sdf_fwd_split");
         return HM_OK;
     };
-    return hm_frac_dispatch(frac_mode, [&](auto frac) {
-        if (mlp->split_kind == HM_SPLIT_BF16X2) return launch(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
-        return launch(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
-    });
+    return sdf_split_dispatch(mlp, frac_mode, launch);
 }
 
 }  // namespace

@@ -305,3 +305,12 @@ static int sdf_split_net(const char *who, int E, const hm_mlp_desc *mlp, int64_t
     if (*lds > 160 * 1024) return hm_fail(HM_ERR_INVALID, std::string(who) + ": network does not fit the 160 KB LDS tile");
     return HM_OK;
 }
+
+// hm_frac_dispatch + the kind of the network's split image: f(kind, frac)
+template <class F>
+int sdf_split_dispatch(const hm_mlp_desc *mlp, int frac_mode, F &&f) {
+    return hm_frac_dispatch(frac_mode, [&](auto frac) {
+        if (mlp->split_kind == HM_SPLIT_BF16X2) return f(std::integral_constant<int, HM_SPLIT_BF16X2>{}, frac);
+        return f(std::integral_constant<int, HM_SPLIT_F16X2>{}, frac);
+    });
+}

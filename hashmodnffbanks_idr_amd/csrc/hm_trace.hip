@@ -14,48 +14,10 @@
 // (p = cam + t*dir as mul-then-add, t +/- sdf, the secant formula's evaluation order); the file
 // is compiled with -ffp-contract=off.
 #include "hm_common.h"
+#include "hm_trace_host.h"   // the fused launches of hm_sdf.hip
 
 #include <stdlib.h>
 #include <string.h>
-
-// hm_sdf.hip (not exported): rounds [first, rounds) of the sphere-tracing march as one persistent launch
-extern "C" int hm_trace_march_tail(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                   const float *B_fourier, int frac_mode, int body16, const void *trace_args, int first,
-                                   int rounds, void *stream);
-
-extern "C" int hm_trace_secant_persistent(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                          const float *B_fourier, int frac_mode, int tile_points, const void *trace_args,
-                                          int n_iters, int scan_rule, void *stream);
-
-// hm_sdf.hip (not exported): a 64-point-tile scan (the closest-approach scan of the exact mode, or a refinement list of the
-// guarded mode) and the secant refinement as ONE launch (workgroups without secant rays start on the scan at once, 64-point
-// tiles handed out by an atomic cursor).  Iterations [it_first, it_first + n_iters) of a chain of it_total; quarter: the
-// list on the quarter-tile schedule
-extern "C" int hm_trace_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                    const float *B_fourier, int frac_mode, const void *trace_args, int it_first,
-                                    int n_iters, int it_total, int quarter, const float *scan_x, float *scan_out,
-                                    int64_t scan_capacity, int c_scan, int small_front, int c_prev1, int grid1,
-                                    int c_prev2, int grid2, void *stream);
-
-// hm_sdf.hip (not exported), guarded mode: the exact refinement of a list and the approximate closest-approach scan as ONE
-// launch (fp32 tiles of the list first, then this launch's range of the scan's split tiles, each from an atomic cursor of
-// its own; which = 0 / 1: the launch of the list cnt[c_ref1] / cnt[c_ref2])
-extern "C" int hm_trace_refine_scan(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                    const float *B_fourier, int frac_mode, const void *trace_args, int c_ref1, int c_ref2,
-                                    int which, int64_t scan_off, int64_t scan_capacity, int64_t chain_tiles, void *stream);
-
-// hm_sdf.hip (not exported), guarded mode: the secant refinement and the split tiles of the closest-approach scan that the
-// hm_trace_refine_scan launches left over as ONE launch
-extern "C" int hm_trace_split_scan_secant(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
-                                          const float *B_fourier, int frac_mode, const void *trace_args, int it_first,
-                                          int n_iters, int it_total, int c_ref1, int c_ref2, int64_t scan_off,
-                                          int64_t scan_capacity, int64_t chain_tiles, void *stream);
-
-// hm_sdf.hip (not exported): hm_sdf_fwd whose 64-point launch completes its last round with tiles of a second point set
-extern "C" int hm_sdf_fwd_fill(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *x, int64_t n,
-                               const float *table, const float *B_fourier, float *out, int frac_mode, const int32_t *n_dev,
-                               const float *x_fill, float *out_fill, const int32_t *n_fill_dev, const int32_t *prev_dev,
-                               int prev_grid, int *grid64_out, void *stream);
 
 namespace {
 
@@ -347,7 +309,7 @@ __global__ __launch_bounds__(kTB) void closest_reduce_kernel(TraceArgs a) {
 // |a - exact| <= tau is monitored, not assumed: guard_patch_kernel sees both values of every refined sample; a deviation
 // above kGuardTrip = tau / 4 sets the workspace's sticky word, and from then on (the following launches of that call
 // included) every sample is marked, i.e. the scans are all-fp32.  The tripping call itself is still exact (tau/4 < tau).
-// Where the refinements are co-scheduled (trace_forward_impl: cosched) the closest-approach rows are selected BEHIND the
+// Where the refinements are co-scheduled (GUARD_COSCHED, GUARD_POOLED) the closest-approach rows are selected BEHIND the
 // sampler's patch, on a list and a counter of their own (C_GUARD_NC): a call in which the sampler's patch trips the monitor
 // marks every closest-approach sample in that same call already - conservative and still exact; that call's refined count
 // is then larger than with HM_TRACE_OVERLAP=1, where both selections run in front of the one patch.
@@ -495,32 +457,394 @@ __global__ void count_evals_kernel(int32_t *cnt, int rounds, int n_secant) {
     cnt[C_EVALS] = (int32_t)tot;
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// ---- workspace ------------------------------------------------------------------------------------------------------------
+// One description of the per-ray arrays: the workspace's size and the kernels' pointers both follow from these lists, so
+// a new array is added here and nowhere else.  Each list is one block of n elements per member.
+constexpr float *TraceWs::*kRayFloats[] = {&TraceWs::t_s,   &TraceWs::t_e,   &TraceWs::t_min, &TraceWs::t_max, &TraceWs::cur_s,
+                                           &TraceWs::cur_e, &TraceWs::nxt_s, &TraceWs::nxt_e, &TraceWs::z_lo,  &TraceWs::z_hi,
+                                           &TraceWs::v_lo,  &TraceWs::v_hi,  &TraceWs::z};
+constexpr int32_t *TraceWs::*kRayInts[] = {&TraceWs::slot_s,   &TraceWs::slot_e,   &TraceWs::list_samp,
+                                           &TraceWs::list_sec, &TraceWs::list_sel, &TraceWs::tail_slot};
+constexpr uint8_t *TraceWs::*kRayBytes[] = {&TraceWs::live_s, &TraceWs::live_e, &TraceWs::stage,
+                                            &TraceWs::it,     &TraceWs::k,      &TraceWs::is_samp};
+template <class T, size_t K>
+void carve_rays(HmCarve &c, TraceWs &w, T *TraceWs::*const (&members)[K], int64_t n) {
+    T *p = c.take<T>((int64_t)K * n);
+    for (size_t k = 0; k < K; ++k) w.*members[k] = p + (p ? (int64_t)k * n : 0);
+}
 
-struct Layout {
-    size_t off_f, off_i, off_b, off_pts, off_vals, off_cnt, off_emb, off_ref, total;
-    int64_t cap;   // points of one SDF launch; pts / vals hold two such regions (the lazy sampler's second pass)
-};
+constexpr int64_t kWsHeader = 256;   // the guard's sticky word: at the same place for every ray count
+constexpr int kWsRegions = 3;   // regions of `cap` points in pts / vals: first pass (+ other launches), second pass, closest approach
 
-constexpr size_t kWsHeader = 256;   // the guard's sticky word: at the same place for every ray count
-
-Layout make_layout(int64_t n, int n_steps, int emb_width = 0, bool guard = false) {
-    Layout L;
-    L.cap = n * (n_steps > 2 ? n_steps : 2);
-    size_t o = kWsHeader;
-    L.off_f = o; o = align_up(o + sizeof(float) * 13 * (size_t)n, 256);
-    L.off_i = o; o = align_up(o + sizeof(int32_t) * 6 * (size_t)n, 256);
-    L.off_b = o; o = align_up(o + 6 * (size_t)n, 256);
-    L.off_pts = o; o = align_up(o + sizeof(float) * 3 * 3 * (size_t)L.cap, 256);    // three regions of `cap` points
-    L.off_vals = o; o = align_up(o + sizeof(float) * 3 * (size_t)L.cap, 256);
-    L.off_cnt = o; o = align_up(o + sizeof(int32_t) * C_COUNT, 256);
-    L.off_emb = o; o = align_up(o + sizeof(float) * (size_t)emb_width * (size_t)L.cap, 256);   // (filter-bank embedders)
+// [header | per-ray floats | ints | bytes | pts | vals | counters | embedding rows | refinement region]; ws == nullptr: the
+// size only
+struct TraceLayout { TraceWs w; float *emb_ws; int64_t bytes; };
+TraceLayout trace_layout(void *ws, int64_t n, int n_steps, int emb_width, bool guard) {
+    TraceLayout L;
+    TraceWs &w = L.w;
+    HmCarve c(ws);
+    w.cap = n * (n_steps > 2 ? n_steps : 2);    // points of one SDF launch
+    w.guard = c.take<int32_t>(kWsHeader / (int64_t)sizeof(int32_t));
+    carve_rays(c, w, kRayFloats, n);
+    carve_rays(c, w, kRayInts, n);
+    carve_rays(c, w, kRayBytes, n);
+    w.pts = c.take<float>(kWsRegions * 3 * w.cap);
+    w.vals = c.take<float>(kWsRegions * w.cap);
+    w.cnt = c.take<int32_t>(C_COUNT);
+    L.emb_ws = c.take<float>((int64_t)emb_width * w.cap);   // (filter-bank embedders)
     // guarded coarse scans: refinement region for every coarse point of a launch (a tripped guard refines them all):
     // points [cap,3], exact values [cap], slots [cap]
-    L.off_ref = o; o = align_up(o + (guard ? sizeof(float) * 5 * (size_t)L.cap : 0), 256);
-    L.total = o;
+    w.ref_pts = c.take<float>(guard ? 5 * w.cap : 0);
+    w.ref_vals = w.ref_pts + (ws ? 3 * w.cap : 0);
+    w.ref_slot = reinterpret_cast<int32_t *>(w.ref_vals + (ws ? w.cap : 0));
+    L.bytes = c.bytes;
     return L;
 }
+int nffb_emb_width(int n_levels) { return 3 + 8 + 8 * n_levels; }
+
+// ---- the plan: which launches a call enqueues -------------------------------------------------------------------------------
+// Environment switches, read once per call (the tests flip them within one process):
+//   HM_TRACE_OVERLAP            A/B, tests.  unset: the default sequences.  0: the closest-approach scan joins the sampler's
+//                               launch and the secant runs behind it on a few dozen workgroups (no FILL, no co-scheduling).
+//                               1: the default, except that the guarded scans run every launch on its own, with one list
+//                               (GUARD_SERIAL).  2: guarded, the whole scan in front of the secant chain (GUARD_COSCHED).
+//   HM_TRACE_POOL_CHAIN_TILES   A/B, tests.  k >= 0: the chain hides k split tiles per workgroup instead of
+//                               trace_chain_tiles' - 0 leaves the whole scan in front of it.
+//   HM_TRACE_CHAIN_TAIL         A/B, tests.  r >= 0: r secant rounds behind the cut of the chain instead of kTraceChainTail,
+//                               0 = the chain is not cut.
+//   HM_TRACE_TAIL_FIRST         tests.  k >= 1: the march hands over to the persistent kernel after k rounds already.
+//   HM_TRACE_GUARD_NOISE        tests.  f (0 < f < 1): worst-case errors of up to f * tau on the approximate values;
+//                               nan:K: every K-th of them NaN or +Inf (guard_noise_kernel).
+struct TraceSwitches {
+    int overlap, chain_tiles, chain_tail;   // -1: unset
+    int tail_first;                         // 0: unset
+    float noise_amp; int noise_nan;  // 0: none
+};
+TraceSwitches trace_switches() {
+    const auto num = [](const char *name, int unset) {
+        const char *e = getenv(name);
+        return e ? atoi(e) : unset;
+    };
+    TraceSwitches s = {num("HM_TRACE_OVERLAP", -1), num("HM_TRACE_POOL_CHAIN_TILES", -1), num("HM_TRACE_CHAIN_TAIL", -1),
+                       num("HM_TRACE_TAIL_FIRST", 0), 0.0f, 0};
+    const char *e = getenv("HM_TRACE_GUARD_NOISE");
+    if (e && strncmp(e, "nan:", 4) == 0) s.noise_nan = atoi(e + 4) > 0 ? atoi(e + 4) : 0;
+    else if (e) { const double f_ = atof(e); if (f_ > 0.0 && f_ < 1.0) s.noise_amp = (float)(f_ * kGuardTau); }
+    return s;
+}
+
+using TracePlan = hm_trace_plan_info;
+
+// Every decision of a call, from its shape alone: no pointer, no stream.
+TracePlan trace_plan(const hm_trace_cfg &cfg, int64_t n_rays, int tile_points, bool has_nffb, const TraceSwitches &sw) {
+    TracePlan P = {};
+    const bool guard = cfg.coarse_bf16 == 3;
+    const int n_sec = cfg.n_secant_steps;
+    // Closest-approach scan and secant refinement in one launch: training, hash-grid network, tile size left to the
+    // library, a batch of small-tile secant launches
+    const bool overlap_shape = sw.overlap != 0 && cfg.training && !has_nffb && tile_points == 0 && n_sec > 0 && n_rays <= kSdfSmall;
+    const bool fill = overlap_shape && cfg.coarse_bf16 == 0;
+    const bool cosched = guard && overlap_shape && sw.overlap != 1;
+    const bool pooled = cosched && sw.overlap != 2;
+    P.sequence = fill ? HM_TRACE_SEQ_FILL : pooled ? HM_TRACE_SEQ_GUARD_POOLED : cosched ? HM_TRACE_SEQ_GUARD_COSCHED
+                 : guard ? HM_TRACE_SEQ_GUARD_SERIAL : HM_TRACE_SEQ_JOINT;
+    // Guarded scans take the values of the exact scan they stand for, and which fp32 tile body that scan runs on follows
+    // the live count of ITS launch: where the exact mode scans the closest-approach rows in a launch of their own, the
+    // guarded mode evaluates them by their own count too (and the secant picks its tiles by the rule of that launch).
+    P.sel_own = fill || (guard && overlap_shape);
+    // lazy sampler: a first pass over samples 0..head-1 and n_steps-1 only pays when it leaves something out
+    P.head = (cfg.sampler_head >= 1 && cfg.sampler_head + 1 < cfg.n_steps) ? cfg.sampler_head : 0;
+    P.per_ray = P.head > 0 ? P.head + 1 : cfg.n_steps;
+    // (single pass: the first pass IS the sampler's evaluation count; lazy: the second pass adds to it later)
+    P.c_first = P.head > 0 ? (int)C_HEAD_PTS : (int)C_NSAMP_PTS;
+    // Chains of at most the wanted tail run whole in front of the closest-approach rows' refinement.
+    // (The scan's ranges do not follow the cut: the first launch keeps the tiles the whole chain would hide and runs the
+    //  ones its shorter chain does not cover as a last round of all its workgroups, ~165 us.  Counting only the rounds in
+    //  front of the cut sends them to the refine-scan launch instead, whose fp32 workgroups reach the scan late: +290 us
+    //  there on the bench step, profiles/chain_tail_ab.json.)
+    const int tail_want = sw.chain_tail >= 0 ? sw.chain_tail : kTraceChainTail;
+    P.k_tail = (pooled && tail_want > 0 && n_sec > tail_want) ? tail_want : 0;
+    P.chain_tiles = pooled ? trace_chain_tiles(n_sec, sw.chain_tiles >= 0 ? sw.chain_tiles : -1) : 0;
+    P.c_ref2 = (pooled && P.head > 0) ? (int)C_GUARD_N2 : -1;
+    // the guard's exact launch runs the tile body the exact mode's launch of the same live count runs: the 64-point one
+    // with the tile size left to the library (smaller launches were exact already and mark nothing), the caller's otherwise
+    P.guard_min = tile_points == 0 ? kSdfSmall + 1 : 1;
+    if (guard) { P.noise_amp = sw.noise_amp; P.noise_nan = sw.noise_nan; }
+    // The march needs 1 + sphere_tracing_iters rounds when no ray runs a line search, march_rounds when one does in every
+    // iteration.  Hash-grid networks with the tile size left to the library (or fixed at 16) run the surplus rounds as
+    // ONE persistent launch in which every workgroup carries eight rays to the end (hm_sdf.hip: trace_march_tail_kernel;
+    // it returns at once when no ray is left) instead of 30 (empty SDF launch, empty update launch) pairs.
+    const int64_t cap = n_rays * (cfg.n_steps > 2 ? cfg.n_steps : 2);
+    P.march_rounds = 1 + cfg.sphere_tracing_iters * (1 + cfg.line_step_iters);
+    P.march_tail = !has_nffb && (tile_points == 0 || tile_points == 16) && cap >= ((n_rays + 7) / 8) * 16 &&
+                   cfg.line_step_iters > 0;
+    P.march_launched = P.march_tail ? 1 + cfg.sphere_tracing_iters : P.march_rounds;
+    if (P.march_tail && sw.tail_first >= 1 && sw.tail_first < P.march_launched) P.march_launched = sw.tail_first;
+    // The secant refinement.  Hash-grid networks with small-tile SDF launches (tile size left to the library, or 4 / 8 / 16)
+    // and a batch small enough for them: all iterations as ONE launch in which a tile of secant rays stays with its
+    // workgroup (hm_sdf.hip: trace_secant_kernel; the sequences that scan beside the chain have it in their own launches);
+    // otherwise an (SDF launch, update launch) pair per iteration
+    if (n_sec == 0) P.secant = HM_TRACE_SECANT_NONE;
+    else if (fill || cosched) P.secant = HM_TRACE_SECANT_IN_SEQUENCE;
+    else if (!has_nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
+             (tile_points != 0 || n_rays <= kSdfSmall))
+        P.secant = HM_TRACE_SECANT_PERSISTENT;
+    else P.secant = HM_TRACE_SECANT_PER_ITERATION;
+    P.scan_rule = P.secant == HM_TRACE_SECANT_PERSISTENT && P.sel_own;
+    return P;
+}
+
+// ---- the plan's executor: the steps the sequences are made of, then one function per sequence -----------------------------
+struct TraceRun {
+    HmTraceCtx cx; const hm_trace_cfg *cfg;
+    TracePlan P; TraceArgs a;
+    float *emb_ws;   // (filter-bank embedders: the embedding rows of a launch, emb_width floats each)
+    int emb_width;
+
+    // counters of the launches that evaluate the sampler's first pass / the closest-approach rows
+    int c_samp() const { return P.sel_own ? P.c_first : (int)C_BIG_PTS; }
+    int c_sel() const { return P.sel_own ? (int)C_NSEL_PTS : (int)C_BIG_PTS; }
+    int64_t n_scan() const { return a.n * a.n_steps; }                     // capacity of a coarse launch: a whole pass
+    int64_t n_tail() const { return a.n * (a.n_steps - a.head - 1); }      // ... the lazy sampler's second pass
+
+    template <class K, class... A>
+    void launch(K kernel, int64_t threads, A... args) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + kTB - 1) / kTB)), dim3(kTB), 0, as_stream(cx.stream), args...);
+    }
+    template <class K, class... A> void per_ray(K kernel, A... args) { launch(kernel, a.n, a, args...); }
+    // (guard select kernels: a wave per ray)
+    template <class K, class... A> void per_row(K kernel, A... args) { launch(kernel, a.n * (kTB / kGuardRows), a, args...); }
+
+    // One SDF evaluation of up to `capacity` points (*n_dev live) of the region of pts / vals that starts at point `off`.
+    // mode 0: exact fp32, the caller's tile size (march, secant, exact coarse scans); hm_trace_cfg.coarse_bf16 1 / 2 / 3:
+    // coarse scans on the 16-bit matrix cores above kSdfSmall live points, exact fp32 small tiles below.
+    int eval(int64_t off, int64_t capacity, const int32_t *n_dev, int mode = 0) {
+        const float *p = a.w.pts + off * 3;
+        float *v = a.w.vals + off;
+        const int64_t run_min = kSdfSmall + 1;   // (16-bit coarse kernels: the counts the small-tile launch leaves)
+        const int tile = mode ? -1 : cx.tile_points;
+        if (cx.nffb) {   // filter-bank embedder: its own fused kernel, then the MLP on the embedding rows
+            HM_TRY(hm_nffb_fwd(cx.desc, cx.nffb, p, capacity, cx.table, cx.B_fourier, emb_ws, emb_width, cx.frac_mode, n_dev,
+                               cx.stream));
+            HM_TRY(hm_sdf_fwd_emb(cx.mlp, emb_ws, emb_width, emb_width, capacity, v, 1, 1, tile, n_dev, 0, cx.stream));
+            if (!mode) return HM_OK;
+            return mode == 2 ? hm_sdf_fwd_emb_split(cx.mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, cx.stream)
+                             : hm_sdf_fwd_emb_bf16(cx.mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, cx.stream);
+        }
+        if (mode == 3 && cx.tile_points != 0)   // fixed tile size: every count is approximated (and refined on that tile)
+            return hm_sdf_fwd_split(cx.desc, cx.mlp, p, capacity, cx.table, cx.B_fourier, v, 1, cx.frac_mode, n_dev, 1, cx.stream);
+        HM_TRY(hm_sdf_fwd(cx.desc, cx.mlp, p, capacity, cx.table, cx.B_fourier, v, 1, 1, cx.frac_mode, tile, n_dev, 0, cx.stream));
+        if (!mode) return HM_OK;
+        return mode >= 2 ? hm_sdf_fwd_split(cx.desc, cx.mlp, p, capacity, cx.table, cx.B_fourier, v, 1, cx.frac_mode, n_dev, run_min,
+                                            cx.stream)
+                         : hm_sdf_fwd_bf16(cx.desc, cx.mlp, p, capacity, cx.table, cx.B_fourier, v, 1, cx.frac_mode, n_dev, run_min,
+                                           cx.stream);
+    }
+    // the coarse scans (sampler passes, closest approach)
+    int coarse(int64_t off, int64_t capacity, int c_live) { return eval(off, capacity, a.w.cnt + c_live, cfg->coarse_bf16); }
+
+    // The points of the sampler's first pass and of the closest-approach rows.  The mask-loss rays (ray_tracing.py:71-92)
+    // are exactly the rays the sampler does NOT touch, so their n_steps random-fraction samples do not depend on the
+    // sampler's outcome: they are appended behind the sampler's points (one launch over both sets: one dependent launch
+    // and one partial last wave less) or go to a region of their own (sel_own).
+    void first_pass_points() {
+        if (cfg->training) per_ray(tail_prepare_kernel);
+        launch(ray_samples_kernel, a.n * P.per_ray, a, a.w.list_samp, (int)C_NSAMP, P.c_first, a.w.t_s, a.w.t_e, a.fracs, -1,
+               P.per_ray);
+        if (cfg->training)
+            launch(ray_samples_kernel, n_scan(), a, a.w.list_sel, (int)C_NSEL, (int)C_NSEL_PTS, a.w.t_min, a.w.t_max, a.steps_u,
+                   P.sel_own ? -2 : P.c_first, a.n_steps);
+    }
+    // lazy sampler: the remaining samples of the rays the head samples did not resolve
+    void second_pass_points() {
+        per_ray(sampler_head_kernel);
+        launch(sampler_tail_points_kernel, n_scan(), a);
+    }
+
+    // The guard's steps.  Behind the approximate launch(es) of a coarse evaluation: [test noise] -> select -> one exact
+    // launch over the compact refinement region -> patch.
+    void noise(int64_t off, int64_t capacity, int c_live) {
+        if (P.noise_amp > 0.0f || P.noise_nan > 0)
+            launch(guard_noise_kernel, capacity, a.w.vals, off, a.w.cnt + c_live, P.guard_min, P.noise_amp, P.noise_nan);
+    }
+    void select_sampler(int pass, int c_live, int c_live2, int c_ref) {
+        per_row(guard_select_sampler_kernel, pass, c_live, c_live2, P.guard_min, c_ref);
+    }
+    void select_closest(int c_live, int c_ref) { per_row(guard_select_closest_kernel, c_live, P.guard_min, c_ref); }
+    // the stand-alone exact launch.  quarter: a list of at most 16 points per workgroup runs quarter tiles (the same values in
+    // two thirds of the time of the half tiles; only where the launch stands alone - the closest-approach rows' list
+    // behind the secant chain)
+    int refine(int c_ref, bool quarter = false) {
+        return hm_sdf_fwd(cx.desc, cx.mlp, a.w.ref_pts, a.w.cap, cx.table, cx.B_fourier, a.w.ref_vals, 1, 1, cx.frac_mode,
+                          cx.tile_points == 0 ? (quarter ? HM_SDF_TILE64_QUARTER : 64) : cx.tile_points, a.w.cnt + c_ref, 0,
+                          cx.stream);
+    }
+    // ... beside its range of the closest-approach rows' split tiles (which = 0 / 1: the launch of the first / second pass)
+    int refine_beside_scan(int which) {
+        return hm_trace_refine_scan(&cx, &a, C_GUARD_N1, P.c_ref2, which, a.sel_off, n_scan(), P.chain_tiles);
+    }
+    void patch(int c_ref) { launch(guard_patch_kernel, a.w.cap, a, c_ref); }
+    // the lazy sampler's second pass; guarded: its marks see the first pass's (patched) samples too
+    int second_pass() {
+        if (a.head == 0) return HM_OK;
+        second_pass_points();
+        HM_TRY(coarse(a.tail_off, n_tail(), C_TAIL_PTS));
+        if (cfg->coarse_bf16 != 3) return HM_OK;
+        noise(a.tail_off, n_tail(), C_TAIL_PTS);
+        select_sampler(2, C_TAIL_PTS, c_samp(), C_GUARD_N2);
+        // (pooled: the tiles and values of the stand-alone launch, beside its range of the scan)
+        HM_TRY(P.c_ref2 >= 0 ? refine_beside_scan(1) : refine(C_GUARD_N2));
+        patch(C_GUARD_N2);
+        return HM_OK;
+    }
+    // The sampler of the co-scheduled and the pooled sequence: the marks of the first pass are refined beside the
+    // closest-approach rows' approximate scan (all of it, or the refine-scan launches' share of it).  The closest-approach
+    // rows are then selected BEHIND the sampler's patch (see guard_mark_row), on a list of their own.
+    int sampler_beside_scan() {
+        HM_TRY(coarse(0, n_scan(), c_samp()));
+        noise(0, n_scan(), c_samp());
+        select_sampler(1, c_samp(), -1, C_GUARD_N1);
+        HM_TRY(refine_beside_scan(0));
+        patch(C_GUARD_N1);
+        HM_TRY(second_pass());
+        per_ray(sampler_reduce_kernel);
+        per_ray(secant_points_kernel);
+        return HM_OK;
+    }
+    // ... selected here, refined by `refine_launch`, patched and reduced
+    template <class F>
+    int closest_rows_own_list(F refine_launch) {
+        noise(a.sel_off, n_scan(), C_NSEL_PTS);
+        select_closest(C_NSEL_PTS, C_GUARD_NC);
+        HM_TRY(refine_launch());
+        patch(C_GUARD_NC);
+        per_ray(closest_reduce_kernel);
+        return HM_OK;
+    }
+    // the secant chain (or a part of it) with the closest-approach rows' refinement list as the launch's scan
+    int secant_beside_list(int it_first, int n_iters, int quarter) {
+        return hm_trace_scan_secant(&cx, &a, it_first, n_iters, a.n_secant, quarter, a.w.ref_pts, a.w.ref_vals, a.w.cap,
+                                    C_GUARD_NC, 0, -1, 0, -1, 0);
+    }
+    // the sampler's reduction and the secant refinement of the sequences that do not scan beside it
+    int reduce_and_secant() {
+        per_ray(sampler_reduce_kernel);
+        if (P.secant == HM_TRACE_SECANT_NONE) return HM_OK;
+        per_ray(secant_points_kernel);
+        if (P.secant == HM_TRACE_SECANT_PERSISTENT) return hm_trace_secant_persistent(&cx, &a, a.n_secant, P.scan_rule);
+        for (int s = 0; s < a.n_secant; ++s) {
+            HM_TRY(eval(0, a.n, a.w.cnt + C_NSEC));
+            per_ray(secant_advance_kernel, s == a.n_secant - 1 ? 1 : 0);
+        }
+        return HM_OK;
+    }
+
+    // ---- 1. bidirectional sphere tracing: one state-machine round per SDF launch, the surplus rounds as one launch
+    int march() {
+        per_ray(trace_init_kernel);
+        for (int r = 0; r < P.march_launched; ++r) {
+            HM_TRY(eval(0, 2 * a.n, a.w.cnt + C_ROUND0 + r));
+            // round r+1 cursor (the last advance appends nothing that is evaluated; it only closes states)
+            per_ray(trace_advance_kernel, r + 1 < 64 ? r + 1 : 63);
+        }
+        if (P.march_tail) HM_TRY(hm_trace_march_tail(&cx, &a, P.march_launched, P.march_rounds));
+        per_ray(trace_finalize_kernel);
+        return HM_OK;
+    }
+
+    // ---- 2. sampler, closest approach (training) and secant refinement: the plan's sequence, behind first_pass_points()
+    // JOINT: ONE coarse launch over the sampler's points and the closest-approach points behind them (every precision
+    // but the guarded one; the exact mode where the shape or HM_TRACE_OVERLAP=0 rules FILL out).
+    int seq_joint() {
+        HM_TRY(coarse(0, n_scan(), C_BIG_PTS));
+        if (cfg->training) per_ray(closest_reduce_kernel);
+        HM_TRY(second_pass());
+        return reduce_and_secant();
+    }
+    // FILL: closest-approach scan and secant refinement as one launch (hm_sdf.hip: sdf_scan_secant_kernel).  The sampler's
+    // launches evaluate the sampler's points only - and complete their last round with tiles of the scan (fill_quota).
+    int seq_fill() {
+        int grid_p1 = 0, grid_p2 = 0;      // grids of the sampler launches that took filler tiles of the scan
+        const float *x_fill = a.w.pts + a.sel_off * 3;
+        float *out_fill = a.w.vals + a.sel_off;
+        HM_TRY(hm_sdf_fwd_fill(&cx, a.w.pts, n_scan(), a.w.vals, a.w.cnt + P.c_first, x_fill, out_fill, a.w.cnt + C_NSEL_PTS,
+                               nullptr, 0, &grid_p1));
+        if (a.head > 0) {
+            second_pass_points();
+            HM_TRY(hm_sdf_fwd_fill(&cx, a.w.pts + a.tail_off * 3, n_tail(), a.w.vals + a.tail_off, a.w.cnt + C_TAIL_PTS, x_fill,
+                                   out_fill, a.w.cnt + C_NSEL_PTS, a.w.cnt + P.c_first, grid_p1, &grid_p2));
+        }
+        per_ray(sampler_reduce_kernel);
+        per_ray(secant_points_kernel);
+        HM_TRY(hm_trace_scan_secant(&cx, &a, 0, a.n_secant, a.n_secant, 0, x_fill, out_fill, n_scan(), C_NSEL_PTS, 1, P.c_first,
+                                    grid_p1, C_TAIL_PTS, grid_p2));
+        per_ray(closest_reduce_kernel);
+        return HM_OK;
+    }
+    // GUARD_SERIAL: every launch on its own, and ONE list for the first pass's marks and the closest-approach rows'
+    // (both selections in front of the one patch).  The closest-approach rows are behind the sampler's points in one
+    // launch, or - sel_own: HM_TRACE_OVERLAP=1, the A/B form of the two sequences below - in a launch by their own count.
+    int seq_guard_serial() {
+        HM_TRY(coarse(0, n_scan(), c_samp()));
+        if (P.sel_own) HM_TRY(coarse(a.sel_off, n_scan(), c_sel()));
+        noise(0, n_scan(), c_samp());
+        if (P.sel_own) noise(a.sel_off, n_scan(), c_sel());
+        select_sampler(1, c_samp(), -1, C_GUARD_N1);
+        if (cfg->training) select_closest(c_sel(), C_GUARD_N1);
+        HM_TRY(refine(C_GUARD_N1));
+        patch(C_GUARD_N1);
+        if (cfg->training) per_ray(closest_reduce_kernel);
+        HM_TRY(second_pass());
+        return reduce_and_secant();
+    }
+    // GUARD_COSCHED (HM_TRACE_OVERLAP=2: A/B, tests).  Guarded scans keep the chip busy through the guard's exact
+    // refinements, which are one round of fp32 tiles on a third of the chip each: the refinement of the sampler's marks
+    // runs beside the closest-approach rows' split tiles (hm_sdf.hip: sdf_refine_scan_kernel), and the refinement of the
+    // closest-approach rows' marks beside the secant chain (sdf_scan_secant_kernel with the list as its scan) - by the
+    // workgroups the chain leaves free, on the 64-point body whatever the list's length, as refine() asks.  Same tiles,
+    // same values, one stream; the rows of the two lists are disjoint and the sampler's list is patched before the
+    // closest-approach rows are selected, so both lists start at the head of the refinement region.
+    int seq_guard_cosched() {
+        HM_TRY(sampler_beside_scan());
+        return closest_rows_own_list([&] { return secant_beside_list(0, a.n_secant, 0); });
+    }
+    // GUARD_POOLED, the default of the guarded scans: the closest-approach scan is shared out between the launches
+    // (hm_sdf.hip: hm_scan_pool.h).  The refinement launches - both passes' of the lazy sampler - take as many of its split
+    // tiles as they have idle workgroups, the secant chain's launch (sdf_split_scan_secant_kernel) runs the rest beside the
+    // chain, and the closest-approach rows are selected, refined and reduced behind it.
+    // The chain is cut in two launches: the first rounds beside ALL remaining tiles of the scan, then - behind the selection
+    // of the closest-approach rows - the last k_tail rounds with the one round of exact tiles that refines those rows'
+    // marks under them (sdf_scan_secant_kernel<., true>: the tiles and values of refine()'s quarter launch), on the
+    // workgroups that own no secant tile.  The chain's state lives in global memory between rounds, so the cut changes no
+    // value.  k_tail = 0: the whole chain in front, and the list on the quarter launch alone.
+    int seq_guard_pooled() {
+        const int n_front = a.n_secant - P.k_tail;
+        HM_TRY(sampler_beside_scan());
+        HM_TRY(hm_trace_split_scan_secant(&cx, &a, 0, n_front, a.n_secant, C_GUARD_N1, P.c_ref2, a.sel_off, n_scan(),
+                                          P.chain_tiles));
+        return closest_rows_own_list(
+            [&] { return P.k_tail > 0 ? secant_beside_list(n_front, P.k_tail, 1) : refine(C_GUARD_NC, true); });
+    }
+
+    int run(int32_t *stats_out) {
+        hm_zero_u32_async(a.w.cnt, C_COUNT, as_stream(cx.stream));
+        HM_TRY(march());
+        first_pass_points();
+        switch (P.sequence) {
+        case HM_TRACE_SEQ_FILL: HM_TRY(seq_fill()); break;
+        case HM_TRACE_SEQ_GUARD_SERIAL: HM_TRY(seq_guard_serial()); break;
+        case HM_TRACE_SEQ_GUARD_COSCHED: HM_TRY(seq_guard_cosched()); break;
+        case HM_TRACE_SEQ_GUARD_POOLED: HM_TRY(seq_guard_pooled()); break;
+        default: HM_TRY(seq_joint()); break;
+        }
+        hipLaunchKernelGGL(count_evals_kernel, dim3(1), dim3(64), 0, as_stream(cx.stream), a.w.cnt, P.march_rounds + 1, a.n_secant);
+        if (stats_out)
+            hipLaunchKernelGGL(hm_copy_u32_kernel, dim3(1), dim3(64), 0, as_stream(cx.stream), reinterpret_cast<uint32_t *>(stats_out),
+                               reinterpret_cast<const uint32_t *>(a.w.cnt + C_NSAMP), 16);
+        HM_CHECK_LAUNCH("hm_trace_forward");
+        return HM_OK;
+    }
+};
 
 }  // namespace
 
@@ -528,11 +852,11 @@ extern "C" {
 
 int64_t hm_trace_workspace_bytes(int64_t n_rays, const hm_trace_cfg *cfg) {
     if (n_rays < 0 || !cfg || cfg->n_steps < 1) return hm_fail(HM_ERR_INVALID, "hm_trace_workspace_bytes: bad argument");
-    return (int64_t)make_layout(n_rays, cfg->n_steps, 0, cfg->coarse_bf16 == 3).total;
+    return trace_layout(nullptr, n_rays, cfg->n_steps, 0, cfg->coarse_bf16 == 3).bytes;
 }
 
 int hm_trace_guard_clear(void *workspace, int64_t workspace_bytes, void *stream) {
-    HM_CHECK_ARG(workspace && workspace_bytes >= (int64_t)kWsHeader, "hm_trace_guard_clear: no workspace");
+    HM_CHECK_ARG(workspace && workspace_bytes >= kWsHeader, "hm_trace_guard_clear: no workspace");
     hm_zero_u32_async(reinterpret_cast<int32_t *>(workspace), kWsHeader / sizeof(int32_t), as_stream(stream));
     HM_CHECK_LAUNCH("hm_trace_guard_clear");
     return HM_OK;
@@ -548,48 +872,21 @@ int hm_trace_guard_tolerances(float *tau, float *tau_trip) {
 int64_t hm_trace_workspace_bytes_nffb(int64_t n_rays, const hm_trace_cfg *cfg, int n_levels) {
     if (n_rays < 0 || !cfg || cfg->n_steps < 1 || n_levels < 1 || n_levels > HM_MAX_LEVELS)
         return hm_fail(HM_ERR_INVALID, "hm_trace_workspace_bytes_nffb: bad argument");
-    return (int64_t)make_layout(n_rays, cfg->n_steps, 3 + 8 + 8 * n_levels).total;
+    return trace_layout(nullptr, n_rays, cfg->n_steps, nffb_emb_width(n_levels), false).bytes;
 }
 
-static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb, const hm_mlp_desc *mlp,
-                              const float *table, const float *B_fourier, int frac_mode, int tile_points,
-                              const hm_trace_cfg *cfg, const float *cam_loc, const float *ray_dirs,
+int hm_diag_trace_plan(int64_t n_rays, const hm_trace_cfg *cfg, int tile_points, int has_nffb, hm_trace_plan_info *info) {
+    HM_CHECK_ARG(n_rays >= 0 && cfg && info && cfg->n_steps >= 2, "hm_diag_trace_plan: bad argument");
+    *info = trace_plan(*cfg, n_rays, tile_points, has_nffb != 0, trace_switches());
+    return HM_OK;
+}
+
+static int trace_forward_impl(const HmTraceCtx &cx, const hm_trace_cfg *cfg, const float *cam_loc, const float *ray_dirs,
                               const uint8_t *object_mask, const float *t_sphere, const uint8_t *hit_mask, int64_t n_rays,
-                              int64_t rays_per_image, const float *sampler_fracs, const float *steps_u,
-                              float *out_points, uint8_t *out_net_mask, float *out_dists, void *workspace,
-                              int64_t workspace_bytes, int32_t *stats_out, void *stream);
-
-int hm_trace_forward(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
-                     int frac_mode, int tile_points, const hm_trace_cfg *cfg, const float *cam_loc,
-                     const float *ray_dirs, const uint8_t *object_mask, const float *t_sphere,
-                     const uint8_t *hit_mask, int64_t n_rays, int64_t rays_per_image, const float *sampler_fracs,
-                     const float *steps_u, float *out_points, uint8_t *out_net_mask, float *out_dists,
-                     void *workspace, int64_t workspace_bytes, int32_t *stats_out, void *stream) {
-    return trace_forward_impl(desc, nullptr, mlp, table, B_fourier, frac_mode, tile_points, cfg, cam_loc, ray_dirs,
-                              object_mask, t_sphere, hit_mask, n_rays, rays_per_image, sampler_fracs, steps_u, out_points,
-                              out_net_mask, out_dists, workspace, workspace_bytes, stats_out, stream);
-}
-
-int hm_trace_forward_nffb(const hm_grid_desc *desc, const hm_nffb_desc *nffb, const hm_mlp_desc *mlp, const float *table,
-                          const float *B_fourier, int frac_mode, int tile_points, const hm_trace_cfg *cfg,
-                          const float *cam_loc, const float *ray_dirs, const uint8_t *object_mask, const float *t_sphere,
-                          const uint8_t *hit_mask, int64_t n_rays, int64_t rays_per_image, const float *sampler_fracs,
-                          const float *steps_u, float *out_points, uint8_t *out_net_mask, float *out_dists,
-                          void *workspace, int64_t workspace_bytes, int32_t *stats_out, void *stream) {
-    HM_CHECK_ARG(nffb != nullptr, "hm_trace_forward_nffb: NULL embedder descriptor");
-    return trace_forward_impl(desc, nffb, mlp, table, B_fourier, frac_mode, tile_points, cfg, cam_loc, ray_dirs,
-                              object_mask, t_sphere, hit_mask, n_rays, rays_per_image, sampler_fracs, steps_u, out_points,
-                              out_net_mask, out_dists, workspace, workspace_bytes, stats_out, stream);
-}
-
-static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb, const hm_mlp_desc *mlp,
-                              const float *table, const float *B_fourier, int frac_mode, int tile_points,
-                              const hm_trace_cfg *cfg, const float *cam_loc, const float *ray_dirs,
-                              const uint8_t *object_mask, const float *t_sphere, const uint8_t *hit_mask, int64_t n_rays,
-                              int64_t rays_per_image, const float *sampler_fracs, const float *steps_u,
-                              float *out_points, uint8_t *out_net_mask, float *out_dists, void *workspace,
-                              int64_t workspace_bytes, int32_t *stats_out, void *stream) {
-    HM_CHECK_ARG(desc && mlp && cfg, "hm_trace_forward: NULL descriptor");
+                              int64_t rays_per_image, const float *sampler_fracs, const float *steps_u, float *out_points,
+                              uint8_t *out_net_mask, float *out_dists, void *workspace, int64_t workspace_bytes,
+                              int32_t *stats_out) {
+    HM_CHECK_ARG(cx.desc && cx.mlp && cfg, "hm_trace_forward: NULL descriptor");
     HM_CHECK_ARG(n_rays >= 0 && rays_per_image >= 1, "hm_trace_forward: bad ray counts");
     HM_CHECK_ARG(cfg->n_steps >= 2 && cfg->n_steps <= 4096, "hm_trace_forward: n_steps out of range");
     HM_CHECK_ARG(cfg->sphere_tracing_iters >= 0 && cfg->sphere_tracing_iters <= 15 && cfg->line_step_iters >= 0 &&
@@ -599,39 +896,23 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     HM_CHECK_ARG(cfg->n_secant_steps >= 0 && cfg->n_secant_steps <= 64, "hm_trace_forward: n_secant_steps out of range");
     if (n_rays == 0) return HM_OK;
     HM_CHECK_ARG(n_rays * (int64_t)cfg->n_steps < (1ll << 31), "hm_trace_forward: too many rays for one call");
-    HM_CHECK_ARG(table && B_fourier && cam_loc && ray_dirs && object_mask && t_sphere && hit_mask && sampler_fracs &&
+    HM_CHECK_ARG(cx.table && cx.B_fourier && cam_loc && ray_dirs && object_mask && t_sphere && hit_mask && sampler_fracs &&
                      out_points && out_net_mask && out_dists && workspace,
                  "hm_trace_forward: NULL pointer");
     HM_CHECK_ARG(!cfg->training || steps_u, "hm_trace_forward: training mode needs steps_u");
     HM_CHECK_ARG(cfg->coarse_bf16 >= 0 && cfg->coarse_bf16 <= 3, "hm_trace_forward: coarse_bf16 must be 0, 1, 2 or 3");
     const bool guard = cfg->coarse_bf16 == 3;
-    HM_CHECK_ARG(!guard || !nffb, "hm_trace_forward: the guarded coarse scans do not cover filter-bank embedders");
+    HM_CHECK_ARG(!guard || !cx.nffb, "hm_trace_forward: the guarded coarse scans do not cover filter-bank embedders");
     HM_CHECK_ARG(!guard || 3 * n_rays * (int64_t)cfg->n_steps < (1ll << 31), "hm_trace_forward: too many rays for one call");
-    const int emb_width = nffb ? 3 + 8 + 8 * nffb->n_levels : 0;
-    const Layout L = make_layout(n_rays, cfg->n_steps, emb_width, guard);
-    HM_CHECK_ARG(workspace_bytes >= (int64_t)L.total, "hm_trace_forward: workspace too small");
-    hipStream_t st = as_stream(stream);
-    char *base = static_cast<char *>(workspace);
-    const size_t n = (size_t)n_rays;
-    TraceArgs a;
-    float *f = reinterpret_cast<float *>(base + L.off_f);
-    a.w.t_s = f; a.w.t_e = f + n; a.w.t_min = f + 2 * n; a.w.t_max = f + 3 * n; a.w.cur_s = f + 4 * n;
-    a.w.cur_e = f + 5 * n; a.w.nxt_s = f + 6 * n; a.w.nxt_e = f + 7 * n; a.w.z_lo = f + 8 * n; a.w.z_hi = f + 9 * n;
-    a.w.v_lo = f + 10 * n; a.w.v_hi = f + 11 * n; a.w.z = f + 12 * n;
-    int32_t *ip = reinterpret_cast<int32_t *>(base + L.off_i);
-    a.w.slot_s = ip; a.w.slot_e = ip + n; a.w.list_samp = ip + 2 * n; a.w.list_sec = ip + 3 * n; a.w.list_sel = ip + 4 * n;
-    a.w.tail_slot = ip + 5 * n;
-    uint8_t *bp = reinterpret_cast<uint8_t *>(base + L.off_b);
-    a.w.live_s = bp; a.w.live_e = bp + n; a.w.stage = bp + 2 * n; a.w.it = bp + 3 * n; a.w.k = bp + 4 * n;
-    a.w.is_samp = bp + 5 * n;
-    a.w.pts = reinterpret_cast<float *>(base + L.off_pts);
-    a.w.vals = reinterpret_cast<float *>(base + L.off_vals);
-    a.w.cnt = reinterpret_cast<int32_t *>(base + L.off_cnt);
-    a.w.cap = L.cap;
-    a.w.ref_pts = reinterpret_cast<float *>(base + L.off_ref);
-    a.w.ref_vals = a.w.ref_pts + 3 * (size_t)L.cap;
-    a.w.ref_slot = reinterpret_cast<int32_t *>(a.w.ref_vals + (size_t)L.cap);
-    a.w.guard = reinterpret_cast<int32_t *>(base);
+    TraceRun R;
+    R.cx = cx; R.cfg = cfg;
+    R.P = trace_plan(*cfg, n_rays, cx.tile_points, cx.nffb != nullptr, trace_switches());
+    R.emb_width = cx.nffb ? nffb_emb_width(cx.nffb->n_levels) : 0;
+    const TraceLayout L = trace_layout(workspace, n_rays, cfg->n_steps, R.emb_width, guard);
+    HM_CHECK_ARG(workspace_bytes >= L.bytes, "hm_trace_forward: workspace too small");
+    R.emb_ws = L.emb_ws;
+    TraceArgs &a = R.a;
+    a.w = L.w;
     a.cam = cam_loc; a.dirs = ray_dirs; a.obj = object_mask; a.t_sphere = t_sphere; a.hit = hit_mask;
     a.fracs = sampler_fracs; a.steps_u = steps_u;
     a.out_pts = out_points; a.out_mask = out_net_mask; a.out_t = out_dists;
@@ -640,303 +921,33 @@ static int trace_forward_impl(const hm_grid_desc *desc, const hm_nffb_desc *nffb
     for (int k = 0; k < 4; ++k) a.back[k] = (float)((1.0 - cfg->line_search_step) / (double)(1 << k));
     a.ls_iters = cfg->line_step_iters; a.max_it = cfg->sphere_tracing_iters; a.n_steps = cfg->n_steps;
     a.n_secant = cfg->n_secant_steps; a.training = cfg->training;
-    // lazy sampler: a first pass over samples 0..head-1 and n_steps-1 only pays when it leaves something out
-    a.head = (cfg->sampler_head >= 1 && cfg->sampler_head + 1 < cfg->n_steps) ? cfg->sampler_head : 0;
-    a.tail_off = L.cap;
-    // Closest-approach scan and secant refinement as one launch (hm_sdf.hip: sdf_scan_secant_kernel): training, hash-grid
-    // network, exact-fp32 coarse scans, tile size left to the library.  HM_TRACE_OVERLAP=0: the scan joins the sampler's
-    // launch and the secant runs behind it on a few dozen workgroups (A/B).  =1: the default, except that the guarded
-    // scans run every launch on its own (see cosched below).
-    const char *e_ov = getenv("HM_TRACE_OVERLAP");      // (read per call: the tests compare both forms in one process)
-    const bool overlap_ok = !(e_ov && atoi(e_ov) == 0);
-    const bool overlap_shape = overlap_ok && cfg->training && !nffb && tile_points == 0 && cfg->n_secant_steps > 0 &&
-                               n_rays <= kSdfSmall;
-    const bool overlap = overlap_shape && !cfg->coarse_bf16;
-    // Guarded scans take the values of the exact scan they stand for, and which fp32 tile body that scan runs on follows
-    // the live count of ITS launch: where the exact mode scans the closest-approach rows in a launch of their own, the
-    // guarded mode evaluates them by their own count too (and the secant picks its tiles by the rule of that launch).
-    const bool sel_own = overlap || (guard && overlap_shape);
-    a.sel_off = sel_own ? 2 * L.cap : -1;
-    // Guarded scans of that shape keep the chip busy through the guard's exact refinements, which are one round of fp32
-    // tiles on a third of the chip each: the refinement of the sampler's marks runs beside the closest-approach rows' split
-    // tiles (hm_sdf.hip: sdf_refine_scan_kernel), and the refinement of the closest-approach rows' marks beside the secant
-    // chain (sdf_scan_secant_kernel with the list as its scan).  Same tiles, same values, one stream; the rows of the two
-    // lists are disjoint and the sampler's list is patched before the closest-approach rows are selected, so both lists
-    // start at the head of the refinement region.  HM_TRACE_OVERLAP=1: every launch on its own, one list (A/B, tests).
-    const bool cosched = guard && overlap_shape && !(e_ov && atoi(e_ov) == 1);
-    // The default shares the closest-approach scan out between the launches (hm_sdf.hip: hm_scan_pool.h): the refinement
-    // launches - both passes' of the lazy sampler - take as many of its split tiles as they have idle workgroups, the
-    // secant chain's launch (sdf_split_scan_secant_kernel) runs the rest beside the chain, and the closest-approach rows
-    // are selected, refined (a plain 64-point launch) and reduced behind it.  HM_TRACE_OVERLAP=2: the sequence above, the
-    // whole scan in front of the chain (A/B, tests).  HM_TRACE_POOL_CHAIN_TILES=k (A/B, tests; read per call): the chain
-    // hides k tiles per workgroup instead of trace_chain_tiles' - 0 leaves the whole scan in front of it.
-    const bool pool = cosched && !(e_ov && atoi(e_ov) == 2);
-    const char *e_ct = getenv("HM_TRACE_POOL_CHAIN_TILES");
-    // The pooled sequence cuts the secant chain in two launches: the first rounds beside ALL remaining tiles of the scan,
-    // then - behind the selection of the closest-approach rows - the last k_tail rounds with the one round of exact tiles
-    // that refines those rows' marks under them (sdf_scan_secant_kernel<., true>), on the workgroups that own no secant tile.
-    // The chain's state lives in global memory between rounds, so the cut changes no value.  Chains of at most k_tail
-    // rounds run whole in front of the refinement.  HM_TRACE_CHAIN_TAIL=r (A/B, tests; read per call): r rounds behind the
-    // cut, 0 = none.
-    const char *e_tl = getenv("HM_TRACE_CHAIN_TAIL");
-    const int tail_want = (e_tl && atoi(e_tl) >= 0) ? atoi(e_tl) : kTraceChainTail;
-    const int k_tail = (pool && tail_want > 0 && cfg->n_secant_steps > tail_want) ? tail_want : 0;
-    // (The scan's ranges do not follow the cut: the first launch keeps the tiles the whole chain would hide and runs the
-    //  ones its shorter chain does not cover as a last round of all its workgroups, ~165 us.  Counting only the rounds in
-    //  front of the cut sends them to the refine-scan launch instead, whose fp32 workgroups reach the scan late: +290 us
-    //  there on the bench step, profiles/chain_tail_ab.json.)
-    const int64_t chain_tiles = pool ? trace_chain_tiles(cfg->n_secant_steps, (e_ct && atoi(e_ct) >= 0) ? atoi(e_ct) : -1) : 0;
-    const int c_ref2 = (pool && a.head > 0) ? (int)C_GUARD_N2 : -1;    // list of the second refine-scan launch
+    a.head = R.P.head;
+    a.tail_off = a.w.cap;
+    a.sel_off = R.P.sel_own ? 2 * a.w.cap : -1;
+    return R.run(stats_out);
+}
 
-    hm_zero_u32_async(a.w.cnt, C_COUNT, st);
-    const unsigned g_rays = (unsigned)((n_rays + kTB - 1) / kTB);
-    const unsigned g_samp = (unsigned)((n_rays * cfg->n_steps + kTB - 1) / kTB);
-    const unsigned g_rows = (unsigned)((n_rays + kGuardRows - 1) / kGuardRows);   // guard select kernels: a wave per ray
+int hm_trace_forward(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table, const float *B_fourier,
+                     int frac_mode, int tile_points, const hm_trace_cfg *cfg, const float *cam_loc,
+                     const float *ray_dirs, const uint8_t *object_mask, const float *t_sphere,
+                     const uint8_t *hit_mask, int64_t n_rays, int64_t rays_per_image, const float *sampler_fracs,
+                     const float *steps_u, float *out_points, uint8_t *out_net_mask, float *out_dists,
+                     void *workspace, int64_t workspace_bytes, int32_t *stats_out, void *stream) {
+    return trace_forward_impl({desc, nullptr, mlp, table, B_fourier, frac_mode, tile_points, stream}, cfg, cam_loc, ray_dirs,
+                              object_mask, t_sphere, hit_mask, n_rays, rays_per_image, sampler_fracs, steps_u, out_points,
+                              out_net_mask, out_dists, workspace, workspace_bytes, stats_out);
+}
 
-    float *emb_ws = reinterpret_cast<float *>(base + L.off_emb);
-    auto sdf = [&](int64_t capacity, const int32_t *n_dev) -> int {
-        if (nffb) {   // filter-bank embedder: its own fused kernel, then the MLP on the embedding rows
-            const int rc = hm_nffb_fwd(desc, nffb, a.w.pts, capacity, table, B_fourier, emb_ws, emb_width, frac_mode,
-                                       n_dev, stream);
-            if (rc != HM_OK) return rc;
-            return hm_sdf_fwd_emb(mlp, emb_ws, emb_width, emb_width, capacity, a.w.vals, 1, 1, tile_points, n_dev, 0,
-                                  stream);
-        }
-        return hm_sdf_fwd(desc, mlp, a.w.pts, capacity, table, B_fourier, a.w.vals, 1, 1, frac_mode, tile_points, n_dev,
-                          0, stream);
-    };
-    // the coarse scans (sampler passes, closest approach): `off` = first point of the region in pts / vals
-    auto coarse = [&](int64_t off, int64_t capacity, const int32_t *n_dev) -> int {
-        const float *p = a.w.pts + off * 3;
-        float *v = a.w.vals + off;
-        const int64_t run_min = kSdfSmall + 1;   // (16-bit coarse kernels: the counts the small-tile launch leaves)
-        int rc;
-        if (!cfg->coarse_bf16) {
-            if (nffb) {
-                rc = hm_nffb_fwd(desc, nffb, p, capacity, table, B_fourier, emb_ws, emb_width, frac_mode, n_dev, stream);
-                if (rc == HM_OK)
-                    rc = hm_sdf_fwd_emb(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, 1, tile_points, n_dev, 0, stream);
-            } else {
-                rc = hm_sdf_fwd(desc, mlp, p, capacity, table, B_fourier, v, 1, 1, frac_mode, tile_points, n_dev, 0, stream);
-            }
-        } else if (nffb) {   // coarse scans on the 16-bit matrix cores above kSdfSmall live points, exact fp32 small tiles below
-            rc = hm_nffb_fwd(desc, nffb, p, capacity, table, B_fourier, emb_ws, emb_width, frac_mode, n_dev, stream);
-            if (rc == HM_OK)
-                rc = hm_sdf_fwd_emb(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, 1, -1, n_dev, 0, stream);
-            if (rc == HM_OK)
-                rc = cfg->coarse_bf16 == 2
-                         ? hm_sdf_fwd_emb_split(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, stream)
-                         : hm_sdf_fwd_emb_bf16(mlp, emb_ws, emb_width, emb_width, capacity, v, 1, n_dev, run_min, stream);
-        } else if (guard && tile_points != 0) {   // fixed tile size: every count is approximated (and refined on that tile)
-            rc = hm_sdf_fwd_split(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, 1, stream);
-        } else {
-            rc = hm_sdf_fwd(desc, mlp, p, capacity, table, B_fourier, v, 1, 1, frac_mode, -1, n_dev, 0, stream);
-            if (rc == HM_OK)
-                rc = cfg->coarse_bf16 >= 2
-                         ? hm_sdf_fwd_split(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, run_min, stream)
-                         : hm_sdf_fwd_bf16(desc, mlp, p, capacity, table, B_fourier, v, 1, frac_mode, n_dev, run_min, stream);
-        }
-        return rc;
-    };
-    // Guarded mode, behind the approximate launch(es) of a coarse evaluation: [test noise] -> select -> one exact launch
-    // over the compact refinement region -> patch.  The exact launch runs the tile body the exact mode's launch of the
-    // same live count runs: the 64-point one with the tile size left to the library (smaller launches were exact already
-    // and mark nothing: guard_min), the caller's otherwise.
-    const int64_t guard_min = tile_points == 0 ? kSdfSmall + 1 : 1;
-    float noise_amp = 0.0f;
-    int noise_nan = 0;
-    if (guard) {   // HM_TRACE_GUARD_NOISE = f (0 < f < 1) | nan:K  (tests; read per call)
-        const char *e = getenv("HM_TRACE_GUARD_NOISE");
-        if (e && strncmp(e, "nan:", 4) == 0) noise_nan = atoi(e + 4) > 0 ? atoi(e + 4) : 0;
-        else if (e) { const double f_ = atof(e); if (f_ > 0.0 && f_ < 1.0) noise_amp = (float)(f_ * kGuardTau); }
-    }
-    auto guard_noise = [&](int64_t off, int64_t capacity, int c_live) {
-        if (noise_amp > 0.0f || noise_nan > 0)
-            hipLaunchKernelGGL(guard_noise_kernel, dim3((unsigned)((capacity + kTB - 1) / kTB)), dim3(kTB), 0, st, a.w.vals,
-                               off, a.w.cnt + c_live, guard_min, noise_amp, noise_nan);
-    };
-    auto guard_patch = [&](int c_ref) {
-        hipLaunchKernelGGL(guard_patch_kernel, dim3((unsigned)((L.cap + kTB - 1) / kTB)), dim3(kTB), 0, st, a, c_ref);
-    };
-    // quarter: a list of at most 16 points per workgroup runs quarter tiles (the same values in two thirds of the time of the half
-    // tiles; only where the launch stands alone - the closest-approach rows' list behind the secant chain)
-    auto guard_refine = [&](int c_ref, bool quarter = false) -> int {
-        const int rc = hm_sdf_fwd(desc, mlp, a.w.ref_pts, L.cap, table, B_fourier, a.w.ref_vals, 1, 1, frac_mode,
-                                  tile_points == 0 ? (quarter ? HM_SDF_TILE64_QUARTER : 64) : tile_points,
-                                  a.w.cnt + c_ref, 0, stream);
-        if (rc != HM_OK) return rc;
-        guard_patch(c_ref);
-        return HM_OK;
-    };
-
-    // ---- 1. bidirectional sphere tracing: one state-machine round per SDF launch -------------------
-    // 1 + sphere_tracing_iters rounds are needed when no ray runs a line search, `rounds` when one does in every
-    // iteration.  Hash-grid networks with the tile size left to the library (or fixed at 16) run the surplus rounds as
-    // ONE persistent launch in which every workgroup carries eight rays to the end (hm_sdf.hip: trace_march_tail_kernel;
-    // it returns at once when no ray is left) instead of 30 (empty SDF launch, empty update launch) pairs.
-    const int rounds = 1 + cfg->sphere_tracing_iters * (1 + cfg->line_step_iters);
-    const bool tail = !nffb && (tile_points == 0 || tile_points == 16) &&
-                      a.w.cap >= ((n_rays + 7) / 8) * 16 && cfg->line_step_iters > 0;
-    int launched = tail ? 1 + cfg->sphere_tracing_iters : rounds;
-    if (tail) {   // HM_TRACE_TAIL_FIRST=k (tests): hand over to the persistent kernel after k rounds already (read per call)
-        const char *e = getenv("HM_TRACE_TAIL_FIRST");
-        const int k = e ? atoi(e) : 0;
-        if (k >= 1 && k < launched) launched = k;
-    }
-    hipLaunchKernelGGL(trace_init_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-    for (int r = 0; r < launched; ++r) {
-        int rc = sdf(2 * n_rays, a.w.cnt + C_ROUND0 + r);
-        if (rc != HM_OK) return rc;
-        // round r+1 cursor (the last advance appends nothing that is evaluated; it only closes states)
-        hipLaunchKernelGGL(trace_advance_kernel, dim3(g_rays), dim3(kTB), 0, st, a, r + 1 < 64 ? r + 1 : 63);
-    }
-    if (tail) {
-        const int rc = hm_trace_march_tail(desc, mlp, table, B_fourier, frac_mode, tile_points == 16 ? 1 : 0, &a, launched,
-                                           rounds, stream);
-        if (rc != HM_OK) return rc;
-    }
-    hipLaunchKernelGGL(trace_finalize_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-
-    // ---- 2. sampler + (training) closest approach: ONE SDF launch over both point sets ----------------------
-    // The mask-loss rays (ray_tracing.py:71-92) are exactly the rays the sampler does NOT touch, so their
-    // n_steps random-fraction samples do not depend on the sampler's outcome: they are appended behind the
-    // sampler's points and evaluated by the same launch (one dependent launch and one partial last wave less).
-    if (cfg->training) hipLaunchKernelGGL(tail_prepare_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-    const int per_ray = a.head > 0 ? a.head + 1 : cfg->n_steps;    // samples per ray in the sampler's first pass
-    // (single pass: the first pass IS the sampler's evaluation count; lazy: the second pass adds to it later)
-    const int c_first = a.head > 0 ? (int)C_HEAD_PTS : (int)C_NSAMP_PTS;
-    hipLaunchKernelGGL(ray_samples_kernel, dim3((unsigned)((n_rays * per_ray + kTB - 1) / kTB)), dim3(kTB), 0, st, a,
-                       a.w.list_samp, (int)C_NSAMP, c_first, a.w.t_s, a.w.t_e, sampler_fracs, -1, per_ray);
-    if (cfg->training)
-        hipLaunchKernelGGL(ray_samples_kernel, dim3(g_samp), dim3(kTB), 0, st, a, a.w.list_sel, (int)C_NSEL,
-                           (int)C_NSEL_PTS, a.w.t_min, a.w.t_max, steps_u, sel_own ? -2 : c_first, cfg->n_steps);
-    int grid_p1 = 0, grid_p2 = 0;      // overlap: grids of the sampler launches that took filler tiles of the scan
-    if (overlap) {
-        // the sampler's points only - the closest-approach scan runs with the secant refinement below, except for the
-        // tiles that complete the last round of this launch (hm_sdf.hip: fill_quota)
-        int rc = hm_sdf_fwd_fill(desc, mlp, a.w.pts, n_rays * cfg->n_steps, table, B_fourier, a.w.vals, frac_mode,
-                                 a.w.cnt + c_first, a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, a.w.cnt + C_NSEL_PTS,
-                                 nullptr, 0, &grid_p1, stream);
-        if (rc != HM_OK) return rc;
-    } else {
-        // (guarded, closest-approach rows in their own region: two launches, each by its own count)
-        const int c_samp = sel_own ? c_first : (int)C_BIG_PTS, c_sel = sel_own ? (int)C_NSEL_PTS : (int)C_BIG_PTS;
-        int rc = coarse(0, n_rays * cfg->n_steps, a.w.cnt + c_samp);
-        if (rc == HM_OK && sel_own && !cosched) rc = coarse(a.sel_off, n_rays * cfg->n_steps, a.w.cnt + c_sel);
-        if (rc != HM_OK) return rc;
-        if (cosched) {
-            // the sampler's marks are refined beside the closest-approach rows' approximate scan; those rows are selected,
-            // refined and reduced with the secant chain below
-            guard_noise(0, n_rays * cfg->n_steps, c_samp);
-            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
-                               (int)C_GUARD_N1);
-            rc = hm_trace_refine_scan(desc, mlp, table, B_fourier, frac_mode, &a, (int)C_GUARD_N1, c_ref2, 0, a.sel_off,
-                                      n_rays * cfg->n_steps, chain_tiles, stream);
-            if (rc != HM_OK) return rc;
-            guard_patch((int)C_GUARD_N1);
-        } else if (guard) {
-            guard_noise(0, n_rays * cfg->n_steps, c_samp);
-            if (sel_own) guard_noise(a.sel_off, n_rays * cfg->n_steps, c_sel);
-            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 1, c_samp, -1, guard_min,
-                               (int)C_GUARD_N1);
-            if (cfg->training)
-                hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, c_sel, guard_min,
-                                   (int)C_GUARD_N1);
-            rc = guard_refine((int)C_GUARD_N1);
-            if (rc != HM_OK) return rc;
-        }
-    }
-    if (cfg->training && !overlap && !cosched) hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-    if (a.head > 0) {   // second pass: the remaining samples of the rays the head samples did not resolve
-        hipLaunchKernelGGL(sampler_head_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-        hipLaunchKernelGGL(sampler_tail_points_kernel, dim3(g_samp), dim3(kTB), 0, st, a);
-        int rc = overlap ? hm_sdf_fwd_fill(desc, mlp, a.w.pts + a.tail_off * 3, n_rays * (cfg->n_steps - a.head - 1), table,
-                                           B_fourier, a.w.vals + a.tail_off, frac_mode, a.w.cnt + C_TAIL_PTS,
-                                           a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, a.w.cnt + C_NSEL_PTS,
-                                           a.w.cnt + c_first, grid_p1, &grid_p2, stream)
-                         : coarse(a.tail_off, n_rays * (cfg->n_steps - a.head - 1), a.w.cnt + C_TAIL_PTS);
-        if (rc != HM_OK) return rc;
-        if (guard) {
-            guard_noise(a.tail_off, n_rays * (cfg->n_steps - a.head - 1), (int)C_TAIL_PTS);
-            hipLaunchKernelGGL(guard_select_sampler_kernel, dim3(g_rows), dim3(kTB), 0, st, a, 2, (int)C_TAIL_PTS,
-                               sel_own ? c_first : (int)C_BIG_PTS, guard_min, (int)C_GUARD_N2);
-            if (c_ref2 >= 0) {   // (the tiles and values of guard_refine's launch, beside its range of the scan)
-                rc = hm_trace_refine_scan(desc, mlp, table, B_fourier, frac_mode, &a, (int)C_GUARD_N1, c_ref2, 1, a.sel_off,
-                                          n_rays * cfg->n_steps, chain_tiles, stream);
-                guard_patch(c_ref2);
-            } else {
-                rc = guard_refine((int)C_GUARD_N2);
-            }
-            if (rc != HM_OK) return rc;
-        }
-    }
-    hipLaunchKernelGGL(sampler_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-    if (cfg->n_secant_steps > 0) {
-        hipLaunchKernelGGL(secant_points_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-        // hash-grid networks with small-tile SDF launches (tile size left to the library, or 4 / 8 / 16) and a batch
-        // small enough for them: all iterations as ONE launch in which a tile of secant rays stays with its workgroup
-        // (hm_sdf.hip: trace_secant_kernel; with the closest-approach scan in the same launch: sdf_scan_secant_kernel);
-        // otherwise an (SDF launch, update launch) pair per iteration
-        if (overlap) {
-            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, 0, cfg->n_secant_steps,
-                                                cfg->n_secant_steps, 0, a.w.pts + a.sel_off * 3, a.w.vals + a.sel_off, n_rays * cfg->n_steps,
-                                                (int)C_NSEL_PTS, 1, c_first, grid_p1, (int)C_TAIL_PTS, grid_p2, stream);
-            if (rc != HM_OK) return rc;
-            hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-        } else if (pool) {
-            // the rest of the closest-approach scan runs beside the chain; its rows' marks (selected behind the sampler's
-            // patch: see guard_mark_row) are refined behind it
-            const int n_front = cfg->n_secant_steps - k_tail;
-            int rc = hm_trace_split_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, 0, n_front, cfg->n_secant_steps,
-                                                (int)C_GUARD_N1, c_ref2, a.sel_off, n_rays * cfg->n_steps, chain_tiles,
-                                                stream);
-            if (rc != HM_OK) return rc;
-            guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
-            hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
-                               (int)C_GUARD_NC);
-            if (k_tail > 0) {
-                // the chain's last rounds with the list under them: the tiles and values of guard_refine's quarter launch
-                // (no secant ray, which only the device knows: that launch alone)
-                rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, n_front, k_tail, cfg->n_secant_steps, 1,
-                                          a.w.ref_pts, a.w.ref_vals, L.cap, (int)C_GUARD_NC, 0, -1, 0, -1, 0, stream);
-                if (rc == HM_OK) guard_patch((int)C_GUARD_NC);
-            } else {
-                rc = guard_refine((int)C_GUARD_NC, true);
-            }
-            if (rc != HM_OK) return rc;
-            hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-        } else if (cosched) {
-            // the closest-approach rows' marks (selected behind the sampler's patch: see guard_mark_row) are refined by the
-            // workgroups the secant chain leaves free - the 64-point body whatever the list's length, as guard_refine asks
-            guard_noise(a.sel_off, n_rays * cfg->n_steps, (int)C_NSEL_PTS);
-            hipLaunchKernelGGL(guard_select_closest_kernel, dim3(g_rows), dim3(kTB), 0, st, a, (int)C_NSEL_PTS, guard_min,
-                               (int)C_GUARD_NC);
-            const int rc = hm_trace_scan_secant(desc, mlp, table, B_fourier, frac_mode, &a, 0, cfg->n_secant_steps,
-                                                cfg->n_secant_steps, 0, a.w.ref_pts, a.w.ref_vals, L.cap, (int)C_GUARD_NC, 0, -1, 0, -1, 0, stream);
-            if (rc != HM_OK) return rc;
-            guard_patch((int)C_GUARD_NC);
-            hipLaunchKernelGGL(closest_reduce_kernel, dim3(g_rays), dim3(kTB), 0, st, a);
-        } else if (!nffb && (tile_points == 0 || tile_points == 4 || tile_points == 8 || tile_points == 16) &&
-            (tile_points != 0 || n_rays <= kSdfSmall)) {
-            const int rc = hm_trace_secant_persistent(desc, mlp, table, B_fourier, frac_mode, tile_points, &a,
-                                                      cfg->n_secant_steps, sel_own ? 1 : 0, stream);
-            if (rc != HM_OK) return rc;
-        } else {
-            for (int s = 0; s < cfg->n_secant_steps; ++s) {
-                int rc = sdf(n_rays, a.w.cnt + C_NSEC);
-                if (rc != HM_OK) return rc;
-                hipLaunchKernelGGL(secant_advance_kernel, dim3(g_rays), dim3(kTB), 0, st, a,
-                                   s == cfg->n_secant_steps - 1 ? 1 : 0);
-            }
-        }
-    }
-    hipLaunchKernelGGL(count_evals_kernel, dim3(1), dim3(64), 0, st, a.w.cnt, rounds + 1, cfg->n_secant_steps);
-    if (stats_out) {
-        hipLaunchKernelGGL(hm_copy_u32_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t *>(stats_out),
-                           reinterpret_cast<const uint32_t *>(a.w.cnt + C_NSAMP), 16);
-    }
-    HM_CHECK_LAUNCH("hm_trace_forward");
-    return HM_OK;
+int hm_trace_forward_nffb(const hm_grid_desc *desc, const hm_nffb_desc *nffb, const hm_mlp_desc *mlp, const float *table,
+                          const float *B_fourier, int frac_mode, int tile_points, const hm_trace_cfg *cfg,
+                          const float *cam_loc, const float *ray_dirs, const uint8_t *object_mask, const float *t_sphere,
+                          const uint8_t *hit_mask, int64_t n_rays, int64_t rays_per_image, const float *sampler_fracs,
+                          const float *steps_u, float *out_points, uint8_t *out_net_mask, float *out_dists,
+                          void *workspace, int64_t workspace_bytes, int32_t *stats_out, void *stream) {
+    HM_CHECK_ARG(nffb != nullptr, "hm_trace_forward_nffb: NULL embedder descriptor");
+    return trace_forward_impl({desc, nffb, mlp, table, B_fourier, frac_mode, tile_points, stream}, cfg, cam_loc, ray_dirs,
+                              object_mask, t_sphere, hit_mask, n_rays, rays_per_image, sampler_fracs, steps_u, out_points,
+                              out_net_mask, out_dists, workspace, workspace_bytes, stats_out);
 }
 
 }  // extern "C"

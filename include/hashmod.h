@@ -424,6 +424,42 @@ HM_API int hm_trace_guard_tolerances(float *tau, float *tau_trip);
  * chain_tiles: tiles one workgroup finishes under the whole secant chain, -1 = derived from n_iters.                 */
 HM_API int hm_trace_scan_pool_plan(int64_t n_scan, int64_t n_ref1, int64_t n_ref2, int two_x, int grid_x,
                                    int64_t n_sec_bound, int n_iters, int64_t chain_tiles, int64_t *first, int64_t *quota);
+/* Diagnostic, host only: the launch sequence hm_trace_forward (has_nffb = 0) / hm_trace_forward_nffb (1) would enqueue
+ * for n_rays rays - the plan the call itself computes (csrc/hm_trace.hip: trace_plan), with the HM_TRACE_* environment
+ * switches read as a call reads them.  tests/test_trace_plan_cpu.py pins the decision table.
+ *   sequence        how the sampler's rows and the closest-approach rows are evaluated:
+ *     JOINT           one coarse launch over both point sets (any coarse_bf16 but 3)
+ *     FILL            exact fp32: the closest-approach scan completes the sampler launches' last rounds and runs beside
+ *                     the secant chain
+ *     GUARD_SERIAL    guarded: every launch on its own, one refinement list per sampler pass
+ *     GUARD_COSCHED   guarded: the sampler's refinement beside the whole closest-approach scan, that of the
+ *                     closest-approach rows beside the secant chain
+ *     GUARD_POOLED    guarded: the closest-approach scan shared out between the refinement launches and the chain's
+ *   secant          none; inside the sequence's own launches; all iterations as one persistent launch (scan_rule: with
+ *                   the tile rule of the scan-secant launch); an (SDF launch, update launch) pair per iteration          */
+enum { HM_TRACE_SEQ_JOINT = 0, HM_TRACE_SEQ_FILL = 1, HM_TRACE_SEQ_GUARD_SERIAL = 2, HM_TRACE_SEQ_GUARD_COSCHED = 3,
+       HM_TRACE_SEQ_GUARD_POOLED = 4 };
+enum { HM_TRACE_SECANT_NONE = 0, HM_TRACE_SECANT_IN_SEQUENCE = 1, HM_TRACE_SECANT_PERSISTENT = 2,
+       HM_TRACE_SECANT_PER_ITERATION = 3 };
+typedef struct hm_trace_plan_info {
+    int32_t sequence;         /* HM_TRACE_SEQ_*                                                                         */
+    int32_t sel_own;          /* the closest-approach rows are evaluated by their own count, in a region of their own   */
+    int32_t head;             /* lazy sampler: samples of the first pass in front of the last one (0: single pass)      */
+    int32_t per_ray, c_first; /* first pass: samples per ray, and the statistics counter that receives its points       */
+    int32_t k_tail;           /* pooled: secant rounds behind the cut of the chain (0: the chain is one launch)         */
+    int32_t c_ref2;           /* pooled: counter of the second refine-scan launch's list (-1: there is none)            */
+    int32_t march_tail;       /* the march hands over to the persistent kernel ...                                      */
+    int32_t march_launched;   /* ... after this many (SDF launch, update launch) rounds ...                             */
+    int32_t march_rounds;     /* ... of the search's 1 + sphere_tracing_iters * (1 + line_step_iters)                   */
+    int32_t secant;           /* HM_TRACE_SECANT_*                                                                      */
+    int32_t scan_rule;        /* persistent secant: tiles by the rule of the scan-secant launch                         */
+    int32_t noise_nan;        /* HM_TRACE_GUARD_NOISE=nan:K (guarded sequences only)                                    */
+    float noise_amp;          /* HM_TRACE_GUARD_NOISE=f: f * tau (guarded sequences only)                               */
+    int64_t chain_tiles;      /* pooled: split tiles one workgroup finishes under the secant chain                      */
+    int64_t guard_min;        /* guarded: launches of fewer live points were exact already and mark nothing             */
+} hm_trace_plan_info;
+HM_API int hm_diag_trace_plan(int64_t n_rays, const hm_trace_cfg *cfg, int tile_points, int has_nffb,
+                              hm_trace_plan_info *info);
 HM_API int hm_trace_forward(const hm_grid_desc *desc, const hm_mlp_desc *mlp, const float *table,
                             const float *B_fourier, int frac_mode, int tile_points, const hm_trace_cfg *cfg,
                             const float *cam_loc, const float *ray_dirs, const uint8_t *object_mask,
