@@ -147,13 +147,18 @@ struct Tile16 {
                  [&](int, int u, const float4 (&w)[4]) { if (u & 1) block16(bO, w); else block16(bE, w); });
     }
     __device__ __forceinline__ void reduce() {}
-    // bias, activation and store of the wave's ntw feature tiles (first: u0) -> Xn
-    __device__ __forceinline__ void epilogue(const float *__restrict__ bias, int u0, int ntw, bool act, bool div, float *Xn) {
+    // bias (bias64: the wave's 64 bias floats in LDS, see sdf_small_body), activation and store of the wave's ntw feature
+    // tiles (first: u0) -> Xn.  bias64 lies in the part of Xn this epilogue fills: every quad is read before the first store.
+    __device__ __forceinline__ void epilogue(const float *bias64, int u0, int ntw, bool act, bool div, float *Xn) {
+        if (ntw <= 0) return;
+        float4 bq[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) bq[a] = *reinterpret_cast<const float4 *>(bias64 + 16 * a + 4 * q);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             if (a >= ntw) continue;
             const int f = 16 * (u0 + a) + 4 * q;
-            const float4 bb = *reinterpret_cast<const float4 *>(bias + f);
+            const float4 bb = bq[a];
             float v[4] = {acc[a][0] + bb.x, acc[a][1] + bb.y, acc[a][2] + bb.z, acc[a][3] + bb.w};
             act_quads(v, act, div);
             *reinterpret_cast<float4 *>(Xn + (f >> 2) * kGF + j * 4) = make_float4(v[0], v[1], v[2], v[3]);
@@ -254,10 +259,11 @@ struct Tile8 {
             r1[r] = TWO ? keep1 + __shfl_xor(send1, 16) : 0.0f;
         }
     }
-    __device__ __forceinline__ void epilogue(const float *__restrict__ bias, int u0, int ntw, bool act, bool div, float *Xn) {
+    // (Tile16::epilogue: the lane's one quad of bias64 is read before its stores)
+    __device__ __forceinline__ void epilogue(const float *bias64, int u0, int ntw, bool act, bool div, float *Xn) {
         if (q < ntw) {
             const int f = 16 * (u0 + q) + 4 * jj;
-            const float4 bb = *reinterpret_cast<const float4 *>(bias + f);
+            const float4 bb = *reinterpret_cast<const float4 *>(bias64 + 16 * q + 4 * jj);
             float v[8] = {r0[0] + bb.x, r0[1] + bb.y, r0[2] + bb.z, r0[3] + bb.w,
                           r1[0] + bb.x, r1[1] + bb.y, r1[2] + bb.z, r1[3] + bb.w};
             act_quads(v, act, div);
@@ -307,7 +313,6 @@ __device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet 
     float *X0 = lds;
     float *X1 = lds + at.x1;
     float *EMB = lds + at.emb;
-    float *SX = lds + at.sx;     // [ST][3] (+ pad)
     float *RED = lds + at.red;   // [8 waves][ST]
 
     const int tid = threadIdx.x;
@@ -322,18 +327,18 @@ __device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet 
         const int cnt = (int)min((int64_t)PTS, n - base);
         HM_PROBE_S(0);
         float *X = X0, *Xn = X1;     // X: the image the current layer reads; Xn: the one its epilogue fills
-        __syncthreads();
-        load_points(FRAC != kFracEmb, SX, x, base, cnt, ST, tid);
-        __syncthreads();
+        __syncthreads();   // the workgroup is done with its previous tile
 
-        // ---- encode: thread -> (point p, slot c0); 512 / ST slots cover channels / levels
+        // ---- encode: thread -> (point p, slot group c0); the 512 / ST groups walk the Fourier channels and the levels side
+        // by side (embed_slots).  The lanes of a point read its 12 bytes themselves: no staging in LDS, no barrier
         if constexpr (FRAC == kFracEmb) {
             load_emb_tile(EMB, x, net.emb_stride, base, cnt, E, emb_groups16, PTS, GF, tid, kThreadsSdf);
         } else {
             const int p = tid & (ST - 1);
             const int c0 = tid / ST;
-            const float x0 = SX[p * 3], x1 = SX[p * 3 + 1], x2 = SX[p * 3 + 2];
-            embed_point<FRAC>(lv, table, Bf, x0, x1, x2, c0, kThreadsSdf / ST, emb_groups16 * 4,
+            const float *xp = x + (base + min(p, cnt - 1)) * 3;      // (zero beyond cnt)
+            const float x0 = p < cnt ? xp[0] : 0.0f, x1 = p < cnt ? xp[1] : 0.0f, x2 = p < cnt ? xp[2] : 0.0f;
+            embed_slots<FRAC>(lv, table, Bf, x0, x1, x2, c0, kThreadsSdf / ST, emb_groups16 * 4,
                               [&](int e, float v) { EMB[(e >> 2) * GF + p * 4 + (e & 3)] = v; });
         }
         __syncthreads();
@@ -352,6 +357,15 @@ __device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet 
             const int so[4] = {0, (1 < ntp ? 1 : 0) * ts, (2 < ntp ? 2 : 0) * ts, (3 < ntp ? 3 : 0) * ts};
             ring.fill(rp, so, nbp);
         };
+        // The epilogue's bias: the wave's 64 floats (its four feature tiles, clamped into the padded bias [nt16][16]), one per
+        // lane, requested a layer ahead - in front of the encode / of the previous layer's epilogue - so that no layer waits
+        // for a round trip to memory behind its k-loop.  The lanes exchange them through LDS (bias64, below).
+        const auto mfma_layer = [&](int l) { return l < net.n_layers && !(l == net.n_layers - 1 && out_cols == 1); };
+        const auto wave_bias = [&](int l) {
+            const hm_mlp_layer &Lb = net.layer[l];
+            return Lb.bias[min(64 * wave + lane, 32 * Lb.n_tiles - 1)];
+        };
+        float bias_nx = mfma_layer(0) ? wave_bias(0) : 0.0f;
         for (int li = 0; li < net.n_layers; ++li) {
             const hm_mlp_layer &Ly = net.layer[li];
             if (li == net.n_layers - 1 && out_cols == 1) {
@@ -364,6 +378,15 @@ __device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet 
             const int u0 = 4 * wave;
             const int ntw = max(0, min(4, nt16 - u0));
             tl.zero();
+            // bias64: the first 64 floats of the part of Xn that this wave alone fills (feature tile u0).  Nobody else reads or
+            // writes them before the barrier behind the epilogue, which reads its quads before its first store.
+            float *bias64 = Xn + 4 * u0 * GF;
+            if (ntw > 0) {
+                bias64[lane] = bias_nx;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
             if (ntw > 0) {
                 const __amdgpu_buffer_rsrc_t rA = w_rsrc(Ly.w_packed_m16 + ((size_t)u0 * nb) * 256);
                 const int tstride = nb * 1024;  // bytes to the next feature tile
@@ -376,8 +399,9 @@ __device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet 
             }
             // request the next layer's first blocks now: they travel while this layer's epilogue and the two
             // barriers run (weights do not depend on the activations)
-            if (li + 1 < net.n_layers && !(li + 1 == net.n_layers - 1 && out_cols == 1)) {
+            if (mfma_layer(li + 1)) {
                 if (2 * net.layer[li + 1].n_tiles - 4 * wave > 0) {
+                    bias_nx = wave_bias(li + 1);
                     prefetch(li + 1);
                     ring_ready = true;
                 }
@@ -387,8 +411,9 @@ __device__ __forceinline__ void sdf_small_body(const HmLevels &lv, const SdfNet 
             HM_PROBE_S(3 + 4 * li);
             if (li == 0) __syncthreads();   // (layer 0 only: its epilogue rescales EMB in place, which every wave has read)
             HM_PROBE_S(4 + 4 * li);
-            tl.epilogue(Ly.bias, u0, ntw, Ly.activation != 0, Ly.post_div_sqrt2 != 0, Xn);
+            tl.epilogue(bias64, u0, ntw, Ly.activation != 0, Ly.post_div_sqrt2 != 0, Xn);
             if (li == 0) rescale_emb(EMB, emb_groups16 * GF, tid, kThreadsSdf);
+            HM_PROBE_S(40 + li);
             __syncthreads();
             { float *t_ = X; X = Xn; Xn = t_; }
             HM_PROBE_S(5 + 4 * li);

@@ -258,6 +258,16 @@ __device__ __forceinline__ void embed_slot(const HmLevels &lv, const float *__re
     }
 }
 
+// the thread owns slots 1 + first, 1 + first + step, ... of its point (and slot 0 where first == 0): Fourier channels and
+// levels side by side, each on threads of its own where step covers the 2L slots
+template <int FRAC, class Put>
+__device__ __forceinline__ void embed_slots(const HmLevels &lv, const float *__restrict__ table,
+                                            const float *__restrict__ Bf, float x0, float x1, float x2, int first,
+                                            int step, int e_pad, Put &&put) {
+    if (first == 0) embed_passthrough(lv.E, e_pad, x0, x1, x2, put);
+    for (int slot = 1 + first; slot <= 2 * lv.L; slot += step) embed_slot<FRAC>(lv, table, Bf, x0, x1, x2, slot, e_pad, put);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 // hm_diag_sdf_lds: the byte offsets of a layout's regions, in order, and its size
 static void sdf_lds_report(const SdfLds &l, int32_t *regions) {
