@@ -355,7 +355,9 @@ class StaticGradExchange:
         for t in self.tables:
             over = int(t.status.item())
             if over:
-                raise RuntimeError(f"TouchedRowExchange: {over} touched rows did not fit the payload (cap {t.cap})")
+                raise RuntimeError(f"TouchedRowExchange: {over} touched rows did not fit the payload (cap {t.cap}); the "
+                                   "rows claimed beyond the cap keep their claim bit and their dense value and are "
+                                   "never listed again: rebuild the exchange object")
 
 
 class GradAllReducer:

@@ -741,7 +741,10 @@ HM_API int hm_colsum_acc_multi_det(const hm_colsum_item *items, int n_items, voi
  * touched_count [1] the number of listed rows, touched_rows [cap] their ids in the fused table.  Several calls of one
  * step share the three buffers.  hm_rows_pack turns the list into this rank's payload [cap, 1+F] int32 (row id, then
  * the F gradient values as fp32 bits; entries beyond the count carry row -1), zeroing the listed rows of d_table and
- * their claim bits; status[0] (optional) receives the overflow if more than `cap` rows were claimed.  After ONE
+ * their claim bits; status[0] (optional) receives the overflow if more than `cap` rows were claimed (the largest
+ * count - cap seen so far; the first `cap` rows are packed as usual).  The rows claimed beyond `cap` keep their claim
+ * bit and their dense value: they are never listed again, so after an overflow the three tracking buffers and
+ * d_table have to be set up afresh.  After ONE
  * all-gather of the payloads hm_rows_apply adds list r = lists + r*list_stride (r = 0..n_lists-1, one launch each, in
  * that order) into d_table scaled by `scale` (1/world): rows are unique inside a list, so plain read-modify-writes
  * suffice and every replica sums every row in the same (rank) order - bitwise identical replicas, no sort.
